@@ -7,14 +7,19 @@ Columns are independent, so ranks shard columns with no data-path collective.  "
 always owns `--cols` columns.  --scaling strong: BASELINE configs[3] as stated -- `--cols` columns IN TOTAL, cols / N per GPU
 (64 columns, 8 per GPU on 8 GPUs).  Rank 0 prints ONE JSON line.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--logn 24] [--cols 64] [--scaling weak|strong]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--logn 24] [--cols 64] [--scaling weak|strong] [--dump-outputs DIR] [--full]
   N > 1 is launched by torch.distributed.run (one process per GPU, RCCL for the barrier/MAX only).
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...).  Everything
+below -- the exchange loops, the pipeline / batch-proof / configs[4] probes, the roofline, the size sweep and the CPU baselines --
+runs only with --full (the --no-* options then leave parts of it out).  --dump-outputs DIR writes a fixed, seeded sample of what the
+last timed step computed as float64 .npy files (dump_outputs()); the inputs are seeded, so two builds can be compared output for output.
 
 The exchange step the path really has -- column shards -> row shards before leaf hashing, ONE all-to-all over xGMI -- is timed in its own
 K-step loops ("pipeline.exchange": the bare all-to-all with GB/s per link, and the whole sharded commitment zp_merkle_commit_sharded;
 median + min), on the RCCL communicator behind the C-ABI (a communicator of one rank at N = 1).
 
-Extra objects on the line: "roofline" (dominant kernel, HIP-event timing of every pass launch taken
+Extra objects on the line of a --full run: "roofline" (dominant kernel, HIP-event timing of every pass launch taken
 live inside this run), "cpu_baseline" (oracle/ CPU restatement timed on this host, rank 0, N=1) and
 "pipeline" (LDE + Poseidon Merkle commit of the same shard, timed outside the K steps).
 The oracle is only used as the CPU baseline here, never in the measured path.
@@ -50,6 +55,29 @@ def random_field_tensor(torch, shape, device, seed):
     bad = (x < 0) & (x >= -((1 << 32) - 1))
     x = torch.where(bad, x + ((1 << 32) - 1), x)
     return x
+
+
+DUMP_SAMPLE = 1 << 20   # output elements kept by --dump-outputs over all ranks: three float64 files of 8 MiB each
+
+
+def dump_outputs(torch, x, directory, rank=0, world=1):
+    """--dump-outputs: what the last timed step handed its caller -- the transformed columns, u64[cols][2^logn], in place in `x` -- as
+    a fixed, seeded sample of DUMP_SAMPLE / world elements per rank (all of them when there are fewer), exact in float64:
+      ntt_output_index  flat index column * 2^logn + row (sorted)
+      ntt_output_hi     the upper 32 bits of the canonical value
+      ntt_output_lo     the lower 32 bits
+    At N > 1 every rank writes its own shard's files with a _rank<r> suffix."""
+    import numpy as np
+    total, keep = x.numel(), max(1, DUMP_SAMPLE // world)
+    if total <= keep:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(0xD0B5 + rank).integers(0, total, size=keep, dtype=np.int64))
+    vals = x.reshape(-1)[torch.from_numpy(idx).to(x.device)].cpu().numpy().view(np.uint64)
+    tag = "_rank%d" % rank if world > 1 else ""
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in (("ntt_output_index", idx), ("ntt_output_hi", vals >> np.uint64(32)), ("ntt_output_lo", vals & np.uint64(0xFFFFFFFF))):
+        np.save(os.path.join(directory, name + tag + ".npy"), arr.astype(np.float64))
 
 
 def host_cpu_info():
@@ -192,6 +220,76 @@ def integer_roofline(prover, pass_rows, alg_bytes, elems_per_launch, launches_pe
         return {"error": repr(e)}
 
 
+def ntt_roofline(prover, plan, passes, logn, cols, steps, dev_ms, copy_gbs):
+    """--full: the `roofline` block of the line, from the per-launch events of the timed steps (set_profiling) and the committed PMC
+    files: HBM fraction of every pass of the plan, the measured copy ceiling, the integer-VALU roofline"""
+    N = 1 << logn
+    npass = max(1, len(plan["passes"]))
+    # Every launch of the timed region is one instantiation of ntt_pass2_kernel (one pass of the plan over chunk_cols
+    # columns).  The roofline figure is TIME-WEIGHTED over all of them: algorithmic bytes of all launches / summed launch
+    # time -- no instantiation is left out (round 2 reported the two cheaper ones only).  pass_timings() keys: radix log,
+    # negative = the transposing first pass.
+    by_kind, by_pass = {}, {}
+    for j, (rl, ms) in enumerate(passes):
+        by_kind.setdefault(rl, []).append(ms)
+        by_pass.setdefault(j % npass, []).append(ms)       # launches are recorded in order: pass 0 .. npass-1 of every chunk of columns
+    chunk_cols = min(cols, max(1, (1 << int(os.environ.get("ZP_NTT_CHUNK_LOG", "28"))) >> logn))
+    # algorithmic bytes of one launch: SURVEY 8d gives 16*N bytes per column transform (ideal single
+    # pass); a launch does one of the `npass` passes over chunk_cols columns -> 16*N*chunk/npass
+    alg_bytes = 16.0 * N * chunk_cols / npass
+    launches = sum(len(v) for v in by_kind.values())
+    total_ms = sum(sum(v) for v in by_kind.values())
+    avg_ms = total_ms / launches if launches else float("nan")
+    achieved = alg_bytes / (avg_ms * 1e-3) / 1e9 if launches else float("nan")
+    pass_rows = []
+    for i, ps in enumerate(plan["passes"]):
+        first, last = i == 0, i == len(plan["passes"]) - 1
+        tw1 = first and plan.get("first_pass_table", False)
+        mode = (3 if tw1 else 1) if first else (0 if last else 1)   # forward transform: table passes in the middle, plain last pass
+        logt = {1: 0, 2: 1, 4: 2, 8: 3, 16: 4, 32: 5}[ps["tile"]]
+        # <A1, A2, A3, LOGT, TRANSPOSE, PADDED, MODE, BIG, LIMB>: the canonical-arithmetic instantiations (knob ntt_limb = 0, the default)
+        name = "ntt_pass2_kernel<%d, %d, %d, %d, %s, false, %d, false, false>" % (ps["rounds"][0], ps["rounds"][1], ps["rounds"][2], logt,
+                                                                                    "true" if first else "false", mode)
+        ms_l = by_pass.get(i, [])
+        assert all(abs(rl) == ps["radix_log"] for rl, _ in passes[i::npass]), "pass timings out of step with the plan"
+        a_ms = sum(ms_l) / len(ms_l) if ms_l else None
+        pass_rows.append({"kernel": name, "role": ("transposing first pass (full twiddle table, shared by the columns through L2)" if tw1 else
+                                                   "transposing first pass (per-lane twiddle chain)") if first else
+                          ("plain last pass" if last else "pass with a per-tile twiddle table"),
+                          "launches": len(ms_l), "avg_launch_ms": a_ms,
+                          "frac": (alg_bytes / (a_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if a_ms else None})
+    slowest = max((r for r in pass_rows if r["avg_launch_ms"]), key=lambda r: r["avg_launch_ms"], default=None)
+    traffic, traffic_src = None, None
+    for tp in ("r6c_ntt_traffic.json", "r6_ntt_traffic.json", "r5_ntt_traffic.json", "r4_ntt_traffic.json"):
+        tp = os.path.join(ROOT, "profiles", tp)
+        if os.path.exists(tp):
+            try:
+                traffic = json.load(open(tp)).get("hbm_bytes_per_launch_dominant")
+                traffic_src = ("committed PMC measurement %s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes, FETCH x 2 "
+                               "per the gfx950 correction); not re-measured in this run" % os.path.relpath(tp, ROOT))
+                break
+            except Exception:
+                traffic = None
+    integer = integer_roofline(prover, pass_rows, alg_bytes, N * chunk_cols, launches_per_step=(None, steps), ms_per_step=dev_ms / steps)
+    return {
+        "bound": "hbm",
+        "kernel": "ntt_pass2_kernel: all %d instantiations of the plan, time-weighted (slowest: %s)" % (len(pass_rows), slowest["kernel"] if slowest else "?"),
+        "passes": pass_rows,
+        "launch_columns": chunk_cols,
+        "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": achieved / HBM_PEAK_GBS if launches else None,
+        "traffic": traffic, "traffic_source": traffic_src,
+        "hbm_copy_ceiling_GBs": copy_gbs,
+        "frac_of_copy_ceiling": (achieved / copy_gbs) if (launches and copy_gbs) else None,
+        "algorithmic_bytes_per_launch": alg_bytes,
+        "avg_launch_ms": avg_ms, "launches_timed": launches,
+        "whole_transform_GBs": 16.0 * N * cols * steps / (dev_ms * 1e-3) / 1e9,
+        "whole_transform_frac": 16.0 * N * cols * steps / (dev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+        "per_pass_avg_ms": {str(k): sum(v) / len(v) for k, v in sorted(by_kind.items())},
+        "integer": integer,
+    }
+
+
 _REAL_STDOUT = [None]
 
 
@@ -267,8 +365,19 @@ def main():
     ap.add_argument("--c5-msm-log", type=int, default=26)
     ap.add_argument("--stage-roofline", action="store_true",
                     help="cpu_baseline leg also times every hot-path stage on GPU and CPU restatement (tools/stage_roofline.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every probe, baseline and roofline figure beyond the headline (a plain run times the K steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed seeded sample of the last step's output to DIR/<name>.npy (float64)")
     ap.add_argument("--child-probe", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.stage_roofline and not args.full:
+        ap.error("--stage-roofline is part of the --full run")
+    if not args.full:
+        # the headline only: no probe, baseline or roofline outside the timed steps
+        args.no_pipeline = args.no_cpu = args.no_config5 = True
     if args.scaling is None:
         args.scaling = "weak"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.child_probe:
@@ -352,7 +461,7 @@ def main():
     for _ in range(args.warmup):
         prover.ntt(x, x, logn, cols)
     barrier()
-    prover.set_profiling(True)
+    prover.set_profiling(args.full)         # per-launch events for the roofline block (--full)
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     ev0.record()
@@ -366,8 +475,11 @@ def main():
     wall = time.perf_counter() - t0
     dev_ms = ev0.elapsed_time(ev1)
     per_step = sorted(step_ev[k].elapsed_time(step_ev[k + 1]) for k in range(args.steps))   # median + min
-    passes = prover.pass_timings()
+    passes = prover.pass_timings() if args.full else []
     prover.set_profiling(False)
+    if args.dump_outputs:
+        # before anything below reuses the buffer (the sweep transforms its first columns in place)
+        dump_outputs(torch, x, args.dump_outputs, rank, world)
 
     t = torch.tensor([wall], dtype=torch.float64, device=dev)
     if world > 1:
@@ -377,7 +489,7 @@ def main():
     # achievable HBM ceiling on this device (report against both the vendor peak and a measured copy):
     # device-to-device copy of the same 2^logn x cols matrix, read + write bytes counted
     copy_gbs = None
-    if rank == 0:
+    if rank == 0 and args.full:
         y = torch.empty_like(x)
         ms = prover.hbm_copy_probe(x, y, x.numel() * 8, reps=5)     # libzethprover's own 16 B/lane non-temporal copy kernel
         copy_gbs = 2.0 * x.numel() * 8 / (ms * 1e-3) / 1e9
@@ -386,7 +498,7 @@ def main():
     # north_star: "Goldilocks NTT field-elems/s on synthetic 2^20-2^26 traces ... as absolute numbers and as fraction of HBM roofline" -- a compact live
     # sweep on the buffer of the timed region (16 columns; the full sweep with LDE and Merkle: tools/size_sweep.py -> profiles/r6_size_sweep.jsonl)
     sweep = None
-    if rank == 0 and world == 1 and logn == 24 and cols >= 64:
+    if rank == 0 and world == 1 and logn == 24 and cols >= 64 and args.full:
         try:
             sweep = []
             for lg in range(20, 27):
@@ -408,54 +520,7 @@ def main():
 
     if rank == 0:
         plan = prover.ntt_plan(logn)
-        npass = max(1, len(plan["passes"]))
         elems_total = world * cols * N * args.steps
-        # Every launch of the timed region is one instantiation of ntt_pass2_kernel (one pass of the plan over chunk_cols
-        # columns).  The roofline figure is TIME-WEIGHTED over all of them: algorithmic bytes of all launches / summed launch
-        # time -- no instantiation is left out (round 2 reported the two cheaper ones only).  pass_timings() keys: radix log,
-        # negative = the transposing first pass.
-        by_kind, by_pass = {}, {}
-        for j, (rl, ms) in enumerate(passes):
-            by_kind.setdefault(rl, []).append(ms)
-            by_pass.setdefault(j % npass, []).append(ms)       # launches are recorded in order: pass 0 .. npass-1 of every chunk of columns
-        chunk_cols = min(cols, max(1, (1 << int(os.environ.get("ZP_NTT_CHUNK_LOG", "28"))) >> logn))
-        # algorithmic bytes of one launch: SURVEY 8d gives 16*N bytes per column transform (ideal single
-        # pass); a launch does one of the `npass` passes over chunk_cols columns -> 16*N*chunk/npass
-        alg_bytes = 16.0 * N * chunk_cols / npass
-        launches = sum(len(v) for v in by_kind.values())
-        total_ms = sum(sum(v) for v in by_kind.values())
-        avg_ms = total_ms / launches if launches else float("nan")
-        achieved = alg_bytes / (avg_ms * 1e-3) / 1e9 if launches else float("nan")
-        pass_rows = []
-        for i, ps in enumerate(plan["passes"]):
-            first, last = i == 0, i == len(plan["passes"]) - 1
-            tw1 = first and plan.get("first_pass_table", False)
-            mode = (3 if tw1 else 1) if first else (0 if last else 1)   # forward transform: table passes in the middle, plain last pass
-            logt = {1: 0, 2: 1, 4: 2, 8: 3, 16: 4, 32: 5}[ps["tile"]]
-            # <A1, A2, A3, LOGT, TRANSPOSE, PADDED, MODE, BIG, LIMB>: the canonical-arithmetic instantiations (knob ntt_limb = 0, the default)
-            name = "ntt_pass2_kernel<%d, %d, %d, %d, %s, false, %d, false, false>" % (ps["rounds"][0], ps["rounds"][1], ps["rounds"][2], logt,
-                                                                                        "true" if first else "false", mode)
-            ms_l = by_pass.get(i, [])
-            assert all(abs(rl) == ps["radix_log"] for rl, _ in passes[i::npass]), "pass timings out of step with the plan"
-            a_ms = sum(ms_l) / len(ms_l) if ms_l else None
-            pass_rows.append({"kernel": name, "role": ("transposing first pass (full twiddle table, shared by the columns through L2)" if tw1 else
-                                                       "transposing first pass (per-lane twiddle chain)") if first else
-                              ("plain last pass" if last else "pass with a per-tile twiddle table"),
-                              "launches": len(ms_l), "avg_launch_ms": a_ms,
-                              "frac": (alg_bytes / (a_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if a_ms else None})
-        slowest = max((r for r in pass_rows if r["avg_launch_ms"]), key=lambda r: r["avg_launch_ms"], default=None)
-        traffic, traffic_src = None, None
-        for tp in ("r6c_ntt_traffic.json", "r6_ntt_traffic.json", "r5_ntt_traffic.json", "r4_ntt_traffic.json"):
-            tp = os.path.join(ROOT, "profiles", tp)
-            if os.path.exists(tp):
-                try:
-                    traffic = json.load(open(tp)).get("hbm_bytes_per_launch_dominant")
-                    traffic_src = ("committed PMC measurement %s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes, FETCH x 2 "
-                                   "per the gfx950 correction); not re-measured in this run" % os.path.relpath(tp, ROOT))
-                    break
-                except Exception:
-                    traffic = None
-        integer = integer_roofline(prover, pass_rows, alg_bytes, N * chunk_cols, launches_per_step=(None, args.steps), ms_per_step=dev_ms / args.steps)
         out = {
             "metric": "goldilocks_ntt_field_elems_per_s",
             "value": elems_total / wall_max,
@@ -469,6 +534,7 @@ def main():
             "vs_baseline": None,
             "dtype": "u64",
             "data": "synthetic",
+            "full": args.full,            # false: the headline only; true: the probes, baselines and roofline below are on the line too
             "degraded": False,            # true: an optional probe failed or stalled; the K timed steps above are complete either way
             "exchange_stalled": False,    # true: a collective of the exchange probes never completed (watchdog) or returned an error
             "rccl": rccl_seen,
@@ -478,28 +544,13 @@ def main():
                                     "configs[3] as stated" % (logn, cols * world, cols)),
                        "logn": logn, "cols_per_gpu": cols, "cols_total": cols * world, "sharding": "columns, no data-path collective",
                        "plan": plan},
-            "sweep": sweep,
             "device_ms_per_step": dev_ms / args.steps,
             "device_ms_per_step_median": per_step[len(per_step) // 2],
             "device_ms_per_step_min": per_step[0],
-            "roofline": {
-                "bound": "hbm",
-                "kernel": "ntt_pass2_kernel: all %d instantiations of the plan, time-weighted (slowest: %s)" % (len(pass_rows), slowest["kernel"] if slowest else "?"),
-                "passes": pass_rows,
-                "launch_columns": chunk_cols,
-                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS if launches else None,
-                "traffic": traffic, "traffic_source": traffic_src,
-                "hbm_copy_ceiling_GBs": copy_gbs,
-                "frac_of_copy_ceiling": (achieved / copy_gbs) if (launches and copy_gbs) else None,
-                "algorithmic_bytes_per_launch": alg_bytes,
-                "avg_launch_ms": avg_ms, "launches_timed": launches,
-                "whole_transform_GBs": 16.0 * N * cols * args.steps / (dev_ms * 1e-3) / 1e9,
-                "whole_transform_frac": 16.0 * N * cols * args.steps / (dev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "per_pass_avg_ms": {str(k): sum(v) / len(v) for k, v in sorted(by_kind.items())},
-                "integer": integer,
-            },
         }
+        if args.full:
+            out["sweep"] = sweep
+            out["roofline"] = ntt_roofline(prover, plan, passes, logn, cols, args.steps, dev_ms, copy_gbs)
 
     # ---- optional probes.  At N > 1 they contain collectives that cannot be rehearsed on the one-GPU development box:
     # a watchdog prints the line with the headline numbers and ends every rank if they do not return in time.
@@ -597,7 +648,7 @@ def main():
                     extra["cpu_baseline"]["stages"] = stage_roofline.run(22, 32, cpu=types.SimpleNamespace(O=O, CpuBackend=CpuBackend, B1=B1))
                 except Exception as e:
                     extra["cpu_baseline"]["stages"] = {"error": repr(e)}
-        else:
+        elif args.full:
             extra["cpu_baseline"] = None
         with out_lock:
             if not printed[0]:

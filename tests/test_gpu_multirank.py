@@ -62,7 +62,8 @@ def test_bench_n2_plain_launch_on_one_gpu():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", ZP_BENCH_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--logn", "20", "--cols", "16", "--stark-logn", "14"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--logn", "20", "--cols", "16", "--stark-logn", "14",
+           "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -100,8 +101,8 @@ def test_bench_strong_scaling_mode_and_the_timed_exchange_loops():
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["scaling"] == "strong" and line["config"]["cols_per_gpu"] == 8 and line["config"]["cols_total"] == 16 and line["n_gpus"] == 2
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--logn", "18", "--cols", "16", "--no-cpu", "--no-config5",
-           "--stark-logn", "12"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--logn", "18", "--cols", "16", "--full", "--no-cpu",
+           "--no-config5", "--stark-logn", "12"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

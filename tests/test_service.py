@@ -5,7 +5,6 @@ The CPU runs use the oracle backend (BASELINE.json configs[0]: plumbing, no GPU)
 uses the HIP backend and must produce the same chunk proofs."""
 import json
 import os
-import re
 
 import pytest
 
@@ -16,7 +15,6 @@ from eigen_zeth_amd.service.server import ProverService, make_server
 from eigen_zeth_amd.service.store import BatchStore
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_PROTO = "/root/reference/proto/prover/v1/prover.proto"
 
 
 def parse_proof_like_eigen_zeth(js):
@@ -32,27 +30,16 @@ def parse_public_input_like_eigen_zeth(js):
 
 
 def test_schema_matches_reference_proto_text():
-    if not os.path.exists(REF_PROTO):
-        pytest.skip("reference not present on this machine")
-    txt = re.sub(r"//[^\n]*", "", open(REF_PROTO).read())
-
-    def body_of(name):
-        m = re.search(r"message\s+%s\s*\{" % name, txt)
-        assert m, name
-        depth, i = 1, m.end()
-        while depth:
-            depth += {"{": 1, "}": -1}.get(txt[i], 0)
-            i += 1
-        body = txt[m.end():i - 1]
-        return re.sub(r"enum\s+\w+\s*\{.*?\}", "", body, flags=re.S)   # nested enums are not fields
-
+    """the mirror's messages declare exactly the fields -- names and numbers -- of the reference's prover.proto, and the one rpc is
+    bidirectionally streaming (tests/golden/ref_proto_schema.json, made from the schema by tests/golden/extract_ref_proto.py)"""
+    with open(os.path.join(ROOT, "tests", "golden", "ref_proto_schema.json")) as f:
+        ref = json.load(f)
     for mname, fields in proto.SCHEMA.items():
-        body = body_of(mname)
-        for (fname, num, *_rest) in fields:
-            assert re.search(r"\b%s\s*=\s*%d\s*;" % (fname, num), body), (mname, fname, num)
-        declared = set(re.findall(r"\b(\w+)\s*=\s*\d+\s*;", body))
-        assert declared == {f[0] for f in fields}, (mname, declared)
-    assert "rpc ProverStream(stream ProverRequest) returns (stream ProverResponse)" in txt
+        assert mname in ref["messages"], mname
+        assert {fname: num for (fname, num, *_rest) in fields} == ref["messages"][mname], mname
+    assert ref["rpc"] == {"service": "ProverService", "method": "ProverStream", "request": "ProverRequest", "request_stream": True,
+                          "response": "ProverResponse", "response_stream": True}
+    assert proto.METHOD == "/prover.v1.%s/%s" % (ref["rpc"]["service"], ref["rpc"]["method"])
 
 
 def test_schema_frozen_numbers():

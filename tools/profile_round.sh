@@ -7,7 +7,7 @@ TAG=${1:-rX}
 ROOT=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$ROOT/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}_bench -- python3 $ROOT/bench.py --no-cpu --no-pipeline --no-config5 --steps 10 > $OUT/${TAG}_bench_under_profiler.json 2> $OUT/${TAG}_bench_under_profiler.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}_bench -- python3 $ROOT/bench.py --full --no-cpu --no-pipeline --no-config5 --steps 10 > $OUT/${TAG}_bench_under_profiler.json 2> $OUT/${TAG}_bench_under_profiler.err
 cp $(ls $OUT/prof_${TAG}_bench/*/*kernel_stats.csv | head -1) $OUT/${TAG}_bench_kernel_stats.csv
 echo "kernel stats done"
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT --output-format csv -d $OUT/prof_${TAG}_sq -- python3 $ROOT/tools/pmc_ntt.py > /dev/null 2>&1

@@ -1,7 +1,7 @@
 """Per-stage measurement for every hot-path row of SURVEY.md 8a (N1..N6 + DEEP/OOD): HIP-side time
 (wall around sync'd calls, 3 reps after a warm-up), algorithmic bytes per SURVEY 8d and fraction of the
 8 TB/s HBM roof.  Run directly it measures the GPU only; the CPU restatement column is added when bench.py calls
-run() from its cpu_baseline leg (`python bench.py --stage-roofline`), which is the only place that may hand the
+run() from its cpu_baseline leg (`python bench.py --full --stage-roofline`), which is the only place that may hand the
 oracle modules in.  usage: python tools/stage_roofline.py [logn=22] [W=32]"""
 import json, os, sys, time, random
 os.environ.setdefault("OMP_WAIT_POLICY", "PASSIVE")  # idle OpenMP workers of the CPU checker must not spin beside the GPU timing
