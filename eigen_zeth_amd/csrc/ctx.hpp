@@ -197,6 +197,15 @@ int32_t zpi_merkle16_levels_bn254(zp_ctx *ctx, u64 *d_tree, size_t n);   // the 
 struct zp_comm;
 zp_ctx *zpi_comm_ctx(const zp_comm *comm);      // the ctx a communicator was created on (csrc/comm.hip)
 int32_t zpi_comm_fail(zp_comm *comm, int32_t rc);   // rc != ZP_OK: kill the communicator (no peer waits for this rank); returns rc
+// the slice rule of the sharded entry points: with k = ceil(n / world), rank r owns [r k, min((r + 1) k, n)) -- the tail ranks fewer, or none
+inline void zpi_shard_range(size_t n, int world, int rank, size_t *first, size_t *count) {
+    const size_t k = (n + (size_t)world - 1) / (size_t)world, lo = (size_t)rank * k;
+    *first = lo < n ? lo : n;
+    *count = lo >= n ? 0 : (n - lo < k ? n - lo : k);
+}
+// out = the sum, in order, of `count` affine BN254 points in the zp_msm_bn254 layout (g2 = 0: u32[16] each; 1: G2, u32[32]; all-zero = infinity),
+// on the host: the partial sums of a sharded MSM (csrc/msm.hip)
+void zpi_bn254_affine_sum(int g2, const uint32_t *pts, int count, uint32_t *out);
 int32_t zpi_twiddle_rows(zp_ctx *ctx, u64 *d_rows, int logn_row, int W, u64 row0, int logn_total, bool inverse);
 int32_t zpi_lde(zp_ctx *ctx, const u64 *d_in, u64 *d_out, u64 *d_coef, int logn, int logb, int W, u64 shift);
 int32_t zpi_ntt_run(zp_ctx *ctx, const u64 *d_in, u64 *d_out, int logn, int W, bool inverse,

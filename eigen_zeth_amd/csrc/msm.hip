@@ -1183,6 +1183,18 @@ int32_t msm_chunk(zp_ctx *ctx, const uint32_t *d_points, const uint32_t *d_scala
 // that footprint its rate halves (2^26 in one run: 3.7 G additions/s against 8.1 G/s at 2^24); the partial sums are
 // added on the host.
 #define MSM_CHUNK_LOG 24
+// a Jacobian sum as affine words in the layout of the entry points (standard form; infinity leaves h_out as it is: the callers zero it)
+template <class F>
+void jac_to_words(const jacT<F> &acc, uint32_t *h_out) {
+    if (f_is_zero(acc.Z)) return;  // infinity: all-zero output
+    F zi = f_inv_host(acc.Z);
+    F zi2 = f_sqr(zi);
+    F x = f_from_mont(f_mul(acc.X, zi2));
+    F y = f_from_mont(f_mul(acc.Y, f_mul(zi2, zi)));
+    FT<F>::to_words(x, h_out);
+    FT<F>::to_words(y, h_out + FT<F>::WORDS);
+}
+
 template <class F>
 int32_t msm_run(zp_ctx *ctx, const uint32_t *d_points, const uint32_t *d_scalars, size_t n, uint32_t *h_out) {
     constexpr int PW = FT<F>::WORDS * 2;   // words per affine point
@@ -1199,17 +1211,72 @@ int32_t msm_run(zp_ctx *ctx, const uint32_t *d_points, const uint32_t *d_scalars
         ZP_TRY(msm_chunk<F>(ctx, d_points + off * PW, d_scalars + off * 8, len, &part));
         acc = jac_add(acc, part);
     }
-    if (f_is_zero(acc.Z)) return ZP_OK;  // infinity: all-zero output
-    F zi = f_inv_host(acc.Z);
-    F zi2 = f_sqr(zi);
-    F x = f_from_mont(f_mul(acc.X, zi2));
-    F y = f_from_mont(f_mul(acc.Y, f_mul(zi2, zi)));
-    FT<F>::to_words(x, h_out);
-    FT<F>::to_words(y, h_out + FT<F>::WORDS);
+    jac_to_words(acc, h_out);
     return ZP_OK;
 }
 
+// ---- sharded MSM: rank r sums its slice of the points (the rule of zpi_shard_range) with msm_run, the world partial sums travel as affine words in
+// ONE all-gather, and every rank adds them in rank order on the host.  The affine sum is unique: every rank returns what zp_msm_bn254 / _g2 returns
+// for the whole input on one ctx, word for word.
+template <class F>
+int32_t msm_sharded(zp_comm *comm, const uint32_t *d_points, const uint32_t *d_scalars, size_t n_total, uint32_t *h_out) {
+    constexpr int PW = FT<F>::WORDS * 2;   // u32 per affine point: PW / 2 u64 words per rank in the exchange
+    zp_ctx *ctx = zpi_comm_ctx(comm);
+    if (!ctx) return ZP_ERR_ARG;
+    ZpStage stage_(ctx, PW == 16 ? "msm_bn254_sharded" : "msm_bn254_g2_sharded");
+    const int world = zp_comm_world(comm), rank = zp_comm_rank(comm);
+    size_t first = 0, count = 0;
+    zpi_shard_range(n_total, world, rank, &first, &count);
+    const size_t xbytes = (size_t)(world + 1) * PW * 4;
+    void *d_x = nullptr;
+    int32_t rc = ZP_OK;
+    try {
+        std::vector<uint32_t> parts((size_t)world * PW, 0);
+        if (!h_out || n_total >= (1ULL << 31) || (count && !(d_points && d_scalars))) {
+            ctx->err = "bad argument: null output or slice, or too many points";
+            rc = ZP_ERR_ARG;
+        }
+        if (rc == ZP_OK) rc = msm_run<F>(ctx, d_points, d_scalars, count, parts.data());       // an empty slice: infinity
+        if (rc == ZP_OK) rc = zpi_pool_alloc(ctx, xbytes, &d_x);
+        if (rc == ZP_OK) rc = zpi_h2d_small(ctx, d_x, parts.data(), PW * 4);
+        if (rc == ZP_OK) rc = zp_comm_all_gather(comm, (const uint64_t *)d_x, (uint64_t *)d_x + PW / 2, PW / 2);
+        if (rc == ZP_OK) rc = zpi_d2h_small(ctx, parts.data(), (const uint64_t *)d_x + PW / 2, (size_t)world * PW * 4);
+        if (d_x) zpi_pool_release(ctx, d_x, xbytes);
+        if (rc != ZP_OK) return zpi_comm_fail(comm, rc);
+        zpi_bn254_affine_sum(PW == 32, parts.data(), world, h_out);
+        return ZP_OK;
+    } catch (...) {
+        if (d_x) zpi_pool_release(ctx, d_x, xbytes);
+        ctx->err = "out of host memory in a sharded MSM";
+        return zpi_comm_fail(comm, ZP_ERR_NOMEM);
+    }
+}
+
+template <class F>
+void affine_sum(const uint32_t *pts, int count, uint32_t *out) {
+    constexpr int W = FT<F>::WORDS;
+    jacT<F> acc = jac_inf<F>();
+    for (int i = 0; i < count; i++) {
+        const uint32_t *p = pts + (size_t)i * 2 * W;
+        bool inf = true;
+        for (int k = 0; k < 2 * W; k++) inf = inf && p[k] == 0;
+        if (inf) continue;
+        jacT<F> q;
+        q.X = f_to_mont(FT<F>::from_words(p));
+        q.Y = f_to_mont(FT<F>::from_words(p + W));
+        q.Z = FT<F>::one();
+        acc = jac_add(acc, q);
+    }
+    memset(out, 0, 2 * W * sizeof(uint32_t));
+    jac_to_words(acc, out);
+}
+
 }  // namespace
+
+void zpi_bn254_affine_sum(int g2, const uint32_t *pts, int count, uint32_t *out) {
+    if (g2) affine_sum<fq2>(pts, count, out);
+    else affine_sum<fq>(pts, count, out);
+}
 
 extern "C" int32_t zp_msm_bn254(zp_ctx *ctx, const uint32_t *d_points, const uint32_t *d_scalars, size_t n,
                                 uint32_t *h_out) {
@@ -1223,6 +1290,14 @@ extern "C" int32_t zp_msm_bn254_g2(zp_ctx *ctx, const uint32_t *d_points, const 
     if (!ctx) return ZP_ERR_ARG;
     ZpStage stage_(ctx, "msm_bn254_g2");
     return msm_run<fq2>(ctx, d_points, d_scalars, n, h_out);
+}
+
+extern "C" int32_t zp_msm_bn254_sharded(zp_comm *comm, const uint32_t *d_points_local, const uint32_t *d_scalars_local, size_t n_total, uint32_t *h_out) {
+    return msm_sharded<fq>(comm, d_points_local, d_scalars_local, n_total, h_out);
+}
+
+extern "C" int32_t zp_msm_bn254_g2_sharded(zp_comm *comm, const uint32_t *d_points_local, const uint32_t *d_scalars_local, size_t n_total, uint32_t *h_out) {
+    return msm_sharded<fq2>(comm, d_points_local, d_scalars_local, n_total, h_out);
 }
 
 // ---- fixed-base multiplication: out_i = s_i * B for ONE base B -- the group elements of a Groth16 key ([u_j(tau)]_1, [v_j(tau)]_2, ...: millions of

@@ -152,6 +152,10 @@ SIGNATURES = {
     "zp_exchange_columns_to_rows": (C.c_int32, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp]),
     "zp_ntt_sharded": (C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32]),
     "zp_merkle_commit_sharded": (C.c_int32, [_vp, _vp, C.c_size_t, C.c_int32, _vp, _u64p]),
+    "zp_msm_bn254_sharded": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "zp_msm_bn254_g2_sharded": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "zp_groth16_prove_sharded": (C.c_int32, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             _vp, _vp]),
     "zp_msm_bn254": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_uint32)]),
     "zp_msm_bn254_g2": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_uint32)]),
     "zp_ntt_host": (C.c_int32, [_vp, _u64p, C.c_int32, C.c_int32, C.c_int32]),
@@ -568,6 +572,61 @@ class Comm:
         root = (C.c_uint64 * 4)()
         self.prover._chk(self.prover.lib.zp_merkle_commit_sharded(self.h, _ptr(d_cols), M, Wl, _ptr(d_tree_local), root))
         return [int(v) for v in root]
+
+    def my_range(self, n_total):
+        """this rank's slice of n_total indices, (first, count): the rule of my_columns (and of every sharded entry point)"""
+        return self.my_columns(n_total)
+
+    def msm_bn254_sharded(self, d_points_local, d_scalars_local, n_total, g2=False):
+        """zp_msm_bn254_sharded (g2: zp_msm_bn254_g2_sharded): this rank's slice of the points and scalars in (device, my_range(n_total); None for
+        an empty slice), the affine sum of ALL n_total terms out on every rank: u32[16] (G2: u32[32]), all zero = infinity"""
+        out = (C.c_uint32 * (32 if g2 else 16))()
+        fn = self.prover.lib.zp_msm_bn254_g2_sharded if g2 else self.prover.lib.zp_msm_bn254_sharded
+        self.prover._chk(fn(self.h, _ptr(d_points_local), _ptr(d_scalars_local), int(n_total), out))
+        return np.array(out, dtype=np.uint32)
+
+    def groth16_prove_sharded(self, blob, dev, delta1_words, set_idx, set_val, r, s):
+        """zp_groth16_prove_sharded: Prover.groth16_prove over the ranks -- dev holds THIS rank's slices of the key's point arrays (u1x, v1x, v2x,
+        l1, h1; None where the slice is empty) and of "v_wires", and "n_v" (the total); the same result on every rank"""
+        return self.prover._groth16(self.prover.lib.zp_groth16_prove_sharded, self.h, blob, dev, delta1_words, set_idx, set_val, r, s)
+
+
+def over_ranks(provers, fn, timeout_ms=None):
+    """fn(rank, prover, comm) on one thread per rank: provers[r] joined as rank r to a fresh in-process CommGroup (the ranks of
+    prove_native_sharded).  Returns the list of results; raises the first rank's own error -- not a peer's ZP_ERR_COMM -- after every thread
+    has ended (a rank that fails calls zp_comm_abort first, so no peer waits for it)."""
+    world = len(provers)
+    group = CommGroup(world)
+    out, errs = [None] * world, [None] * world
+
+    def body(r):
+        c = None
+        try:
+            c = Comm(provers[r], r, world, group=group)
+            if timeout_ms is not None:
+                c.set_timeout_ms(timeout_ms)
+            out[r] = fn(r, provers[r], c)
+        except BaseException as e:          # noqa: every rank's error is looked at below
+            errs[r] = e
+            if c is not None:
+                try:
+                    c.abort()
+                except Exception:
+                    pass
+        finally:
+            if c is not None:
+                c.close()
+    ts = [threading.Thread(target=body, args=(r,), name="rank-%d" % r) for r in range(world)]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join()
+    group.close()
+    bad = [e for e in errs if e is not None]
+    if bad:
+        real = [e for e in bad if not (isinstance(e, ZpError) and e.code == -6)]       # ZP_ERR_COMM: a peer of the rank that failed
+        raise (real or bad)[0]
+    return out
 
 
 class Prover:
@@ -1058,6 +1117,9 @@ class Prover:
     def groth16_prove(self, blob, dev, delta1_words, set_idx, set_val, r, s):
         """zp_groth16_prove -> (pi_a u32[16], pi_b u32[32], pi_c u32[16], public inputs [int], [ms witness, ms QAP, ms MSMs]); dev: name -> device
         buffer of the key's points (u1x, v1x, v2x, l1, h1) + "v_wires" (device u32 list of the wires in B) and "n_v"; ValueError when the assignment does not satisfy the circuit"""
+        return self._groth16(self.lib.zp_groth16_prove, self.ctx, blob, dev, delta1_words, set_idx, set_val, r, s)
+
+    def _groth16(self, fn, handle, blob, dev, delta1_words, set_idx, set_val, r, s):
         blob = np.ascontiguousarray(blob, dtype=np.uint64)
         set_idx = np.ascontiguousarray(set_idx, dtype=np.uint64)
         set_val = np.ascontiguousarray(set_val, dtype=np.uint64)
@@ -1068,7 +1130,7 @@ class Prover:
         pub = np.zeros((n_pub, 4), dtype=np.uint64)
         ms = (C.c_double * 8)()
         bad = C.c_int64(-1)
-        rc = self.lib.zp_groth16_prove(self.ctx, blob.ctypes.data, blob.size, _ptr(dev["u1x"]), _ptr(dev["v_wires"]), int(dev["n_v"]), _ptr(dev["v1x"]),
+        rc = fn(handle, blob.ctypes.data, blob.size, _ptr(dev["u1x"]), _ptr(dev["v_wires"]), int(dev["n_v"]), _ptr(dev["v1x"]),
                                        _ptr(dev["v2x"]), _ptr(dev["l1"]), _ptr(dev["h1"]),
                                        d1.ctypes.data, set_idx.ctypes.data, set_val.ctypes.data, set_idx.size, rw.ctypes.data, sw.ctypes.data, a.ctypes.data,
                                        b.ctypes.data, c.ctypes.data, pub.ctypes.data, ms, C.byref(bad))

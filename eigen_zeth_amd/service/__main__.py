@@ -32,14 +32,24 @@ def main():
                     help="GenFinalProof's STARK as ONE proof over this many ranks of the process (a power of two; zp_stark_prove_sharded_bn128 on an in-process "
                          "communicator), rank r on the r-th id of --final-devices (default: all on --device, which only rehearses the path)")
     ap.add_argument("--final-devices", default=None, help="comma-separated GPU ids of the ranks of --final-ranks")
+    ap.add_argument("--wrap-ranks", type=int, default=1,
+                    help="GenFinalProof's Groth16 wrap as ONE proof over this many ranks of the process (a power of two; zp_groth16_prove_sharded on an "
+                         "in-process communicator, each rank holding its slice of the key), rank r on the r-th id of --wrap-devices (default: all on --device)")
+    ap.add_argument("--wrap-devices", default=None, help="comma-separated GPU ids of the ranks of --wrap-ranks")
     a = ap.parse_args()
     if a.final_ranks < 1 or a.final_ranks > 64 or a.final_ranks & (a.final_ranks - 1):
         ap.error("--final-ranks must be a power of two between 1 and 64")
     if a.final_devices and len(a.final_devices.split(",")) != a.final_ranks:
         ap.error("--final-devices must name one GPU id per rank of --final-ranks")
+    if a.wrap_ranks < 1 or a.wrap_ranks > 64 or a.wrap_ranks & (a.wrap_ranks - 1):
+        ap.error("--wrap-ranks must be a power of two between 1 and 64")
+    if a.wrap_devices and len(a.wrap_devices.split(",")) != a.wrap_ranks:
+        ap.error("--wrap-devices must name one GPU id per rank of --wrap-ranks")
     server, port = serve(a.port, a.host, a.state_dir, EngineConfig(a.air, a.logn, logb=a.logb, chunks_per_block=a.chunks_per_block, l2_addr=a.l2_addr, n_queries=a.n_queries, pow_bits=a.pow_bits,
                                                                agg_queries=a.agg_queries, final_queries=a.final_queries, aggregate_all_chunks=a.aggregate_all_chunks, final_ranks=a.final_ranks,
-                                                               final_devices=[int(x) for x in a.final_devices.split(',')] if a.final_devices else None), a.device,
+                                                               final_devices=[int(x) for x in a.final_devices.split(',')] if a.final_devices else None,
+                                                               wrap_ranks=a.wrap_ranks, wrap_devices=[int(x) for x in a.wrap_devices.split(',')] if a.wrap_devices else None),
+                         a.device,
                          metrics_port=a.metrics_port,
                          devices=[int(x) for x in a.devices.split(',')] if a.devices else None, prewarm=not a.no_prewarm)
     print("prover.v1.ProverService listening on %s:%d  (chunk STARKs: %d queries x blow-up %d + %d grinding bits = %d bits conjectured)"

@@ -75,7 +75,7 @@ class EngineConfig:
                  witness_threads=8, prover_streams=8, pow_bits=20,
                  final_air="chunk16", final_logn=10, final_logb=2, final_queries=50, native_prover=True,
                  agg_queries=50, agg_pow_bits=0, aggregate_all_chunks=False, groth16_seed=None, witness="device",
-                 speculate_recursion=False, verify_before_wrap=True, final_ranks=1, final_devices=None):
+                 speculate_recursion=False, verify_before_wrap=True, final_ranks=1, final_devices=None, wrap_ranks=1, wrap_devices=None):
         self.air, self.logn, self.logb = air, logn, logb
         # GenFinalProof: check natively, before the final STARK and the wrap are made, what no query of the aggregation STARK covers (its
         # constraint identity at the out-of-domain point, its final layer, its grinding: stark/verifier.py).  Off only for timing experiments.
@@ -119,6 +119,14 @@ class EngineConfig:
         if final_devices is not None and (len(final_devices) != final_ranks or any(not isinstance(d, int) or d < 0 for d in final_devices)):
             raise ValueError("final_devices must name one GPU id per rank of final_ranks (%d), not %r" % (final_ranks, final_devices))
         self.final_ranks, self.final_devices = final_ranks, final_devices
+        # wrap_ranks > 1 (a power of two): the Groth16 wrap is ONE proof over that many ranks of this process -- zp_groth16_prove_sharded on an
+        # in-process communicator, rank r on wrap_devices[r] (default: all on the engine's GPU, which only rehearses the path) holding its slice of
+        # the key's points; witness and QAP replicated, the five MSMs split by points.  Same proof.json as with one rank.
+        if not isinstance(wrap_ranks, int) or isinstance(wrap_ranks, bool) or not 1 <= wrap_ranks <= 64 or wrap_ranks & (wrap_ranks - 1):
+            raise ValueError("wrap_ranks must be a power of two between 1 and 64, not %r" % (wrap_ranks,))
+        if wrap_devices is not None and (len(wrap_devices) != wrap_ranks or any(not isinstance(d, int) or d < 0 for d in wrap_devices)):
+            raise ValueError("wrap_devices must name one GPU id per rank of wrap_ranks (%d), not %r" % (wrap_ranks, wrap_devices))
+        self.wrap_ranks, self.wrap_devices = wrap_ranks, wrap_devices
         self.prover_streams = prover_streams   # chunk proofs in flight on one GPU (each on its own ctx / stream); 8 measured best (profiles/r2_streams_sweep.txt)
         # the final STARK (BN128-hash mode, no grinding: 50 queries x blow-up 4 = 100 bits conjectured)
         self.final_air, self.final_logn, self.final_logb, self.final_queries = final_air, final_logn, final_logb, final_queries
@@ -678,10 +686,15 @@ class Engine:
         if k not in self._g16:
             wc = WC.wrap_circuit(layout, st)
             key = groth16.Key(wc.blob)
-            if hasattr(self.be, "p"):          # the GPU backend: the key's points are made now and stay in HBM
+            if self._wrap_sharded():           # the key's points are made now, each rank's slice on its own device, and stay there
+                self.be.groth16_sharded_key(key, self.cfg.wrap_ranks, self.cfg.wrap_devices)
+            elif hasattr(self.be, "p"):          # the GPU backend: the key's points are made now and stay in HBM
                 key.load_points(self.be)
             self._g16[k] = (wc, key)
         return self._g16[k]
+
+    def _wrap_sharded(self):
+        return self.cfg.wrap_ranks > 1 and hasattr(self.be, "groth16_sharded")
 
     def groth16_keys(self, n_proofs=2, logn=None):
         """make (or fetch) the wrap circuit and key for the usual request -- two chunk proofs of the configured size"""
@@ -884,11 +897,16 @@ class Engine:
             det = lambda tag: int(hashlib.sha256(("%s|%s|%s|%s" % (self.cfg.groth16_seed, fs_digest, aggregator_addr or "", tag)).encode()).hexdigest(), 16) % bn254.R or 1
             rnd = (det("r"), det("s"))
         t0 = time.perf_counter()
-        proof, pub, g16_ms = groth16.prove(key, set_idx, set_val, self.be, rnd)      # ValueError: the openings do not hash to the roots -> no witness
+        if self._wrap_sharded():         # the same proof over cfg.wrap_ranks ranks (zp_groth16_prove_sharded)
+            proof, pub, g16_ms = self.be.groth16_sharded(key, set_idx, set_val, rnd, self.cfg.wrap_ranks, self.cfg.wrap_devices)
+        else:
+            proof, pub, g16_ms = groth16.prove(key, set_idx, set_val, self.be, rnd)      # ValueError: the openings do not hash to the roots -> no witness
         self.stage_timings["final/" + batch_id] = {"final_stark(bn128)": t_fs, "wrap-assign": t_wit, "groth16": time.perf_counter() - t0,
                                                    "groth16/witness": g16_ms[0] / 1e3, "groth16/qap": g16_ms[1] / 1e3, "groth16/msm": g16_ms[2] / 1e3,
                                                    **({"groth16/msm/" + k: v / 1e3 for k, v in zip(("A", "B1", "B2", "l", "h"), g16_ms[3:8])} if len(g16_ms) >= 8 else {}),
                                                    **{"final/" + k: v for k, v in tmf.items()}}
+        if self._wrap_sharded():
+            self.stage_timings["final/" + batch_id]["groth16/ranks"] = self.cfg.wrap_ranks
         n_v = key.dev["v_wires"][1] if key.dev else int((key.v != 0).any(axis=1).sum())      # wires with a non-zero column in B
         self.wrap_info = {"constraints": wc.c.n_constraints, "qap_domain_log2": wc.c.logm(), "wires": wc.c.n_wires,
                           "msm_points": {"A (G1)": wc.c.n_wires + 2, "B (G1)": n_v + 2, "B (G2)": n_v + 2, "C: l (G1)": wc.c.n_wires,

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import hashlib
 import json
+import threading
 
 import numpy as np
 
@@ -68,16 +69,10 @@ class Key:
             return self.dev
         p, t = be.p, self.toxic
         g1, g2 = _g1_words(bn254.G1), _g2_words(bn254.G2)
-        tail_a = native.fr_words([t["alpha"], t["delta"]])
-        tail_b = native.fr_words([t["beta"], t["delta"]])
-        l_priv = self.l.copy()
-        l_priv[:1 + self.n_pub] = 0                       # the public part of C is the verifier's (IC), not the prover's
+        scalars, v_wires = self._point_scalars()
         dev = {}
-        # a third of the gadget's wires (the x^4 of every S-box) never stand in B: the B side of the key holds the other wires only
-        v_wires = np.flatnonzero((self.v != 0).any(axis=1)).astype(np.uint32)
-        vs = np.concatenate([self.v[v_wires], tail_b])
-        for name, sc, is_g2 in (("u1x", np.concatenate([self.u, tail_a]), False), ("v1x", vs, False), ("v2x", vs, True), ("l1", l_priv, False),
-                                ("h1", self.h, False)):
+        for name, sc in scalars.items():
+            is_g2 = name == "v2x"
             pts = p.fixed_base_mul(g2 if is_g2 else g1, sc, g2=is_g2)
             d = p.alloc(pts.size // 2)
             p._chk(p.lib.zp_h2d(p.ctx, d.ptr, pts.ctypes.data, pts.nbytes))
@@ -88,6 +83,75 @@ class Key:
         dev["delta1"] = bn254.g1_mul(t["delta"])
         self.dev = dev
         return dev
+
+    def _point_scalars(self):
+        """the scalars of the five point arrays (u1x, v1x, v2x, l1, h1, in that order) and the wires in B"""
+        t = self.toxic
+        l_priv = self.l.copy()
+        l_priv[:1 + self.n_pub] = 0                       # the public part of C is the verifier's (IC), not the prover's
+        # a third of the gadget's wires (the x^4 of every S-box) never stand in B: the B side of the key holds the other wires only
+        v_wires = np.flatnonzero((self.v != 0).any(axis=1)).astype(np.uint32)
+        vs = np.concatenate([self.v[v_wires], native.fr_words([t["beta"], t["delta"]])])
+        return {"u1x": np.concatenate([self.u, native.fr_words([t["alpha"], t["delta"]])]), "v1x": vs, "v2x": vs, "l1": l_priv, "h1": self.h}, v_wires
+
+    def load_slices(self, provers):
+        """rank r's slice of every point array (the rule of the sharded entry points: ceil(n / world) per rank, the tail ranks fewer or none),
+        made by zp_fixed_base_mul_bn254(_g2) on provers[r]'s device and left there -- key generation splits over the ranks too, and each
+        rank holds 1 / world of the key.  Cached per key for this list of provers (as load_points caches the whole key)."""
+        cached = getattr(self, "_slices", None)
+        if cached is not None and len(cached[0]) == len(provers) and all(a is b for a, b in zip(cached[0], provers)):
+            return cached[1]
+        if cached is not None:
+            for sl in cached[1]:
+                for v in sl.values():
+                    if isinstance(v, native.DeviceBuffer):
+                        v.free()
+        self._slices = None
+        world = len(provers)
+        g1, g2 = _g1_words(bn254.G1), _g2_words(bn254.G2)
+        scalars, v_wires = self._point_scalars()
+        n_v = int(v_wires.size)
+
+        def cut(n, r):
+            k = -(-n // world)
+            first = min(r * k, n)
+            return first, min(k, n - first)
+
+        def upload(q, arr):
+            d = q.alloc((arr.nbytes + 7) // 8)
+            q._chk(q.lib.zp_h2d(q.ctx, d.ptr, arr.ctypes.data, arr.nbytes))
+            return d
+
+        def build(r, q):
+            sl = {"n_v": n_v}
+            for name, sc in scalars.items():
+                first, count = cut(sc.shape[0], r)
+                sl[name] = upload(q, q.fixed_base_mul(g2 if name == "v2x" else g1, sc[first:first + count], g2=name == "v2x")) if count else None
+            first, count = cut(n_v + 2, r)
+            vw = v_wires[first:min(first + count, n_v)]
+            sl["v_wires"] = upload(q, np.ascontiguousarray(vw)) if vw.size else None
+            return sl
+
+        out, errs = [None] * world, [None] * world
+
+        def body(r):
+            try:
+                out[r] = build(r, provers[r])
+            except BaseException as e:      # noqa: raised below
+                errs[r] = e
+        ts = [threading.Thread(target=body, args=(r,), name="key-slice-%d" % r) for r in range(world)]
+        for th in ts:
+            th.start()
+        for th in ts:
+            th.join()
+        if any(e is not None for e in errs):
+            for sl in out:
+                for v in (sl or {}).values():
+                    if isinstance(v, native.DeviceBuffer):
+                        v.free()
+            raise next(e for e in errs if e is not None)
+        self._slices = (list(provers), out)
+        return out
 
 
 def _g1_point(w):
@@ -114,6 +178,19 @@ def prove_on_gpu(key, set_idx, set_val, be, rand):
     handles = {k: v[0] for k, v in dev.items() if k != "delta1"}
     handles["n_v"] = dev["v_wires"][1]
     a, b, c, pub, ms = be.p.groth16_prove(key.blob, handles, _g1_words(dev["delta1"]), set_idx, set_val, *rand)
+    return {"pi_a": _g1_point(a), "pi_b": _g2_point(b), "pi_c": _g1_point(c)}, pub, ms
+
+
+def prove_sharded(key, set_idx, set_val, provers, rand):
+    """zp_groth16_prove_sharded over len(provers) thread-ranks (one Prover each, rank r = provers[r]) over the key's slices (Key.load_slices):
+    the proof prove_on_gpu makes, byte for byte (every rank's result is compared); ms as there, rank 0's clocks"""
+    slices = key.load_slices(provers)
+    if getattr(key, "_delta1", None) is None:
+        key._delta1 = _g1_words(bn254.g1_mul(key.toxic["delta"]))
+    d1 = key._delta1
+    res = native.over_ranks(provers, lambda r, q, c: c.groth16_prove_sharded(key.blob, slices[r], d1, set_idx, set_val, *rand))
+    a, b, c, pub, ms = res[0]
+    assert all((x[0] == a).all() and (x[1] == b).all() and (x[2] == c).all() and x[3] == pub for x in res)
     return {"pi_a": _g1_point(a), "pi_b": _g2_point(b), "pi_c": _g1_point(c)}, pub, ms
 
 

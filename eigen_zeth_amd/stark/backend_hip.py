@@ -225,21 +225,7 @@ class HipBackend:
         devs = list(devices) if devices else [self.p_device] * ranks
         assert len(devs) == ranks
         W, N = air.width, 1 << params.logn
-        with self._up_lock:
-            provers = getattr(self, "_rank_provers", None)
-            if provers is None or [d for d, _ in provers] != devs:
-                for _, q in provers or []:
-                    q.close()
-                provers = []
-                for d in devs:
-                    q = native.Prover(d)
-                    for kind, n in ((native.ZP_CONST_POSEIDON_RC, 360), (native.ZP_CONST_POSEIDON_MDS, 144), (native.ZP_CONST_ROOT32, 1),
-                                    (native.ZP_CONST_COSET_SHIFT, 1)):
-                        q.set_constants(kind, self.p.get_constants(kind, n))         # this backend's field / hash configuration
-                    if bn:
-                        q.install_poseidon_bn254(17)
-                    provers.append((d, q))
-                self._rank_provers = provers
+        provers = self._rank_provers_for(devs)
         dev_trace = isinstance(trace, native.DeviceBuffer)
         if dev_trace:
             self.p.sync()                                   # the witness builder's last kernels, before other ctxs read the buffer
@@ -298,6 +284,25 @@ class HipBackend:
             raise (real or bad)[0]
         assert all(t == texts[0] for t in texts)
         return texts[0], rec[0]
+
+    def _rank_provers_for(self, devs):
+        """[(device, Prover)] of the thread-ranks, rank r on devs[r]: kept between calls (self._rank_provers), made again when the devices change"""
+        with self._up_lock:
+            provers = getattr(self, "_rank_provers", None)
+            if provers is None or [d for d, _ in provers] != devs:
+                for _, q in provers or []:
+                    q.close()
+                provers = []
+                for d in devs:
+                    q = native.Prover(d)
+                    for kind, n in ((native.ZP_CONST_POSEIDON_RC, 360), (native.ZP_CONST_POSEIDON_MDS, 144), (native.ZP_CONST_ROOT32, 1),
+                                    (native.ZP_CONST_COSET_SHIFT, 1)):
+                        q.set_constants(kind, self.p.get_constants(kind, n))         # this backend's field / hash configuration
+                    if self.hash_mode == "bn128":
+                        q.install_poseidon_bn254(17)
+                    provers.append((d, q))
+                self._rank_provers = provers
+        return provers
 
     def poseidon_sponge(self, state, blocks, extra):
         return self.p.poseidon_sponge(state, blocks, extra)
@@ -530,6 +535,20 @@ class HipBackend:
         """the Groth16 wrap's prover (service/groth16.py: prove): witness completion, QAP quotient and the five MSMs behind zp_groth16_prove"""
         from ..service import groth16 as G16
         return G16.prove_on_gpu(key, set_idx, set_val, self, rand)
+
+    def groth16_sharded(self, key, set_idx, set_val, rand, ranks, devices=None):
+        """the same proof over `ranks` thread-ranks of this process (zp_groth16_prove_sharded on an in-process communicator): rank r on devices[r]
+        (default: every rank on this backend's GPU, a rehearsal) holds only its slice of the key's points, made there (Key.load_slices)"""
+        from ..service import groth16 as G16
+        assert ranks >= 1 and (ranks & (ranks - 1)) == 0
+        devs = list(devices) if devices else [self.p_device] * ranks
+        assert len(devs) == ranks
+        return G16.prove_sharded(key, set_idx, set_val, [q for _, q in self._rank_provers_for(devs)], rand)
+
+    def groth16_sharded_key(self, key, ranks, devices=None):
+        """the key's points for groth16_sharded: each rank's slice made on its device now (key generation, not proving)"""
+        devs = list(devices) if devices else [self.p_device] * ranks
+        return key.load_slices([q for _, q in self._rank_provers_for(devs)])
 
     def msm_g1(self, points, scalars):
         return self.p.msm_bn254([p if p is not None else (0, 0) for p in points], [int(s) for s in scalars])

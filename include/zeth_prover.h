@@ -494,6 +494,21 @@ int32_t zp_sha256(const uint8_t *data, size_t len, uint8_t *out32);
  *                                 which needs one row per leaf: more than 28 trace columns (the 47-column verifier AIR); the
  *                                 narrow stage-2 and quotient trees, whose leaves hold rows of every shard, are built replicated
  *                                 from columns every rank holds whole anyway.  zp_set_poseidon_bn254(ctx, 17, ..) on every ctx.
+ *   zp_msm_bn254_sharded / _g2_sharded: ONE multi-scalar multiplication over the ranks.  Every rank passes n_total and ITS slice of
+ *                                 the points and the scalars: with k = ceil(n_total / world), rank r owns indices [r k, min((r+1) k,
+ *                                 n_total)) (the tail ranks fewer, or none: an empty slice adds infinity and may pass NULL).  Each
+ *                                 rank runs Pippenger on its slice, the partial sums travel as affine words in one all-gather, and
+ *                                 every rank adds them in rank order: h_out is, word for word, what zp_msm_bn254 / _g2 returns for
+ *                                 the whole input on one ctx, on every rank.
+ *   zp_groth16_prove_sharded    : zp_groth16_prove over the ranks (the Groth16 wrap of GenFinalProof).  Arguments as zp_groth16_prove,
+ *                                 but every KEY array is this rank's slice by the rule above over the array the unsharded call reads:
+ *                                 d_u1x of n_wires + 2 points, d_v1x / d_v2x of n_v + 2 (d_v_wires: the same slice cut at n_v; n_v
+ *                                 stays the total), d_l1 of n_wires, d_h1 of 2^logm - 1.  Witness completion, A w, B w, C w and the QAP
+ *                                 quotient run on every rank (replicated, no exchange); each rank's five MSMs cover its slices, ONE
+ *                                 all-gather carries the five partial sums (96 words per rank), the pi_c tail runs replicated.  Every
+ *                                 rank returns out_a / out_b / out_c / out_pub byte-identical to zp_groth16_prove on the whole key with
+ *                                 the same (h_r, h_s).  -20 / -21 (*bad) come from the replicated witness: every rank returns them, and
+ *                                 the communicator stays usable.
  * FAILURE: no rank waits for ever.  A rank whose step fails inside a collective or a sharded entry point takes the communicator down
  * before it returns its own error; its peers return ZP_ERR_COMM (in-process group: at once, woken from the barrier; RCCL: when their
  * watchdog expires and aborts the communicator, ncclCommAbort).  A host whose rank fails BETWEEN collectives calls zp_comm_abort.  A
@@ -537,6 +552,12 @@ int32_t zp_exchange_columns_to_rows(zp_comm *comm, const uint64_t *d_cols, size_
  * inverse != 0: inverse transform incl. 1/N.  Bit-identical to zp_ntt / zp_intt of the whole column on one GPU. */
 int32_t zp_ntt_sharded(zp_comm *comm, uint64_t *d_data, uint64_t *d_tmp, int32_t logn, int32_t inverse, int32_t natural_output);
 int32_t zp_merkle_commit_sharded(zp_comm *comm, const uint64_t *d_cols, size_t M, int32_t Wl, uint64_t *d_tree_local, uint64_t *h_root4);
+int32_t zp_msm_bn254_sharded(zp_comm *comm, const uint32_t *d_points_local, const uint32_t *d_scalars_local, size_t n_total, uint32_t *h_out);
+int32_t zp_msm_bn254_g2_sharded(zp_comm *comm, const uint32_t *d_points_local, const uint32_t *d_scalars_local, size_t n_total, uint32_t *h_out);
+int32_t zp_groth16_prove_sharded(zp_comm *comm, const uint64_t *circ, size_t words, const uint32_t *d_u1x, const uint32_t *d_v_wires, size_t n_v,
+                                 const uint32_t *d_v1x, const uint32_t *d_v2x, const uint32_t *d_l1, const uint32_t *d_h1, const uint32_t *h_delta1,
+                                 const uint64_t *set_idx, const uint64_t *set_val, size_t n_set, const uint64_t *h_r, const uint64_t *h_s, uint32_t *out_a,
+                                 uint32_t *out_b, uint32_t *out_c, uint64_t *out_pub, double *h_ms, int64_t *bad);
 
 /* ---- N6: BN254 (alt_bn128) G1 multi-scalar multiplication ---------------------------------------
  * d_points u32[n][16]: affine x (8 little-endian 32-bit limbs) then y, standard (non-Montgomery)
