@@ -191,20 +191,31 @@ struct Trees {
     }
 };
 
-// the binary openings record of a BN128-mode proof ("PZOPEN02": zp_stark_openings documents the layout), kept on the ctx.  trees: trace,
-// quotient, [stage 2], FRI layers
-struct TreeOut { size_t width, rows; const u64 *root; const std::vector<u64> *vals, *paths; size_t pw; };
+// what a prover opened in one tree at the query indices: per query `width` values (one leaf) and `pw` path words, the tree over `rows` leaves
+struct Opened {
+    std::vector<u64> vals, paths;
+    size_t width = 0, rows = 0, pw = 0;
+    void shape(size_t nq, size_t width_, size_t rows_, size_t pw_) {
+        width = width_; rows = rows_; pw = pw_;
+        vals.resize(nq * width);
+        paths.resize(nq * pw);
+    }
+};
+
+// the binary openings record of a BN128-mode proof (zp_stark_openings documents the layout), kept on the ctx.  trees: trace, quotient,
+// [stage 2], FRI layers
+struct TreeOut { const u64 *root; const Opened *o; };
 void openings_record(zp_ctx *ctx, const Transcript &tr, const std::vector<u64> &qidx, int logm, const std::vector<TreeOut> &trees) {
     std::vector<u64> &rec = ctx->last_openings;
     rec.clear();
     rec.insert(rec.end(), {0x33304e45504f5a50ULL /* "PZOPEN03" */, (u64)qidx.size(), (u64)trees.size(), (u64)logm});
-    for (const TreeOut &t : trees) rec.insert(rec.end(), {(u64)t.width, (u64)t.rows, (u64)Trees::levels16(t.rows)});
+    for (const TreeOut &t : trees) rec.insert(rec.end(), {(u64)t.o->width, (u64)t.o->rows, (u64)Trees::levels16(t.o->rows)});
     for (const TreeOut &t : trees) rec.insert(rec.end(), t.root, t.root + 4);
     for (size_t i = 0; i < qidx.size(); i++) {
         rec.push_back(qidx[i]);
         for (const TreeOut &t : trees) {
-            rec.insert(rec.end(), t.vals->begin() + i * t.width, t.vals->begin() + (i + 1) * t.width);
-            rec.insert(rec.end(), t.paths->begin() + i * t.pw, t.paths->begin() + (i + 1) * t.pw);
+            rec.insert(rec.end(), t.o->vals.begin() + i * t.o->width, t.o->vals.begin() + (i + 1) * t.o->width);
+            rec.insert(rec.end(), t.o->paths.begin() + i * t.o->pw, t.o->paths.begin() + (i + 1) * t.o->pw);
         }
     }
     // the transcript (round 5: the wrap circuit hashes it too): every absorbed block, then the rate elements the indices were read from
@@ -213,7 +224,7 @@ void openings_record(zp_ctx *ctx, const Transcript &tr, const std::vector<u64> &
     rec.insert(rec.end(), tr.log_blocks.begin(), tr.log_blocks.end());
     rec.insert(rec.end(), tr.last_rates.begin(), tr.last_rates.end());
     rec.insert(rec.end(), tr.log_caps.begin(), tr.log_caps.end());         // one per permutation: n_blocks + (n_rates - 1)
-    rec.push_back((u64)(tr.log_chal.size() / 4));                           // "PZOPEN03": the rate element behind every challenge, in squeeze order
+    rec.push_back((u64)(tr.log_chal.size() / 4));                           // the rate element behind every challenge, in squeeze order
     rec.insert(rec.end(), tr.log_chal.begin(), tr.log_chal.end());
 }
 
@@ -359,86 +370,157 @@ void j_opening(std::string &s, const u64 *vals, size_t W, const u64 *path, size_
         if (rc_ != ZP_OK) return rc_;                                   \
     } while (0)
 
-}  // namespace
+// ======================================================================================================================
+// The steps of the protocol that the single-device prover (prove_impl) and the sharded one (prove_sharded_impl) share: what defines the
+// transcript and the proof text exists once.  A step works on the ctx stream with the DevBufs of its caller and never touches a communicator.
 
-int32_t zpi_pool_alloc(zp_ctx *ctx, size_t bytes, void **out) {
-    DevBufs b(ctx);
-    u64 *p = nullptr;
-    const int32_t rc = b.alloc((bytes + 7) / 8, &p);
-    if (rc != ZP_OK) return rc;
-    b.forget(p);
-    *out = p;
-    return ZP_OK;
-}
-void zpi_pool_release(zp_ctx *ctx, void *p, size_t bytes) {
-    DevBufs b(ctx);
-    b.give_back(p, ((bytes + 7) / 8 ? (bytes + 7) / 8 : 1) * 8);
-}
-void zpi_sha256(const uint8_t *data, size_t len, uint8_t *out32) { Sha256::digest(data, len, out32); }
+// the arguments of the four entry points (pow_bits = 0 in BN128 mode; the sharded ones pass this rank's columns as d_trace)
+struct ProveArgs {
+    const char *air_name;
+    const uint64_t *h_program;
+    size_t program_words;
+    const uint64_t *d_trace;
+    size_t trace_words;
+    const uint64_t *h_pubs;
+    int32_t n_pubs, logn, logb, fri_logf, fri_final_log, n_queries, pow_bits;
+    char **out_json;
+    size_t *out_len;
+};
 
-extern "C" {
-
-int32_t zp_free_buffer(void *p) {
-    free(p);
-    return ZP_OK;
-}
-
-// A generated constraint kernel (AIR plug-in ABI: stark/air.py writes it, `zpair_<air>_quotient` in its own shared library) for the one-call
-// provers of THIS ctx: proofs of the program with this digest evaluate their constraints through it instead of the interpreter -- the same
-// values (whole proofs are byte-identical whichever evaluator ran), 0.7 instead of 1.2 ms at 2^21 x 76.  fn = NULL forgets it.  Programs with
-// sparse periodic fixed columns stay with the interpreter (the generated kernels do not read them), and so do sharded proofs (row windows).
-typedef int (*zp_air_quotient_fn)(void *stream, const u64 *cols, const u64 *fixedc, u64 M, u64 b, const u64 *pub, const u64 *apow, const u64 *zhinv,
-                                  const u64 *xs_lo, const u64 *xs_hi, int lb, u64 shift, u64 wlast, u64 *out);
-static std::string digest_hex64(const uint64_t *h_program, size_t program_words) {
-    uint8_t dg[32];
-    Sha256::digest((const uint8_t *)h_program, program_words * 8, dg);
-    char hex[65];
-    for (int i = 0; i < 32; i++) snprintf(hex + 2 * i, 3, "%02x", dg[i]);
-    return std::string(hex, 64);
-}
-int32_t zp_stark_set_air_kernel(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, void *quotient_fn) {
-    if (!ctx) return ZP_ERR_ARG;
-    ZP_ARG(ctx, h_program && program_words >= 8 && program_words < ((size_t)1 << 28), "null / implausible program");
-    try {
-        const std::string k = digest_hex64(h_program, program_words);
-        if (quotient_fn) ctx->air_kernels[k] = quotient_fn;
-        else ctx->air_kernels.erase(k);
-    } catch (...) {
-        ctx->err = "out of host memory";
-        return ZP_ERR_NOMEM;
+// measurement aid (ZP_PROVE_TRACE=1): host-clock milliseconds since entry at the stage boundaries, the stream drained at each -- where the
+// wall time of a proof goes that the per-entry-point GPU times do not show.  The shared steps mark their own end.
+struct StageClock {
+    zp_ctx *ctx;
+    const char *air_name;
+    int logn;
+    std::chrono::steady_clock::time_point t_entry;
+    void operator()(const char *what) const {
+        static const bool trace_on = getenv("ZP_PROVE_TRACE") != nullptr;
+        if (!trace_on) return;
+        (void)hipStreamSynchronize(ctx->stream);
+        fprintf(stderr, "[prove %s 2^%d] %-28s %8.3f ms\n", air_name, logn, what,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count());
     }
-    return ZP_OK;
-}
-// The ROW-WINDOW form of a generated constraint kernel (`zpair_<air>_quotient_rows` of the same library; round 6): the sharded provers of this ctx
-// (zp_stark_prove_sharded, zp_stark_prove_sharded_bn128: every rank evaluates the quotient on ITS rows) use it instead of the interpreter -- same
-// values, proofs byte-identical either way.  fn = NULL forgets it.
-typedef int (*zp_air_quotient_rows_fn)(void *stream, const u64 *cols, u64 sc, const u64 *fixedc, u64 sf, u64 M, u64 b, u64 row0, u64 nrows, const u64 *pub,
-                                       const u64 *apow, const u64 *zhinv, const u64 *xs_lo, const u64 *xs_hi, int lb, u64 shift, u64 wlast, u64 *out, u64 so);
-int32_t zp_stark_set_air_kernel_rows(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, void *quotient_rows_fn) {
-    if (!ctx) return ZP_ERR_ARG;
-    ZP_ARG(ctx, h_program && program_words >= 8 && program_words < ((size_t)1 << 28), "null / implausible program");
-    try {
-        const std::string k = "rows:" + digest_hex64(h_program, program_words);
-        if (quotient_rows_fn) ctx->air_kernels[k] = quotient_rows_fn;
-        else ctx->air_kernels.erase(k);
-    } catch (...) {
-        ctx->err = "out of host memory";
-        return ZP_ERR_NOMEM;
-    }
-    return ZP_OK;
-}
+};
 
-// SHA-256 of a constraint program blob: the AIR digest.  out32 = the 32 digest bytes (a proof text names the first 8 as 16 hex digits);
-// out_words4 (may be NULL) = the four little-endian 64-bit words, each reduced mod p, that the provers absorb into the transcript.
-int32_t zp_program_digest(const uint64_t *h_program, size_t program_words, uint8_t *out32, uint64_t *out_words4) {
-    if (!h_program || !out32 || program_words == 0) return ZP_ERR_ARG;
-    Sha256::digest((const uint8_t *)h_program, program_words * 8, out32);
-    if (out_words4)
-        for (int i = 0; i < 4; i++) {
-            uint64_t w = 0;
-            for (int b = 7; b >= 0; b--) w = (w << 8) | out32[8 * i + b];
-            out_words4[i] = w % GL_P;
+// ... validated, with what the provers read from the program header and derive from the parameters
+struct Shape : ProveArgs {
+    bool bn;
+    size_t W, W2, Wt, K, Q, n_s2;
+    const u64 *stage2;                 // the stage-2 table of the program: n_s2 x (kind, three trace columns)
+    std::vector<ZpFixedCol> fxc;
+    int logm;
+    size_t N, M;
+    u64 shift, root32, wN;
+    uint8_t dg[32];                    // AIR digest: sha256 of the blob; the first 16 hex digits name it, four little-endian words go into the transcript
+    char dg_hex[17];
+    StageClock mark;
+    // BN128 mode: a leaf holds 2^g rows i, i + M', ... of its tree (the column-major matrix reinterpreted as [width 2^g][M'], like a
+    // FRI layer), g the largest with width 2^g <= 56 values = one width-17 permutation per leaf (stark/prover.py:
+    // bn128_rows_per_leaf_log; Goldilocks mode: g = 0)
+    int rows_per_leaf_log(size_t width) const {
+        int g = 0;
+        if (bn && width)
+            while ((width << (g + 1)) <= 56 && g + 1 <= logm - 4) g++;
+        return g;
+    }
+};
+
+// everything both provers require of their arguments (d_trace and trace_words depend on who holds the columns: the provers check them)
+int32_t make_shape(zp_ctx *ctx, bool bn, const ProveArgs &a, Shape *sh) {
+    ZP_ARG(ctx, a.air_name && a.h_program && a.out_json && a.out_len && (a.h_pubs || a.n_pubs == 0), "null pointer");
+    {   // the name goes into the proof text verbatim: letters, digits, '_', '-', '.' only
+        const size_t nl = strlen(a.air_name);
+        bool ok = nl >= 1 && nl <= 64;
+        for (size_t i = 0; ok && i < nl; i++) {
+            const char ch = a.air_name[i];
+            ok = (ch >= 'a' && ch <= 'z') || (ch >= 'A' && ch <= 'Z') || (ch >= '0' && ch <= '9') || ch == '_' || ch == '-' || ch == '.';
         }
+        ZP_ARG(ctx, ok, "air_name must be 1..64 characters of [A-Za-z0-9_.-]");
+    }
+    const uint64_t *h_program = a.h_program;
+    ZP_ARG(ctx, a.program_words >= 12, "constraint program shorter than its header");
+    static const unsigned char magic[8] = {'Z', 'P', 'A', 'I', 'R', '1', 0, 0};
+    ZP_ARG(ctx, memcmp(h_program, magic, 8) == 0, "not a ZPAIR1 constraint program");
+    const size_t W = h_program[1], W2 = h_program[2], n_pub_prog = h_program[4], n_chal = h_program[5], n_const = h_program[6],
+                 n_instr = h_program[7], K = h_program[8], n_s2 = h_program[10], Q = h_program[11];
+    ZP_ARG(ctx, n_const < (1u << 16) && n_instr < (1u << 24) && n_s2 < (1u << 16) && zpi_program_fixed_table(h_program, a.program_words, &sh->fxc),
+           "constraint program length does not match its header");
+    ZP_ARG(ctx, (size_t)a.n_pubs == n_pub_prog, "number of public inputs does not match the program");
+    ZP_ARG(ctx, W >= 1 && W < 4096 && W2 < 4096 && K >= 1 && Q >= 1 && Q <= 16, "program dimensions out of range");
+    ZP_ARG(ctx, a.logn >= 1 && a.logb >= 1 && a.logn + a.logb <= 30 && a.fri_logf >= 1 && a.fri_logf <= 4 && a.fri_final_log >= 0 &&
+                    a.fri_final_log < a.logn && a.n_queries >= 1 && a.n_queries <= 4096 && a.pow_bits >= 0 && a.pow_bits <= 40,
+           "STARK parameters out of range");
+    ZP_ARG(ctx, Q <= ((size_t)1 << a.logb), "the blow-up must cover the quotient degree");
+    ZP_ARG(ctx, (n_s2 == 0) == (W2 == 0) && (n_s2 == 0 || n_chal == 3), "stage-2 table and widths disagree");
+    for (int i = 0; i < a.n_pubs; i++) ZP_ARG(ctx, a.h_pubs[i] < GL_P, "public input not canonical");
+    const u64 *stage2 = (const u64 *)h_program + 12 + n_const + n_instr;
+    size_t w2sum = 0;
+    for (size_t k = 0; k < n_s2; k++) {
+        const u64 kind = stage2[4 * k];
+        ZP_ARG(ctx, kind == 1 || kind == 2, "unknown stage-2 argument");
+        ZP_ARG(ctx, stage2[4 * k + 1] < W && stage2[4 * k + 2] < W && stage2[4 * k + 3] < W, "stage-2 column out of range");
+        w2sum += kind == 1 ? 3 : 9;
+    }
+    ZP_ARG(ctx, w2sum == W2, "stage-2 width does not match its table");
+
+    static_cast<ProveArgs &>(*sh) = a;
+    sh->bn = bn;
+    sh->W = W; sh->W2 = W2; sh->Wt = W + W2; sh->K = K; sh->Q = Q; sh->n_s2 = n_s2;
+    sh->stage2 = stage2;
+    sh->logm = a.logn + a.logb; sh->N = (size_t)1 << a.logn; sh->M = (size_t)1 << sh->logm;
+    sh->shift = ctx->coset_shift; sh->root32 = ctx->root32; sh->wN = gl_root(sh->root32, a.logn);
+    program_digest(ctx, h_program, a.program_words, sh->dg);
+    for (int i = 0; i < 8; i++) snprintf(sh->dg_hex + 2 * i, 3, "%02x", sh->dg[i]);
+    sh->mark = StageClock{ctx, a.air_name, a.logn, std::chrono::steady_clock::now()};
+    return ZP_OK;
+}
+
+// the first block of the transcript: parameters, domain, AIR digest, public inputs
+int32_t transcript_head(zp_ctx *ctx, const Shape &sh, Transcript &tr, const Trees &T, DevBufs &dev) {
+    std::vector<u64> first = {(u64)sh.logn, (u64)sh.logb, (u64)sh.W, (u64)sh.W2, (u64)sh.fri_logf, (u64)sh.fri_final_log, (u64)sh.n_queries, (u64)sh.pow_bits,
+                              sh.root32, sh.shift};
+    for (int i = 0; i < 4; i++) {
+        u64 wd = 0;
+        for (int k = 0; k < 8; k++) wd |= (u64)sh.dg[8 * i + k] << (8 * k);
+        first.push_back(wd % GL_P);
+    }
+    first.push_back((u64)sh.n_pubs);
+    if (sh.n_pubs <= 64) {
+        for (int i = 0; i < sh.n_pubs; i++) first.push_back(sh.h_pubs[i]);
+        tr.absorb(first);
+        sh.mark("transcript head");
+        return ZP_OK;
+    }
+    // a long public-input vector (a verifier AIR: every root, index and opened value of its inner proofs) enters the transcript
+    // as ONE commitment instead of thousands of dependent sponge permutations: Goldilocks mode: rows of 8 values (zero padded,
+    // row count a power of two >= 2), binary Poseidon tree;  BN128 mode: rows of 48 values, column-major, 16-ary tree
+    // (the sharded prover too, replicated: a few thousand permutations at most)
+    tr.absorb(first);
+    size_t Mp;
+    std::vector<u64> mat;
+    if (!sh.bn) {
+        Mp = 2;
+        while (Mp * 8 < (size_t)sh.n_pubs) Mp <<= 1;
+        mat.assign(Mp * 8, 0);
+        for (int i = 0; i < sh.n_pubs; i++) mat[i] = sh.h_pubs[i];
+    } else {
+        Mp = ((size_t)sh.n_pubs + 47) / 48;
+        mat.assign(Mp * 48, 0);
+        for (int i = 0; i < sh.n_pubs; i++) mat[(size_t)(i % 48) * Mp + (size_t)(i / 48)] = sh.h_pubs[i];
+    }
+    u64 *dmat, *dtree;
+    PV_TRY(dev.alloc(mat.size(), &dmat));
+    PV_TRY(dev.alloc(T.tree_words(Mp), &dtree));
+    PV_TRY(zp_h2d(ctx, dmat, mat.data(), mat.size() * 8));
+    if (!sh.bn) PV_TRY(zp_merkle_commit_rows(ctx, (const uint64_t *)dmat, Mp, 8, (uint64_t *)dtree));
+    else PV_TRY(T.commit(dmat, Mp, 48, dtree));
+    u64 rootp[4];
+    PV_TRY(T.root(dtree, Mp, rootp));
+    dev.release(dmat);
+    dev.release(dtree);
+    tr.absorb_root(rootp);
+    sh.mark("transcript head");
     return ZP_OK;
 }
 
@@ -446,20 +528,19 @@ int32_t zp_program_digest(const uint64_t *h_program, size_t program_words, uint8
 // column), from the ctx's cache: they depend on the domain and the program only; columns that hold public inputs (expected roots / indices /
 // transcript words of a verifier AIR: 37 of 104 at the service's size) are refreshed in place per proof, the others stay.  The buffer belongs
 // to the ctx.  (Both provers: the sharded one cuts its row windows out of it.)
-static int32_t fixed_columns_cached(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const std::vector<ZpFixedCol> &fxc, const uint64_t *h_pubs,
-                             int32_t n_pubs, int32_t logn, int32_t logb, u64 shift, u64 root32, const char *dg_hex, u64 **out) {
+int32_t fixed_columns_cached(zp_ctx *ctx, const Shape &sh, u64 **out) {
     bool has_pub = false;
-    for (const ZpFixedCol &fc : fxc) has_pub |= fc.has_pub;
-    const size_t fwords = zp_fixed_columns_words(h_program, program_words, logn, logb);
+    for (const ZpFixedCol &fc : sh.fxc) has_pub |= fc.has_pub;
+    const size_t fwords = zp_fixed_columns_words(sh.h_program, sh.program_words, sh.logn, sh.logb);
     ZP_ARG(ctx, fwords != 0, "fixed column longer than the trace");
     char key[128];
-    snprintf(key, sizeof key, "%d/%d/%llx/%llx/%s", logn, logb, (unsigned long long)shift, (unsigned long long)root32, fxc.empty() ? "" : dg_hex);
+    snprintf(key, sizeof key, "%d/%d/%llx/%llx/%s", sh.logn, sh.logb, (unsigned long long)sh.shift, (unsigned long long)sh.root32, sh.fxc.empty() ? "" : sh.dg_hex);
     auto it = ctx->prove_fixed.find(key);
     if (it != ctx->prove_fixed.end()) {
         *out = it->second;
         if (has_pub) {
             ZpStage stage_fx(ctx, "fixed_columns");
-            PV_TRY(zpi_fixed_columns_build(ctx, h_program, program_words, h_pubs, n_pubs, logn, logb, shift, (uint64_t *)*out, fwords, true));
+            PV_TRY(zpi_fixed_columns_build(ctx, sh.h_program, sh.program_words, sh.h_pubs, sh.n_pubs, sh.logn, sh.logb, sh.shift, (uint64_t *)*out, fwords, true));
         }
         return ZP_OK;
     }
@@ -473,7 +554,7 @@ static int32_t fixed_columns_cached(zp_ctx *ctx, const uint64_t *h_program, size
     }
     void *pf = nullptr;
     PV_TRY(zp_dev_alloc(ctx, fwords * 8, &pf));
-    const int32_t r = zp_fixed_columns(ctx, h_program, program_words, h_pubs, n_pubs, logn, logb, shift, (uint64_t *)pf, fwords);
+    const int32_t r = zp_fixed_columns(ctx, sh.h_program, sh.program_words, sh.h_pubs, sh.n_pubs, sh.logn, sh.logb, sh.shift, (uint64_t *)pf, fwords);
     if (r != ZP_OK) { (void)zp_dev_free(ctx, pf); return r; }
     ctx->prove_fixed[key] = (u64 *)pf;
     ctx->prove_fixed_bytes += fwords * 8;
@@ -481,124 +562,268 @@ static int32_t fixed_columns_cached(zp_ctx *ctx, const uint64_t *h_program, size
     return ZP_OK;
 }
 
-static int32_t prove_impl(zp_ctx *ctx, bool bn, const char *air_name, const uint64_t *h_program, size_t program_words, const uint64_t *d_trace,
-                          size_t trace_words, const uint64_t *h_pubs, int32_t n_pubs, int32_t logn, int32_t logb, int32_t fri_logf, int32_t fri_final_log,
-                          int32_t n_queries, int32_t pow_bits, char **out_json, size_t *out_len) {
+// Generated constraint kernels (AIR plug-in ABI: stark/air.py writes them) are kept per ctx under the 64 hex digits of the program's
+// digest: form "" = the whole-domain kernel (`zpair_<air>_quotient`), form "rows:" = its row-window form (`zpair_<air>_quotient_rows`)
+typedef int (*zp_air_quotient_fn)(void *stream, const u64 *cols, const u64 *fixedc, u64 M, u64 b, const u64 *pub, const u64 *apow, const u64 *zhinv,
+                                  const u64 *xs_lo, const u64 *xs_hi, int lb, u64 shift, u64 wlast, u64 *out);
+typedef int (*zp_air_quotient_rows_fn)(void *stream, const u64 *cols, u64 sc, const u64 *fixedc, u64 sf, u64 M, u64 b, u64 row0, u64 nrows, const u64 *pub,
+                                       const u64 *apow, const u64 *zhinv, const u64 *xs_lo, const u64 *xs_hi, int lb, u64 shift, u64 wlast, u64 *out, u64 so);
+std::string air_kernel_key(const char *form, const uint8_t dg[32]) {
+    char hex[65];
+    for (int i = 0; i < 32; i++) snprintf(hex + 2 * i, 3, "%02x", dg[i]);
+    return std::string(form) + std::string(hex, 64);
+}
+int32_t set_air_kernel(zp_ctx *ctx, const char *form, const uint64_t *h_program, size_t program_words, void *fn) {
+    if (!ctx) return ZP_ERR_ARG;
+    ZP_ARG(ctx, h_program && program_words >= 8 && program_words < ((size_t)1 << 28), "null / implausible program");
+    try {
+        uint8_t dg[32];
+        Sha256::digest((const uint8_t *)h_program, program_words * 8, dg);
+        const std::string k = air_kernel_key(form, dg);
+        if (fn) ctx->air_kernels[k] = fn;
+        else ctx->air_kernels.erase(k);
+    } catch (...) {
+        ctx->err = "out of host memory";
+        return ZP_ERR_NOMEM;
+    }
+    return ZP_OK;
+}
+
+// the small operands of the constraint quotient: powers of alpha and 1 / Z_H (host; what the interpreter takes), and, when a generated
+// kernel of this program is registered under `form`, that kernel with its operands on the device
+struct QuotientOps {
+    std::vector<u64> apow, zhinv;      // alpha^k, k < K (3 words each); 1 / Z_H on the 2^logb cosets of the trace domain
+    void *plug = nullptr;              // the generated kernel, or none: the interpreter runs.  With a kernel:
+    u64 *d_ops = nullptr;              // ONE device buffer [pub | 0 | apow | zhinv] from the caller's DevBufs (the caller releases it)
+    size_t o_ap = 0, o_zh = 0;         // where apow and zhinv start in it
+    const uint64_t *xlo = nullptr, *xhi = nullptr;      // zp_domain_tables
+    int32_t xlb = 0;
+};
+int32_t quotient_operands(zp_ctx *ctx, const Shape &sh, const char *form, const e3 &alpha, const std::vector<u64> &pubchal, DevBufs &dev, QuotientOps *q) {
+    q->apow.resize(3 * sh.K);
+    e3 cur = e3_make(1, 0, 0);
+    for (size_t k = 0; k < sh.K; k++) { memcpy(&q->apow[3 * k], cur.c, 24); cur = e3_mul(cur, alpha); }
+    q->zhinv.resize((size_t)1 << sh.logb);
+    const u64 sN = gl_pow(sh.shift, (u64)sh.N), wb = gl_root(sh.root32, sh.logb);
+    u64 p = 1;
+    for (size_t j = 0; j < q->zhinv.size(); j++) { q->zhinv[j] = gl_inv(gl_sub(gl_mul(sN, p), 1)); p = gl_mul(p, wb); }
+    if (ctx->air_kernels.empty()) return ZP_OK;
+    // (the digest of the Shape -- through the per-ctx cache, a memcmp for a program seen before -- not a second SHA-256 of the blob: for a
+    // verifier AIR's 7 MB that second hash was 16 ms of every recursion STARK, round 5.  Since that round the generated kernels read the
+    // sparse periodic fixed columns too -- one extended period each, zp_fixed_columns' layout)
+    auto it = ctx->air_kernels.find(air_kernel_key(form, sh.dg));
+    if (it == ctx->air_kernels.end()) return ZP_OK;
+    q->plug = it->second;
+    std::vector<u64> ops(pubchal);
+    ops.push_back(0);
+    q->o_ap = ops.size();
+    ops.insert(ops.end(), q->apow.begin(), q->apow.end());
+    q->o_zh = ops.size();
+    ops.insert(ops.end(), q->zhinv.begin(), q->zhinv.end());
+    PV_TRY(dev.alloc(ops.size(), &q->d_ops));
+    PV_TRY(zp_h2d(ctx, q->d_ops, ops.data(), ops.size() * 8));
+    return zp_domain_tables(ctx, sh.logm, &q->xlo, &q->xhi, &q->xlb);
+}
+
+// Q > 1: q(x) = sum_j (x / shift)^(jN) qt_j(x): the pieces are slices of the coefficient vector of q(shift X) (c_i shift^i); their LDEs
+// (*pext: u64[3 Q][M]) get committed.  (Q == 1: the quotient is committed as it stands and never leaves the evaluation form.)  Ends with
+// the forward transform ENQUEUED: the caller synchronises before it releases *dqcoef and *pad, its own way
+int32_t split_quotient(zp_ctx *ctx, const Shape &sh, DevBufs &dev, const u64 *dq, u64 **dqcoef, u64 **pad, u64 **pext) {
+    const size_t Q = sh.Q, N = sh.N, M = sh.M;
+    PV_TRY(dev.alloc(3 * M, dqcoef));
+    PV_TRY(zp_intt(ctx, (const uint64_t *)dq, (uint64_t *)*dqcoef, sh.logm, 3));
+    PV_TRY(dev.alloc(3 * Q * M, pad));
+    PV_TRY(zp_dev_zero(ctx, *pad, 3 * Q * M * 8));
+    for (size_t j = 0; j < Q; j++)
+        for (int c = 0; c < 3; c++) PV_TRY(zp_d2d(ctx, *pad + (3 * j + c) * M, *dqcoef + c * M + j * N, N * 8));
+    PV_TRY(dev.alloc(3 * Q * M, pext));
+    return zp_ntt(ctx, (const uint64_t *)*pad, (uint64_t *)*pext, sh.logm, (int32_t)(3 * Q));
+}
+
+// FRI over the DEEP quotient df (u64[3][M], whole on the device): commit a layer, fold it with the challenge its root yields, until the
+// final layer, which enters the transcript in the clear
+struct FriLayer { int lg, f; u64 *tree, *data; u64 root[4]; };
+struct Fri {
+    std::vector<FriLayer> layers;
+    std::vector<u64> final_l;          // u64[3][2^final_log]
+    int final_log;
+};
+int32_t fri_commit(zp_ctx *ctx, const Shape &sh, Transcript &tr, const Trees &T, DevBufs &dev, u64 *df, Fri *fri) {
+    const int stop = sh.fri_final_log + sh.logb;
+    int cur = sh.logm;
+    u64 cur_shift = sh.shift;
+    u64 *dlayer = df;
+    while (cur > stop) {
+        const int f = sh.fri_logf < cur - stop ? sh.fri_logf : cur - stop;
+        FriLayer L;
+        L.lg = cur; L.f = f; L.data = dlayer;
+        const size_t m = (size_t)1 << (cur - f);
+        PV_TRY(dev.alloc(T.tree_words(m), &L.tree));
+        PV_TRY(T.commit(dlayer, m, 3 << f, L.tree));   // leaf = the 2^f * 3 values folded together
+        PV_TRY(T.root(L.tree, m, L.root));
+        tr.absorb_root(L.root);
+        const e3 beta = tr.challenge();
+        PV_TRY(tr.rc);
+        u64 *next;
+        PV_TRY(dev.alloc((size_t)3 << (cur - f), &next));
+        PV_TRY(zp_fri_fold(ctx, (const uint64_t *)dlayer, (uint64_t *)next, cur, f, (const uint64_t *)beta.c, cur_shift));
+        fri->layers.push_back(L);
+        dlayer = next;
+        cur_shift = gl_pow(cur_shift, (u64)1 << f);
+        cur -= f;
+    }
+    fri->final_log = cur;
+    fri->final_l.resize((size_t)3 << cur);
+    PV_TRY(zp_d2h(ctx, fri->final_l.data(), dlayer, fri->final_l.size() * 8));
+    for (int c = 0; c < 3; c++) tr.absorb(&fri->final_l[(size_t)c << cur], (size_t)1 << cur);   // plane by plane (BN128 mode pads every call)
+    sh.mark("DEEP + FRI");
+    return ZP_OK;
+}
+
+// proof of work, then the query indices (rows of the 2^logm-point domain)
+int32_t grind_and_indices(zp_ctx *ctx, const Shape &sh, Transcript &tr, u64 *nonce, std::vector<u64> *qidx) {
+    *nonce = 0;
+    if (sh.pow_bits) {
+        const std::vector<u64> seed = tr.squeeze(4);
+        PV_TRY(tr.rc);
+        PV_TRY(zp_pow_grind(ctx, (const uint64_t *)seed.data(), sh.pow_bits, (uint64_t *)nonce));
+        tr.absorb(nonce, 1);
+    }
+    *qidx = tr.squeeze((size_t)sh.n_queries);
+    PV_TRY(tr.rc);
+    for (u64 &v : *qidx) v &= (sh.M - 1);
+    return ZP_OK;
+}
+
+// open a tree that is whole on this device at the queries: leaf i of `rows` leaves = row i of mat u64[width][rows]
+int32_t open_tree(zp_ctx *ctx, const Trees &T, const u64 *mat, const u64 *tree, size_t rows, size_t width, const std::vector<u64> &qidx, Opened *o) {
+    std::vector<u64> idx = qidx;
+    for (u64 &v : idx) v &= (rows - 1);
+    o->shape(qidx.size(), width, rows, T.path_words(rows));
+    PV_TRY(zp_gather_rows(ctx, (const uint64_t *)mat, rows, (int32_t)width, (const uint64_t *)idx.data(), (int32_t)qidx.size(), (uint64_t *)o->vals.data()));
+    return T.open(tree, rows, idx.data(), (int)qidx.size(), o->paths.data());
+}
+int32_t fri_open(zp_ctx *ctx, const Shape &sh, const Trees &T, const Fri &fri, const std::vector<u64> &qidx, std::vector<Opened> *fo) {
+    fo->resize(fri.layers.size());
+    for (size_t li = 0; li < fri.layers.size(); li++) {
+        const FriLayer &L = fri.layers[li];
+        PV_TRY(open_tree(ctx, T, L.data, L.tree, (size_t)1 << (L.lg - L.f), (size_t)3 << L.f, qidx, &(*fo)[li]));
+    }
+    sh.mark("queries opened");
+    return ZP_OK;
+}
+
+// what a proof says besides its header; the provers differ in how they came by it, not in how it is written down
+struct ProofBody {
+    const u64 *root1, *rootq, *root2;                  // root2, stage2: read when the program has stage-2 arguments
+    const std::vector<u64> &ev_all, &ev_next;
+    const Fri &fri;
+    u64 nonce;
+    const std::vector<u64> &qidx;
+    const Opened &trace, &quotient, &stage2;
+    const std::vector<Opened> &fo;
+};
+// the openings record (BN128 mode), the text, and its hand-over to the caller
+int32_t write_proof(zp_ctx *ctx, const Shape &sh, const Transcript &tr, const ProofBody &p) {
+    const bool bn = sh.bn;
+    const size_t nl = p.fri.layers.size();
+    if (bn) {       // the same openings in binary, for the Groth16 wrap's witness (zp_stark_openings -> zp_wrap_assign): no text round trip
+        std::vector<TreeOut> trees = {{p.root1, &p.trace}, {p.rootq, &p.quotient}};
+        if (sh.n_s2) trees.push_back({p.root2, &p.stage2});
+        for (size_t li = 0; li < nl; li++) trees.push_back({p.fri.layers[li].root, &p.fo[li]});
+        openings_record(ctx, tr, p.qidx, sh.logm, trees);
+    }
+    std::string s;
+    s.reserve(p.qidx.size() * (sh.Wt + 3 * sh.Q + 64) * 24 + (1 << 16));
+    s += "{\"air\":\"";
+    s += sh.air_name;
+    s += "\",\"air_digest\":\"";
+    s += sh.dg_hex;
+    s += "\",\"params\":{\"logn\":";
+    j_u64(s, (u64)sh.logn); s += ",\"logb\":"; j_u64(s, (u64)sh.logb); s += ",\"fri_logf\":"; j_u64(s, (u64)sh.fri_logf);
+    s += ",\"fri_final_log\":"; j_u64(s, (u64)sh.fri_final_log); s += ",\"n_queries\":"; j_u64(s, (u64)sh.n_queries);
+    s += ",\"pow_bits\":"; j_u64(s, (u64)sh.pow_bits);
+    if (bn) s += ",\"hash\":\"bn128\"";
+    s += "},\"root32\":"; j_u64(s, sh.root32);
+    s += ",\"shift\":"; j_u64(s, sh.shift);
+    s += ",\"publics\":"; j_list(s, (const u64 *)sh.h_pubs, (size_t)sh.n_pubs);
+    s += ",\"roots\":{\"trace\":"; j_root(s, p.root1, bn);
+    s += ",\"quotient\":"; j_root(s, p.rootq, bn);
+    if (sh.n_s2) { s += ",\"stage2\":"; j_root(s, p.root2, bn); }
+    s += "},\"evals\":{\"z\":"; j_e3list(s, p.ev_all);
+    s += ",\"zw\":"; j_e3list(s, p.ev_next);
+    s += "},\"fri\":{\"roots\":[";
+    for (size_t li = 0; li < nl; li++) { if (li) s += ','; j_root(s, p.fri.layers[li].root, bn); }
+    s += "],\"final\":[";
+    for (int c = 0; c < 3; c++) { if (c) s += ','; j_list(s, &p.fri.final_l[(size_t)c << p.fri.final_log], (size_t)1 << p.fri.final_log); }
+    s += "]},\"queries\":[";
+    for (size_t i = 0; i < p.qidx.size(); i++) {
+        if (i) s += ',';
+        s += "{\"index\":"; j_u64(s, p.qidx[i]);
+        auto opening = [&](const Opened &o) {      // a binary tree's path has one digest per level: log2(rows) of them
+            size_t depth = 0;
+            while (((size_t)1 << depth) < o.rows) depth++;
+            if (bn) j_opening_bn(s, &o.vals[i * o.width], o.width, &o.paths[i * o.pw], Trees::levels16(o.rows));
+            else j_opening(s, &o.vals[i * o.width], o.width, &o.paths[i * o.pw], depth);
+        };
+        s += ",\"trace\":"; opening(p.trace);
+        s += ",\"quotient\":"; opening(p.quotient);
+        if (sh.n_s2) { s += ",\"stage2\":"; opening(p.stage2); }
+        s += ",\"fri\":[";
+        for (size_t li = 0; li < nl; li++) { if (li) s += ','; opening(p.fo[li]); }
+        s += "]}";
+    }
+    s += ']';
+    if (sh.pow_bits) { s += ",\"pow_nonce\":"; j_u64(s, p.nonce); }
+    s += '}';
+    sh.mark("proof text");
+    char *buf = (char *)malloc(s.size() + 1);
+    if (!buf) { ctx->err = "out of host memory for the proof text"; return ZP_ERR_NOMEM; }
+    memcpy(buf, s.data(), s.size() + 1);
+    *sh.out_json = buf;
+    *sh.out_len = s.size();
+    return ZP_OK;
+}
+
+// no C++ exception may cross the C ABI (a Rust or ctypes caller cannot unwind it): allocation failures of the host-side vectors /
+// strings (sizes follow caller parameters: n_queries * path words, 3 << fri_final_log, ...) come back as error codes
+template <class Body>
+int32_t guarded(zp_ctx *ctx, Body body) {
+    try {
+        return body();
+    } catch (const std::bad_alloc &) {
+        try { ctx->err = "out of host memory while building the proof"; } catch (...) {}
+        return ZP_ERR_NOMEM;
+    } catch (const std::exception &e) {
+        try { ctx->err = std::string("internal error: ") + e.what(); } catch (...) {}
+        return ZP_ERR_INTERNAL;
+    } catch (...) {
+        return ZP_ERR_INTERNAL;
+    }
+}
+
+// zp_stark_prove / zp_stark_prove_bn128: the whole trace on one device
+int32_t prove_impl(zp_ctx *ctx, bool bn, const ProveArgs &a) {
     ZpStage stage_(ctx, bn ? "stark_prove_bn128" : "stark_prove");
-    ZP_ARG(ctx, air_name && h_program && d_trace && out_json && out_len && (h_pubs || n_pubs == 0), "null pointer");
-    {   // the name goes into the proof text verbatim: letters, digits, '_', '-', '.' only
-        const size_t nl = strlen(air_name);
-        bool ok = nl >= 1 && nl <= 64;
-        for (size_t i = 0; ok && i < nl; i++) {
-            const char ch = air_name[i];
-            ok = (ch >= 'a' && ch <= 'z') || (ch >= 'A' && ch <= 'Z') || (ch >= '0' && ch <= '9') || ch == '_' || ch == '-' || ch == '.';
-        }
-        ZP_ARG(ctx, ok, "air_name must be 1..64 characters of [A-Za-z0-9_.-]");
-    }
-    ZP_ARG(ctx, program_words >= 12, "constraint program shorter than its header");
-    static const unsigned char magic[8] = {'Z', 'P', 'A', 'I', 'R', '1', 0, 0};
-    ZP_ARG(ctx, memcmp(h_program, magic, 8) == 0, "not a ZPAIR1 constraint program");
-    const size_t W = h_program[1], W2 = h_program[2], n_pub_prog = h_program[4], n_chal = h_program[5], n_const = h_program[6],
-                 n_instr = h_program[7], K = h_program[8], n_s2 = h_program[10], Q = h_program[11];
-    std::vector<ZpFixedCol> fxc;
-    ZP_ARG(ctx, n_const < (1u << 16) && n_instr < (1u << 24) && n_s2 < (1u << 16) && zpi_program_fixed_table(h_program, program_words, &fxc),
-           "constraint program length does not match its header");
-    ZP_ARG(ctx, (size_t)n_pubs == n_pub_prog, "number of public inputs does not match the program");
-    ZP_ARG(ctx, W >= 1 && W < 4096 && W2 < 4096 && K >= 1 && Q >= 1 && Q <= 16, "program dimensions out of range");
-    ZP_ARG(ctx, logn >= 1 && logb >= 1 && logn + logb <= 30 && fri_logf >= 1 && fri_logf <= 4 && fri_final_log >= 0 && fri_final_log < logn &&
-                    n_queries >= 1 && n_queries <= 4096 && pow_bits >= 0 && pow_bits <= 40, "STARK parameters out of range");
-    ZP_ARG(ctx, Q <= ((size_t)1 << logb), "the blow-up must cover the quotient degree");
-    ZP_ARG(ctx, trace_words == (W << logn), "trace_words must be W * 2^logn (W from the program header)");
-    ZP_ARG(ctx, (n_s2 == 0) == (W2 == 0) && (n_s2 == 0 || n_chal == 3), "stage-2 table and widths disagree");
-    for (int i = 0; i < n_pubs; i++) ZP_ARG(ctx, h_pubs[i] < GL_P, "public input not canonical");
-    const u64 *stage2 = (const u64 *)h_program + 12 + n_const + n_instr;
-    size_t w2sum = 0;
-    for (size_t k = 0; k < n_s2; k++) {
-        const u64 kind = stage2[4 * k];
-        ZP_ARG(ctx, kind == 1 || kind == 2, "unknown stage-2 argument");
-        ZP_ARG(ctx, stage2[4 * k + 1] < W && stage2[4 * k + 2] < W && stage2[4 * k + 3] < W, "stage-2 column out of range");
-        w2sum += kind == 1 ? 3 : 9;
-    }
-    ZP_ARG(ctx, w2sum == W2, "stage-2 width does not match its table");
-
-    const int logm = logn + logb;
-    const size_t N = (size_t)1 << logn, M = (size_t)1 << logm, Wt = W + W2;
-    const u64 shift = ctx->coset_shift, root32 = ctx->root32;
-    const u64 wN = gl_root(root32, logn);
+    ZP_ARG(ctx, a.d_trace, "null pointer");
+    Shape sh;
+    PV_TRY(make_shape(ctx, bn, a, &sh));
+    const size_t W = sh.W, W2 = sh.W2, Wt = sh.Wt, n_s2 = sh.n_s2, Q = sh.Q, N = sh.N, M = sh.M;
+    const int logn = sh.logn, logb = sh.logb, logm = sh.logm;
+    const u64 shift = sh.shift, wN = sh.wN;
+    const uint64_t *d_trace = a.d_trace;
+    ZP_ARG(ctx, a.trace_words == (W << logn), "trace_words must be W * 2^logn (W from the program header)");
     DevBufs dev(ctx);
-    // measurement aid (ZP_PROVE_TRACE=1): host-clock milliseconds since entry at the stage boundaries, the stream drained at each -- where the
-    // wall time of a proof goes that the per-entry-point GPU times do not show
-    static const bool trace_on = getenv("ZP_PROVE_TRACE") != nullptr;
-    const auto t_entry = std::chrono::steady_clock::now();
-    auto mark = [&](const char *what) {
-        if (!trace_on) return;
-        (void)hipStreamSynchronize(ctx->stream);
-        fprintf(stderr, "[prove %s 2^%d] %-28s %8.3f ms\n", air_name, logn, what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_entry).count());
-    };
-
-    // AIR digest: sha256 of the blob; the first 16 hex digits name it, four little-endian words go into the transcript
-    uint8_t dg[32];
-    program_digest(ctx, h_program, program_words, dg);
-    char dg_hex[17];
-    for (int i = 0; i < 8; i++) snprintf(dg_hex + 2 * i, 3, "%02x", dg[i]);
-    std::vector<u64> first = {(u64)logn, (u64)logb, (u64)W, (u64)W2, (u64)fri_logf, (u64)fri_final_log, (u64)n_queries, (u64)pow_bits, root32, shift};
-    for (int i = 0; i < 4; i++) {
-        u64 wd = 0;
-        for (int k = 0; k < 8; k++) wd |= (u64)dg[8 * i + k] << (8 * k);
-        first.push_back(wd % GL_P);
-    }
-    first.push_back((u64)n_pubs);
     Transcript tr(ctx, bn);
     const Trees T{ctx, bn};
-    if (n_pubs <= 64) {
-        for (int i = 0; i < n_pubs; i++) first.push_back(h_pubs[i]);
-        tr.absorb(first);
-    } else {
-        // a long public-input vector (a verifier AIR: every root, index and opened value of its inner proofs) enters the transcript
-        // as ONE commitment instead of thousands of dependent sponge permutations: Goldilocks mode: rows of 8 values (zero padded,
-        // row count a power of two >= 2), binary Poseidon tree;  BN128 mode: rows of 48 values, column-major, 16-ary tree
-        tr.absorb(first);
-        size_t Mp;
-        std::vector<u64> mat;
-        if (!bn) {
-            Mp = 2;
-            while (Mp * 8 < (size_t)n_pubs) Mp <<= 1;
-            mat.assign(Mp * 8, 0);
-            for (int i = 0; i < n_pubs; i++) mat[i] = h_pubs[i];
-        } else {
-            Mp = ((size_t)n_pubs + 47) / 48;
-            mat.assign(Mp * 48, 0);
-            for (int i = 0; i < n_pubs; i++) mat[(size_t)(i % 48) * Mp + (size_t)(i / 48)] = h_pubs[i];
-        }
-        u64 *dmat, *dtree;
-        PV_TRY(dev.alloc(mat.size(), &dmat));
-        PV_TRY(dev.alloc(T.tree_words(Mp), &dtree));
-        PV_TRY(zp_h2d(ctx, dmat, mat.data(), mat.size() * 8));
-        if (!bn) PV_TRY(zp_merkle_commit_rows(ctx, (const uint64_t *)dmat, Mp, 8, (uint64_t *)dtree));
-        else PV_TRY(T.commit(dmat, Mp, 48, dtree));
-        u64 rootp[4];
-        PV_TRY(T.root(dtree, Mp, rootp));
-        dev.release(dmat);
-        dev.release(dtree);
-        tr.absorb_root(rootp);
-    }
+    PV_TRY(transcript_head(ctx, sh, tr, T, dev));
 
-    mark("transcript head");
     // 1. commit the trace (ext has room for the stage-2 columns behind the trace columns).  No coefficient buffer since round 5: the
     //    out-of-domain evaluations come from the resident extension (zp_ood_eval), so the extensions run without their coefficient
     //    store -- on the fused seam kernel where the plan allows it (csrc/ntt.hip) -- and W N 8 bytes per proof are never written
     u64 *ext, *tree1;
     PV_TRY(dev.alloc(Wt * M, &ext));
-    // BN128 mode: a leaf holds 2^g rows i, i + M', ... of its tree (the column-major matrix reinterpreted as [width 2^g][M'], like a
-    // FRI layer), g the largest with width 2^g <= 56 values = one width-17 permutation per leaf (stark/prover.py:
-    // bn128_rows_per_leaf_log; Goldilocks mode: g = 0)
-    auto rows_per_leaf_log = [&](size_t width) {
-        int g = 0;
-        if (bn && width)
-            while ((width << (g + 1)) <= 56 && g + 1 <= logm - 4) g++;
-        return g;
-    };
-    const int gt = rows_per_leaf_log(W), g2 = rows_per_leaf_log(W2);
+    const int gt = sh.rows_per_leaf_log(W), g2 = sh.rows_per_leaf_log(W2);
     const size_t Mt = M >> gt, Wtg = W << gt, M2 = M >> g2, W2g = W2 << g2;
     PV_TRY(dev.alloc(T.tree_words(Mt), &tree1));
     PV_TRY(zp_lde(ctx, d_trace, (uint64_t *)ext, nullptr, logn, logb, (int32_t)W, shift));
@@ -606,7 +831,7 @@ static int32_t prove_impl(zp_ctx *ctx, bool bn, const char *air_name, const uint
     u64 root1[4], root2[4] = {0, 0, 0, 0}, rootq[4];
     PV_TRY(T.root(tree1, Mt, root1));
     tr.absorb_root(root1);
-    std::vector<u64> pubchal(h_pubs, h_pubs + n_pubs);
+    std::vector<u64> pubchal(a.h_pubs, a.h_pubs + a.n_pubs);
     u64 *tree2 = nullptr, *s2_kept = nullptr;
     if (n_s2) {
         const e3 chal = tr.challenge();
@@ -615,7 +840,7 @@ static int32_t prove_impl(zp_ctx *ctx, bool bn, const char *air_name, const uint
         PV_TRY(dev.alloc(W2 * N, &s2));
         size_t at = 0;
         for (size_t k = 0; k < n_s2; k++) {
-            const u64 *st = stage2 + 4 * k;
+            const u64 *st = sh.stage2 + 4 * k;
             if (st[0] == 1) {
                 PV_TRY(zp_grand_product(ctx, d_trace + st[1] * N, d_trace + st[2] * N, N, (const uint64_t *)chal.c, (uint64_t *)(s2 + at * N)));
                 at += 3;
@@ -635,75 +860,35 @@ static int32_t prove_impl(zp_ctx *ctx, bool bn, const char *air_name, const uint
     const e3 alpha = tr.challenge();
     PV_TRY(tr.rc);
 
-    mark("trace (+stage 2) committed");
+    sh.mark("trace (+stage 2) committed");
     // 2. constraint quotient on the coset
-    u64 *fixed, *dq, *dqcoef;
-    PV_TRY(fixed_columns_cached(ctx, h_program, program_words, fxc, h_pubs, n_pubs, logn, logb, shift, root32, dg_hex, &fixed));
-    mark("fixed columns");
-    std::vector<u64> apow(3 * K);
-    {
-        e3 cur = e3_make(1, 0, 0);
-        for (size_t k = 0; k < K; k++) { memcpy(&apow[3 * k], cur.c, 24); cur = e3_mul(cur, alpha); }
-    }
-    std::vector<u64> zhinv((size_t)1 << logb);
-    {
-        const u64 sN = gl_pow(shift, (u64)N), wb = gl_root(root32, logb);
-        u64 p = 1;
-        for (size_t j = 0; j < zhinv.size(); j++) { zhinv[j] = gl_inv(gl_sub(gl_mul(sN, p), 1)); p = gl_mul(p, wb); }
-    }
+    u64 *fixed, *dq;
+    PV_TRY(fixed_columns_cached(ctx, sh, &fixed));
+    sh.mark("fixed columns");
     PV_TRY(dev.alloc(3 * M, &dq));
-    zp_air_quotient_fn plug = nullptr;
-    if (!ctx->air_kernels.empty()) {       // (round 5: generated kernels read the sparse periodic fixed columns too -- one extended period each, zp_fixed_columns' layout)
-        // (the digest computed above -- through the per-ctx cache, a memcmp for a program seen before -- not a second SHA-256 of the blob:
-        // for a verifier AIR's 7 MB that second hash was 16 ms of every recursion STARK, round 5)
-        char hex[65];
-        for (int i = 0; i < 32; i++) snprintf(hex + 2 * i, 3, "%02x", dg[i]);
-        auto it = ctx->air_kernels.find(std::string(hex, 64));
-        if (it != ctx->air_kernels.end()) plug = (zp_air_quotient_fn)it->second;
-    }
-    if (plug) {
-        // the generated kernel of this program (zp_stark_set_air_kernel): its small operands go up in one buffer [pub | 0 | apow | zhinv]
-        std::vector<u64> ops(pubchal);
-        ops.push_back(0);
-        const size_t o_ap = ops.size();
-        ops.insert(ops.end(), apow.begin(), apow.end());
-        const size_t o_zh = ops.size();
-        ops.insert(ops.end(), zhinv.begin(), zhinv.end());
-        u64 *d_ops;
-        PV_TRY(dev.alloc(ops.size(), &d_ops));
-        PV_TRY(zp_h2d(ctx, d_ops, ops.data(), ops.size() * 8));
-        const uint64_t *xlo, *xhi;
-        int32_t xlb;
-        PV_TRY(zp_domain_tables(ctx, logm, &xlo, &xhi, &xlb));
-        const int hrc = plug((void *)ctx->stream, (const u64 *)ext, (const u64 *)fixed, (u64)M, (u64)1 << logb, d_ops, d_ops + o_ap, d_ops + o_zh, (const u64 *)xlo,
-                             (const u64 *)xhi, (int)xlb, shift, gl_inv(wN), dq);
+    QuotientOps qo;
+    PV_TRY(quotient_operands(ctx, sh, "", alpha, pubchal, dev, &qo));
+    if (qo.plug) {       // the generated kernel of this program (zp_stark_set_air_kernel)
+        const int hrc = ((zp_air_quotient_fn)qo.plug)((void *)ctx->stream, (const u64 *)ext, (const u64 *)fixed, (u64)M, (u64)1 << logb, qo.d_ops, qo.d_ops + qo.o_ap,
+                                                      qo.d_ops + qo.o_zh, (const u64 *)qo.xlo, (const u64 *)qo.xhi, (int)qo.xlb, shift, gl_inv(wN), dq);
         if (hrc != 0) {
             ctx->err = "generated constraint kernel: launch failed (hip error " + std::to_string(hrc) + ")";
             return ZP_ERR_HIP;
         }
         PV_TRY(zp_sync(ctx));
-        dev.release(d_ops);
+        dev.release(qo.d_ops);
     } else {
-        PV_TRY(zp_eval_quotient(ctx, h_program, program_words, (const uint64_t *)ext, (const uint64_t *)fixed, logm, logb, (const uint64_t *)pubchal.data(),
-                                (int32_t)pubchal.size(), (const uint64_t *)apow.data(), (const uint64_t *)zhinv.data(), shift, gl_inv(wN), (uint64_t *)dq));
+        PV_TRY(zp_eval_quotient(ctx, a.h_program, a.program_words, (const uint64_t *)ext, (const uint64_t *)fixed, logm, logb, (const uint64_t *)pubchal.data(),
+                                (int32_t)pubchal.size(), (const uint64_t *)qo.apow.data(), (const uint64_t *)qo.zhinv.data(), shift, gl_inv(wN), (uint64_t *)dq));
     }
-    mark("quotient evaluated");
+    sh.mark("quotient evaluated");
     int q_logn = logm;
     size_t Wq = 3;
     u64 *treeq;
     PV_TRY(dev.alloc(T.tree_words(M), &treeq));
     if (Q > 1) {
-        // q(x) = sum_j (x / shift)^(jN) qt_j(x): the pieces are slices of the coefficient vector of q(shift X) (c_i shift^i); their LDEs get
-        // committed.  (Q == 1: the quotient is committed as it stands and never leaves the evaluation form.)
-        u64 *pad, *pext;
-        PV_TRY(dev.alloc(3 * M, &dqcoef));
-        PV_TRY(zp_intt(ctx, (const uint64_t *)dq, (uint64_t *)dqcoef, logm, 3));
-        PV_TRY(dev.alloc(3 * Q * M, &pad));
-        PV_TRY(zp_dev_zero(ctx, pad, 3 * Q * M * 8));
-        for (size_t j = 0; j < Q; j++)
-            for (int c = 0; c < 3; c++) PV_TRY(zp_d2d(ctx, pad + (3 * j + c) * M, dqcoef + c * M + j * N, N * 8));
-        PV_TRY(dev.alloc(3 * Q * M, &pext));
-        PV_TRY(zp_ntt(ctx, (const uint64_t *)pad, (uint64_t *)pext, logm, (int32_t)(3 * Q)));
+        u64 *dqcoef, *pad, *pext;
+        PV_TRY(split_quotient(ctx, sh, dev, dq, &dqcoef, &pad, &pext));
         PV_TRY(zp_sync(ctx));
         dev.release(pad);
         dev.release(dq);
@@ -714,7 +899,7 @@ static int32_t prove_impl(zp_ctx *ctx, bool bn, const char *air_name, const uint
     }
     // BN128 mode: 2^qg rows of the quotient per leaf (rows i, i + M', ...: the matrix reinterpreted as [Wq 2^qg][M'], like a FRI layer),
     // qg the largest with Wq 2^qg <= 48 values = one width-17 permutation per leaf (stark/prover.py: bn128_rows_per_leaf_log)
-    const int qg = rows_per_leaf_log(Wq);
+    const int qg = sh.rows_per_leaf_log(Wq);
     const size_t Mq = M >> qg, Wqg = Wq << qg;
     PV_TRY(T.commit(dq, Mq, (int)Wqg, treeq));
     PV_TRY(T.root(treeq, Mq, rootq));
@@ -722,7 +907,7 @@ static int32_t prove_impl(zp_ctx *ctx, bool bn, const char *air_name, const uint
     const e3 zeta = tr.challenge();
     PV_TRY(tr.rc);
 
-    mark("quotient committed");
+    sh.mark("quotient committed");
     // 3. out-of-domain evaluations FROM VALUES (barycentric form, zp_ood_eval): a polynomial of degree < 2^d is read on a 2^d-point domain it is
     //    known on; the trace and stage-2 columns at zeta and zeta w in ONE pass
     const e3 zeta_w = e3_scale(zeta, wN);
@@ -743,216 +928,27 @@ static int32_t prove_impl(zp_ctx *ctx, bool bn, const char *air_name, const uint
     const e3 gamma = tr.challenge();
     PV_TRY(tr.rc);
 
-    mark("out-of-domain evaluations");
-    // 4. DEEP quotient
+    sh.mark("out-of-domain evaluations");
+    // 4. DEEP quotient, 5. FRI
     u64 *df;
     PV_TRY(dev.alloc(3 * M, &df));
     PV_TRY(zp_deep_quotient(ctx, (const uint64_t *)ext, (int32_t)Wt, (const uint64_t *)dq, (int32_t)Wq, logm, (int32_t)Wt, (const uint64_t *)zeta.c, (const uint64_t *)zeta_w.c, (const uint64_t *)gamma.c,
                             (const uint64_t *)ev_all.data(), (const uint64_t *)ev_next.data(), shift, (uint64_t *)df));
+    Fri fri;
+    PV_TRY(fri_commit(ctx, sh, tr, T, dev, df, &fri));
 
-    // 5. FRI
-    struct Layer { int lg, f; u64 *tree, *data; u64 root[4]; };
-    std::vector<Layer> layers;
-    int cur = logm;
-    u64 cur_shift = shift;
-    u64 *dlayer = df;
-    while (cur > fri_final_log + logb) {
-        const int f = fri_logf < cur - (fri_final_log + logb) ? fri_logf : cur - (fri_final_log + logb);
-        Layer L;
-        L.lg = cur; L.f = f; L.data = dlayer;
-        const size_t m = (size_t)1 << (cur - f);
-        PV_TRY(dev.alloc(T.tree_words(m), &L.tree));
-        PV_TRY(T.commit(dlayer, m, 3 << f, L.tree));   // leaf = the 2^f * 3 values folded together
-        PV_TRY(T.root(L.tree, m, L.root));
-        tr.absorb_root(L.root);
-        const e3 beta = tr.challenge();
-        PV_TRY(tr.rc);
-        u64 *next;
-        PV_TRY(dev.alloc((size_t)3 << (cur - f), &next));
-        PV_TRY(zp_fri_fold(ctx, (const uint64_t *)dlayer, (uint64_t *)next, cur, f, (const uint64_t *)beta.c, cur_shift));
-        layers.push_back(L);
-        dlayer = next;
-        cur_shift = gl_pow(cur_shift, (u64)1 << f);
-        cur -= f;
-    }
-    const int final_log = cur;
-    std::vector<u64> final_l((size_t)3 << final_log);
-    PV_TRY(zp_d2h(ctx, final_l.data(), dlayer, final_l.size() * 8));
-    for (int c = 0; c < 3; c++) tr.absorb(&final_l[(size_t)c << final_log], (size_t)1 << final_log);   // plane by plane (BN128 mode pads every call)
-
-    mark("DEEP + FRI");
-    // 6. proof of work, then the queries
-    u64 nonce = 0;
-    if (pow_bits) {
-        const std::vector<u64> seed = tr.squeeze(4);
-        PV_TRY(tr.rc);
-        PV_TRY(zp_pow_grind(ctx, (const uint64_t *)seed.data(), pow_bits, (uint64_t *)&nonce));
-        tr.absorb(&nonce, 1);
-    }
-    std::vector<u64> qidx = tr.squeeze((size_t)n_queries);
-    PV_TRY(tr.rc);
-    for (u64 &v : qidx) v &= (M - 1);
-    const size_t nq = (size_t)n_queries, depth = (size_t)logm;
-    const size_t pwq = T.path_words(Mq), pwt = T.path_words(Mt), pw2 = T.path_words(M2);
-    std::vector<u64> v_tr(nq * Wtg), p_tr(nq * pwt), v_s2, p_s2, v_q(nq * Wqg), p_q(nq * pwq);
-    {
-        std::vector<u64> rows = qidx;
-        for (u64 &v : rows) v &= (Mt - 1);
-        PV_TRY(zp_gather_rows(ctx, (const uint64_t *)ext, Mt, (int32_t)Wtg, (const uint64_t *)rows.data(), n_queries, (uint64_t *)v_tr.data()));
-        PV_TRY(T.open(tree1, Mt, rows.data(), n_queries, p_tr.data()));
-    }
-    if (n_s2) {
-        v_s2.resize(nq * W2g);
-        p_s2.resize(nq * pw2);
-        std::vector<u64> rows = qidx;
-        for (u64 &v : rows) v &= (M2 - 1);
-        PV_TRY(zp_gather_rows(ctx, (const uint64_t *)(ext + W * M), M2, (int32_t)W2g, (const uint64_t *)rows.data(), n_queries, (uint64_t *)v_s2.data()));
-        PV_TRY(T.open(tree2, M2, rows.data(), n_queries, p_s2.data()));
-    }
-    {
-        std::vector<u64> qrows = qidx;
-        for (u64 &v : qrows) v &= (Mq - 1);
-        PV_TRY(zp_gather_rows(ctx, (const uint64_t *)dq, Mq, (int32_t)Wqg, (const uint64_t *)qrows.data(), n_queries, (uint64_t *)v_q.data()));
-        PV_TRY(T.open(treeq, Mq, qrows.data(), n_queries, p_q.data()));
-    }
-    struct FriOpen { std::vector<u64> vals, paths; size_t width, depth, pw, m; };
-    std::vector<FriOpen> fo(layers.size());
-    {
-        std::vector<u64> pos = qidx;
-        for (size_t li = 0; li < layers.size(); li++) {
-            const Layer &L = layers[li];
-            const size_t m = (size_t)1 << (L.lg - L.f);
-            for (u64 &p : pos) p &= (m - 1);
-            fo[li].width = (size_t)3 << L.f;
-            fo[li].depth = (size_t)(L.lg - L.f);
-            fo[li].m = m;
-            fo[li].pw = T.path_words(m);
-            fo[li].vals.resize(nq * fo[li].width);
-            fo[li].paths.resize(nq * fo[li].pw);
-            PV_TRY(zp_gather_rows(ctx, (const uint64_t *)L.data, m, (int32_t)fo[li].width, (const uint64_t *)pos.data(), n_queries, (uint64_t *)fo[li].vals.data()));
-            PV_TRY(T.open(L.tree, m, pos.data(), n_queries, fo[li].paths.data()));
-        }
-    }
-
-    if (bn) {       // the same openings in binary, for the Groth16 wrap's witness (zp_stark_openings -> zp_wrap_assign): no text round trip
-        std::vector<TreeOut> trees = {{Wtg, Mt, root1, &v_tr, &p_tr, pwt}, {Wqg, Mq, rootq, &v_q, &p_q, pwq}};
-        if (n_s2) trees.push_back({W2g, M2, root2, &v_s2, &p_s2, pw2});
-        for (size_t li = 0; li < layers.size(); li++) trees.push_back({fo[li].width, fo[li].m, layers[li].root, &fo[li].vals, &fo[li].paths, fo[li].pw});
-        openings_record(ctx, tr, qidx, logm, trees);
-    }
-
-    mark("queries opened");
-    // the proof text
-    std::string s;
-    s.reserve(nq * (Wt + Wq + 64) * 24 + (1 << 16));
-    s += "{\"air\":\"";
-    s += air_name;
-    s += "\",\"air_digest\":\"";
-    s += dg_hex;
-    s += "\",\"params\":{\"logn\":";
-    j_u64(s, (u64)logn); s += ",\"logb\":"; j_u64(s, (u64)logb); s += ",\"fri_logf\":"; j_u64(s, (u64)fri_logf);
-    s += ",\"fri_final_log\":"; j_u64(s, (u64)fri_final_log); s += ",\"n_queries\":"; j_u64(s, (u64)n_queries);
-    s += ",\"pow_bits\":"; j_u64(s, (u64)pow_bits);
-    if (bn) s += ",\"hash\":\"bn128\"";
-    s += "},\"root32\":"; j_u64(s, root32);
-    s += ",\"shift\":"; j_u64(s, shift);
-    s += ",\"publics\":"; j_list(s, (const u64 *)h_pubs, (size_t)n_pubs);
-    s += ",\"roots\":{\"trace\":"; j_root(s, root1, bn);
-    s += ",\"quotient\":"; j_root(s, rootq, bn);
-    if (n_s2) { s += ",\"stage2\":"; j_root(s, root2, bn); }
-    s += "},\"evals\":{\"z\":"; j_e3list(s, ev_all);
-    s += ",\"zw\":"; j_e3list(s, ev_next);
-    s += "},\"fri\":{\"roots\":[";
-    for (size_t li = 0; li < layers.size(); li++) { if (li) s += ','; j_root(s, layers[li].root, bn); }
-    s += "],\"final\":[";
-    for (int c = 0; c < 3; c++) { if (c) s += ','; j_list(s, &final_l[(size_t)c << final_log], (size_t)1 << final_log); }
-    s += "]},\"queries\":[";
-    for (size_t i = 0; i < nq; i++) {
-        if (i) s += ',';
-        s += "{\"index\":"; j_u64(s, qidx[i]);
-        auto opening = [&](const u64 *vals, size_t width, const u64 *path, size_t rows, size_t bin_depth) {
-            if (bn) j_opening_bn(s, vals, width, path, Trees::levels16(rows));
-            else j_opening(s, vals, width, path, bin_depth);
-        };
-        s += ",\"trace\":"; opening(&v_tr[i * Wtg], Wtg, &p_tr[i * pwt], Mt, depth);
-        s += ",\"quotient\":"; opening(&v_q[i * Wqg], Wqg, &p_q[i * pwq], Mq, depth);
-        if (n_s2) { s += ",\"stage2\":"; opening(&v_s2[i * W2g], W2g, &p_s2[i * pw2], M2, depth); }
-        s += ",\"fri\":[";
-        for (size_t li = 0; li < layers.size(); li++) {
-            if (li) s += ',';
-            opening(&fo[li].vals[i * fo[li].width], fo[li].width, &fo[li].paths[i * fo[li].pw], fo[li].m, fo[li].depth);
-        }
-        s += "]}";
-    }
-    s += ']';
-    if (pow_bits) { s += ",\"pow_nonce\":"; j_u64(s, nonce); }
-    s += '}';
-    mark("proof text");
-    char *buf = (char *)malloc(s.size() + 1);
-    if (!buf) { ctx->err = "out of host memory for the proof text"; return ZP_ERR_NOMEM; }
-    memcpy(buf, s.data(), s.size() + 1);
-    *out_json = buf;
-    *out_len = s.size();
-    return ZP_OK;
+    // 6. proof of work, then the queries: every tree is whole here
+    u64 nonce;
+    std::vector<u64> qidx;
+    PV_TRY(grind_and_indices(ctx, sh, tr, &nonce, &qidx));
+    Opened o_tr, o_s2, o_q;
+    std::vector<Opened> fo;
+    PV_TRY(open_tree(ctx, T, ext, tree1, Mt, Wtg, qidx, &o_tr));
+    if (n_s2) PV_TRY(open_tree(ctx, T, ext + W * M, tree2, M2, W2g, qidx, &o_s2));
+    PV_TRY(open_tree(ctx, T, dq, treeq, Mq, Wqg, qidx, &o_q));
+    PV_TRY(fri_open(ctx, sh, T, fri, qidx, &fo));
+    return write_proof(ctx, sh, tr, {root1, rootq, root2, ev_all, ev_next, fri, nonce, qidx, o_tr, o_q, o_s2, fo});
 }
-
-// no C++ exception may cross the C ABI (a Rust or ctypes caller cannot unwind it): allocation failures of the host-side vectors /
-// strings (sizes follow caller parameters: n_queries * path words, 3 << fri_final_log, ...) come back as error codes
-static int32_t prove_guarded(zp_ctx *ctx, bool bn, const char *air_name, const uint64_t *h_program, size_t program_words, const uint64_t *d_trace,
-                             size_t trace_words, const uint64_t *h_pubs, int32_t n_pubs, int32_t logn, int32_t logb, int32_t fri_logf, int32_t fri_final_log,
-                             int32_t n_queries, int32_t pow_bits, char **out_json, size_t *out_len) {
-    if (!ctx) return ZP_ERR_ARG;
-    if (out_json) *out_json = nullptr;
-    if (out_len) *out_len = 0;
-    try {
-        return prove_impl(ctx, bn, air_name, h_program, program_words, d_trace, trace_words, h_pubs, n_pubs, logn, logb, fri_logf, fri_final_log,
-                          n_queries, pow_bits, out_json, out_len);
-    } catch (const std::bad_alloc &) {
-        try { ctx->err = "out of host memory while building the proof"; } catch (...) {}
-        return ZP_ERR_NOMEM;
-    } catch (const std::exception &e) {
-        try { ctx->err = std::string("internal error: ") + e.what(); } catch (...) {}
-        return ZP_ERR_INTERNAL;
-    } catch (...) {
-        return ZP_ERR_INTERNAL;
-    }
-}
-
-int32_t zp_stark_prove(zp_ctx *ctx, const char *air_name, const uint64_t *h_program, size_t program_words, const uint64_t *d_trace,
-                       size_t trace_words, const uint64_t *h_pubs, int32_t n_pubs, int32_t logn, int32_t logb, int32_t fri_logf,
-                       int32_t fri_final_log, int32_t n_queries, int32_t pow_bits, char **out_json, size_t *out_len) {
-    return prove_guarded(ctx, false, air_name, h_program, program_words, d_trace, trace_words, h_pubs, n_pubs, logn, logb, fri_logf, fri_final_log,
-                         n_queries, pow_bits, out_json, out_len);
-}
-
-// the same prover in BN128-hash mode (the last STARK before the Groth16 wrap): 16-ary Poseidon-BN254 trees, transcript over the
-// BN254 scalar field, no grinding.  zp_set_poseidon_bn254(ctx, 17, ...) must have installed the tables.
-int32_t zp_stark_prove_bn128(zp_ctx *ctx, const char *air_name, const uint64_t *h_program, size_t program_words, const uint64_t *d_trace,
-                             size_t trace_words, const uint64_t *h_pubs, int32_t n_pubs, int32_t logn, int32_t logb, int32_t fri_logf,
-                             int32_t fri_final_log, int32_t n_queries, char **out_json, size_t *out_len) {
-    return prove_guarded(ctx, true, air_name, h_program, program_words, d_trace, trace_words, h_pubs, n_pubs, logn, logb, fri_logf, fri_final_log,
-                         n_queries, 0, out_json, out_len);
-}
-
-// Binary openings of the LAST proof zp_stark_prove_bn128 made on this ctx (what its text carries under "roots", "fri.roots" and "queries"):
-//   [0] "PZOPEN01" [1] n_queries [2] n_trees [3] log2 of the LDE size (bits of a query index), then per tree (trace, quotient, [stage 2], FRI
-//   layers): values per leaf, leaves, levels of the 16-ary tree; per tree the root (4 words); per query: the index, then per tree values[width]
-//   and path[levels][16][4].  *out points into the ctx (valid until the next proof on it); ZP_ERR_ARG when there is none.
-int32_t zp_stark_openings(zp_ctx *ctx, const uint64_t **out, size_t *words) {
-    if (!ctx || !out || !words) return ZP_ERR_ARG;
-    ZP_ARG(ctx, !ctx->last_openings.empty(), "no BN128-mode proof has been made on this ctx");
-    *out = (const uint64_t *)ctx->last_openings.data();
-    *words = ctx->last_openings.size();
-    return ZP_OK;
-}
-
-int32_t zp_sha256(const uint8_t *data, size_t len, uint8_t *out32) {
-    if ((!data && len) || !out32) return ZP_ERR_ARG;
-    Sha256::digest(data, len, out32);
-    return ZP_OK;
-}
-
-}  // extern "C"
 
 // ======================================================================================================================
 // zp_stark_prove_sharded: ONE chunk STARK over the G ranks of a communicator (BASELINE configs[3]) -- what
@@ -968,7 +964,6 @@ int32_t zp_sha256(const uint8_t *data, size_t len, uint8_t *out32) {
 //     DEEP quotient              rows                                                  all-gather of the result: "gather before FRI"
 //     FRI, proof of work         replicated                                            none
 //     query openings             the owner of a row answers                            one all-reduce of values and sub-tree paths
-namespace {
 
 struct ShardTop {                       // the top log2 G levels of a row-sharded tree, known to every rank
     std::vector<std::vector<u64>> levels;   // levels[l]: (G >> l) nodes of 4 words
@@ -1040,47 +1035,16 @@ int32_t shard_join(zp_ctx *ctx, const u64 *gathered, u64 *full, int C, size_t nl
     return ZP_OK;
 }
 
-int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, const char *air_name, const uint64_t *h_program, size_t program_words,
-                           const uint64_t *d_trace, size_t trace_words, const uint64_t *h_pubs, int32_t n_pubs, int32_t logn, int32_t logb,
-                           int32_t fri_logf, int32_t fri_final_log, int32_t n_queries, int32_t pow_bits, bool bn, char **out_json, size_t *out_len) {
+int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, bool bn, const ProveArgs &a) {
     ZpStage stage_(ctx, bn ? "stark_prove_sharded_bn128" : "stark_prove_sharded");
     const int G = zp_comm_world(comm), rank = zp_comm_rank(comm);
-    ZP_ARG(ctx, air_name && h_program && out_json && out_len && (h_pubs || n_pubs == 0), "null pointer");
-    {
-        const size_t nl = strlen(air_name);
-        bool ok = nl >= 1 && nl <= 64;
-        for (size_t i = 0; ok && i < nl; i++) {
-            const char ch = air_name[i];
-            ok = (ch >= 'a' && ch <= 'z') || (ch >= 'A' && ch <= 'Z') || (ch >= '0' && ch <= '9') || ch == '_' || ch == '-' || ch == '.';
-        }
-        ZP_ARG(ctx, ok, "air_name must be 1..64 characters of [A-Za-z0-9_.-]");
-    }
-    ZP_ARG(ctx, program_words >= 12, "constraint program shorter than its header");
-    static const unsigned char magic[8] = {'Z', 'P', 'A', 'I', 'R', '1', 0, 0};
-    ZP_ARG(ctx, memcmp(h_program, magic, 8) == 0, "not a ZPAIR1 constraint program");
-    const size_t W = h_program[1], W2 = h_program[2], n_pub_prog = h_program[4], n_chal = h_program[5], n_const = h_program[6],
-                 n_instr = h_program[7], K = h_program[8], n_s2 = h_program[10], Q = h_program[11];
-    std::vector<ZpFixedCol> fxc;
-    ZP_ARG(ctx, n_const < (1u << 16) && n_instr < (1u << 24) && n_s2 < (1u << 16) && zpi_program_fixed_table(h_program, program_words, &fxc),
-           "constraint program length does not match its header");
-    ZP_ARG(ctx, (size_t)n_pubs == n_pub_prog, "number of public inputs does not match the program");
-    ZP_ARG(ctx, W >= 1 && W < 4096 && W2 < 4096 && K >= 1 && Q >= 1 && Q <= 16, "program dimensions out of range");
-    ZP_ARG(ctx, logn >= 1 && logb >= 1 && logn + logb <= 30 && fri_logf >= 1 && fri_logf <= 4 && fri_final_log >= 0 && fri_final_log < logn &&
-                    n_queries >= 1 && n_queries <= 4096 && pow_bits >= 0 && pow_bits <= 40, "STARK parameters out of range");
-    ZP_ARG(ctx, Q <= ((size_t)1 << logb), "the blow-up must cover the quotient degree");
-    ZP_ARG(ctx, (n_s2 == 0) == (W2 == 0) && (n_s2 == 0 || n_chal == 3), "stage-2 table and widths disagree");
-    for (int i = 0; i < n_pubs; i++) ZP_ARG(ctx, h_pubs[i] < GL_P, "public input not canonical");
-    const u64 *stage2 = (const u64 *)h_program + 12 + n_const + n_instr;
-    size_t w2sum = 0;
-    for (size_t k = 0; k < n_s2; k++) {
-        const u64 kind = stage2[4 * k];
-        ZP_ARG(ctx, kind == 1 || kind == 2, "unknown stage-2 argument");
-        ZP_ARG(ctx, stage2[4 * k + 1] < W && stage2[4 * k + 2] < W && stage2[4 * k + 3] < W, "stage-2 column out of range");
-        w2sum += kind == 1 ? 3 : 9;
-    }
-    ZP_ARG(ctx, w2sum == W2, "stage-2 width does not match its table");
-    const int logm = logn + logb;
-    const size_t N = (size_t)1 << logn, M = (size_t)1 << logm, Wt = W + W2, b = (size_t)1 << logb;
+    Shape sh;
+    PV_TRY(make_shape(ctx, bn, a, &sh));
+    const size_t W = sh.W, W2 = sh.W2, Wt = sh.Wt, n_s2 = sh.n_s2, Q = sh.Q, N = sh.N, M = sh.M, b = (size_t)1 << sh.logb;
+    const int logn = sh.logn, logb = sh.logb, logm = sh.logm;
+    const u64 shift = sh.shift, wN = sh.wN;
+    const uint64_t *d_trace = a.d_trace;
+    // what can fail on one rank alone is checked before that rank's first collective
     ZP_ARG(ctx, G >= 1 && M % (size_t)G == 0, "the domain rows must split evenly over the ranks");
     // columns: rank r owns [r wl, min((r + 1) wl, W)), wl = ceil(W / G) -- the last ranks may hold fewer (a 47-column verifier AIR over
     // 8 ranks: 6,6,6,6,6,6,6,5) or none; the exchange moves wl columns per rank, the missing ones as zeros (they land behind column W)
@@ -1088,69 +1052,21 @@ int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, const char *air_name, con
     const size_t wr = (size_t)rank * wl >= W ? 0 : (W - (size_t)rank * wl < wl ? W - (size_t)rank * wl : wl);      // my real columns
     ZP_ARG(ctx, d_trace || wr == 0, "null pointer");
     ZP_ARG(ctx, nloc >= b && nloc % b == 0 && nloc >= 2, "row shards must hold whole blow-up groups");
-    ZP_ARG(ctx, trace_words == (wr << logn), "trace_words must be (this rank's columns) * 2^logn: ceil(W / world) columns per rank, the tail ranks fewer");
-    const u64 shift = ctx->coset_shift, root32 = ctx->root32;
-    const u64 wN = gl_root(root32, logn);
+    ZP_ARG(ctx, a.trace_words == (wr << logn), "trace_words must be (this rank's columns) * 2^logn: ceil(W / world) columns per rank, the tail ranks fewer");
+    // BN128 mode (the last STARK before the Groth16 wrap, zp_stark_prove_bn128's text): a leaf of a narrow tree holds 2^g rows i, i + M', ...
+    // (Shape::rows_per_leaf_log) -- rows of DIFFERENT shards.  The trace tree is the sharded one and must have one row per leaf
+    // (W > 28: the 47-column verifier AIR this mode exists for); the stage-2 and quotient trees are narrow, their columns are whole on
+    // every rank anyway (stage 2 is replicated, the quotient is gathered for its out-of-domain evaluation), and 2^g rows per leaf make
+    // them M / 2^g permutations against the trace tree's M: they are committed and opened replicated, exactly as prove_impl does
+    ZP_ARG(ctx, !bn || sh.rows_per_leaf_log(W) == 0, "BN128 mode shards the trace tree by rows: it needs one row per leaf (more than 28 trace columns)");
     DevBufs dev(ctx);
-
-    uint8_t dg[32];
-    program_digest(ctx, h_program, program_words, dg);
-    char dg_hex[17];
-    for (int i = 0; i < 8; i++) snprintf(dg_hex + 2 * i, 3, "%02x", dg[i]);
-    std::vector<u64> first = {(u64)logn, (u64)logb, (u64)W, (u64)W2, (u64)fri_logf, (u64)fri_final_log, (u64)n_queries, (u64)pow_bits, root32, shift};
-    for (int i = 0; i < 4; i++) {
-        u64 wd = 0;
-        for (int k = 0; k < 8; k++) wd |= (u64)dg[8 * i + k] << (8 * k);
-        first.push_back(wd % GL_P);
-    }
-    first.push_back((u64)n_pubs);
     Transcript tr(ctx, bn);
     const Trees T{ctx, bn};
-    if (n_pubs <= 64) {
-        for (int i = 0; i < n_pubs; i++) first.push_back(h_pubs[i]);
-        tr.absorb(first);
-    } else {            // long public vectors enter through their commitment (replicated: a few thousand permutations at most)
-        tr.absorb(first);
-        size_t Mp;
-        std::vector<u64> mat;
-        if (!bn) {
-            Mp = 2;
-            while (Mp * 8 < (size_t)n_pubs) Mp <<= 1;
-            mat.assign(Mp * 8, 0);
-            for (int i = 0; i < n_pubs; i++) mat[i] = h_pubs[i];
-        } else {        // BN128 mode: rows of 48 values, column-major, 16-ary tree (as in prove_impl)
-            Mp = ((size_t)n_pubs + 47) / 48;
-            mat.assign(Mp * 48, 0);
-            for (int i = 0; i < n_pubs; i++) mat[(size_t)(i % 48) * Mp + (size_t)(i / 48)] = h_pubs[i];
-        }
-        u64 *dmat, *dtree;
-        PV_TRY(dev.alloc(mat.size(), &dmat));
-        PV_TRY(dev.alloc(T.tree_words(Mp), &dtree));
-        PV_TRY(zp_h2d(ctx, dmat, mat.data(), mat.size() * 8));
-        if (!bn) PV_TRY(zp_merkle_commit_rows(ctx, (const uint64_t *)dmat, Mp, 8, (uint64_t *)dtree));
-        else PV_TRY(T.commit(dmat, Mp, 48, dtree));
-        u64 rootp[4];
-        PV_TRY(T.root(dtree, Mp, rootp));
-        dev.release(dmat);
-        dev.release(dtree);
-        tr.absorb_root(rootp);
-    }
+    PV_TRY(transcript_head(ctx, sh, tr, T, dev));
 
     // 1. trace: LDE of my columns, ONE exchange columns -> rows, local subtree, sub-roots
     u64 *ext, *tree1 = nullptr;
     ShardTop top1, top2, topq;
-    // BN128 mode (the last STARK before the Groth16 wrap, zp_stark_prove_bn128's text): a leaf of a narrow tree holds 2^g rows i, i + M', ...
-    // (prove_impl: rows_per_leaf_log) -- rows of DIFFERENT shards.  The trace tree is the sharded one and must have one row per leaf
-    // (W > 28: the 47-column verifier AIR this mode exists for); the stage-2 and quotient trees are narrow, their columns are whole on
-    // every rank anyway (stage 2 is replicated, the quotient is gathered for its out-of-domain evaluation), and 2^g rows per leaf make
-    // them M / 2^g permutations against the trace tree's M: they are committed and opened replicated, exactly as prove_impl does
-    auto rows_per_leaf_log = [&](size_t width) {
-        int g = 0;
-        if (bn && width)
-            while ((width << (g + 1)) <= 56 && g + 1 <= logm - 4) g++;
-        return g;
-    };
-    ZP_ARG(ctx, !bn || rows_per_leaf_log(W) == 0, "BN128 mode shards the trace tree by rows: it needs one row per leaf (more than 28 trace columns)");
     ShardTopBn bt1;
     u64 root1[4], root2[4] = {0, 0, 0, 0}, rootq[4];
     PV_TRY(dev.alloc((Wt > (size_t)G * wl ? Wt : (size_t)G * wl) * nloc, &ext));   // [Wt][nloc]: ALL columns (trace, then stage 2), my rows (room for the exchange's zero columns)
@@ -1174,8 +1090,8 @@ int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, const char *air_name, con
         memcpy(root1, top1.root, 32);
     }
     tr.absorb_root(root1);
-    std::vector<u64> pubchal(h_pubs, h_pubs + n_pubs);
-    const int g2 = rows_per_leaf_log(W2);
+    std::vector<u64> pubchal(a.h_pubs, a.h_pubs + a.n_pubs);
+    const int g2 = sh.rows_per_leaf_log(W2);
     const size_t M2 = M >> g2, W2g = W2 << g2;
     u64 *ext2_kept = nullptr;                     // BN128 mode: the stage-2 extension, whole (its tree's leaves mix rows of all shards)
     u64 *tree2 = nullptr, *s2 = nullptr;          // s2: the stage-2 columns on the trace domain (replicated), kept for their out-of-domain evaluations
@@ -1192,7 +1108,7 @@ int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, const char *air_name, con
         };
         size_t at = 0;
         for (size_t k = 0; k < n_s2; k++) {
-            const u64 *st = stage2 + 4 * k;
+            const u64 *st = sh.stage2 + 4 * k;
             PV_TRY(column(st[1], colb));
             PV_TRY(column(st[2], colb + N));
             if (st[0] == 1) {
@@ -1225,69 +1141,40 @@ int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, const char *air_name, con
     }
     const e3 alpha = tr.challenge();
     PV_TRY(tr.rc);
+    sh.mark("trace exchanged, committed");
 
     // 2. constraint quotient on my rows (+ the b halo rows of the next rank)
     u64 *dq_l;
     {
-        const size_t fwords = zp_fixed_columns_words(h_program, program_words, logn, logb);
-        u64 *fixed, *fx_l;             // (round 5: from the ctx's cache, as in prove_impl -- they were rebuilt for every proof)
-        PV_TRY(fixed_columns_cached(ctx, h_program, program_words, fxc, h_pubs, n_pubs, logn, logb, shift, root32, dg_hex, &fixed));
+        const size_t fwords = zp_fixed_columns_words(a.h_program, a.program_words, logn, logb);
+        u64 *fixed, *fx_l;
+        PV_TRY(fixed_columns_cached(ctx, sh, &fixed));
         // my window of the two selectors, then the (whole, periodic) extra columns: the layout zp_eval_quotient_rows reads
         PV_TRY(dev.alloc(2 * nloc + (fwords - 2 * M), &fx_l));
         PV_TRY(zp_d2d(ctx, fx_l, fixed + r0, nloc * 8));
         PV_TRY(zp_d2d(ctx, fx_l + nloc, fixed + M + r0, nloc * 8));
         if (fwords > 2 * M) PV_TRY(zp_d2d(ctx, fx_l + 2 * nloc, fixed + 2 * M, (fwords - 2 * M) * 8));
-        std::vector<u64> apow(3 * K);
-        {
-            e3 cur = e3_make(1, 0, 0);
-            for (size_t k = 0; k < K; k++) { memcpy(&apow[3 * k], cur.c, 24); cur = e3_mul(cur, alpha); }
-        }
-        std::vector<u64> zhinv(b);
-        {
-            const u64 sN = gl_pow(shift, (u64)N), wb = gl_root(root32, logb);
-            u64 p = 1;
-            for (size_t j = 0; j < b; j++) { zhinv[j] = gl_inv(gl_sub(gl_mul(sN, p), 1)); p = gl_mul(p, wb); }
-        }
+        sh.mark("fixed columns, my window");
         PV_TRY(dev.alloc(3 * nloc, &dq_l));
-        // the generated kernel of this program in its row-window form, when the host registered one (zp_stark_set_air_kernel_rows): the small
-        // operands go up in one buffer [pub | 0 | apow | zhinv], as in prove_impl
-        zp_air_quotient_rows_fn plug = nullptr;
-        u64 *d_ops = nullptr;
-        size_t o_ap = 0, o_zh = 0;
-        const uint64_t *xlo = nullptr, *xhi = nullptr;
-        int32_t xlb = 0;
-        if (!ctx->air_kernels.empty()) {
-            char hex[65];
-            for (int i = 0; i < 32; i++) snprintf(hex + 2 * i, 3, "%02x", dg[i]);
-            auto it = ctx->air_kernels.find(std::string("rows:") + std::string(hex, 64));
-            if (it != ctx->air_kernels.end()) plug = (zp_air_quotient_rows_fn)it->second;
-        }
-        if (plug) {
-            std::vector<u64> ops(pubchal);
-            ops.push_back(0);
-            o_ap = ops.size();
-            ops.insert(ops.end(), apow.begin(), apow.end());
-            o_zh = ops.size();
-            ops.insert(ops.end(), zhinv.begin(), zhinv.end());
-            PV_TRY(dev.alloc(ops.size(), &d_ops));
-            PV_TRY(zp_h2d(ctx, d_ops, ops.data(), ops.size() * 8));
-            PV_TRY(zp_domain_tables(ctx, logm, &xlo, &xhi, &xlb));
-        }
-        auto run_plug = [&](const u64 *cols, size_t sc, size_t row0, size_t nrows) -> int32_t {
-            const int hrc = plug((void *)ctx->stream, cols, (u64)sc, (const u64 *)fx_l, (u64)nloc, (u64)M, (u64)b, (u64)row0, (u64)nrows, d_ops, d_ops + o_ap,
-                                 d_ops + o_zh, (const u64 *)xlo, (const u64 *)xhi, (int)xlb, shift, gl_inv(wN), dq_l, (u64)nloc);
+        // the generated kernel of this program in its row-window form, when the host registered one (zp_stark_set_air_kernel_rows)
+        QuotientOps qo;
+        PV_TRY(quotient_operands(ctx, sh, "rows:", alpha, pubchal, dev, &qo));
+        auto quotient_rows = [&](const u64 *cols, size_t sc, size_t row0, size_t nrows) -> int32_t {
+            if (!qo.plug)
+                return zp_eval_quotient_rows(ctx, a.h_program, a.program_words, (const uint64_t *)cols, sc, (const uint64_t *)fx_l, nloc, logm, logb, row0, nrows,
+                                             (const uint64_t *)pubchal.data(), (int32_t)pubchal.size(), (const uint64_t *)qo.apow.data(),
+                                             (const uint64_t *)qo.zhinv.data(), shift, gl_inv(wN), (uint64_t *)dq_l, nloc);
+            const int hrc = ((zp_air_quotient_rows_fn)qo.plug)((void *)ctx->stream, cols, (u64)sc, (const u64 *)fx_l, (u64)nloc, (u64)M, (u64)b, (u64)row0, (u64)nrows,
+                                                           qo.d_ops, qo.d_ops + qo.o_ap, qo.d_ops + qo.o_zh, (const u64 *)qo.xlo, (const u64 *)qo.xhi, (int)qo.xlb, shift,
+                                                           gl_inv(wN), dq_l, (u64)nloc);
             if (hrc != 0) {
                 ctx->err = "generated constraint kernel (row window): launch failed (hip error " + std::to_string(hrc) + ")";
                 return ZP_ERR_HIP;
             }
             return ZP_OK;
         };
-        if (G == 1 && plug) {
-            PV_TRY(run_plug((const u64 *)ext, nloc, 0, M));
-        } else if (G == 1) {
-            PV_TRY(zp_eval_quotient_rows(ctx, h_program, program_words, (const uint64_t *)ext, nloc, (const uint64_t *)fx_l, nloc, logm, logb, 0, M,
-                                         (const uint64_t *)pubchal.data(), (int32_t)pubchal.size(), (const uint64_t *)apow.data(),
-                                         (const uint64_t *)zhinv.data(), shift, gl_inv(wN), (uint64_t *)dq_l, nloc));
+        if (G == 1) {
+            PV_TRY(quotient_rows(ext, nloc, 0, M));
         } else {
             u64 *heads, *allh, *buf;
             PV_TRY(dev.alloc(Wt * b, &heads));
@@ -1298,13 +1185,7 @@ int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, const char *air_name, con
             ZP_HIP(ctx, hipMemcpy2DAsync(buf, (nloc + b) * 8, ext, nloc * 8, nloc * 8, Wt, hipMemcpyDeviceToDevice, ctx->stream));
             ZP_HIP(ctx, hipMemcpy2DAsync(buf + nloc, (nloc + b) * 8, allh + (size_t)((rank + 1) % G) * Wt * b, b * 8, b * 8, Wt, hipMemcpyDeviceToDevice,
                                          ctx->stream));                                                                 // ... of the next rank
-            if (plug) {
-                PV_TRY(run_plug((const u64 *)buf, nloc + b, r0, nloc));
-            } else {
-                PV_TRY(zp_eval_quotient_rows(ctx, h_program, program_words, (const uint64_t *)buf, nloc + b, (const uint64_t *)fx_l, nloc, logm, logb, r0,
-                                             nloc, (const uint64_t *)pubchal.data(), (int32_t)pubchal.size(), (const uint64_t *)apow.data(),
-                                             (const uint64_t *)zhinv.data(), shift, gl_inv(wN), (uint64_t *)dq_l, nloc));
-            }
+            PV_TRY(quotient_rows(buf, nloc + b, r0, nloc));
             PV_TRY(zp_sync(ctx));
             dev.release(heads);
             dev.release(allh);
@@ -1312,8 +1193,9 @@ int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, const char *air_name, con
         }
         PV_TRY(zp_sync(ctx));
         dev.release(fx_l);
-        if (d_ops) dev.release(d_ops);
+        if (qo.d_ops) dev.release(qo.d_ops);
     }
+    sh.mark("quotient on my rows");
     // the quotient is needed whole on every rank: for its out-of-domain evaluation and, with Q > 1, for the coefficients its pieces are slices of
     u64 *dq_whole, *dq_rows = dq_l, *treeq;       // dq_whole: u64[Wq][M], the committed quotient columns (all rows)
     int q_logn = logm;
@@ -1329,14 +1211,7 @@ int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, const char *air_name, con
     }
     if (Q > 1) {
         u64 *dqcoef, *pad, *pext;
-        PV_TRY(dev.alloc(3 * M, &dqcoef));
-        PV_TRY(zp_intt(ctx, (const uint64_t *)dq_whole, (uint64_t *)dqcoef, logm, 3));
-        PV_TRY(dev.alloc(3 * Q * M, &pad));
-        PV_TRY(zp_dev_zero(ctx, pad, 3 * Q * M * 8));
-        for (size_t j = 0; j < Q; j++)
-            for (int c = 0; c < 3; c++) PV_TRY(zp_d2d(ctx, pad + (3 * j + c) * M, dqcoef + c * M + j * N, N * 8));
-        PV_TRY(dev.alloc(3 * Q * M, &pext));
-        PV_TRY(zp_ntt(ctx, (const uint64_t *)pad, (uint64_t *)pext, logm, (int32_t)(3 * Q)));
+        PV_TRY(split_quotient(ctx, sh, dev, dq_whole, &dqcoef, &pad, &pext));
         PV_TRY(dev.alloc(3 * Q * nloc, &dq_rows));
         ZP_HIP(ctx, hipMemcpy2DAsync(dq_rows, nloc * 8, pext + r0, M * 8, nloc * 8, 3 * Q, hipMemcpyDeviceToDevice, ctx->stream));   // my rows of the pieces
         PV_TRY(zp_sync(ctx));
@@ -1348,7 +1223,7 @@ int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, const char *air_name, con
         q_logn = logn;
         Wq = 3 * Q;
     }
-    const int qg = rows_per_leaf_log(Wq);
+    const int qg = sh.rows_per_leaf_log(Wq);
     const size_t Mq = M >> qg, Wqg = Wq << qg;
     if (bn) {
         PV_TRY(dev.alloc(T.tree_words(Mq), &treeq));
@@ -1361,6 +1236,7 @@ int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, const char *air_name, con
     tr.absorb_root(rootq);
     const e3 zeta = tr.challenge();
     PV_TRY(tr.rc);
+    sh.mark("quotient gathered, committed");
 
     // 3. out-of-domain evaluations (barycentric form, zp_ood_eval): every rank evaluates ITS trace columns from their values on the trace
     //    domain (d_trace: shift 1, stride 1), the evaluations are all-gathered; the replicated stage-2 columns and quotient on every rank
@@ -1398,8 +1274,9 @@ int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, const char *air_name, con
     tr.absorb(ev_next);
     const e3 gamma = tr.challenge();
     PV_TRY(tr.rc);
+    sh.mark("evaluations gathered");
 
-    // 4. DEEP quotient on my rows, gathered before FRI
+    // 4. DEEP quotient on my rows, gathered before FRI;  5. FRI (replicated: a layer of the DEEP quotient is 3 columns)
     u64 *df;
     {
         u64 *df_l, *gath;
@@ -1415,55 +1292,25 @@ int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, const char *air_name, con
         dev.release(df_l);
         dev.release(gath);
     }
-
-    // 5. FRI (replicated: a layer of the DEEP quotient is 3 columns)
-    struct Layer { int lg, f; u64 *tree, *data; u64 root[4]; };
-    std::vector<Layer> layers;
-    int cur = logm;
-    u64 cur_shift = shift;
-    u64 *dlayer = df;
-    while (cur > fri_final_log + logb) {
-        const int f = fri_logf < cur - (fri_final_log + logb) ? fri_logf : cur - (fri_final_log + logb);
-        Layer L;
-        L.lg = cur; L.f = f; L.data = dlayer;
-        const size_t m = (size_t)1 << (cur - f);
-        PV_TRY(dev.alloc(T.tree_words(m), &L.tree));
-        PV_TRY(T.commit(dlayer, m, 3 << f, L.tree));
-        PV_TRY(T.root(L.tree, m, L.root));
-        tr.absorb_root(L.root);
-        const e3 beta = tr.challenge();
-        PV_TRY(tr.rc);
-        u64 *next;
-        PV_TRY(dev.alloc((size_t)3 << (cur - f), &next));
-        PV_TRY(zp_fri_fold(ctx, (const uint64_t *)dlayer, (uint64_t *)next, cur, f, (const uint64_t *)beta.c, cur_shift));
-        layers.push_back(L);
-        dlayer = next;
-        cur_shift = gl_pow(cur_shift, (u64)1 << f);
-        cur -= f;
-    }
-    const int final_log = cur;
-    std::vector<u64> final_l((size_t)3 << final_log);
-    PV_TRY(zp_d2h(ctx, final_l.data(), dlayer, final_l.size() * 8));
-    for (int c = 0; c < 3; c++) tr.absorb(&final_l[(size_t)c << final_log], (size_t)1 << final_log);
+    Fri fri;
+    PV_TRY(fri_commit(ctx, sh, tr, T, dev, df, &fri));
 
     // 6. proof of work, then the queries: the owner of a row answers, one all-reduce spreads the answers
-    u64 nonce = 0;
-    if (pow_bits) {
-        const std::vector<u64> seed = tr.squeeze(4);
-        PV_TRY(tr.rc);
-        PV_TRY(zp_pow_grind(ctx, (const uint64_t *)seed.data(), pow_bits, (uint64_t *)&nonce));
-        tr.absorb(&nonce, 1);
-    }
-    std::vector<u64> qidx = tr.squeeze((size_t)n_queries);
-    PV_TRY(tr.rc);
-    for (u64 &v : qidx) v &= (M - 1);
-    const size_t nq = (size_t)n_queries, depth = (size_t)logm;
+    u64 nonce;
+    std::vector<u64> qidx;
+    PV_TRY(grind_and_indices(ctx, sh, tr, &nonce, &qidx));
+    const size_t nq = qidx.size(), depth = (size_t)logm;
     size_t dl = 0;
     while (((size_t)1 << dl) < nloc) dl++;
-    // words of one path: Goldilocks mode `depth` digests; BN128 mode 16 digests per level of the 16-ary tree
-    const size_t pwt = bn ? Trees::levels16(M) * 64 : depth * 4, pw2 = bn ? T.path_words(M2) : depth * 4, pwq = bn ? T.path_words(Mq) : depth * 4;
+    // words of one path of a sharded tree: Goldilocks mode `depth` digests; BN128 mode 16 digests per level of the 16-ary tree
+    const size_t pwt = bn ? Trees::levels16(M) * 64 : depth * 4;
     const size_t ltw = bn ? bt1.h * 64 : dl * 4;          // ... of which the owner of the row supplies (the levels inside its sub-tree)
-    std::vector<u64> v_tr(nq * W), p_tr(nq * pwt), v_s2(nq * W2g), p_s2(n_s2 ? nq * pw2 : 0), v_q(nq * Wqg), p_q(nq * pwq);
+    Opened o_tr, o_s2, o_q;
+    o_tr.shape(nq, W, M, pwt);
+    if (!bn) {                                            // (Goldilocks mode: one row per leaf in every tree)
+        if (n_s2) o_s2.shape(nq, W2, M, pwt);
+        o_q.shape(nq, Wq, M, pwt);
+    }
     {
         std::vector<int> own;
         std::vector<u64> lidx;
@@ -1478,8 +1325,7 @@ int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, const char *air_name, con
         auto fill = [&](const u64 *mat, size_t Wc, size_t voff, const u64 *tree, size_t poff) -> int32_t {
             if (!no) return ZP_OK;
             PV_TRY(zp_gather_rows(ctx, (const uint64_t *)mat, nloc, (int32_t)Wc, (const uint64_t *)lidx.data(), (int32_t)no, (uint64_t *)tv.data()));
-            if (bn) PV_TRY(zp_merkle16_open_batch_bn254(ctx, (const uint64_t *)tree, nloc, (const uint64_t *)lidx.data(), (int32_t)no, (uint64_t *)tp.data()));
-            else PV_TRY(zp_merkle_open_batch(ctx, (const uint64_t *)tree, nloc, (const uint64_t *)lidx.data(), (int32_t)no, (uint64_t *)tp.data()));
+            PV_TRY(T.open(tree, nloc, lidx.data(), (int)no, tp.data()));
             for (size_t k = 0; k < no; k++) {
                 memcpy(&red[(size_t)own[k] * per + voff], &tv[k * Wc], Wc * 8);
                 memcpy(&red[(size_t)own[k] * per + nval + poff], &tp[k * lpw], ltw * 8);     // the first bt1.h levels / all dl levels
@@ -1508,159 +1354,160 @@ int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, const char *air_name, con
             }
         };
         for (size_t i = 0; i < nq; i++) {
-            memcpy(&v_tr[i * W], &red[i * per], W * 8);
+            memcpy(&o_tr.vals[i * W], &red[i * per], W * 8);
             if (bn) continue;
-            if (W2) memcpy(&v_s2[i * W2], &red[i * per + W], W2 * 8);
-            memcpy(&v_q[i * Wq], &red[i * per + W + W2], Wq * 8);
+            if (W2) memcpy(&o_s2.vals[i * W2], &red[i * per + W], W2 * 8);
+            memcpy(&o_q.vals[i * Wq], &red[i * per + W + W2], Wq * 8);
         }
         if (!bn) {
-            paths(p_tr, 0, top1);
-            if (n_s2) paths(p_s2, ltw, top2);
-            paths(p_q, (ntree - 1) * ltw, topq);
+            paths(o_tr.paths, 0, top1);
+            if (n_s2) paths(o_s2.paths, ltw, top2);
+            paths(o_q.paths, (ntree - 1) * ltw, topq);
         } else {
             // trace: the levels above the shards from the replicated top tree (its "leaves" are the nodes of level h)
             const size_t tlv = Trees::levels16(bt1.ntop);
             ZP_ARG(ctx, bt1.h + tlv == Trees::levels16(M), "internal: levels of the sharded 16-ary tree do not add up");
             std::vector<u64> tidx(nq), topp(nq * tlv * 64);
             for (size_t i = 0; i < nq; i++) tidx[i] = qidx[i] >> (4 * bt1.h);
-            PV_TRY(zp_merkle16_open_batch_bn254(ctx, (const uint64_t *)bt1.top, bt1.ntop, (const uint64_t *)tidx.data(), n_queries, (uint64_t *)topp.data()));
+            PV_TRY(zp_merkle16_open_batch_bn254(ctx, (const uint64_t *)bt1.top, bt1.ntop, (const uint64_t *)tidx.data(), (int32_t)nq, (uint64_t *)topp.data()));
             for (size_t i = 0; i < nq; i++) {
-                memcpy(&p_tr[i * pwt], &red[i * per + nval], ltw * 8);
-                memcpy(&p_tr[i * pwt + ltw], &topp[i * tlv * 64], tlv * 64 * 8);
+                memcpy(&o_tr.paths[i * pwt], &red[i * per + nval], ltw * 8);
+                memcpy(&o_tr.paths[i * pwt + ltw], &topp[i * tlv * 64], tlv * 64 * 8);
             }
             // stage 2 and quotient: replicated trees over whole columns, opened as prove_impl opens them
-            std::vector<u64> rows(nq);
-            if (n_s2) {
-                for (size_t i = 0; i < nq; i++) rows[i] = qidx[i] & (M2 - 1);
-                PV_TRY(zp_gather_rows(ctx, (const uint64_t *)ext2_kept, M2, (int32_t)W2g, (const uint64_t *)rows.data(), n_queries, (uint64_t *)v_s2.data()));
-                PV_TRY(T.open(tree2, M2, rows.data(), n_queries, p_s2.data()));
-            }
-            for (size_t i = 0; i < nq; i++) rows[i] = qidx[i] & (Mq - 1);
-            PV_TRY(zp_gather_rows(ctx, (const uint64_t *)dq_whole, Mq, (int32_t)Wqg, (const uint64_t *)rows.data(), n_queries, (uint64_t *)v_q.data()));
-            PV_TRY(T.open(treeq, Mq, rows.data(), n_queries, p_q.data()));
+            if (n_s2) PV_TRY(open_tree(ctx, T, ext2_kept, tree2, M2, W2g, qidx, &o_s2));
+            PV_TRY(open_tree(ctx, T, dq_whole, treeq, Mq, Wqg, qidx, &o_q));
         }
     }
-    struct FriOpen { std::vector<u64> vals, paths; size_t width, depth, pw, m; };
-    std::vector<FriOpen> fo(layers.size());
-    {
-        std::vector<u64> pos = qidx;
-        for (size_t li = 0; li < layers.size(); li++) {
-            const Layer &L = layers[li];
-            const size_t m = (size_t)1 << (L.lg - L.f);
-            for (u64 &p : pos) p &= (m - 1);
-            fo[li].width = (size_t)3 << L.f;
-            fo[li].depth = (size_t)(L.lg - L.f);
-            fo[li].m = m;
-            fo[li].pw = T.path_words(m);
-            fo[li].vals.resize(nq * fo[li].width);
-            fo[li].paths.resize(nq * fo[li].pw);
-            PV_TRY(zp_gather_rows(ctx, (const uint64_t *)L.data, m, (int32_t)fo[li].width, (const uint64_t *)pos.data(), n_queries, (uint64_t *)fo[li].vals.data()));
-            PV_TRY(T.open(L.tree, m, pos.data(), n_queries, fo[li].paths.data()));
-        }
-    }
+    std::vector<Opened> fo;
+    PV_TRY(fri_open(ctx, sh, T, fri, qidx, &fo));
 
-    if (bn) {       // every rank keeps the binary openings record (zp_stark_openings), as zp_stark_prove_bn128 does
-        std::vector<TreeOut> trees = {{W, M, root1, &v_tr, &p_tr, pwt}, {Wqg, Mq, rootq, &v_q, &p_q, pwq}};
-        if (n_s2) trees.push_back({W2g, M2, root2, &v_s2, &p_s2, pw2});
-        for (size_t li = 0; li < layers.size(); li++) trees.push_back({fo[li].width, fo[li].m, layers[li].root, &fo[li].vals, &fo[li].paths, fo[li].pw});
-        openings_record(ctx, tr, qidx, logm, trees);
-    }
+    // every rank writes the text, exactly what zp_stark_prove / zp_stark_prove_bn128 writes, and in BN128 mode keeps the openings record
+    return write_proof(ctx, sh, tr, {root1, rootq, root2, ev_all, ev_next, fri, nonce, qidx, o_tr, o_q, o_s2, fo});
+}
 
-    // the proof text: exactly what zp_stark_prove / zp_stark_prove_bn128 writes
-    std::string s;
-    s.reserve(nq * (Wt + Wq + 64) * 24 + (1 << 16));
-    s += "{\"air\":\"";
-    s += air_name;
-    s += "\",\"air_digest\":\"";
-    s += dg_hex;
-    s += "\",\"params\":{\"logn\":";
-    j_u64(s, (u64)logn); s += ",\"logb\":"; j_u64(s, (u64)logb); s += ",\"fri_logf\":"; j_u64(s, (u64)fri_logf);
-    s += ",\"fri_final_log\":"; j_u64(s, (u64)fri_final_log); s += ",\"n_queries\":"; j_u64(s, (u64)n_queries);
-    s += ",\"pow_bits\":"; j_u64(s, (u64)pow_bits);
-    if (bn) s += ",\"hash\":\"bn128\"";
-    s += "},\"root32\":"; j_u64(s, root32);
-    s += ",\"shift\":"; j_u64(s, shift);
-    s += ",\"publics\":"; j_list(s, (const u64 *)h_pubs, (size_t)n_pubs);
-    s += ",\"roots\":{\"trace\":"; j_root(s, root1, bn);
-    s += ",\"quotient\":"; j_root(s, rootq, bn);
-    if (n_s2) { s += ",\"stage2\":"; j_root(s, root2, bn); }
-    s += "},\"evals\":{\"z\":"; j_e3list(s, ev_all);
-    s += ",\"zw\":"; j_e3list(s, ev_next);
-    s += "},\"fri\":{\"roots\":[";
-    for (size_t li = 0; li < layers.size(); li++) { if (li) s += ','; j_root(s, layers[li].root, bn); }
-    s += "],\"final\":[";
-    for (int c = 0; c < 3; c++) { if (c) s += ','; j_list(s, &final_l[(size_t)c << final_log], (size_t)1 << final_log); }
-    s += "]},\"queries\":[";
-    for (size_t i = 0; i < nq; i++) {
-        if (i) s += ',';
-        s += "{\"index\":"; j_u64(s, qidx[i]);
-        auto opening = [&](const u64 *vals, size_t width, const u64 *path, size_t rows, size_t bin_depth) {
-            if (bn) j_opening_bn(s, vals, width, path, Trees::levels16(rows));
-            else j_opening(s, vals, width, path, bin_depth);
-        };
-        s += ",\"trace\":"; opening(&v_tr[i * W], W, &p_tr[i * pwt], M, depth);
-        s += ",\"quotient\":"; opening(&v_q[i * Wqg], Wqg, &p_q[i * pwq], Mq, depth);
-        if (n_s2) { s += ",\"stage2\":"; opening(&v_s2[i * W2g], W2g, &p_s2[i * pw2], M2, depth); }
-        s += ",\"fri\":[";
-        for (size_t li = 0; li < layers.size(); li++) {
-            if (li) s += ',';
-            opening(&fo[li].vals[i * fo[li].width], fo[li].width, &fo[li].paths[i * fo[li].pw], fo[li].m, fo[li].depth);
-        }
-        s += "]}";
-    }
-    s += ']';
-    if (pow_bits) { s += ",\"pow_nonce\":"; j_u64(s, nonce); }
-    s += '}';
-    char *buf = (char *)malloc(s.size() + 1);
-    if (!buf) { ctx->err = "out of host memory for the proof text"; return ZP_ERR_NOMEM; }
-    memcpy(buf, s.data(), s.size() + 1);
-    *out_json = buf;
-    *out_len = s.size();
+}  // namespace
+
+int32_t zpi_pool_alloc(zp_ctx *ctx, size_t bytes, void **out) {
+    DevBufs b(ctx);
+    u64 *p = nullptr;
+    const int32_t rc = b.alloc((bytes + 7) / 8, &p);
+    if (rc != ZP_OK) return rc;
+    b.forget(p);
+    *out = p;
+    return ZP_OK;
+}
+void zpi_pool_release(zp_ctx *ctx, void *p, size_t bytes) {
+    DevBufs b(ctx);
+    b.give_back(p, ((bytes + 7) / 8 ? (bytes + 7) / 8 : 1) * 8);
+}
+void zpi_sha256(const uint8_t *data, size_t len, uint8_t *out32) { Sha256::digest(data, len, out32); }
+
+extern "C" {
+
+int32_t zp_free_buffer(void *p) {
+    free(p);
     return ZP_OK;
 }
 
-}  // namespace
+// A generated constraint kernel (AIR plug-in ABI: stark/air.py writes it, `zpair_<air>_quotient` in its own shared library) for the one-call
+// provers of THIS ctx: proofs of the program with this digest evaluate their constraints through it instead of the interpreter -- the same
+// values (whole proofs are byte-identical whichever evaluator ran), 0.7 instead of 1.2 ms at 2^21 x 76.  fn = NULL forgets it.  Generated
+// kernels read the sparse periodic fixed columns too; the sharded provers take the row-window form registered below.
+int32_t zp_stark_set_air_kernel(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, void *quotient_fn) {
+    return set_air_kernel(ctx, "", h_program, program_words, quotient_fn);
+}
+// The ROW-WINDOW form of a generated constraint kernel (`zpair_<air>_quotient_rows` of the same library; round 6): the sharded provers of this ctx
+// (zp_stark_prove_sharded, zp_stark_prove_sharded_bn128: every rank evaluates the quotient on ITS rows) use it instead of the interpreter -- same
+// values, proofs byte-identical either way.  fn = NULL forgets it.
+int32_t zp_stark_set_air_kernel_rows(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, void *quotient_rows_fn) {
+    return set_air_kernel(ctx, "rows:", h_program, program_words, quotient_rows_fn);
+}
 
-namespace {
-int32_t prove_sharded_guarded(zp_comm *comm, bool bn, const char *air_name, const uint64_t *h_program, size_t program_words, const uint64_t *d_trace_local,
-                              size_t trace_words, const uint64_t *h_pubs, int32_t n_pubs, int32_t logn, int32_t logb, int32_t fri_logf,
-                              int32_t fri_final_log, int32_t n_queries, int32_t pow_bits, char **out_json, size_t *out_len) {
+// SHA-256 of a constraint program blob: the AIR digest.  out32 = the 32 digest bytes (a proof text names the first 8 as 16 hex digits);
+// out_words4 (may be NULL) = the four little-endian 64-bit words, each reduced mod p, that the provers absorb into the transcript.
+int32_t zp_program_digest(const uint64_t *h_program, size_t program_words, uint8_t *out32, uint64_t *out_words4) {
+    if (!h_program || !out32 || program_words == 0) return ZP_ERR_ARG;
+    Sha256::digest((const uint8_t *)h_program, program_words * 8, out32);
+    if (out_words4)
+        for (int i = 0; i < 4; i++) {
+            uint64_t w = 0;
+            for (int b = 7; b >= 0; b--) w = (w << 8) | out32[8 * i + b];
+            out_words4[i] = w % GL_P;
+        }
+    return ZP_OK;
+}
+
+static int32_t prove_entry(zp_ctx *ctx, bool bn, const ProveArgs &a) {
+    if (!ctx) return ZP_ERR_ARG;
+    if (a.out_json) *a.out_json = nullptr;
+    if (a.out_len) *a.out_len = 0;
+    return guarded(ctx, [&] { return prove_impl(ctx, bn, a); });
+}
+
+int32_t zp_stark_prove(zp_ctx *ctx, const char *air_name, const uint64_t *h_program, size_t program_words, const uint64_t *d_trace,
+                       size_t trace_words, const uint64_t *h_pubs, int32_t n_pubs, int32_t logn, int32_t logb, int32_t fri_logf,
+                       int32_t fri_final_log, int32_t n_queries, int32_t pow_bits, char **out_json, size_t *out_len) {
+    return prove_entry(ctx, false, {air_name, h_program, program_words, d_trace, trace_words, h_pubs, n_pubs, logn, logb, fri_logf, fri_final_log,
+                                    n_queries, pow_bits, out_json, out_len});
+}
+
+// the same prover in BN128-hash mode (the last STARK before the Groth16 wrap): 16-ary Poseidon-BN254 trees, transcript over the
+// BN254 scalar field, no grinding.  zp_set_poseidon_bn254(ctx, 17, ...) must have installed the tables.
+int32_t zp_stark_prove_bn128(zp_ctx *ctx, const char *air_name, const uint64_t *h_program, size_t program_words, const uint64_t *d_trace,
+                             size_t trace_words, const uint64_t *h_pubs, int32_t n_pubs, int32_t logn, int32_t logb, int32_t fri_logf,
+                             int32_t fri_final_log, int32_t n_queries, char **out_json, size_t *out_len) {
+    return prove_entry(ctx, true, {air_name, h_program, program_words, d_trace, trace_words, h_pubs, n_pubs, logn, logb, fri_logf, fri_final_log,
+                                   n_queries, 0, out_json, out_len});
+}
+
+// Binary openings of the LAST BN128-mode proof made on this ctx (what its text carries under "roots", "fri.roots" and "queries", and the
+// transcript behind its challenges), u64 words:
+//   [0] "PZOPEN03" [1] n_queries [2] n_trees [3] log2 of the LDE size (bits of a query index), then per tree (trace, quotient, [stage 2], FRI
+//   layers): values per leaf, leaves, levels of the 16-ary tree; per tree the root (4 words); per query: the index, then per tree values[width]
+//   and path[levels][16][4]; then the transcript: n_blocks, n_rates, the absorbed blocks [n_blocks][16][4], the rate elements the indices
+//   were read from [n_rates][16][4], the capacity after every permutation [n_blocks + n_rates - 1][4]; n_challenges and the rate element
+//   behind every challenge, in squeeze order [n_challenges][4].
+// *out points into the ctx (valid until the next proof on it); ZP_ERR_ARG when there is none.
+int32_t zp_stark_openings(zp_ctx *ctx, const uint64_t **out, size_t *words) {
+    if (!ctx || !out || !words) return ZP_ERR_ARG;
+    ZP_ARG(ctx, !ctx->last_openings.empty(), "no BN128-mode proof has been made on this ctx");
+    *out = (const uint64_t *)ctx->last_openings.data();
+    *words = ctx->last_openings.size();
+    return ZP_OK;
+}
+
+int32_t zp_sha256(const uint8_t *data, size_t len, uint8_t *out32) {
+    if ((!data && len) || !out32) return ZP_ERR_ARG;
+    Sha256::digest(data, len, out32);
+    return ZP_OK;
+}
+
+// Whatever stops a rank of a sharded proof -- a failed allocation, a HIP error, an exception -- its peers are inside the same call, heading
+// for the next collective: zpi_comm_fail takes the communicator down so that they return ZP_ERR_COMM instead of waiting for ever.
+static int32_t prove_sharded_entry(zp_comm *comm, bool bn, const ProveArgs &a) {
     if (!comm) return ZP_ERR_ARG;
     zp_ctx *ctx = zpi_comm_ctx(comm);
-    if (out_json) *out_json = nullptr;
-    if (out_len) *out_len = 0;
-    // Whatever stops this rank -- a failed allocation, a HIP error, an exception -- its peers are inside the same call, heading for
-    // the next collective: zpi_comm_fail takes the communicator down so that they return ZP_ERR_COMM instead of waiting for ever.
-    try {
-        return zpi_comm_fail(comm, prove_sharded_impl(comm, ctx, air_name, h_program, program_words, d_trace_local, trace_words, h_pubs, n_pubs, logn, logb,
-                                                      fri_logf, fri_final_log, n_queries, pow_bits, bn, out_json, out_len));
-    } catch (const std::bad_alloc &) {
-        try { ctx->err = "out of host memory while building the proof"; } catch (...) {}
-        return zpi_comm_fail(comm, ZP_ERR_NOMEM);
-    } catch (const std::exception &e) {
-        try { ctx->err = std::string("internal error: ") + e.what(); } catch (...) {}
-        return zpi_comm_fail(comm, ZP_ERR_INTERNAL);
-    } catch (...) {
-        return zpi_comm_fail(comm, ZP_ERR_INTERNAL);
-    }
+    if (a.out_json) *a.out_json = nullptr;
+    if (a.out_len) *a.out_len = 0;
+    return zpi_comm_fail(comm, guarded(ctx, [&] { return prove_sharded_impl(comm, ctx, bn, a); }));
 }
-}  // namespace
 
-extern "C" int32_t zp_stark_prove_sharded(zp_comm *comm, const char *air_name, const uint64_t *h_program, size_t program_words,
-                                          const uint64_t *d_trace_local, size_t trace_words, const uint64_t *h_pubs, int32_t n_pubs, int32_t logn,
-                                          int32_t logb, int32_t fri_logf, int32_t fri_final_log, int32_t n_queries, int32_t pow_bits, char **out_json,
-                                          size_t *out_len) {
-    return prove_sharded_guarded(comm, false, air_name, h_program, program_words, d_trace_local, trace_words, h_pubs, n_pubs, logn, logb, fri_logf,
-                                 fri_final_log, n_queries, pow_bits, out_json, out_len);
+int32_t zp_stark_prove_sharded(zp_comm *comm, const char *air_name, const uint64_t *h_program, size_t program_words, const uint64_t *d_trace_local,
+                               size_t trace_words, const uint64_t *h_pubs, int32_t n_pubs, int32_t logn, int32_t logb, int32_t fri_logf,
+                               int32_t fri_final_log, int32_t n_queries, int32_t pow_bits, char **out_json, size_t *out_len) {
+    return prove_sharded_entry(comm, false, {air_name, h_program, program_words, d_trace_local, trace_words, h_pubs, n_pubs, logn, logb, fri_logf,
+                                             fri_final_log, n_queries, pow_bits, out_json, out_len});
 }
 
 // the sharded prover in BN128-hash mode: zp_stark_prove_bn128's text (and openings record, on every rank) from W/world columns per rank.
 // The trace tree is sharded by rows and must have one row per leaf (more than 28 trace columns: the verifier AIR of the final STARK);
 // zp_set_poseidon_bn254(ctx, 17, ...) on every rank's ctx.
-extern "C" int32_t zp_stark_prove_sharded_bn128(zp_comm *comm, const char *air_name, const uint64_t *h_program, size_t program_words,
-                                                const uint64_t *d_trace_local, size_t trace_words, const uint64_t *h_pubs, int32_t n_pubs,
-                                                int32_t logn, int32_t logb, int32_t fri_logf, int32_t fri_final_log, int32_t n_queries,
-                                                char **out_json, size_t *out_len) {
-    return prove_sharded_guarded(comm, true, air_name, h_program, program_words, d_trace_local, trace_words, h_pubs, n_pubs, logn, logb, fri_logf,
-                                 fri_final_log, n_queries, 0, out_json, out_len);
+int32_t zp_stark_prove_sharded_bn128(zp_comm *comm, const char *air_name, const uint64_t *h_program, size_t program_words, const uint64_t *d_trace_local,
+                                     size_t trace_words, const uint64_t *h_pubs, int32_t n_pubs, int32_t logn, int32_t logb, int32_t fri_logf,
+                                     int32_t fri_final_log, int32_t n_queries, char **out_json, size_t *out_len) {
+    return prove_sharded_entry(comm, true, {air_name, h_program, program_words, d_trace_local, trace_words, h_pubs, n_pubs, logn, logb, fri_logf,
+                                            fri_final_log, n_queries, 0, out_json, out_len});
 }
+
+}  // extern "C"
