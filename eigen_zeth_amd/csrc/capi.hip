@@ -547,13 +547,13 @@ int32_t zp_ntt_plan_json(zp_ctx *ctx, int32_t logn, char *buf, size_t buflen) {
     ZP_TRY(zpi_get_plan(ctx, logn, false, &pl));
     std::string s = "{\"logn\": " + std::to_string(logn) + ", \"passes\": [";
     for (int i = 0; i < pl->npass; i++) {
-        const NttPass &p = pl->pass[i];
+        const NttPassShape sh = zpi_plan_pass_shape(ctx, pl, i);
         if (i) s += ", ";
-        s += "{\"radix_log\": " + std::to_string(p.L) + ", \"rounds\": [" + std::to_string(p.A1) + ", " +
-             std::to_string(p.A2) + ", " + std::to_string(p.A3) + "], \"tile\": " + std::to_string(p.L == 8 ? (1 << ctx->tune_logt) : p.L == 9 ? (1 << ctx->tune_logt9) : (1 << p.logT)) + "}";
+        s += "{\"radix_log\": " + std::to_string(pl->pass[i].L) + ", \"rounds\": [" + std::to_string(sh.A1) + ", " +
+             std::to_string(sh.A2) + ", " + std::to_string(sh.A3) + "], \"tile\": " + std::to_string(1 << sh.logT) + "}";
     }
     s += "], \"first_pass_table\": ";   // the transposing pass multiplies by the full precomputed table (MODE 3) instead of per-lane chains
-    s += (pl->npass >= 1 && logn > 12 && !pl->tw1_unavailable && logn <= ctx->tune_ntt_tw1 && logn <= 28 && pl->pass[0].A3 == 0 && pl->pass[0].L >= 7) ? "true" : "false";
+    s += zpi_plan_uses_tw1(ctx, pl) ? "true" : "false";
     s += ", \"small_kernel\": ";
     s += (logn <= 12) ? "true" : "false";
     if (logn + 1 <= 32) {     // the extension (blow-up 2) of columns of this size, as the provers issue it (no coefficient store since round 5)

@@ -13,13 +13,13 @@
 #define ZP_SHIFT_DEFAULT 49ULL
 
 struct NttPass {
-    int L, A1, A2, A3, logT;
+    int L;         // log2 of the radix; the rounds and the tile width of a launch come from zpi_pass_shape
     int logPprev;  // log2 of the product of the radices of the previous passes
 };
 
 struct NttPlan {
     int logn = 0;
-    bool inverse = false;
+    bool inverse = false;     // the direction the tables below were made for: what a pass of this plan scales by
     int npass = 0;
     NttPass pass[6];
     int lb = 0;               // twiddle split: w^e = twl[e & (2^lb-1)] * twh[e >> lb]
@@ -55,9 +55,9 @@ struct zp_ctx {
     bool poseidon_dirty = true;
     bool mds_is_default = false;  // compile-time literal fast path for the documented default matrix
     // plans
-    std::map<int, NttPlan> plans;  // key = logn*2 + inverse
+    std::map<int, NttPlan> plans;  // key = (logn, inverse, ntt_maxl, ntt_order, role) packed: zpi_get_plan_role
     std::vector<CosetTable> cosets;
-    // scratch (two ping-pong buffers, grown on demand)
+    // scratch (six slots, each grown on demand)
     u64 *scratch[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // 0, 1: NTT ping-pong; 2: LDE coefficients; 3: small uploads; 4: fixed-column periods; 5: zp_ood_eval's weight vector
     size_t scratch_elems[6] = {0, 0, 0, 0, 0, 0};
     // zp_ood_eval: the barycentric weights last made (scratch 5) are for this domain size and point
@@ -164,9 +164,16 @@ int32_t zpi_pinned(zp_ctx *ctx, size_t bytes, void **out);
 // small copies through the pinned staging buffer (synchronous on the ctx stream)
 int32_t zpi_d2h_small(zp_ctx *ctx, void *h_dst, const void *d_src, size_t bytes);
 int32_t zpi_h2d_small(zp_ctx *ctx, void *d_dst, const void *h_src, size_t bytes);
+int32_t zpi_upload(zp_ctx *ctx, const std::vector<u64> &h, u64 **d);   // a new device buffer holding h (synchronous)
 #define ZP_SMALL_COPY (4u << 20)
 int32_t zpi_get_plan(zp_ctx *ctx, int logn, bool inverse, NttPlan **out);
 int32_t zpi_get_plan_role(zp_ctx *ctx, int logn, bool inverse, int role, NttPlan **out);   // role 1 / 2: ends / starts with a radix-256 pass (csrc/ntt.hip)
+// The shape of one pass of radix 2^L: register rounds of radix 2^A1, 2^A2, 2^A3 on tiles of 2^logT columns.  Decided by the knobs ntt_logt / ntt_logt9 / ntt_logt12, by whether the transform has more than
+// 2^28 rows (big) and, for L = 12, by whether the pass transposes (a first pass) or multiplies (inter-pass twiddle, 1/N or a coset power).  A1 == 0: no kernel is built for this pass.
+struct NttPassShape { int A1, A2, A3, logT; };
+NttPassShape zpi_pass_shape(const zp_ctx *ctx, int L, bool big, bool transpose, bool multiplies);
+NttPassShape zpi_plan_pass_shape(const zp_ctx *ctx, const NttPlan *pl, int i);   // pass i of a plan run on its own (no post-scale)
+bool zpi_plan_uses_tw1(const zp_ctx *ctx, const NttPlan *pl);                      // the first pass multiplies by the plan's full table (d_tw1)
 int32_t zpi_lde_plan_json(zp_ctx *ctx, int logn, int want_coef, std::string *out);           // which path zp_lde takes at this size
 int32_t zpi_get_coset(zp_ctx *ctx, int logn, u64 shift, u64 pre, CosetTable **out);
 int32_t zpi_poseidon_sync_tables(zp_ctx *ctx);

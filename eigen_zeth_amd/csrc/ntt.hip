@@ -15,7 +15,6 @@
 // bank-conflict free (MI355X_MICROARCH.md, LDS: ds_read_b64 = 2x32 lanes over 64 banks).
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
 #include <cstring>
 #include <string>
 
@@ -103,7 +102,6 @@ __device__ __forceinline__ u64 tw_lookup(const u64 *lo, const u64 *hi, int lb, u
     return gl_mul(a, b);
 }
 
-
 // radix-2^A DIF with the canonical root c = 2^12 (order 16): every twiddle is a shift.
 // v[p] receives DFT_c[brev(p)];  the caller maps that to the user's root, w_16 = c^j0:
 // DFT_user[k'] = DFT_c[j0*k' mod 2^A]  =>  register p holds user index  k' = j0inv*brev(p) mod 2^A.
@@ -144,6 +142,20 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// the read half of an exchange: the inputs of the next round (radix 2^ANEXT at bit POSNEXT of the slot) from LDS
+template <typename G, int ANEXT, int POSNEXT>
+__device__ __forceinline__ void exchange_read(u64 *v, const u64 *lds, int tid) {
+    constexpr int GN = 16 >> ANEXT;
+#pragma unroll
+    for (int g = 0; g < GN; g++) {
+        const int gamma = g * G::NT + tid;
+        const int t = gamma & (G::T - 1), o = gamma >> G::LT;
+#pragma unroll
+        for (int j = 0; j < (1 << ANEXT); j++)
+            v[g * (1 << ANEXT) + j] = lds[G::lpos(slot_of(o, j, POSNEXT, ANEXT), t)];
+    }
+}
+
 // twr: LDS copy of w_(2^(POS+A))^e (TWSH = 0) or, for the radix-2^11 / 2^12 passes whose LDS is all tile, the global
 // table of w_4096^e (TWSH = 12 - (POS + A)); 32 KiB, read by every workgroup, L2 / L1 resident
 template <typename G, int A, int POS, int ANEXT, int POSNEXT, int TWSH>
@@ -171,15 +183,7 @@ __device__ __forceinline__ void exchange2(u64 *v, u64 *lds, const u64 *twr, int 
         }
     }
     lds_barrier();
-    constexpr int GN = 16 >> ANEXT;
-#pragma unroll
-    for (int g = 0; g < GN; g++) {
-        const int gamma = g * G::NT + tid;
-        const int t = gamma & (G::T - 1), o = gamma >> G::LT;
-#pragma unroll
-        for (int j = 0; j < (1 << ANEXT); j++)
-            v[g * (1 << ANEXT) + j] = lds[G::lpos(slot_of(o, j, POSNEXT, ANEXT), t)];
-    }
+    exchange_read<G, ANEXT, POSNEXT>(v, lds, tid);
 }
 
 // ---- the same two building blocks on four signed 24-bit-position limbs (gl_limb.hpp): butterflies are carry-free 32-bit adds, every
@@ -256,14 +260,25 @@ __device__ __forceinline__ void exchange2_l4(const gl_l4 *x, u64 *v, u64 *lds, c
         }
     }
     lds_barrier();
-    constexpr int GN = 16 >> ANEXT;
+    exchange_read<G, ANEXT, POSNEXT>(v, lds, tid);
+}
+
+// ---- the step of a tile that ntt_pass2_kernel and lde_seam_kernel share
+// Table copy-out of a first pass: the tile sits in LDS, so v is dead and its registers take the 16 factors (twb: the plan's table at this tile) of the elements this lane copies out to blk
+template <typename G>
+__device__ __forceinline__ void table_copy_out(u64 *v, const u64 *lds, const u64 *twb, u64 *blk, int tid) {
+    constexpr int L = G::L, NT = G::NT;
 #pragma unroll
-    for (int g = 0; g < GN; g++) {
-        const int gamma = g * G::NT + tid;
-        const int t = gamma & (G::T - 1), o = gamma >> G::LT;
+    for (int i = 0; i < 16; i++) v[i] = twb[i * NT + tid];       // cacheable: the other columns of this tile hit in L2
+    lds_barrier();
 #pragma unroll
-        for (int j = 0; j < (1 << ANEXT); j++)
-            v[g * (1 << ANEXT) + j] = lds[G::lpos(slot_of(o, j, POSNEXT, ANEXT), t)];
+    for (int i = 0; i < 16; i += 2) {
+        const int ia = i * NT + tid, ib = (i + 1) * NT + tid;
+        u64 xa = lds[G::lpos(G::sigma_of_k(ia & ((1 << L) - 1)), ia >> L)];
+        u64 xb = lds[G::lpos(G::sigma_of_k(ib & ((1 << L) - 1)), ib >> L)];
+        gl_mul2(xa, v[i], xb, v[i + 1]);
+        ZP_STG(&blk[ia], xa);
+        ZP_STG(&blk[ib], xb);
     }
 }
 
@@ -554,21 +569,7 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
             }
         }
         if constexpr (TW1) {
-            // v is dead (the tile sits in LDS): its registers take the 16 factors of the elements this lane copies out
-            const u64 *twb = a.tw1 + (u0 << L);
-#pragma unroll
-            for (int i = 0; i < 16; i++) v[i] = twb[i * NT + tid];       // cacheable: the other columns of this tile hit in L2
-            lds_barrier();
-            u64 *blk = dst + (u0 << L);
-#pragma unroll
-            for (int i = 0; i < 16; i += 2) {
-                const int ia = i * NT + tid, ib = (i + 1) * NT + tid;
-                u64 xa = lds[G::lpos(G::sigma_of_k(ia & ((1 << L) - 1)), ia >> L)];
-                u64 xb = lds[G::lpos(G::sigma_of_k(ib & ((1 << L) - 1)), ib >> L)];
-                gl_mul2(xa, v[i], xb, v[i + 1]);
-                ZP_STG(&blk[ia], xa);
-                ZP_STG(&blk[ib], xb);
-            }
+            table_copy_out<G>(v, lds, a.tw1 + (u0 << L), dst + (u0 << L), tid);
         } else if constexpr (TRANSPOSE) {
             lds_barrier();
             u64 *blk = dst + (u0 << L);
@@ -614,7 +615,7 @@ struct SeamArgs {
 // per SIMD, 1.37 ms spilling at three, against 0.70 ms: profiles/r4_lde_seam_ab.txt.  Removed.)
 __global__ void __launch_bounds__(256, 4) lde_seam_kernel(SeamArgs a, int tiles_per_wg) {
     using G = Geo<4, 4, 0, 4>;
-    constexpr int L = 8, R = 256, T = 16, NT = 256, LOGT = 4;
+    constexpr int L = 8, R = 256, T = 16, LOGT = 4;
     extern __shared__ __attribute__((aligned(16))) u64 lds[];
     u64 *tab = lds + R * T;        // 1/N shift^(k N/256)
     u64 *twr_i = tab + R;          // inter-round twiddles of the inverse pass
@@ -711,20 +712,7 @@ __global__ void __launch_bounds__(256, 4) lde_seam_kernel(SeamArgs a, int tiles_
                 }
             }
             const u64 u0f = ((u64)par << logNR) + u0;
-            const u64 *twb = a.tw1 + (u0f << L);
-#pragma unroll
-            for (int i = 0; i < 16; i++) v[i] = twb[i * NT + tid];       // cacheable: the other columns of this tile hit in L2
-            lds_barrier();
-            u64 *blk = dst + (u0f << L);
-#pragma unroll
-            for (int i = 0; i < 16; i += 2) {
-                const int ia = i * NT + tid, ib = (i + 1) * NT + tid;
-                u64 xa = lds[G::lpos(G::sigma_of_k(ia & ((1 << L) - 1)), ia >> L)];
-                u64 xb = lds[G::lpos(G::sigma_of_k(ib & ((1 << L) - 1)), ib >> L)];
-                gl_mul2(xa, v[i], xb, v[i + 1]);
-                ZP_STG(&blk[ia], xa);
-                ZP_STG(&blk[ib], xb);
-            }
+            table_copy_out<G>(v, lds, a.tw1 + (u0f << L), dst + (u0f << L), tid);
             lds_barrier();      // the tile is reused by the second forward tile / the next inverse tile
         }
     }
@@ -835,8 +823,28 @@ __global__ void __launch_bounds__(256) tw1_fill_kernel(u64 *out, int logn, int L
     out[i] = tw_lookup(lo, hi, lb, (u * k) & ((1ULL << logn) - 1));
 }
 
+using PassKernel = void (*)(PassArgs, int);
+
+// The instantiation a launch takes.  First passes: the table form (MODE 3, never BIG, two-round shapes only) with or without limb
+// butterflies, or the per-lane chain (MODE 1); either reads a zero-padded input or a full one.  Later passes: `mode` 0..2, limb or not.
+template <int A1, int A2, int A3, int LOGT, bool BIG>
+PassKernel pick_pass_kernel(bool transpose, bool table, bool padded, int mode, bool limb) {
+    constexpr bool CAN_TABLE = !BIG && A3 == 0, CAN_LIMB = !BIG && A1 + A2 + A3 <= 8;
+    if constexpr (CAN_TABLE) {
+        if (table && limb) return padded ? ntt_pass2_kernel<A1, A2, A3, LOGT, true, true, 3, false, CAN_LIMB> : ntt_pass2_kernel<A1, A2, A3, LOGT, true, false, 3, false, CAN_LIMB>;
+        if (table) return padded ? ntt_pass2_kernel<A1, A2, A3, LOGT, true, true, 3, false> : ntt_pass2_kernel<A1, A2, A3, LOGT, true, false, 3, false>;
+    }
+    if (transpose) return padded ? ntt_pass2_kernel<A1, A2, A3, LOGT, true, true, 1, BIG> : ntt_pass2_kernel<A1, A2, A3, LOGT, true, false, 1, BIG>;
+    if (limb) return mode == 2 ? ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 2, BIG, CAN_LIMB>
+                   : mode == 1 ? ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 1, BIG, CAN_LIMB>
+                               : ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 0, BIG, CAN_LIMB>;
+    return mode == 2 ? ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 2, BIG>
+         : mode == 1 ? ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 1, BIG>
+                     : ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 0, BIG>;
+}
+
 template <int A1, int A2, int A3, int LOGT, bool BIG = false>
-int32_t launch_pass2(zp_ctx *ctx, const PassArgs &a, bool transpose, int W) {
+int32_t launch_pass2(zp_ctx *ctx, PassArgs a, bool transpose, int W) {
     using G = Geo<A1, A2, A3, LOGT>;
     const u64 tiles = (1ULL << (a.logn - G::L)) >> LOGT;
     // tiles per workgroup: a power of two that divides the tile count and (passes >= 2) keeps a
@@ -844,166 +852,124 @@ int32_t launch_pass2(zp_ctx *ctx, const PassArgs &a, bool transpose, int W) {
     int tpw = ctx->tune_tpw;
     while (tpw > 1 && (tiles % tpw != 0 || tiles / tpw * (u64)W < (u64)ctx->num_cu * 4)) tpw >>= 1;
     dim3 grid((unsigned)(tiles / tpw), (unsigned)W), block(G::NT);
-    // tile + (per-tile table: non-transposing passes with a multiplication) + (LDS copies of the inter-round twiddles, L <= 10)
-    const bool has_tab = !transpose && (a.flags & 7) != 0;
+    // table form of a first pass: a one-dimensional grid, XCD-ordered (ntt_pass2_kernel, MODE 3)
+    const bool table = !BIG && A3 == 0 && transpose && a.tw1 && (grid.x & 7u) == 0;
+    // MODE of a later pass: 2 = coset post-scale, 1 = per-tile table (inter-pass twiddle and / or 1/N), 0 = plain
+    const int mode = transpose ? 0 : (a.flags & 4) ? 2 : (a.flags & 3) ? 1 : 0;
     // limb-form butterflies (gl_limb.hpp; knob ntt_limb): every pass with LDS twiddle copies except a first pass without its table
-    constexpr bool CAN_LIMB = !BIG && G::L <= 8;      // (radix 2^9 and up: tiles of 64 / 128 KiB leave no room for the 32-byte table records)
-    const bool limb = CAN_LIMB && ctx->tune_ntt_limb != 0 && !(transpose && !(A3 == 0 && a.tw1 && (grid.x & 7u) == 0));
+    // (radix 2^9 and up: tiles of 64 / 128 KiB leave no room for the 32-byte table records)
+    const bool limb = !BIG && G::L <= 8 && ctx->tune_ntt_limb != 0 && (!transpose || table);
+    // tile + (per-tile table: non-transposing passes with a multiplication) + (LDS copies of the inter-round twiddles, L <= 10)
     const size_t rec = limb ? 4 : 1;
-    const size_t shmem = ((size_t)G::R * G::T + (has_tab ? G::R * rec : 0) + (G::L <= 10 ? (G::R + (1 << (A2 + A3))) * rec : 0)) * sizeof(u64);
-    if constexpr (!BIG && A3 == 0) {
-        if (transpose && a.tw1 && (grid.x & 7u) == 0) {
-            const bool padded = a.in_valid != (1ULL << a.logn);
-            auto k = limb ? (padded ? ntt_pass2_kernel<A1, A2, A3, LOGT, true, true, 3, false, CAN_LIMB> : ntt_pass2_kernel<A1, A2, A3, LOGT, true, false, 3, false, CAN_LIMB>)
-                          : (padded ? ntt_pass2_kernel<A1, A2, A3, LOGT, true, true, 3, false> : ntt_pass2_kernel<A1, A2, A3, LOGT, true, false, 3, false>);
-            PassArgs b = a;
-            b.ncols = W;
-            hipLaunchKernelGGL(k, dim3(grid.x * (unsigned)W), block, shmem, ctx->stream, b, tpw);
-            ZP_HIP(ctx, hipGetLastError());
-            return ZP_OK;
-        }
+    const size_t shmem = ((size_t)G::R * G::T + (mode >= 1 ? G::R * rec : 0) + (G::L <= 10 ? (G::R + (1 << (A2 + A3))) * rec : 0)) * sizeof(u64);
+    const PassKernel k = pick_pass_kernel<A1, A2, A3, LOGT, BIG>(transpose, table, a.in_valid != (1ULL << a.logn), mode, limb);
+    if (shmem > 65536) ZP_HIP(ctx, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    if (table) {
+        a.ncols = W;
+        grid = dim3(grid.x * (unsigned)W);
     }
-    if (transpose) {
-        const bool padded = a.in_valid != (1ULL << a.logn);
-        auto k = padded ? ntt_pass2_kernel<A1, A2, A3, LOGT, true, true, 1, BIG> : ntt_pass2_kernel<A1, A2, A3, LOGT, true, false, 1, BIG>;
-        if (shmem > 65536) ZP_HIP(ctx, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-        hipLaunchKernelGGL(k, grid, block, shmem, ctx->stream, a, tpw);
-    } else {
-        auto k = limb ? ((a.flags & 4) ? ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 2, BIG, CAN_LIMB>
-                         : (a.flags & 3) ? ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 1, BIG, CAN_LIMB>
-                                         : ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 0, BIG, CAN_LIMB>)
-                      : ((a.flags & 4) ? ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 2, BIG>
-                         : (a.flags & 3) ? ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 1, BIG>
-                                         : ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 0, BIG>);
-        if (shmem > 65536) ZP_HIP(ctx, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-        hipLaunchKernelGGL(k, grid, block, shmem, ctx->stream, a, tpw);
-    }
+    hipLaunchKernelGGL(k, grid, block, shmem, ctx->stream, a, tpw);
     ZP_HIP(ctx, hipGetLastError());
     return ZP_OK;
 }
 
+constexpr int shape_key(int A1, int A2, int A3, int logT, bool big) { return (((A1 * 8 + A2) * 8 + A3) * 8 + logT) * 2 + big; }
+
+// one case per shape that is built: the list of what zpi_pass_shape can return
 int32_t dispatch_pass(zp_ctx *ctx, const NttPass &p, const PassArgs &a, bool transpose, int W) {
-    if (a.logn > 28) {   // 64-bit lane offsets: only the shapes the default plan uses above 2^28 rows (digits 7 and 8)
-        switch (p.L) {
-            case 7: return launch_pass2<4, 3, 0, 5, true>(ctx, a, transpose, W);
-            case 8: return launch_pass2<4, 4, 0, 4, true>(ctx, a, transpose, W);
-            default: ctx->err = "pass radix not built for transforms above 2^28 rows"; return ZP_ERR_UNSUPPORTED;
-        }
+    const bool big = a.logn > 28;
+    const NttPassShape s = zpi_pass_shape(ctx, p.L, big, transpose, (a.flags & 7) != 0);
+#define ZP_PASS_SHAPE(A1, A2, A3, LOGT, BIG) case shape_key(A1, A2, A3, LOGT, BIG): return launch_pass2<A1, A2, A3, LOGT, BIG>(ctx, a, transpose, W)
+    switch (shape_key(s.A1, s.A2, s.A3, s.logT, big)) {
+        ZP_PASS_SHAPE(3, 2, 0, 5, false);
+        ZP_PASS_SHAPE(3, 3, 0, 5, false);
+        ZP_PASS_SHAPE(4, 3, 0, 5, false);
+        ZP_PASS_SHAPE(4, 3, 0, 5, true);
+        ZP_PASS_SHAPE(4, 4, 0, 4, false);
+        ZP_PASS_SHAPE(4, 4, 0, 4, true);
+        ZP_PASS_SHAPE(4, 4, 0, 5, false);
+        ZP_PASS_SHAPE(3, 3, 3, 4, false);
+        ZP_PASS_SHAPE(3, 3, 3, 5, false);
+        ZP_PASS_SHAPE(4, 3, 3, 4, false);
+        ZP_PASS_SHAPE(4, 4, 3, 3, false);
+        ZP_PASS_SHAPE(4, 4, 4, 1, false);
+        ZP_PASS_SHAPE(4, 4, 4, 2, false);
+        default: ctx->err = big ? "pass radix not built for transforms above 2^28 rows" : "unsupported pass radix"; return ZP_ERR_UNSUPPORTED;
     }
-    switch (p.L) {
-        case 5: return launch_pass2<3, 2, 0, 5>(ctx, a, transpose, W);
-        case 6: return launch_pass2<3, 3, 0, 5>(ctx, a, transpose, W);
-        case 7: return launch_pass2<4, 3, 0, 5>(ctx, a, transpose, W);
-        case 8: return ctx->tune_logt == 4 ? launch_pass2<4, 4, 0, 4>(ctx, a, transpose, W) : launch_pass2<4, 4, 0, 5>(ctx, a, transpose, W);
-        case 9: return ctx->tune_logt9 == 4 ? launch_pass2<3, 3, 3, 4>(ctx, a, transpose, W) : launch_pass2<3, 3, 3, 5>(ctx, a, transpose, W);
-        // 1024-thread workgroups, 128 KiB tiles: two-pass plans up to 2^20 / 2^22 / 2^24 (runs of 128 / 64 / 32 bytes)
-        case 10: return launch_pass2<4, 3, 3, 4>(ctx, a, transpose, W);
-        case 11: return launch_pass2<4, 4, 3, 3>(ctx, a, transpose, W);
-        // (round 6, review item 4: knob ntt_logt12 = 1 -- 512-thread workgroups on 64-KiB tiles of 2 columns, TWO workgroups per CU, 16-byte runs;
-        //  a pass with a per-tile twiddle table needs 32 KiB more and stays on the 4-column tile)
-        case 12: return (ctx->tune_logt12 == 1 && (transpose || (a.flags & 7) == 0)) ? launch_pass2<4, 4, 4, 1>(ctx, a, transpose, W)
-                                                                                     : launch_pass2<4, 4, 4, 2>(ctx, a, transpose, W);
-        default: ctx->err = "unsupported pass radix"; return ZP_ERR_UNSUPPORTED;
+#undef ZP_PASS_SHAPE
+}
+
+// brackets one launch with HIP events on the ctx stream when profiling is on (zp_get_pass_timings).  radix_log: L of a pass,
+// -L of a first pass, 88 of the seam kernel (inverse radix 2^8 + forward radix 2^8)
+struct PassTimer {
+    zp_ctx *ctx;
+    zp_ctx::PassEv ev;
+    bool on;
+    PassTimer(zp_ctx *c, int radix_log) : ctx(c), on(c->profiling) {
+        ev.radix_log = radix_log;
+        on = on && hipEventCreate(&ev.a) == hipSuccess && hipEventCreate(&ev.b) == hipSuccess && hipEventRecord(ev.a, ctx->stream) == hipSuccess;
+    }
+    ~PassTimer() {
+        if (on && hipEventRecord(ev.b, ctx->stream) == hipSuccess) ctx->pass_events.push_back(ev);
+    }
+};
+
+// what the last pass (or the small kernel) does to its outputs: 1/N of an inverse transform, the coset table of an LDE
+template <typename Args>
+void set_output_scaling(Args &a, bool inverse, const CosetTable *post_scale) {
+    if (inverse) a.flags |= 2;
+    if (post_scale) {
+        a.flags |= 4;
+        a.csl = post_scale->d_lo;
+        a.csh = post_scale->d_hi;
+        a.cslb = post_scale->lb;
     }
 }
 
-void split_digit(NttPass &p) {
-    switch (p.L) {
-        case 5: p.A1 = 3; p.A2 = 2; p.A3 = 0; break;
-        case 6: p.A1 = 3; p.A2 = 3; p.A3 = 0; break;
-        case 7: p.A1 = 4; p.A2 = 3; p.A3 = 0; break;
-        case 8: p.A1 = 4; p.A2 = 4; p.A3 = 0; break;
-        case 10: p.A1 = 4; p.A2 = 3; p.A3 = 3; break;
-        case 11: p.A1 = 4; p.A2 = 4; p.A3 = 3; break;
-        case 12: p.A1 = 4; p.A2 = 4; p.A3 = 4; break;
-        default: p.A1 = 3; p.A2 = 3; p.A3 = 3; break;
-    }
-    p.logT = 5;
+// columns per launch: chunks such that a ping-pong scratch buffer (and the LDE's scaled-coefficient buffer) stays <= 2 GiB.  2^28 elements
+// per launch since round 4 (profiles/r4_chunk_sweep.txt: NTT 2^20 .. 2^25 0-3 % faster than at 2^27, the first pass's shared twiddle table
+// now serving 16 columns of a tile; 2^29 adds nothing.  Round 2, before that table, measured the opposite: profiles/r2_chunk_sweep.txt)
+int chunk_columns(const zp_ctx *ctx, int logn, int W) {
+    const int wc = (int)((1ULL << (ctx->tune_ntt_chunk_log > 0 ? ctx->tune_ntt_chunk_log : 28)) >> logn);
+    return wc < 1 ? 1 : wc > W ? W : wc;
 }
 
 }  // namespace
 
-int32_t zpi_scratch(zp_ctx *ctx, int which, size_t elems, u64 **out) {
-    if (ctx->scratch_elems[which] < elems) {
-        if (ctx->scratch[which]) {
-            ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            ZP_HIP(ctx, hipFree(ctx->scratch[which]));
-            ctx->scratch[which] = nullptr;
-            ctx->scratch_elems[which] = 0;
-        }
-        ZP_HIP(ctx, hipMalloc((void **)&ctx->scratch[which], elems * sizeof(u64)));
-        ctx->scratch_elems[which] = elems;
+NttPassShape zpi_pass_shape(const zp_ctx *ctx, int L, bool big, bool transpose, bool multiplies) {
+    // L = 5 .. 12 at the default knobs.  Radix 2^10 .. 2^12: 1024-thread workgroups on 128 KiB tiles, two-pass plans up to 2^20 / 2^22 / 2^24
+    // (runs of 128 / 64 / 32 bytes)
+    static const NttPassShape by_l[8] = {{3, 2, 0, 5}, {3, 3, 0, 5}, {4, 3, 0, 5}, {4, 4, 0, 4}, {3, 3, 3, 4}, {4, 3, 3, 4}, {4, 4, 3, 3}, {4, 4, 4, 2}};
+    // 64-bit lane offsets (big): only the shapes the default plan uses above 2^28 rows (digits 7 and 8), whatever the knobs
+    if (L < 5 || L > 12 || (big && L != 7 && L != 8)) return {0, 0, 0, 0};
+    NttPassShape s = by_l[L - 5];
+    if (big) return s;
+    if ((L == 8 && ctx->tune_logt != 4) || (L == 9 && ctx->tune_logt9 != 4)) s.logT = 5;
+    // (round 6, review item 4: knob ntt_logt12 = 1 -- 512-thread workgroups on 64-KiB tiles of 2 columns, TWO workgroups per CU, 16-byte runs;
+    //  a pass with a per-tile twiddle table needs 32 KiB more and stays on the 4-column tile)
+    if (L == 12 && ctx->tune_logt12 == 1 && (transpose || !multiplies)) s.logT = 1;
+    return s;
+}
+
+NttPassShape zpi_plan_pass_shape(const zp_ctx *ctx, const NttPlan *pl, int i) {
+    return zpi_pass_shape(ctx, pl->pass[i].L, pl->logn > 28, i == 0, i + 1 < pl->npass || pl->inverse);
+}
+
+// two-level table of pre * base^e, e < 2^logn:  lo[e & (2^lb - 1)] * hi[e >> lb]
+static int32_t upload_power_table(zp_ctx *ctx, int logn, u64 base, u64 pre, int *lb, u64 **d_lo, u64 **d_hi) {
+    *lb = (logn + 1) / 2;
+    std::vector<u64> lo(1ULL << *lb), hi(1ULL << (logn - *lb));
+    lo[0] = pre;
+    u64 sp = 1;
+    for (size_t i = 1; i < lo.size(); i++) {
+        sp = gl_mul(sp, base);
+        lo[i] = gl_mul(pre, sp);
     }
-    *out = ctx->scratch[which];
-    return ZP_OK;
-}
-
-int32_t zpi_pinned(zp_ctx *ctx, size_t bytes, void **out) {
-    if (ctx->pinned_bytes < bytes) {
-        if (ctx->pinned) {
-            ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            ZP_HIP(ctx, hipHostFree(ctx->pinned));
-            ctx->pinned = nullptr;
-            ctx->pinned_bytes = 0;
-        }
-        size_t cap = bytes < (8u << 20) ? (8u << 20) : bytes;
-        ZP_HIP(ctx, hipHostMalloc(&ctx->pinned, cap, hipHostMallocMapped | hipHostMallocPortable));
-        ctx->pinned_bytes = cap;
-    }
-    *out = ctx->pinned;
-    return ZP_OK;
-}
-
-// Small host<->device copies are KERNELS through the pinned (device-visible) staging buffer, not DMA copies: a
-// hipMemcpyAsync of a few hundred bytes queues behind whatever the copy engines are doing -- with a second ctx
-// streaming 512 MB witnesses in, the transcript's tiny copies waited for all of them (0.47 s in the first chunk
-// of a 16-chunk batch).  A copy kernel is ordered on the ctx stream with the compute it feeds and never meets
-// the DMA queues.
-__global__ void __launch_bounds__(256) small_copy_kernel(const u32 *__restrict__ src, u32 *__restrict__ dst, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] = src[i];
-}
-
-static inline bool word_copyable(const void *a, size_t bytes) { return (((uintptr_t)a | bytes) & 3u) == 0; }
-
-static inline void launch_small_copy(zp_ctx *ctx, const void *src, void *dst, size_t bytes) {
-    const size_t n = bytes / 4;
-    const unsigned blocks = (unsigned)(n < 256 * 256 ? (n + 255) / 256 : 256);
-    hipLaunchKernelGGL(small_copy_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, ctx->stream, (const u32 *)src, (u32 *)dst, n);
-}
-
-int32_t zpi_d2h_small(zp_ctx *ctx, void *h_dst, const void *d_src, size_t bytes) {
-    void *st;
-    ZP_TRY(zpi_pinned(ctx, bytes, &st));
-    if (word_copyable(d_src, bytes)) {
-        launch_small_copy(ctx, d_src, st, bytes);
-        ZP_HIP(ctx, hipGetLastError());
-    } else {
-        ZP_HIP(ctx, hipMemcpyAsync(st, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(h_dst, st, bytes);
-    return ZP_OK;
-}
-
-int32_t zpi_h2d_small(zp_ctx *ctx, void *d_dst, const void *h_src, size_t bytes) {
-    void *st;
-    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the staging buffer may still feed an earlier copy
-    ZP_TRY(zpi_pinned(ctx, bytes, &st));
-    memcpy(st, h_src, bytes);
-    if (word_copyable(d_dst, bytes)) {
-        launch_small_copy(ctx, st, d_dst, bytes);
-        ZP_HIP(ctx, hipGetLastError());
-    } else {
-        ZP_HIP(ctx, hipMemcpyAsync(d_dst, st, bytes, hipMemcpyHostToDevice, ctx->stream));
-    }
-    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return ZP_OK;
-}
-
-static int32_t upload(zp_ctx *ctx, const std::vector<u64> &h, u64 **d) {
-    ZP_HIP(ctx, hipMalloc((void **)d, h.size() * sizeof(u64)));
-    ZP_HIP(ctx, hipMemcpy(*d, h.data(), h.size() * sizeof(u64), hipMemcpyHostToDevice));
-    return ZP_OK;
+    const u64 sl = gl_mul(sp, base);  // base^(2^lb)
+    hi[0] = 1;
+    for (size_t i = 1; i < hi.size(); i++) hi[i] = gl_mul(hi[i - 1], sl);
+    ZP_TRY(zpi_upload(ctx, lo, d_lo));
+    return zpi_upload(ctx, hi, d_hi);
 }
 
 // role (the two sides of an extension's seam, zpi_lde): 0 = the default plan; 1 = a plan that ENDS in a radix-256 pass (the inverse
@@ -1058,50 +1024,26 @@ int32_t zpi_get_plan_role(zp_ctx *ctx, int logn, bool inverse, int role, NttPlan
     std::vector<u64> tws(4096);
     tws[0] = 1;
     for (int i = 1; i < 4096; i++) tws[i] = gl_mul(tws[i - 1], w4096);
-    ZP_TRY(upload(ctx, tws, &pl.d_tws));
+    ZP_TRY(zpi_upload(ctx, tws, &pl.d_tws));
+    int dig[6];
     if (logn > 12 && role) {
-        int logP = 0;
         pl.npass = nr + 1;
-        for (int i = 0; i < pl.npass; i++) {
-            NttPass &p = pl.pass[i];
-            p.L = role == 1 ? (i < nr ? rdig[i] : 8) : (i == 0 ? 8 : rdig[i - 1]);
-            split_digit(p);
-            p.logPprev = logP;
-            logP += p.L;
-        }
+        for (int i = 0; i < pl.npass; i++) dig[i] = role == 1 ? (i < nr ? rdig[i] : 8) : (i == 0 ? 8 : rdig[i - 1]);
     } else if (logn > 12) {
-        const int m = (logn + maxl - 1) / maxl;
-        int rem = logn;
-        int logP = 0;
-        pl.npass = m;
-        int digits[6];
+        const int m = pl.npass = (logn + maxl - 1) / maxl;
+        int rem = logn, digits[6];
         for (int i = 0; i < m; i++) {
             digits[i] = (rem + (m - i) - 1) / (m - i);  // balanced, larger digits first
             rem -= digits[i];
         }
-        for (int i = 0; i < m; i++) {
-            NttPass &p = pl.pass[i];
-            // the transposing first pass pays a per-lane twiddle chain on top of its rounds: a three-round radix-512 digit is
-            // cheaper as the (plain) last pass; with digits <= 8 the larger-first order measured 1-4 % faster
-            // (profiles/r2_order_sweep.txt)
-            const bool last = order == 2 || (order == 0 && digits[0] == 9 && digits[m - 1] < 9);
-            p.L = last ? digits[m - 1 - i] : digits[i];
-            split_digit(p);
-            p.logPprev = logP;
-            logP += p.L;
-        }
+        // the transposing first pass pays a per-lane twiddle chain on top of its rounds: a three-round radix-512 digit is
+        // cheaper as the (plain) last pass; with digits <= 8 the larger-first order measured 1-4 % faster
+        // (profiles/r2_order_sweep.txt)
+        const bool last = order == 2 || (order == 0 && digits[0] == 9 && digits[m - 1] < 9);
+        for (int i = 0; i < m; i++) dig[i] = last ? digits[m - 1 - i] : digits[i];
     }
-    {   // two-level table of w^e, e < N (also used by the FRI fold for w_n^-i)
-        pl.lb = (logn + 1) / 2;
-        std::vector<u64> lo(1ULL << pl.lb), hi(1ULL << (logn - pl.lb));
-        lo[0] = 1;
-        for (size_t i = 1; i < lo.size(); i++) lo[i] = gl_mul(lo[i - 1], w);
-        u64 wl = gl_mul(lo.back(), w);  // w^(2^lb)
-        hi[0] = 1;
-        for (size_t i = 1; i < hi.size(); i++) hi[i] = gl_mul(hi[i - 1], wl);
-        ZP_TRY(upload(ctx, lo, &pl.d_twl));
-        ZP_TRY(upload(ctx, hi, &pl.d_twh));
-    }
+    for (int i = 0, logP = 0; i < pl.npass; logP += dig[i++]) pl.pass[i] = {dig[i], logP};
+    ZP_TRY(upload_power_table(ctx, logn, w, 1, &pl.lb, &pl.d_twl, &pl.d_twh));   // w^e, e < N (also used by the FRI fold for w_n^-i)
     auto ins = ctx->plans.emplace(key, pl);
     *out = &ins.first->second;
     return ZP_OK;
@@ -1109,27 +1051,43 @@ int32_t zpi_get_plan_role(zp_ctx *ctx, int logn, bool inverse, int role, NttPlan
 
 int32_t zpi_get_plan(zp_ctx *ctx, int logn, bool inverse, NttPlan **out) { return zpi_get_plan_role(ctx, logn, inverse, 0, out); }
 
+// pass i of a plan is a two-round radix-256 pass, the one lde_seam_kernel has built in on either side, and not the plan's only pass
+static bool is_radix256_pass(const zp_ctx *ctx, const NttPlan *pl, int i) {
+    const NttPassShape s = zpi_plan_pass_shape(ctx, pl, i);
+    return pl->npass >= 2 && pl->pass[i].L == 8 && s.A1 == 4 && s.A2 == 4 && s.A3 == 0;
+}
+
 // the two plans of a fused extension (blow-up 2) of 2^logn-row columns: the default plans where they already meet in radix-256 passes,
 // else the seam-role plans (knob lde_seam_plans: 0 = default plans only).  false: no fused path at this size.
 static bool seam_plans(zp_ctx *ctx, int logn, NttPlan **pi, NttPlan **pf) {
-    auto fits = [](const NttPlan *i, const NttPlan *f) {
-        const NttPass &li = i->pass[i->npass - 1], &ff = f->pass[0];
-        return i->npass >= 2 && f->npass >= 2 && li.L == 8 && li.A1 == 4 && li.A2 == 4 && li.A3 == 0 && ff.L == 8 && ff.A1 == 4 && ff.A2 == 4 && ff.A3 == 0;
-    };
-    NttPlan *di = nullptr, *df = nullptr;
-    if (zpi_get_plan(ctx, logn, true, &di) != ZP_OK || zpi_get_plan(ctx, logn + 1, false, &df) != ZP_OK) return false;
-    NttPlan *ci = di, *cf = df;
+    auto fits = [ctx](const NttPlan *i, const NttPlan *f) { return is_radix256_pass(ctx, i, i->npass - 1) && is_radix256_pass(ctx, f, 0); };
+    if (zpi_get_plan(ctx, logn, true, pi) != ZP_OK || zpi_get_plan(ctx, logn + 1, false, pf) != ZP_OK) return false;
     // measured on one box (profiles/r5_lde_seam_plans_ab.txt): the seam plans win 1-3 % from 2^21 rows on ((7,6,8)+(8,7,7) .. (8,7,8)+(8,8,8)) and LOSE
     // 5-11 % at 2^19 / 2^20, where fixing one digit at 8 leaves radix-32 passes ((6,5,8)+(8,7,5), (7,5,8)+(8,7,6)): default from 2^21 (knob 2: always)
-    if (!fits(ci, cf) && (ctx->tune_lde_seam_plans == 2 || (ctx->tune_lde_seam_plans == 1 && logn >= 21))) {
-        const NttPass &li = di->pass[di->npass - 1], &ff = df->pass[0];
-        if (!(di->npass >= 2 && li.L == 8 && li.A3 == 0) && zpi_get_plan_role(ctx, logn, true, 1, &ci) != ZP_OK) return false;
-        if (!(df->npass >= 2 && ff.L == 8 && ff.A3 == 0) && zpi_get_plan_role(ctx, logn + 1, false, 2, &cf) != ZP_OK) return false;
+    if (!fits(*pi, *pf) && (ctx->tune_lde_seam_plans == 2 || (ctx->tune_lde_seam_plans == 1 && logn >= 21))) {
+        if (!is_radix256_pass(ctx, *pi, (*pi)->npass - 1) && zpi_get_plan_role(ctx, logn, true, 1, pi) != ZP_OK) return false;
+        if (!is_radix256_pass(ctx, *pf, 0) && zpi_get_plan_role(ctx, logn + 1, false, 2, pf) != ZP_OK) return false;
     }
-    if (!fits(ci, cf)) return false;
-    *pi = ci;
-    *pf = cf;
-    return true;
+    return fits(*pi, *pf);
+}
+
+// How zp_lde runs an extension of 2^logn-row columns by 2^logb, with or without a coefficient store.  fused: blow-up 2 with matching
+// radix-256 passes on both sides of the seam -- the last pass of `inv` and the first pass of `fwd` run as ONE kernel (lde_seam_kernel) on
+// `tpw` inverse tiles per workgroup, and the scaled coefficients never travel.  Else the two transforms run one after the other.
+// Measured (profiles/r4_lde_seam_ab.txt, 2^24 x 32): 19.5 -> 18.7 ms without the coefficient store -- the fused kernel does three tile
+// bodies of integer work for three units of traffic and is bound by the former (0.70 ms against 0.73 ms for the two launches it replaces,
+// and the forward transform's remaining passes run on fewer launches): a pass of this library is BALANCED between its integer work and its
+// traffic, so taking away either alone buys little.  On by default where the caller does not want the coefficients (knob lde_seam: 0 never,
+// 1 default, 2 always).  (What this cannot know: the forward plan's table may fail to allocate; zpi_lde then takes the other path.)
+struct LdeRoute { bool fused = false; NttPlan *inv = nullptr, *fwd = nullptr; int tpw = 0; };
+static LdeRoute lde_route(zp_ctx *ctx, int logn, int logb, bool want_coef) {
+    LdeRoute r;
+    r.tpw = (ctx->tune_seam_tpw == 1 || ctx->tune_seam_tpw == 4) ? ctx->tune_seam_tpw : 2;     // a power of two: divides the tile count
+    r.fused = logb == 1 && (ctx->tune_lde_seam == 2 || (ctx->tune_lde_seam == 1 && !want_coef)) &&
+              zpi_pass_shape(ctx, 8, false, true, true).logT == 4 &&                              // the seam kernel's tiles are 16 columns wide
+              logn >= 16 && logn + 1 <= 28 && logn + 1 <= ctx->tune_ntt_tw1 && seam_plans(ctx, logn, &r.inv, &r.fwd) &&
+              ((((1ULL << logn) >> 12) / r.tpw) & 7u) == 0;                                       // its grid is XCD-ordered: a multiple of 8 workgroups per column
+    return r;
 }
 
 int32_t zpi_get_coset(zp_ctx *ctx, int logn, u64 shift, u64 pre, CosetTable **out) {
@@ -1142,26 +1100,20 @@ int32_t zpi_get_coset(zp_ctx *ctx, int logn, u64 shift, u64 pre, CosetTable **ou
     c.logn = logn;
     c.shift = shift;
     c.pre = pre;
-    c.lb = (logn + 1) / 2;
-    std::vector<u64> lo(1ULL << c.lb), hi(1ULL << (logn - c.lb));
-    lo[0] = pre;
-    u64 sp = 1;
-    for (size_t i = 1; i < lo.size(); i++) {
-        sp = gl_mul(sp, shift);
-        lo[i] = gl_mul(pre, sp);
-    }
-    u64 sl = gl_mul(sp, shift);  // shift^(2^lb)
-    hi[0] = 1;
-    for (size_t i = 1; i < hi.size(); i++) hi[i] = gl_mul(hi[i - 1], sl);
-    ZP_TRY(upload(ctx, lo, &c.d_lo));
-    ZP_TRY(upload(ctx, hi, &c.d_hi));
+    ZP_TRY(upload_power_table(ctx, logn, shift, pre, &c.lb, &c.d_lo, &c.d_hi));
     ctx->cosets.push_back(c);
     *out = &ctx->cosets.back();
     return ZP_OK;
 }
 
+bool zpi_plan_uses_tw1(const zp_ctx *ctx, const NttPlan *pl) {
+    const int logn = pl->logn;
+    return pl->npass >= 1 && !pl->tw1_unavailable && logn > 12 && logn <= ctx->tune_ntt_tw1 && logn <= 28 && zpi_plan_pass_shape(ctx, pl, 0).A3 == 0 &&
+           pl->pass[0].L >= 7;
+}
+
 // pass i of a plan over w columns: cur (column stride cur_cs, in_valid real elements per column) -> nxt (column stride N)
-static int32_t run_one_pass(zp_ctx *ctx, NttPlan *pl, int i, bool inverse, const NttRunOpts &opts, const u64 *cur, u64 cur_cs, u64 in_valid, u64 *nxt, int w) {
+static int32_t run_one_pass(zp_ctx *ctx, NttPlan *pl, int i, const NttRunOpts &opts, const u64 *cur, u64 cur_cs, u64 in_valid, u64 *nxt, int w) {
     const int logn = pl->logn, m = pl->npass;
     const bool last = (i == m - 1);
     PassArgs a;
@@ -1175,38 +1127,21 @@ static int32_t run_one_pass(zp_ctx *ctx, NttPlan *pl, int i, bool inverse, const
     a.twh = pl->d_twh;
     a.lb = pl->lb;
     a.tws = pl->d_tws;
-    a.tw1 = (i == 0 && logn <= ctx->tune_ntt_tw1) ? pl->d_tw1 : nullptr;
+    a.tw1 = (i == 0 && zpi_plan_uses_tw1(ctx, pl)) ? pl->d_tw1 : nullptr;
     a.scale = pl->ninv;
     a.logn = logn;
     a.logPprev = pl->pass[i].logPprev;
     a.j0inv = pl->j0inv;
     a.flags = last ? 0 : 1;
-    if (last && inverse) a.flags |= 2;
-    if (last && opts.post_scale) {
-        a.flags |= 4;
-        a.csl = opts.post_scale->d_lo;
-        a.csh = opts.post_scale->d_hi;
-        a.cslb = opts.post_scale->lb;
-    }
-    zp_ctx::PassEv ev;
-    if (ctx->profiling) {
-        ZP_HIP(ctx, hipEventCreate(&ev.a));
-        ZP_HIP(ctx, hipEventCreate(&ev.b));
-        ev.radix_log = (i == 0) ? -pl->pass[i].L : pl->pass[i].L;
-        ZP_HIP(ctx, hipEventRecord(ev.a, ctx->stream));
-    }
-    ZP_TRY(dispatch_pass(ctx, pl->pass[i], a, i == 0, w));
-    if (ctx->profiling) {
-        ZP_HIP(ctx, hipEventRecord(ev.b, ctx->stream));
-        ctx->pass_events.push_back(ev);
-    }
-    return ZP_OK;
+    if (last) set_output_scaling(a, pl->inverse, opts.post_scale);
+    PassTimer timer(ctx, (i == 0) ? -pl->pass[i].L : pl->pass[i].L);
+    return dispatch_pass(ctx, pl->pass[i], a, i == 0, w);
 }
 // the first pass's full table (8 bytes per element of ONE column, shared by all columns and all later calls of this size):
 // built at the first use of a plan by radix-2^7 / 2^8 two-round passes below 2^29 rows
 static int32_t ensure_tw1(zp_ctx *ctx, NttPlan *pl) {
     const int logn = pl->logn;
-    if (!pl->d_tw1 && !pl->tw1_unavailable && logn > 12 && logn <= ctx->tune_ntt_tw1 && logn <= 28 && pl->pass[0].A3 == 0 && pl->pass[0].L >= 7) {
+    if (!pl->d_tw1 && zpi_plan_uses_tw1(ctx, pl)) {
         if (hipMalloc((void **)&pl->d_tw1, sizeof(u64) << logn) != hipSuccess) {
             // the table is an optimisation (8 bytes per row, per plan, per ctx): without it the first pass multiplies by per-lane
             // twiddle chains (MODE 1), same results.  Clear the sticky error and do not try again for this plan.
@@ -1246,30 +1181,16 @@ int32_t zpi_ntt_run(zp_ctx *ctx, const u64 *d_in, u64 *d_out, int logn, int W, b
         a.tws = pl->d_tws;
         a.scale = pl->ninv;
         a.logn = logn;
-        a.flags = inverse ? 2 : 0;
-        if (opts.post_scale) {
-            a.flags |= 4;
-            a.csl = opts.post_scale->d_lo;
-            a.csh = opts.post_scale->d_hi;
-            a.cslb = opts.post_scale->lb;
-        }
+        set_output_scaling(a, pl->inverse, opts.post_scale);
         // in place is safe: a block owns its column and loads all of it into LDS before storing
         // in-wave stages where they measured faster (profiles/r5_dpp_ab.txt: <= 64 points 1.1-1.75x; from 2^8 points the doubled arithmetic loses)
-        if (ctx->tune_ntt_small_wave == 1 || (ctx->tune_ntt_small_wave == 0 && logn <= 6))
-            hipLaunchKernelGGL(ntt_small_kernel<true>, dim3((unsigned)W), dim3(256), (size_t)N * sizeof(u64), ctx->stream, a);
-        else
-            hipLaunchKernelGGL(ntt_small_kernel<false>, dim3((unsigned)W), dim3(256), (size_t)N * sizeof(u64), ctx->stream, a);
+        const bool wave = ctx->tune_ntt_small_wave == 1 || (ctx->tune_ntt_small_wave == 0 && logn <= 6);
+        hipLaunchKernelGGL(wave ? ntt_small_kernel<true> : ntt_small_kernel<false>, dim3((unsigned)W), dim3(256), (size_t)N * sizeof(u64), ctx->stream, a);
         ZP_HIP(ctx, hipGetLastError());
         return ZP_OK;
     }
 
-    // chunk the columns so that each ping-pong scratch buffer stays <= 2 GiB.  2^28 elements per launch since round 4 (profiles/r4_chunk_sweep.txt:
-    // NTT 2^20 .. 2^25 0-3 % faster than at 2^27, the first pass's shared twiddle table now serving 16 columns of a tile; 2^29 adds nothing.
-    // Round 2, before that table, measured the opposite: profiles/r2_chunk_sweep.txt)
-    const u64 cap_elems = 1ULL << (ctx->tune_ntt_chunk_log > 0 ? ctx->tune_ntt_chunk_log : 28);
-    int wc = (int)(cap_elems >> logn);
-    if (wc < 1) wc = 1;
-    if (wc > W) wc = W;
+    const int wc = chunk_columns(ctx, logn, W);
     const int m = pl->npass;
     ZP_TRY(ensure_tw1(ctx, pl));
     u64 *s0 = nullptr, *s1 = nullptr;
@@ -1283,9 +1204,65 @@ int32_t zpi_ntt_run(zp_ctx *ctx, const u64 *d_in, u64 *d_out, int logn, int W, b
         for (int i = 0; i < m; i++) {
             const bool last = (i == m - 1);
             u64 *nxt = last ? d_out + ((u64)c0 << logn) : ((i & 1) ? s1 : s0);
-            ZP_TRY(run_one_pass(ctx, pl, i, inverse, opts, cur, cur_cs, (i == 0) ? in_valid : N, nxt, w));
+            ZP_TRY(run_one_pass(ctx, pl, i, opts, cur, cur_cs, (i == 0) ? in_valid : N, nxt, w));
             cur = nxt;
             cur_cs = N;
+        }
+    }
+    return ZP_OK;
+}
+
+// the fused route of zpi_lde (lde_route): inverse passes but the last, the seam kernel, forward passes from the second on; W columns in chunks of wc
+static int32_t lde_fused(zp_ctx *ctx, const LdeRoute &r, const CosetTable *ct, const u64 *d_in, u64 *d_out, u64 *d_coef, int logn, int W, int wc) {
+    NttPlan *pi = r.inv, *pf = r.fwd;
+    const u64 N = 1ULL << logn;
+    const int mi = pi->npass, mf = pf->npass;
+    const int wf = wc >= 2 ? wc / 2 : 1;                      // columns per forward sub-chunk (2N rows each)
+    const size_t need = (size_t)(wc > 2 * wf ? wc : 2 * wf) << logn;
+    u64 *s0 = nullptr, *s1 = nullptr, *s2 = nullptr;
+    ZP_TRY(zpi_scratch(ctx, 0, need, &s0));
+    ZP_TRY(zpi_scratch(ctx, 1, need, &s1));
+    if (mf >= 3) ZP_TRY(zpi_scratch(ctx, 2, (size_t)wf << (logn + 1), &s2));
+    NttRunOpts none;
+    for (int c0 = 0; c0 < W; c0 += wc) {
+        const int w = (W - c0 < wc) ? (W - c0) : wc;
+        const u64 *cur = d_in + (u64)c0 * N;
+        for (int i = 0; i + 1 < mi; i++) {                     // the inverse transform up to its last pass
+            u64 *nxt = (i & 1) ? s1 : s0;
+            ZP_TRY(run_one_pass(ctx, pi, i, none, cur, N, N, nxt, w));
+            cur = nxt;
+        }
+        u64 *seam_out = (cur == s0) ? s1 : s0;
+        for (int h0 = 0; h0 < w; h0 += wf) {
+            const int wh = (w - h0 < wf) ? (w - h0) : wf;
+            SeamArgs sa;
+            memset(&sa, 0, sizeof(sa));
+            sa.in = cur + (u64)h0 * N;
+            sa.out = seam_out;
+            sa.coef = d_coef ? d_coef + (u64)(c0 + h0) * N : nullptr;
+            sa.tws_i = pi->d_tws;
+            sa.tws_f = pf->d_tws;
+            sa.tw1 = pf->d_tw1;
+            sa.csl = ct->d_lo;
+            sa.csh = ct->d_hi;
+            sa.cslb = ct->lb;
+            sa.scale = pi->ninv;
+            sa.logn = logn;
+            sa.j0inv_i = pi->j0inv;
+            sa.j0inv_f = pf->j0inv;
+            sa.ncols = wh;
+            {
+                PassTimer timer(ctx, 88);
+                hipLaunchKernelGGL(lde_seam_kernel, dim3((unsigned)(((N >> 12) / r.tpw) * (u64)wh)), dim3(256), (size_t)(256 * 16 + 3 * 256) * sizeof(u64), ctx->stream, sa, r.tpw);
+                ZP_HIP(ctx, hipGetLastError());
+            }
+            const u64 *fc = seam_out;                           // the forward transform from its second pass on
+            u64 *out = d_out + ((u64)(c0 + h0) << (logn + 1));
+            for (int i = 1; i < mf; i++) {
+                u64 *nxt = (i == mf - 1) ? out : s2;
+                ZP_TRY(run_one_pass(ctx, pf, i, none, fc, 2 * N, 2 * N, nxt, wh));
+                fc = nxt;
+            }
         }
     }
     return ZP_OK;
@@ -1299,90 +1276,17 @@ int32_t zpi_lde(zp_ctx *ctx, const u64 *d_in, u64 *d_out, u64 *d_coef, int logn,
     if (W == 0) return ZP_OK;
     if (shift == 0) shift = ctx->coset_shift;
     ZP_ARG(ctx, shift < GL_P, "shift not canonical");
-    const u64 N = 1ULL << logn;
     CosetTable *ct;
     ZP_TRY(zpi_get_coset(ctx, logn, shift, 1, &ct));
-    // columns go in chunks so that the scaled-coefficient buffer stays <= 2 GiB
-    int wc = (int)((1ULL << (ctx->tune_ntt_chunk_log > 0 ? ctx->tune_ntt_chunk_log : 28)) >> logn);
-    if (wc < 1) wc = 1;
-    if (wc > W) wc = W;
-    // ---- blow-up 2 with matching radix-256 passes on both sides of the seam: the inverse transform's last pass and the forward
-    // transform's first pass run as ONE kernel (lde_seam_kernel) and the scaled coefficients never travel (knob lde_seam)
-    // Measured (profiles/r4_lde_seam_ab.txt, 2^24 x 32): 19.5 -> 18.7 ms without the coefficient store -- the fused kernel does three tile
-    // bodies of integer work for three units of traffic and is bound by the former (0.70 ms against 0.73 ms for the two launches it replaces,
-    // and the forward transform's remaining passes run on fewer launches): a pass of this library is BALANCED between its integer work and its
-    // traffic, so taking away either alone buys little.  On by default where the caller does not want the coefficients (knob lde_seam: 0 never,
-    // 1 default, 2 always).
-    if (logb == 1 && (ctx->tune_lde_seam == 2 || (ctx->tune_lde_seam == 1 && !d_coef)) && ctx->tune_logt == 4 && logn >= 16 && logn + 1 <= 28 && logn + 1 <= ctx->tune_ntt_tw1) {
-        NttPlan *pi = nullptr, *pf = nullptr;
-        const bool have = seam_plans(ctx, logn, &pi, &pf);
-        if (have) {
-            ZP_TRY(ensure_tw1(ctx, pf));
-            ZP_TRY(ensure_tw1(ctx, pi));
-        }
-        const int tpw = (ctx->tune_seam_tpw == 1 || ctx->tune_seam_tpw == 4) ? ctx->tune_seam_tpw : 2;     // a power of two: divides the tile count
-        if (have && pf->d_tw1 && (((N >> 12) / tpw) & 7u) == 0) {
-            const int mi = pi->npass, mf = pf->npass;
-            const int wf = wc >= 2 ? wc / 2 : 1;                      // columns per forward sub-chunk (2N rows each)
-            size_t need = (size_t)wc << logn;
-            if (((size_t)wf << (logn + 1)) > need) need = (size_t)wf << (logn + 1);
-            u64 *s0 = nullptr, *s1 = nullptr, *s2 = nullptr;
-            ZP_TRY(zpi_scratch(ctx, 0, need, &s0));
-            ZP_TRY(zpi_scratch(ctx, 1, need, &s1));
-            if (mf >= 3) ZP_TRY(zpi_scratch(ctx, 2, (size_t)wf << (logn + 1), &s2));
-            NttRunOpts none;
-            for (int c0 = 0; c0 < W; c0 += wc) {
-                const int w = (W - c0 < wc) ? (W - c0) : wc;
-                const u64 *cur = d_in + (u64)c0 * N;
-                for (int i = 0; i + 1 < mi; i++) {                     // the inverse transform up to its last pass
-                    u64 *nxt = (i & 1) ? s1 : s0;
-                    ZP_TRY(run_one_pass(ctx, pi, i, true, none, cur, N, N, nxt, w));
-                    cur = nxt;
-                }
-                u64 *seam_out = (cur == s0) ? s1 : s0;
-                for (int h0 = 0; h0 < w; h0 += wf) {
-                    const int wh = (w - h0 < wf) ? (w - h0) : wf;
-                    SeamArgs sa;
-                    memset(&sa, 0, sizeof(sa));
-                    sa.in = cur + (u64)h0 * N;
-                    sa.out = seam_out;
-                    sa.coef = d_coef ? d_coef + (u64)(c0 + h0) * N : nullptr;
-                    sa.tws_i = pi->d_tws;
-                    sa.tws_f = pf->d_tws;
-                    sa.tw1 = pf->d_tw1;
-                    sa.csl = ct->d_lo;
-                    sa.csh = ct->d_hi;
-                    sa.cslb = ct->lb;
-                    sa.scale = pi->ninv;
-                    sa.logn = logn;
-                    sa.j0inv_i = pi->j0inv;
-                    sa.j0inv_f = pf->j0inv;
-                    sa.ncols = wh;
-                    zp_ctx::PassEv ev;
-                    if (ctx->profiling) {
-                        ZP_HIP(ctx, hipEventCreate(&ev.a));
-                        ZP_HIP(ctx, hipEventCreate(&ev.b));
-                        ev.radix_log = 88;                              // the seam: inverse radix 2^8 + forward radix 2^8
-                        ZP_HIP(ctx, hipEventRecord(ev.a, ctx->stream));
-                    }
-                    hipLaunchKernelGGL(lde_seam_kernel, dim3((unsigned)(((N >> 12) / tpw) * (u64)wh)), dim3(256), (size_t)(256 * 16 + 3 * 256) * sizeof(u64), ctx->stream, sa, tpw);
-                    ZP_HIP(ctx, hipGetLastError());
-                    if (ctx->profiling) {
-                        ZP_HIP(ctx, hipEventRecord(ev.b, ctx->stream));
-                        ctx->pass_events.push_back(ev);
-                    }
-                    const u64 *fc = seam_out;                           // the forward transform from its second pass on
-                    u64 *out = d_out + ((u64)(c0 + h0) << (logn + 1));
-                    for (int i = 1; i < mf; i++) {
-                        u64 *nxt = (i == mf - 1) ? out : s2;
-                        ZP_TRY(run_one_pass(ctx, pf, i, false, none, fc, 2 * N, 2 * N, nxt, wh));
-                        fc = nxt;
-                    }
-                }
-            }
-            return ZP_OK;
-        }
+    const int wc = chunk_columns(ctx, logn, W);
+    const LdeRoute r = lde_route(ctx, logn, logb, d_coef != nullptr);
+    if (r.fused) {
+        ZP_TRY(ensure_tw1(ctx, r.fwd));
+        ZP_TRY(ensure_tw1(ctx, r.inv));
+        if (r.fwd->d_tw1) return lde_fused(ctx, r, ct, d_in, d_out, d_coef, logn, W, wc);
     }
+    // the two-launch route: the inverse transform (its last pass multiplies c_i by shift^i) into the coefficient buffer, the zero-padded forward one out of it
+    const u64 N = 1ULL << logn;
     u64 *scaled = nullptr;
     if (!d_coef) ZP_TRY(zpi_scratch(ctx, 2, (size_t)wc << logn, &scaled));
     for (int c0 = 0; c0 < W; c0 += wc) {
@@ -1390,7 +1294,7 @@ int32_t zpi_lde(zp_ctx *ctx, const u64 *d_in, u64 *d_out, u64 *d_coef, int logn,
         const u64 *in = d_in + (u64)c0 * N;
         u64 *out = d_out + ((u64)c0 << (logn + logb));
         NttRunOpts inv;
-        inv.post_scale = ct;  // the inverse transform's last pass multiplies c_i by shift^i
+        inv.post_scale = ct;
         // d_coef (optional) IS the scaled-coefficient buffer: the interpolant composed with the coset shift, c_i * shift^i.
         // Nothing downstream needs the plain c_i: p(z) = sum_i (c_i shift^i) (z / shift)^i  (stark/prover.py evaluates there),
         // so the separate copy + scaling pass of round 1 (32*N bytes per column) is gone.
@@ -1406,22 +1310,19 @@ int32_t zpi_lde(zp_ctx *ctx, const u64 *d_in, u64 *d_out, u64 *d_coef, int logn,
 // what zp_lde(blow-up 2) does at this size, as JSON (zp_ntt_plan_json's "lde" member): whether the seam kernel is taken and the radices
 // on both sides of it
 int32_t zpi_lde_plan_json(zp_ctx *ctx, int logn, int want_coef, std::string *out) {
-    NttPlan *pi = nullptr, *pf = nullptr;
-    const int tpw = (ctx->tune_seam_tpw == 1 || ctx->tune_seam_tpw == 4) ? ctx->tune_seam_tpw : 2;
-    bool seam = (ctx->tune_lde_seam == 2 || (ctx->tune_lde_seam == 1 && !want_coef)) && ctx->tune_logt == 4 && logn >= 16 && logn + 1 <= 28 &&
-                logn + 1 <= ctx->tune_ntt_tw1 && seam_plans(ctx, logn, &pi, &pf) && ((((1ULL << logn) >> 12) / tpw) & 7u) == 0;
-    if (!seam) {
+    LdeRoute r = lde_route(ctx, logn, 1, want_coef != 0);
+    if (!r.fused) {
         if (logn + 1 > 32) return ZP_ERR_ARG;
-        ZP_TRY(zpi_get_plan(ctx, logn, true, &pi));
-        ZP_TRY(zpi_get_plan(ctx, logn + 1, false, &pf));
+        ZP_TRY(zpi_get_plan(ctx, logn, true, &r.inv));
+        ZP_TRY(zpi_get_plan(ctx, logn + 1, false, &r.fwd));
     }
     auto digits = [](const NttPlan *p) {
         std::string d = "[";
         for (int i = 0; i < p->npass; i++) d += (i ? ", " : "") + std::to_string(p->pass[i].L);
         return d + "]";
     };
-    *out = std::string("{\"blowup\": 2, \"coefficients_stored\": ") + (want_coef ? "true" : "false") + ", \"seam_fused\": " + (seam ? "true" : "false") +
-           ", \"inverse_radix_logs\": " + digits(pi) + ", \"forward_radix_logs\": " + digits(pf) + "}";
+    *out = std::string("{\"blowup\": 2, \"coefficients_stored\": ") + (want_coef ? "true" : "false") + ", \"seam_fused\": " + (r.fused ? "true" : "false") +
+           ", \"inverse_radix_logs\": " + digits(r.inv) + ", \"forward_radix_logs\": " + digits(r.fwd) + "}";
     return ZP_OK;
 }
 
@@ -1432,114 +1333,6 @@ int32_t zpi_twiddle_rows(zp_ctx *ctx, u64 *d_rows, int logn_row, int W, u64 row0
     const u64 nmask = logn_total >= 64 ? ~0ULL : ((1ULL << logn_total) - 1);
     hipLaunchKernelGGL(twiddle_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_rows, logn_row,
                        total, row0, nmask, pl->d_twl, pl->d_twh, pl->lb);
-    ZP_HIP(ctx, hipGetLastError());
-    return ZP_OK;
-}
-
-// ---- measurement: what this device sustains on a plain copy, with this library's own kernel (16 bytes per lane, one persistent workgroup
-// per CU by default since round 5) -- the ceiling bench.py prints next to the vendor peak
-typedef __attribute__((ext_vector_type(4))) unsigned int zp_u32x4;
-// U loads of 16 bytes in flight per lane, then U stores; NT: non-temporal policy (the data is touched once) or the default one.  Which grid,
-// block size, depth and policy stream fastest is MEASURED (tools/ntt_r5_ab.py -> profiles/r5_ntt_ab.txt; knobs copy_grid / copy_block /
-// copy_unroll / copy_nt): round 5 found one workgroup per CU (256 x 256 lanes, 4 in flight) at 5.6 TB/s against 4.9 for the 2048-workgroup
-// grid of rounds 1-4 -- fewer concurrent streams, not more, is what HBM3E wants.
-template <int U, bool NT>
-__global__ void __launch_bounds__(1024) hbm_copy_kernel(const zp_u32x4 *__restrict__ in, zp_u32x4 *__restrict__ out, size_t n16) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (; i + (U - 1) * stride < n16; i += U * stride) {
-        zp_u32x4 v[U];
-#pragma unroll
-        for (int k = 0; k < U; k++) v[k] = NT ? __builtin_nontemporal_load(in + i + k * stride) : in[i + k * stride];
-#pragma unroll
-        for (int k = 0; k < U; k++) {
-            if (NT) __builtin_nontemporal_store(v[k], out + i + k * stride);
-            else out[i + k * stride] = v[k];
-        }
-    }
-    for (; i < n16; i += stride) out[i] = in[i];
-}
-
-extern "C" int32_t zp_hbm_copy_probe(zp_ctx *ctx, const void *d_src, void *d_dst, size_t bytes, int32_t reps, float *ms_per_copy) {
-    if (!ctx) return ZP_ERR_ARG;
-    ZP_BIND(ctx);
-    ZP_ARG(ctx, d_src && d_dst && ms_per_copy && reps >= 1 && (bytes & 15) == 0 && bytes >= 16, "bad arguments");
-    hipEvent_t e0, e1;
-    ZP_HIP(ctx, hipEventCreate(&e0));
-    ZP_HIP(ctx, hipEventCreate(&e1));
-    const unsigned grid = ctx->tune_copy_grid > 0 ? (unsigned)ctx->tune_copy_grid : 256u;
-    const unsigned block = (ctx->tune_copy_block == 512 || ctx->tune_copy_block == 1024) ? (unsigned)ctx->tune_copy_block : 256u;
-    const bool u8 = ctx->tune_copy_unroll == 8;
-    auto k = ctx->tune_copy_nt ? (u8 ? hbm_copy_kernel<8, true> : hbm_copy_kernel<4, true>) : (u8 ? hbm_copy_kernel<8, false> : hbm_copy_kernel<4, false>);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(block), 0, ctx->stream, (const zp_u32x4 *)d_src, (zp_u32x4 *)d_dst, bytes / 16);
-    ZP_HIP(ctx, hipEventRecord(e0, ctx->stream));
-    for (int r = 0; r < reps; r++)
-        hipLaunchKernelGGL(k, dim3(grid), dim3(block), 0, ctx->stream, (const zp_u32x4 *)d_src, (zp_u32x4 *)d_dst, bytes / 16);
-    ZP_HIP(ctx, hipEventRecord(e1, ctx->stream));
-    ZP_HIP(ctx, hipEventSynchronize(e1));
-    float ms = 0.f;
-    ZP_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    *ms_per_copy = ms / reps;
-    return ZP_OK;
-}
-
-// ---- layout kernels of the multi-GPU paths: the send-buffer packing of the column->row all-to-all and the
-// local transposes of the four-step NTT.  (Round 1 did these with generic tensor copies: 21 G elements/s for a four-step
-// transform on one GPU against 75 G for the plain one.)
-// out[h][w][j] = in[w][h*Mg + j]:  [Wl][G*Mg] -> [G][Wl][Mg]; runs of Mg contiguous elements, 16 bytes per lane
-__global__ void __launch_bounds__(256) pack_blocks_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, u64 Wl, u64 G, u64 Mg) {
-    const u64 total2 = Wl * G * Mg / 2;
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total2; i += (u64)gridDim.x * 256) {
-        const u64 e = 2 * i, j = e % Mg, w = (e / Mg) % Wl, h = e / (Mg * Wl);
-        const u64 *src = in + w * (G * Mg) + h * Mg + j;
-        u64 *dst = out + e;
-        dst[0] = ZP_LDG(src);
-        dst[1] = ZP_LDG(src + 1);
-    }
-}
-// out[c][r] = in[r][c], 64 x 64 tiles through LDS (row length 65: the column reads of the write phase hit 64 banks)
-__global__ void __launch_bounds__(256) transpose_u64_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, u64 R, u64 C) {
-    __shared__ u64 tile[64][65];
-    const u64 tiles_c = (C + 63) / 64;
-    const u64 r0 = (blockIdx.x / tiles_c) * 64, c0 = (blockIdx.x % tiles_c) * 64;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        const u64 r = r0 + i * 4 + w, c = c0 + lane;
-        if (r < R && c < C) tile[i * 4 + w][lane] = ZP_LDG(&in[r * C + c]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        const u64 c = c0 + i * 4 + w, r = r0 + lane;
-        if (r < R && c < C) ZP_STG(&out[c * R + r], tile[lane][i * 4 + w]);
-    }
-}
-
-extern "C" int32_t zp_pack_blocks(zp_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, size_t rows, size_t row_len, int32_t parts) {
-    if (!ctx) return ZP_ERR_ARG;
-    ZpStage stage_(ctx, "pack_blocks");
-    ZP_ARG(ctx, d_in && d_out && d_in != d_out && parts >= 1 && row_len % (size_t)parts == 0, "bad arguments");
-    const size_t Mg = row_len / parts;
-    ZP_ARG(ctx, Mg % 2 == 0 || rows * row_len == 0, "part length must be even");
-    if (rows * row_len == 0) return ZP_OK;
-    const size_t total2 = rows * row_len / 2;
-    const unsigned blocks = (unsigned)(total2 / 256 + 1 < 8192 ? total2 / 256 + 1 : 8192);
-    hipLaunchKernelGGL(pack_blocks_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const u64 *)d_in, (u64 *)d_out, (u64)rows, (u64)parts, (u64)Mg);
-    ZP_HIP(ctx, hipGetLastError());
-    return ZP_OK;
-}
-
-extern "C" int32_t zp_transpose(zp_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, size_t rows, size_t cols) {
-    if (!ctx) return ZP_ERR_ARG;
-    ZpStage stage_(ctx, "transpose");
-    ZP_ARG(ctx, d_in && d_out && d_in != d_out, "bad arguments");
-    if (rows * cols == 0) return ZP_OK;
-    const size_t tiles = ((rows + 63) / 64) * ((cols + 63) / 64);
-    ZP_ARG(ctx, tiles < (1ULL << 31), "matrix too large for one launch");
-    hipLaunchKernelGGL(transpose_u64_kernel, dim3((unsigned)tiles), dim3(256), 0, ctx->stream, (const u64 *)d_in, (u64 *)d_out, (u64)rows, (u64)cols);
     ZP_HIP(ctx, hipGetLastError());
     return ZP_OK;
 }

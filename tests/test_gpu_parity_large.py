@@ -119,7 +119,8 @@ def test_config1_ntt_and_merkle_2p20_rows_bit_exact_vs_cpu(prover, tables):
 @pytest.mark.parametrize("maxl,logn,W", [(10, 20, 3), (11, 22, 2), (12, 24, 1), (12, 23, 1), (11, 21, 2), (10, 19, 2)])
 def test_two_pass_ntt_plans_match_oracle(prover, maxl, logn, W):
     """ntt_maxl = 10 / 11 / 12: the radix-2^10 .. 2^12 passes (1024-thread workgroups, twiddles from L2, XCD-aware tile
-    order) -- forward, inverse and a zero-padded LDE against the oracle"""
+    order) -- forward, inverse and a zero-padded LDE against the oracle.  The plan reports the tile that runs for the
+    `maxl` pass: 16, 8, 4 columns at the default knobs"""
     x = O.random_field((W, 1 << logn), 4100 + maxl + logn)
     x[0, :4] = np.array([0, P - 1, 1, 2 ** 32], dtype=np.uint64)
     ref = O.ntt(x)
@@ -127,6 +128,7 @@ def test_two_pass_ntt_plans_match_oracle(prover, maxl, logn, W):
         prover.set_tuning("ntt_maxl", maxl)
         plan = prover.ntt_plan(logn)
         assert len(plan["passes"]) == 2 and max(q["radix_log"] for q in plan["passes"]) == maxl, plan
+        assert {q["tile"] for q in plan["passes"] if q["radix_log"] == maxl} == {{10: 16, 11: 8, 12: 4}[maxl]}, plan
         d_in = prover.upload(x)
         d_out = prover.alloc(W << logn)
         prover.ntt(d_in, d_out, logn, W)
@@ -148,7 +150,8 @@ def test_two_pass_ntt_plans_match_oracle(prover, maxl, logn, W):
 def test_first_pass_table_and_chain_forms_match_oracle(prover, logn, W):
     """the transposing first pass in both forms -- MODE 3 (default: the N twiddles from one table shared by the columns, a
     one-dimensional XCD-ordered grid, any column count) and the per-lane chain (knob ntt_tw1 = 0) -- forward, inverse and a
-    zero-padded LDE against the oracle"""
+    zero-padded LDE against the oracle.  2^16 rows (8 + 8: a radix-256 first pass in table form) run once more on 32-column
+    tiles (knob ntt_logt = 5: 67 712 bytes of LDS, above the 64 KiB a launch gets without asking), forward and inverse"""
     x = O.random_field((W, 1 << logn), 4300 + logn)
     x[0, :4] = np.array([0, P - 1, 1, 2 ** 32], dtype=np.uint64)
     ref = O.ntt(x)
@@ -167,8 +170,18 @@ def test_first_pass_table_and_chain_forms_match_oracle(prover, logn, W):
             if ext is not None:
                 prover.lde(d_in, d_ext, logn, 1, W)
                 assert (prover.download(d_ext, (W, 2 << logn)) == ext).all()
+        if logn == 16:
+            prover.set_tuning("ntt_tw1", 26)
+            prover.set_tuning("ntt_logt", 5)
+            plan = prover.ntt_plan(logn)
+            assert plan["first_pass_table"] and plan["passes"][0] == {"radix_log": 8, "rounds": [4, 4, 0], "tile": 32}, plan
+            prover.ntt(d_in, d_out, logn, W)
+            assert (prover.download(d_out, (W, 1 << logn)) == ref).all()
+            prover.intt(d_out, d_out, logn, W)
+            assert (prover.download(d_out, (W, 1 << logn)) == x).all()
     finally:
         prover.set_tuning("ntt_tw1", 26)
+        prover.set_tuning("ntt_logt", 4)
         d_in.free()
         d_out.free()
         if d_ext is not None:
