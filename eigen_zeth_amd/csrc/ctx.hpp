@@ -95,6 +95,7 @@ struct zp_ctx {
     int tune_ntt_chunk_log = 0;   // 0 = 28: columns per launch such that a ping-pong scratch buffer is <= 2 GiB
     int tune_p254_bulk_log = 0;   // 0 = 14: Poseidon-BN254 t = 17 launches of >= 2^14 permutations use the lane-per-permutation kernel (31 = never)
     int tune_msm_c = 0;           // 0 = window width chosen from n
+    int tune_verify_lane_min = 0;   // 0 = 256: zp_merkle_verify_batch / zp_stark_verify* use the lane-per-opening kernel from this many openings per call on (fewer: the 12-lane walk kernel).  256 (four full waves) is A GUESS until tools/verify_measure.py has run on the device: unmeasured
     int tune_msm_chunk_log = 0;   // 0 = default (2^24 points per Pippenger run)
     // zp_stark_prove: device buffers kept between proofs (chunk after chunk has the same shapes; hipMalloc / hipFree of ~20 buffers
     // cost milliseconds per proof) and the LDE of the two boundary selectors per (logn, logb, shift, root)
@@ -180,6 +181,12 @@ int32_t zpi_poseidon_sync_tables(zp_ctx *ctx);
 int32_t zpi_poseidon_chains(zp_ctx *ctx, const u64 *d_blocks, const unsigned char *d_absorb, const unsigned int *d_first, int nchains, u64 *d_out);
 int32_t zpi_poseidon_openings_walk(zp_ctx *ctx, const u64 *d_op, const u64 *d_vals, u64 mw, const u64 *d_index, const u64 *d_sib, const u64 *d_sib_off,
                                    size_t count, u64 *d_inputs, u64 *d_digests);
+// one Merkle opening a verifier checks: `width` leaf values, `depth` siblings of four words (bottom-up), the leaf's position, and which of the
+// caller's roots it must hash to.  Host pointers; the words are canonical (the caller reduces what it read from a text)
+struct ZpOpening { const u64 *values, *path; u64 index; uint32_t width, depth, root_slot; };
+// ok[o] = 1 iff opening o hashes to roots[4 * root_slot ..): every opening of a call in ONE launch (csrc/poseidon.hip).  Openings of one
+// (width, depth) should be adjacent: a wave then walks one tree shape
+int32_t zpi_merkle_verify_openings(zp_ctx *ctx, const ZpOpening *ops, size_t n, const u64 *h_roots, size_t n_roots, uint8_t *ok);
 // run the transform on W columns; in/out column strides are 2^logn (or in_valid for zero-padded input)
 struct NttRunOpts {
     const CosetTable *post_scale = nullptr;  // multiply output i by table(i) (last pass)

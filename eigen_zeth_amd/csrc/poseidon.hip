@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <new>
 
 #include "ctx.hpp"
 // the Poseidon kernels fit 64 VGPRs (8 waves per SIMD) with the literal-table MDS: low scratch window
@@ -456,6 +457,61 @@ __global__ void __launch_bounds__(64) openings_walk_kernel(const u64 *__restrict
     if (e < 4) digests[o * 4 + e] = cur[e];
 }
 
+// ---- a verifier's openings, throughput form: ONE LANE PER OPENING, the state in registers.  A lane absorbs its leaf in blocks of 8 with the digest
+// so far as the next capacity (merkle_leaves_kernel's linear hash; <= 4 values are their own digest, zero padded), then hashes `depth` nodes
+// along the bits of its index and compares with its root: one flag per opening.  Openings of one launch come from trees of different width and
+// depth; the host sorts them into SEGMENTS of one (width, depth) each and packs a segment word-major -- word k of its opening i at
+// vals[voff + k n + i], word w of the sibling of level l at sibs[soff + (4 l + w) n + i] -- so that the lanes of a wave read consecutive
+// words.  A wave runs as many steps as its longest lane needs; a lane past its own count keeps its digest (predicated, no early exit).
+struct VerifySeg { u64 voff, soff; u32 o0, n, width, depth; };
+__device__ __forceinline__ int wave_max_i32(int v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) { const int o = __shfl_xor(v, m); v = o > v ? o : v; }
+    return v;
+}
+template <bool DEFMDS>
+__global__ void __launch_bounds__(256) openings_lane_kernel(const VerifySeg *__restrict__ segs, const u32 *__restrict__ seg_of, const u32 *__restrict__ root_slot,
+                                                           const u64 *__restrict__ index, const u64 *__restrict__ roots, const u64 *__restrict__ vals,
+                                                           const u64 *__restrict__ sibs, size_t count, unsigned char *__restrict__ ok, const u64 *rc,
+                                                           const u32 *mds) {
+    __shared__ u32 smds[DEFMDS ? 1 : 144];
+    mds = stage_mds<DEFMDS>(mds, smds);
+    const size_t o = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = o < count;
+    VerifySeg sg = {0, 0, 0, 1, 0, 0};
+    if (live) sg = segs[seg_of[o]];
+    const size_t i = live ? o - sg.o0 : 0;
+    const int nblk = sg.width > 4 ? (int)((sg.width + 7) / 8) : 0, nsteps = live ? nblk + (int)sg.depth : 0;
+    const u64 idx = live ? index[o] : 0;
+    u64 cur[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) cur[j] = (live && sg.width <= 4 && (u32)j < sg.width) ? vals[sg.voff + (size_t)j * sg.n + i] : 0ULL;
+    const int wsteps = wave_max_i32(nsteps);
+#pragma unroll 1
+    for (int st = 0; st < wsteps; st++) {
+        const bool on = st < nsteps, leaf = st < nblk;
+        u64 s[12];
+        const bool bit = on && !leaf && ((idx >> (st - nblk)) & 1);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            // a leaf step reads values 8 st + j and 8 st + 4 + j, a node step word j of the level's sibling
+            const u32 k = 8u * (u32)st + (u32)j;
+            const u64 a = !on ? 0ULL : leaf ? (k < sg.width ? vals[sg.voff + (size_t)k * sg.n + i] : 0ULL) : sibs[sg.soff + (size_t)(4 * (st - nblk) + j) * sg.n + i];
+            const u64 b = (on && leaf && k + 4 < sg.width) ? vals[sg.voff + (size_t)(k + 4) * sg.n + i] : 0ULL;
+            s[j] = (leaf || bit) ? a : cur[j];
+            s[4 + j] = leaf ? b : (bit ? cur[j] : a);
+            s[8 + j] = leaf ? cur[j] : 0ULL;           // the digest so far is the next block's capacity (zero before the first)
+        }
+        poseidon_perm<DEFMDS, true>(s, rc, mds);
+#pragma unroll
+        for (int j = 0; j < 4; j++) cur[j] = on ? s[j] : cur[j];
+    }
+    if (live) {
+        const u64 *r = roots + 4 * (size_t)root_slot[o];
+        ok[o] = (cur[0] == r[0] && cur[1] == r[1] && cur[2] == r[2] && cur[3] == r[3]) ? 1 : 0;
+    }
+}
+
 // proof-of-work grinding (before the query phase of a STARK): lane = candidate nonce base + gid; a hit is a nonce with
 // Poseidon(seed[0..3] || nonce || 0^7)[0] >> (64 - bits) == 0; the smallest hit of the batch wins (atomicMin).
 template <bool DEFMDS>
@@ -833,6 +889,104 @@ int32_t zpi_poseidon_openings_walk(zp_ctx *ctx, const u64 *d_op, const u64 *d_va
     return ZP_OK;
 }
 
+// The openings of a verifier in one call.  From `verify_lane_min` openings on: the lane-per-opening kernel (packed word-major, one upload, one
+// launch, one download); below it the 12-lane walk kernel of the recursion witness, fed a scratch buffer for the permutation inputs it writes, and
+// the digests compared here.  Both give the same flags (tests/test_gpu_stark_verify.py forces each through the knob).  Both are packed straight
+// into the ctx's pinned staging buffer (a batch of chunk proofs is tens of MB: no pageable copy, and nothing the copy reads dies on an early return)
+// and their results come back through it.  One synchronisation after the launch (the one before packing finds an idle stream: it only keeps an
+// earlier small copy from still reading the staging buffer).
+int32_t zpi_merkle_verify_openings(zp_ctx *ctx, const ZpOpening *ops, size_t n, const u64 *h_roots, size_t n_roots, uint8_t *ok) {
+    if (!n) return ZP_OK;
+    ZP_ARG(ctx, ops && h_roots && ok && n < (1u << 28) && n_roots >= 1 && n_roots < (1u << 28), "bad openings");
+    for (size_t o = 0; o < n; o++)
+        ZP_ARG(ctx, ops[o].values && (ops[o].path || !ops[o].depth) && ops[o].width >= 1 && ops[o].width < (1u << 16) && ops[o].depth <= 40 &&
+                        ops[o].root_slot < n_roots, "opening out of range");
+    ZP_TRY(zpi_poseidon_sync_tables(ctx));
+    const bool lane_form = n >= (size_t)(ctx->tune_verify_lane_min > 0 ? ctx->tune_verify_lane_min : 256);      // 256: unmeasured (ctx.hpp)
+    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    void *stv = nullptr;
+    if (lane_form) {
+        // segments: runs of one (width, depth) in the caller's order
+        std::vector<VerifySeg> segs;
+        std::vector<u32> seg_of(n);
+        size_t nv = 0, ns = 0;
+        for (size_t o = 0; o < n; o++) {
+            if (segs.empty() || segs.back().width != ops[o].width || segs.back().depth != ops[o].depth) {
+                if (!segs.empty()) { nv += (size_t)segs.back().width * segs.back().n; ns += (size_t)segs.back().depth * 4 * segs.back().n; }
+                segs.push_back({(u64)nv, (u64)ns, (u32)o, 0u, ops[o].width, ops[o].depth});
+            }
+            segs.back().n++;
+            seg_of[o] = (u32)(segs.size() - 1);
+        }
+        nv += (size_t)segs.back().width * segs.back().n; ns += (size_t)segs.back().depth * 4 * segs.back().n;
+        // one buffer: [segments][segment of an opening (u32)][root slot (u32)][index][roots][values][siblings][flags]
+        const size_t w_seg = segs.size() * (sizeof(VerifySeg) / 8), w_u32 = (n + 1) / 2, o_segof = w_seg, o_slot = o_segof + w_u32, o_idx = o_slot + w_u32,
+                     o_roots = o_idx + n, o_vals = o_roots + 4 * n_roots, o_sibs = o_vals + nv, o_ok = o_sibs + ns, total = o_ok + (n + 7) / 8;
+        static_assert(sizeof(VerifySeg) % 8 == 0, "segment records are whole words");
+        ZP_TRY(zpi_pinned(ctx, total * 8, &stv));
+        u64 *buf = (u64 *)stv;
+        memcpy(buf, segs.data(), segs.size() * sizeof(VerifySeg));
+        buf[o_slot - 1] = buf[o_idx - 1] = 0;              // the odd half word behind each u32 array
+        memcpy(buf + o_segof, seg_of.data(), n * 4);
+        u32 *slot = (u32 *)(buf + o_slot);
+        for (size_t o = 0; o < n; o++) { slot[o] = ops[o].root_slot; buf[o_idx + o] = ops[o].index; }
+        // the transpose to word-major in tiles of 64 openings: the writes run along the openings (one wave's worth of consecutive words per row),
+        // the reads stay inside the 64 rows of the tile
+        for (const VerifySeg &sg : segs)
+            for (size_t i0 = 0; i0 < sg.n; i0 += 64) {
+                const size_t i1 = i0 + 64 < sg.n ? i0 + 64 : sg.n;
+                u64 *v = buf + o_vals + sg.voff, *sb = buf + o_sibs + sg.soff;
+                for (u32 k = 0; k < sg.width; k++)
+                    for (size_t i = i0; i < i1; i++) v[(size_t)k * sg.n + i] = ops[sg.o0 + i].values[k];
+                for (u32 k = 0; k < 4 * sg.depth; k++)
+                    for (size_t i = i0; i < i1; i++) sb[(size_t)k * sg.n + i] = ops[sg.o0 + i].path[k];
+            }
+        memcpy(buf + o_roots, h_roots, 32 * n_roots);
+        u64 *d = nullptr;
+        ZP_TRY(zpi_scratch(ctx, 3, total, &d));
+        ZP_HIP(ctx, hipMemcpyAsync(d, buf, o_ok * 8, hipMemcpyHostToDevice, ctx->stream));
+        const dim3 grid((unsigned)((n + 255) / 256));
+        if (ctx->mds_is_default)
+            hipLaunchKernelGGL(openings_lane_kernel<true>, grid, dim3(256), 0, ctx->stream, (const VerifySeg *)d, (const u32 *)(d + o_segof), (const u32 *)(d + o_slot),
+                               d + o_idx, d + o_roots, d + o_vals, d + o_sibs, n, (unsigned char *)(d + o_ok), ctx->d_rc, ctx->d_mds);
+        else
+            hipLaunchKernelGGL(openings_lane_kernel<false>, grid, dim3(256), 0, ctx->stream, (const VerifySeg *)d, (const u32 *)(d + o_segof), (const u32 *)(d + o_slot),
+                               d + o_idx, d + o_roots, d + o_vals, d + o_sibs, n, (unsigned char *)(d + o_ok), ctx->d_rc, ctx->d_mds);
+        ZP_HIP(ctx, hipGetLastError());
+        ZP_HIP(ctx, hipMemcpyAsync(buf + o_ok, d + o_ok, n, hipMemcpyDeviceToHost, ctx->stream));
+        ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        memcpy(ok, buf + o_ok, n);
+        return ZP_OK;
+    }
+    // latency form: rows of mw words per opening, the siblings one opening after the other
+    u64 mw = 4, nsib = 0, nperm = 0;
+    for (size_t o = 0; o < n; o++) { if (ops[o].width > mw) mw = ops[o].width; nsib += 4 * (u64)ops[o].depth; }
+    const size_t o_op = 0, o_idx = 3 * n, o_off = o_idx + n, o_vals = o_off + n, o_sib = o_vals + n * mw, o_dig = o_sib + nsib, o_in_at = o_dig + 4 * n;
+    ZP_TRY(zpi_pinned(ctx, o_in_at * 8, &stv));
+    u64 *buf = (u64 *)stv;
+    memset(buf + o_vals, 0, n * mw * 8);                   // a row shorter than its last block of 8 ends in zeros
+    nsib = 0;
+    for (size_t o = 0; o < n; o++) {
+        const u64 na = ops[o].width > 4 ? (ops[o].width + 7) / 8 : 0;
+        buf[o_op + 3 * o] = nperm; buf[o_op + 3 * o + 1] = na; buf[o_op + 3 * o + 2] = ops[o].depth;
+        buf[o_idx + o] = ops[o].index;
+        buf[o_off + o] = nsib;
+        memcpy(&buf[o_vals + o * mw], ops[o].values, 8 * (size_t)ops[o].width);
+        if (ops[o].depth) memcpy(&buf[o_sib + nsib], ops[o].path, 32 * (size_t)ops[o].depth);
+        nsib += 4 * (u64)ops[o].depth;
+        nperm += na + ops[o].depth;
+    }
+    u64 *d = nullptr;
+    ZP_TRY(zpi_scratch(ctx, 3, o_in_at + 12 * nperm, &d));
+    ZP_HIP(ctx, hipMemcpyAsync(d, buf, o_dig * 8, hipMemcpyHostToDevice, ctx->stream));
+    ZP_TRY(zpi_poseidon_openings_walk(ctx, d + o_op, d + o_vals, mw, d + o_idx, d + o_sib, d + o_off, n, d + o_in_at, d + o_dig));
+    const u64 *dig = buf + o_dig;
+    ZP_HIP(ctx, hipMemcpyAsync(buf + o_dig, d + o_dig, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
+    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t o = 0; o < n; o++) ok[o] = memcmp(&dig[4 * o], h_roots + 4 * (size_t)ops[o].root_slot, 32) == 0 ? 1 : 0;
+    return ZP_OK;
+}
+
 extern "C" {
 
 int32_t zp_poseidon_perm(zp_ctx *ctx, uint64_t *d_states, size_t count) {
@@ -1006,6 +1160,33 @@ int32_t zp_merkle_open(zp_ctx *ctx, const uint64_t *d_tree, size_t M, size_t idx
     }
     ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return ZP_OK;
+}
+
+// n openings into ONE binary tree (see the header): the device primitive of the verifier on its own
+int32_t zp_merkle_verify_batch(zp_ctx *ctx, const uint64_t *h_values, size_t width, const uint64_t *h_index, const uint64_t *h_paths, int32_t depth,
+                               const uint64_t *h_root4, size_t n, uint8_t *h_ok) {
+    if (!ctx) return ZP_ERR_ARG;
+    ZpStage stage_(ctx, "merkle_verify_batch");
+    try {
+        if (n == 0) return ZP_OK;
+        ZP_ARG(ctx, h_values && h_index && h_root4 && h_ok && (h_paths || depth == 0), "null pointer");
+        ZP_ARG(ctx, width >= 1 && width < (1u << 16) && depth >= 0 && depth <= 40 && n < (1u << 28), "width, depth or count out of range");
+        // field elements are read mod p, as the hash takes them; an index beyond the tree is no opening of it
+        std::vector<u64> v(n * width), p((size_t)depth * 4 * n), root(h_root4, h_root4 + 4);
+        for (size_t i = 0; i < v.size(); i++) v[i] = gl_canon(h_values[i]);
+        for (size_t i = 0; i < p.size(); i++) p[i] = gl_canon(h_paths[i]);
+        std::vector<ZpOpening> ops(n);
+        for (size_t o = 0; o < n; o++) ops[o] = {&v[o * width], depth ? &p[o * (size_t)depth * 4] : nullptr, h_index[o], (uint32_t)width, (uint32_t)depth, 0u};
+        ZP_TRY(zpi_merkle_verify_openings(ctx, ops.data(), n, root.data(), 1, h_ok));
+        for (size_t o = 0; o < n; o++)
+            if (depth < 64 && (h_index[o] >> depth)) h_ok[o] = 0;
+        return ZP_OK;
+    } catch (const std::bad_alloc &) {
+        try { ctx->err = "out of host memory"; } catch (...) {}
+        return ZP_ERR_NOMEM;
+    } catch (...) {
+        return ZP_ERR_INTERNAL;
+    }
 }
 
 int32_t zp_merkle_commit_host(zp_ctx *ctx, const uint64_t *h_cols, size_t M, int32_t W, uint64_t *h_tree) {

@@ -7,11 +7,30 @@
 // seconds in Python, milliseconds here (one shared inversion per column by Montgomery's trick, columns spread over threads).
 // No reference counterpart (the prover behind the gRPC boundary is external); the checker's own statement of the same: oracle/air_program.py
 // (fixed_eval_ext, evaluate_ext) -- the tests compare the two.
+#include <cstdio>
 #include <cstring>
+#include <exception>
+#include <new>
+#include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "ctx.hpp"
+#include "jsoncur.hpp"
+#include "sha256.hpp"
+#include "poseidon_default_table.inc"      // ctx = NULL verifies with the library's default tables
+
+// What the verifier takes from other translation units, as WEAK references: this file is also built on its own as plain C++ under the host
+// sanitizers (tests/test_verify_fuzz.py, tests/test_r1cs_fuzz.py link it without the rest of the library).  The openings of a text are read by
+// csrc/proofparse.hip (absent: only ZP_VERIFY_HEADER_ONLY can be served); the device side is csrc/poseidon.hip (absent: only ctx = NULL).
+extern "C" {
+int32_t zp_proof_queries_scan(const char *text, size_t len, size_t *q_begin, size_t *q_end, int32_t *n_queries, int32_t *has_stage2, int32_t *n_fri, int32_t *widths,
+                              int32_t *depths, int32_t max_trees) __attribute__((weak));
+int32_t zp_proof_queries_parse(const char *text, size_t q_begin, size_t q_end, int32_t n_queries, int32_t has_stage2, int32_t n_fri, const int32_t *widths,
+                               const int32_t *depths, uint64_t *index, uint64_t *values, uint64_t *paths) __attribute__((weak));
+}
+extern int32_t zpi_merkle_verify_openings(zp_ctx *ctx, const ZpOpening *ops, size_t n, const u64 *h_roots, size_t n_roots, uint8_t *ok) __attribute__((weak));
 
 namespace {
 
@@ -19,8 +38,9 @@ inline e3 e3_base(u64 v) { return e3_make(v, 0, 0); }
 inline e3 e3_pow2k(e3 a, int k) { for (int i = 0; i < k; i++) a = e3_mul(a, a); return a; }
 
 // g(y) (y^p - 1) form of one sparse periodic column at zeta: sum_e v_e w_p^pos / (p (y - w_p^pos)) * (y^p - 1), y = zeta^(N / p)
-bool fixed_col_at(const uint64_t *prog, const ZpFixedCol &fc, const uint64_t *pubs, int logn, u64 root32, const e3 &zeta, const e3 &zh, e3 *out) {
-    if (fc.lp > logn) return false;
+enum { FIXED_OK = 0, FIXED_BAD = 1, FIXED_NOMEM = 2, FIXED_ON_DOMAIN = 3 };
+int fixed_col_at(const uint64_t *prog, const ZpFixedCol &fc, const uint64_t *pubs, int logn, u64 root32, const e3 &zeta, const e3 &zh, e3 *out) {
+    if (fc.lp > logn) return FIXED_BAD;
     const e3 y = e3_pow2k(zeta, logn - fc.lp);
     const u64 wp = fc.lp ? gl_root(root32, fc.lp) : 1;
     const u64 pinv = gl_inv((1ULL << fc.lp) % GL_P);
@@ -49,7 +69,7 @@ bool fixed_col_at(const uint64_t *prog, const ZpFixedCol &fc, const uint64_t *pu
     for (size_t i = 0; i < den.size(); i++) { pre[i] = run; run = e3_mul(run, den[i]); }
     u64 det;
     const e3 adj = e3_adj(run, &det);
-    if (!den.empty() && det == 0) return false;              // zeta on the domain
+    if (!den.empty() && det == 0) return FIXED_ON_DOMAIN;
     e3 inv = den.empty() ? e3_base(1) : e3_scale(adj, gl_inv(det));
     e3 acc = e3_base(0);
     for (size_t i = den.size(); i-- > 0;) {
@@ -58,7 +78,7 @@ bool fixed_col_at(const uint64_t *prog, const ZpFixedCol &fc, const uint64_t *pu
         acc = e3_add(acc, e3_scale(dinv, coef[i]));
     }
     *out = e3_mul(acc, zh);
-    return true;
+    return FIXED_OK;
 }
 
 }  // namespace
@@ -105,10 +125,12 @@ extern "C" {
 //   zeta[3]; h_ev_z / h_ev_zw u64[n_cols][3]: the committed columns' evaluations at zeta / zeta w (n_cols must be the program's W + W2)
 //   h_out u64[n_out][3]: constraint k at zeta (n_out must be the program's K) (numerators: the caller combines them with its alpha powers and compares with q(zeta) Z_H(zeta))
 // Fixed columns: 0 / 1 the first-row / last-row selectors (Lagrange basis polynomials), then the sparse periodic columns; "x - last" is
-// zeta - w^(N-1).  ZP_ERR_ARG: malformed program, non-canonical input, zeta on the trace domain.  threads <= 0: one per core, at most 16.
+// zeta - w^(N-1).  ZP_ERR_ARG: malformed program, non-canonical input, zeta on the trace domain (*zeta_on_domain, when given, tells the last from the
+// others: to a verifier it is a property of the proof, not a mistake of its caller).  threads <= 0: one per core, at most 16.
 static int32_t program_eval_ext_impl(const uint64_t *h_program, size_t program_words, const uint64_t *h_pubchal, int32_t n_pubchal, int32_t logn, uint64_t root32,
                                      const uint64_t zeta3[3], const uint64_t *h_ev_z, const uint64_t *h_ev_zw, int32_t n_cols, uint64_t *h_out, int32_t n_out,
-                                     int32_t threads, uint64_t *h_fixed_out, int32_t n_fixed_out) {
+                                     int32_t threads, uint64_t *h_fixed_out, int32_t n_fixed_out, bool *zeta_on_domain = nullptr) {
+    if (zeta_on_domain) *zeta_on_domain = false;
     const bool only_fixed = h_fixed_out != nullptr;
     try {
         if (!h_program || !zeta3 || program_words < 12 || logn < 1 || logn > 32 || n_pubchal < 0 || (n_pubchal && !h_pubchal)) return ZP_ERR_ARG;
@@ -139,7 +161,7 @@ static int32_t program_eval_ext_impl(const uint64_t *h_program, size_t program_w
         {
             u64 d0, d1;
             const e3 a0 = e3_adj(e3_make(gl_sub(zeta.c[0], 1), zeta.c[1], zeta.c[2]), &d0), a1 = e3_adj(e3_make(gl_sub(zeta.c[0], wlast), zeta.c[1], zeta.c[2]), &d1);
-            if (d0 == 0 || d1 == 0) return ZP_ERR_ARG;
+            if (d0 == 0 || d1 == 0) { if (zeta_on_domain) *zeta_on_domain = true; return ZP_ERR_ARG; }
             fixed[0] = e3_mul(e3_scale(zh, ninv), e3_scale(a0, gl_inv(d0)));
             fixed[1] = e3_mul(e3_scale(zh, gl_mul(ninv, wlast)), e3_scale(a1, gl_inv(d1)));
         }
@@ -151,8 +173,8 @@ static int32_t program_eval_ext_impl(const uint64_t *h_program, size_t program_w
         auto work = [&](unsigned t) noexcept {
             try {
                 for (size_t k = t; k < fxc.size(); k += nt)
-                    if (!fixed_col_at(h_program, fxc[k], h_pubchal, logn, root32, zeta, zh, &fixed[2 + k])) { bad[t] = 1; return; }
-            } catch (...) { bad[t] = 2; }
+                    if (const int r = fixed_col_at(h_program, fxc[k], h_pubchal, logn, root32, zeta, zh, &fixed[2 + k])) { bad[t] = r; return; }
+            } catch (...) { bad[t] = FIXED_NOMEM; }
         };
         {
             std::vector<std::thread> th;
@@ -163,7 +185,11 @@ static int32_t program_eval_ext_impl(const uint64_t *h_program, size_t program_w
             for (auto &x : th) x.join();
         }
         for (int b : bad)
-            if (b) return b == 2 ? ZP_ERR_NOMEM : ZP_ERR_ARG;
+            if (b == FIXED_NOMEM) return ZP_ERR_NOMEM;
+        for (int b : bad)
+            if (b == FIXED_BAD) return ZP_ERR_ARG;
+        for (int b : bad)
+            if (b) { if (zeta_on_domain) *zeta_on_domain = true; return ZP_ERR_ARG; }
         if (only_fixed) {
             for (size_t k = 0; k < n_fixed; k++) memcpy(h_fixed_out + 3 * k, fixed[k].c, 24);
             return ZP_OK;
@@ -221,6 +247,619 @@ int32_t zp_program_fixed_eval_ext(const uint64_t *h_program, size_t program_word
                                   const uint64_t zeta3[3], uint64_t *h_fixed, int32_t n_fixed, int32_t threads) {
     if (!h_fixed) return ZP_ERR_ARG;
     return program_eval_ext_impl(h_program, program_words, h_pubchal, n_pubchal, logn, root32, zeta3, nullptr, nullptr, 0, nullptr, 0, threads, h_fixed, n_fixed);
+}
+
+}  // extern "C"
+
+// ================================================================================================================================
+// The STARK verifier (Goldilocks-hash mode) behind zp_stark_verify / zp_stark_verify_batch: what a host that was handed a chunk proof as
+// TEXT asks before it spends anything on it.  The protocol is stark/prover.py's; the checks and their order are restated here from the
+// protocol (the CPU checker's independent statement of the same is oracle/stark_verify.py -- the tests run the two side by side).
+// Everything in this file is host code: the header of the text, the transcript (a textbook-schedule Poseidon, the only host one in the
+// product), the identity at zeta, the final layer's degree, the DEEP sum and every fold at every query.  The one O(openings) part -- the
+// leaf hash and the path of every opening -- goes to the device in one launch when a ctx is given (csrc/poseidon.hip:
+// zpi_merkle_verify_openings) and runs here otherwise (ctx = NULL: the sanitizer build and a machine without a GPU).
+// Numbers: a number of the text that the protocol takes as a field element (public input, evaluation, opened value, path word) is read
+// mod p, as the checker reads it; where the protocol COMPARES a number of the text (parameters, roots, indices, the nonce, an opened FRI
+// value against the previous fold) a value >= p equals nothing.
+namespace {
+
+using zpjson::Cur;
+using zpjson::each_member;
+
+struct HostPoseidon {
+    const u64 *rc, *mds;
+    void perm(u64 *s) const {                     // ARK -> S-box -> MDS, 4 + 22 + 4 rounds; canonical in and out
+        for (int r = 0; r < 30; r++) {
+            const bool full = r < 4 || r >= 26;
+            for (int i = 0; i < 12; i++) {
+                u64 x = gl_add(s[i], rc[r * 12 + i]);
+                if (full || i == 0) { const u64 x2 = gl_mul(x, x), x3 = gl_mul(x2, x); x = gl_mul(gl_mul(x2, x2), x3); }
+                s[i] = x;
+            }
+            u64 o[12];
+            for (int i = 0; i < 12; i++) {
+                unsigned __int128 acc = 0;        // 12 terms < 2^28 * 2^64
+                for (int j = 0; j < 12; j++) acc += (unsigned __int128)mds[i * 12 + j] * s[j];
+                o[i] = gl_reduce96((u64)acc, (u32)(acc >> 64), 0u);
+            }
+            memcpy(s, o, sizeof o);
+        }
+    }
+    void pair(const u64 *l, const u64 *r, u64 *out4) const {
+        u64 s[12] = {l[0], l[1], l[2], l[3], r[0], r[1], r[2], r[3], 0, 0, 0, 0};
+        perm(s);
+        memcpy(out4, s, 32);
+    }
+    // the leaf hash of zp_merkle_commit: blocks of 8 with the digest so far as the next capacity; <= 4 values are their own digest
+    void leaf(const u64 *v, size_t w, u64 *out4) const {
+        u64 s[12] = {0};
+        if (w <= 4) { for (size_t j = 0; j < 4; j++) out4[j] = j < w ? v[j] : 0; return; }
+        for (size_t off = 0; off < w; off += 8) {
+            for (size_t j = 0; j < 8; j++) s[j] = off + j < w ? v[off + j] : 0;
+            perm(s);
+            memcpy(s + 8, s, 32);
+        }
+        memcpy(out4, s + 8, 32);
+    }
+    bool opening_ok(const ZpOpening &op, const u64 *root4) const {
+        u64 cur[4];
+        leaf(op.values, op.width, cur);
+        for (uint32_t l = 0; l < op.depth; l++) {
+            if ((op.index >> l) & 1) pair(op.path + 4 * l, cur, cur);
+            else pair(cur, op.path + 4 * l, cur);
+        }
+        return memcmp(cur, root4, 32) == 0;
+    }
+};
+
+// stark/transcript.py: absorb queues; a squeeze first absorbs the queue in blocks of 8 that overwrite the rate (one permutation when nothing is
+// queued), then hands out the rate
+struct HostSponge {
+    const HostPoseidon &H;
+    u64 st[12] = {0};
+    std::vector<u64> q;
+    int pos = 8;
+    explicit HostSponge(const HostPoseidon &h) : H(h) {}
+    void absorb(const u64 *v, size_t n) { for (size_t i = 0; i < n; i++) q.push_back(gl_canon(v[i])); pos = 8; }
+    void squeeze(size_t n, u64 *out) {
+        for (size_t k = 0; k < n; k++) {
+            if (!q.empty() || pos == 8) {
+                if (q.empty()) H.perm(st);
+                for (size_t off = 0; off < q.size(); off += 8) {
+                    for (size_t j = 0; j < 8; j++) st[j] = off + j < q.size() ? q[off + j] : 0;
+                    H.perm(st);
+                }
+                q.clear();
+                pos = 0;
+            }
+            out[k] = st[pos++];
+        }
+    }
+    e3 challenge() { u64 c[3]; squeeze(3, c); return e3_make(c[0], c[1], c[2]); }
+};
+
+// the commitment a long public-input vector enters the transcript as (stark/prover.py publics_rows: rows of 8, zero padded, 2^k >= 2 rows)
+void publics_digest_host(const HostPoseidon &H, const std::vector<u64> &pubs, u64 *out4) {
+    size_t M = 2;
+    while (M * 8 < pubs.size()) M <<= 1;
+    std::vector<u64> lvl(4 * M);
+    for (size_t r = 0; r < M; r++) {
+        u64 s[12] = {0};
+        for (size_t j = 0; j < 8; j++) s[j] = 8 * r + j < pubs.size() ? pubs[8 * r + j] : 0;
+        H.perm(s);
+        memcpy(&lvl[4 * r], s, 32);
+    }
+    for (; M > 1; M >>= 1)
+        for (size_t r = 0; r < M / 2; r++) H.pair(&lvl[8 * r], &lvl[8 * r + 4], &lvl[4 * r]);
+    memcpy(out4, lvl.data(), 32);
+}
+
+// ---- the header of a proof text (everything but "queries")
+struct ProofHeader {
+    static constexpr int NPARAM = 6;
+    bool has_params = false, has_param[NPARAM] = {}, has_root32 = false, has_shift = false, has_digest = false, has_pubs = false, has_nonce = false, has_queries = false;
+    bool has_root[3] = {};                     // trace, stage2, quotient
+    bool has_z = false, has_zw = false, has_fri_roots = false, has_final = false;
+    uint64_t param[NPARAM] = {}, root32 = 0, shift = 0, nonce = 0;
+    std::string hash = "gl", digest;
+    std::vector<u64> pubs, root[3], ev_z, ev_zw, fri_roots;
+    std::vector<std::vector<u64>> final_l;
+    bool rows_ok = true;                       // every row of the evaluations has 3 words, every root 4
+};
+const char *const PARAM_KEYS[ProofHeader::NPARAM] = {"logn", "logb", "fri_logf", "fri_final_log", "n_queries", "pow_bits"};
+
+bool once(Cur &c, bool &got) { if (got) c.ok = false; got = true; return c.ok; }      // a repeated key is not this grammar
+
+bool u64_list(Cur &c, std::vector<u64> *out) {
+    if (!c.need('[')) return false;
+    if (c.eat(']')) return true;
+    for (;;) {
+        uint64_t v;
+        if (!c.u64v(&v)) return c.ok = false;
+        out->push_back(v);
+        if (c.eat(',')) continue;
+        return c.need(']');
+    }
+}
+// [[..],[..]]: rows of `row` words each, flattened (another row length clears *rows_ok)
+bool u64_rows(Cur &c, size_t row, std::vector<u64> *out, bool *rows_ok) {
+    if (!c.need('[')) return false;
+    if (c.eat(']')) return true;
+    for (;;) {
+        const size_t before = out->size();
+        if (!u64_list(c, out)) return false;
+        if (out->size() - before != row) *rows_ok = false;
+        if (c.eat(',')) continue;
+        return c.need(']');
+    }
+}
+
+bool parse_header(const char *text, size_t len, ProofHeader *h) {
+    Cur c{text, text + len};
+    const bool ok = each_member(c, [&](const char *b, const char *e) {
+        if (c.key_is(b, e, "params")) {
+            if (!once(c, h->has_params)) return;
+            bool got_hash = false;
+            each_member(c, [&](const char *kb, const char *ke) {
+                for (int i = 0; i < ProofHeader::NPARAM; i++)
+                    if (c.key_is(kb, ke, PARAM_KEYS[i])) { if (once(c, h->has_param[i])) c.u64v(&h->param[i]); return; }
+                if (c.key_is(kb, ke, "hash")) {
+                    const char *sb, *se;
+                    if (once(c, got_hash) && c.str(&sb, &se)) h->hash.assign(sb, se);
+                    return;
+                }
+                c.skip_value();
+            });
+        } else if (c.key_is(b, e, "root32")) { if (once(c, h->has_root32)) c.u64v(&h->root32); }
+        else if (c.key_is(b, e, "shift")) { if (once(c, h->has_shift)) c.u64v(&h->shift); }
+        else if (c.key_is(b, e, "pow_nonce")) { if (once(c, h->has_nonce)) c.u64v(&h->nonce); }
+        else if (c.key_is(b, e, "air_digest")) {
+            const char *sb, *se;
+            if (once(c, h->has_digest) && c.str(&sb, &se)) h->digest.assign(sb, se);
+        } else if (c.key_is(b, e, "publics")) { if (once(c, h->has_pubs)) u64_list(c, &h->pubs); }
+        else if (c.key_is(b, e, "roots")) {
+            each_member(c, [&](const char *kb, const char *ke) {
+                const int t = c.key_is(kb, ke, "trace") ? 0 : c.key_is(kb, ke, "stage2") ? 1 : c.key_is(kb, ke, "quotient") ? 2 : -1;
+                if (t < 0) { c.skip_value(); return; }
+                if (once(c, h->has_root[t]) && u64_list(c, &h->root[t]) && h->root[t].size() != 4) h->rows_ok = false;
+            });
+        } else if (c.key_is(b, e, "evals")) {
+            each_member(c, [&](const char *kb, const char *ke) {
+                if (c.key_is(kb, ke, "z")) { if (once(c, h->has_z)) u64_rows(c, 3, &h->ev_z, &h->rows_ok); }
+                else if (c.key_is(kb, ke, "zw")) { if (once(c, h->has_zw)) u64_rows(c, 3, &h->ev_zw, &h->rows_ok); }
+                else c.skip_value();
+            });
+        } else if (c.key_is(b, e, "fri")) {
+            each_member(c, [&](const char *kb, const char *ke) {
+                if (c.key_is(kb, ke, "roots")) { if (once(c, h->has_fri_roots)) u64_rows(c, 4, &h->fri_roots, &h->rows_ok); }
+                else if (c.key_is(kb, ke, "final")) {
+                    if (!once(c, h->has_final) || !c.need('[')) return;
+                    if (c.eat(']')) return;
+                    for (;;) {
+                        if (h->final_l.size() >= 4) { c.ok = false; return; }
+                        h->final_l.emplace_back();
+                        if (!u64_list(c, &h->final_l.back())) return;
+                        if (c.eat(',')) continue;
+                        c.need(']');
+                        return;
+                    }
+                } else c.skip_value();
+            });
+        } else if (c.key_is(b, e, "queries")) { if (once(c, h->has_queries)) c.skip_value(); }
+        else c.skip_value();
+    });
+    c.ws();
+    return ok && c.ok && c.p == c.end;
+}
+
+// in-place inverse transform of 2^lg values up to the factor 1 / 2^lg (the degree test looks for zeros only)
+void intt_unscaled(std::vector<u64> &a, int lg, u64 root32) {
+    const size_t n = (size_t)1 << lg;
+    for (size_t i = 0, j = 0; i < n; i++) {
+        if (i < j) std::swap(a[i], a[j]);
+        size_t m = n >> 1;
+        for (; m && (j & m); m >>= 1) j ^= m;
+        j |= m;
+    }
+    for (int s = 1; s <= lg; s++) {
+        const size_t half = (size_t)1 << (s - 1);
+        const u64 w = gl_inv(gl_root(root32, s));
+        for (size_t k = 0; k < n; k += 2 * half) {
+            u64 t = 1;
+            for (size_t j = 0; j < half; j++) {
+                const u64 u = a[k + j], v = gl_mul(a[k + j + half], t);
+                a[k + j] = gl_add(u, v);
+                a[k + j + half] = gl_sub(u, v);
+                t = gl_mul(t, w);
+            }
+        }
+    }
+}
+
+struct VerifyParams { int logn, logb, fri_logf, fri_final_log, n_queries, pow_bits; uint32_t flags; int threads; u64 root32, shift; };
+struct ProgramInfo { const uint64_t *words; size_t n_words; size_t W, W2, n_pub, n_chal, K, Q, n_s2; char digest_hex[17]; u64 digest_words[4]; };
+
+// one proof between the header checks and the verdict: what the query phase needs
+struct Pending {
+    int verdict = ZP_VERDICT_ACCEPT, where = -1;
+    bool queries_live = false;                 // the header passed and there are openings to check
+    std::vector<u64> qidx, index, values, paths, roots;      // roots: 4 words per tree (raw: a word >= p matches no digest)
+    std::vector<int32_t> widths, depths;
+    std::vector<size_t> voff, poff;            // where tree t's block starts in values / paths
+    std::vector<std::pair<int, int>> sched;    // (log size of the layer, log fold factor)
+    std::vector<u64> ev_z, ev_zw, final_raw;   // canonical evaluations; the final layer as the text has it, plane-major
+    std::vector<e3> betas;
+    e3 zeta, gamma;
+    int final_log = 0, T = 0;
+    size_t Wt = 0, Wall = 0;
+    std::vector<uint8_t> open_ok, arith;       // per (query, tree): the opening hashes to its root; per (query, 0..n_fri): layer l's value / the final value is consistent
+    size_t root0 = 0;                          // the slot of its first root in the batch's list
+};
+
+int32_t header_phase(const char *text, size_t len, const ProgramInfo &pg, const VerifyParams &vp, const HostPoseidon &H, Pending *pd) {
+    auto verdict = [&](int v) { pd->verdict = v; return ZP_OK; };
+    ProofHeader h;
+    if (!parse_header(text, len, &h)) return verdict(ZP_VERDICT_MALFORMED);
+    // 1. parameters, domain, statement, counts
+    const u64 want[ProofHeader::NPARAM] = {(u64)vp.logn, (u64)vp.logb, (u64)vp.fri_logf, (u64)vp.fri_final_log, (u64)vp.n_queries, (u64)vp.pow_bits};
+    if (!h.has_params) return verdict(ZP_VERDICT_MALFORMED);
+    for (int i = 0; i < ProofHeader::NPARAM; i++)
+        if (!h.has_param[i] || h.param[i] != want[i]) return verdict(ZP_VERDICT_PARAMS);
+    if (h.hash == "bn128") return ZP_ERR_UNSUPPORTED;
+    if (h.hash != "gl") return verdict(ZP_VERDICT_PARAMS);
+    if (!h.has_root32 || !h.has_shift || !h.has_digest || !h.has_pubs) return verdict(ZP_VERDICT_MALFORMED);
+    if (h.root32 != vp.root32 || h.shift != vp.shift) return verdict(ZP_VERDICT_PARAMS);
+    if (h.digest != pg.digest_hex) return verdict(ZP_VERDICT_PARAMS);
+    if (pg.Q > ((size_t)1 << vp.logb)) return verdict(ZP_VERDICT_PARAMS);
+    if (h.pubs.size() != pg.n_pub) return verdict(ZP_VERDICT_PARAMS);
+    const int logn = vp.logn, logb = vp.logb, logm = logn + logb;
+    const size_t W = pg.W, W2 = pg.W2, Wt = W + W2, Q = pg.Q, nq = (size_t)vp.n_queries;
+    const u64 M = (u64)1 << logm;
+    for (u64 &v : h.pubs) v = gl_canon(v);
+    // the transcript
+    HostSponge tr(H);
+    {
+        std::vector<u64> head = {(u64)logn, (u64)logb, (u64)W, (u64)W2, (u64)vp.fri_logf, (u64)vp.fri_final_log, (u64)vp.n_queries, (u64)vp.pow_bits, vp.root32, vp.shift,
+                                 pg.digest_words[0], pg.digest_words[1], pg.digest_words[2], pg.digest_words[3], (u64)h.pubs.size()};
+        tr.absorb(head.data(), head.size());
+        if (h.pubs.size() <= 64) tr.absorb(h.pubs.data(), h.pubs.size());      // PUBLICS_INLINE
+        else { u64 dg[4]; publics_digest_host(H, h.pubs, dg); tr.absorb(dg, 4); }
+    }
+    if (!h.has_root[0] || !h.has_root[2] || !h.rows_ok) return verdict(ZP_VERDICT_MALFORMED);
+    tr.absorb(h.root[0].data(), 4);
+    std::vector<u64> pubchal = h.pubs;
+    if (pg.n_s2) {
+        if (!h.has_root[1]) return verdict(ZP_VERDICT_MALFORMED);
+        u64 ch[3];
+        tr.squeeze(3, ch);
+        pubchal.insert(pubchal.end(), ch, ch + 3);
+        tr.absorb(h.root[1].data(), 4);
+    }
+    const e3 alpha = tr.challenge();
+    tr.absorb(h.root[2].data(), 4);
+    const e3 zeta = tr.challenge();
+    if (!h.has_z || !h.has_zw || h.ev_z.size() != 3 * (Wt + 3 * Q) || h.ev_zw.size() != 3 * Wt) return verdict(ZP_VERDICT_MALFORMED);
+    for (u64 &v : h.ev_z) v = gl_canon(v);
+    for (u64 &v : h.ev_zw) v = gl_canon(v);
+    tr.absorb(h.ev_z.data(), h.ev_z.size());
+    tr.absorb(h.ev_zw.data(), h.ev_zw.size());
+    const e3 gamma = tr.challenge();
+
+    // 2. the constraint identity at zeta: sum_k alpha^k C_k(zeta) = q(zeta) Z_H(zeta)
+    {
+        std::vector<u64> cs(3 * pg.K);
+        if (pubchal.empty()) pubchal.push_back(0);
+        bool on_domain = false;
+        const int32_t rc = program_eval_ext_impl(pg.words, pg.n_words, (const uint64_t *)pubchal.data(), (int32_t)(pg.n_pub + pg.n_chal), logn, vp.root32, (const uint64_t *)zeta.c,
+                                                 (const uint64_t *)h.ev_z.data(), (const uint64_t *)h.ev_zw.data(), (int32_t)Wt, (uint64_t *)cs.data(), (int32_t)pg.K, vp.threads, nullptr, 0, &on_domain);
+        if (rc != ZP_OK && !on_domain) return rc;                   // a blob the evaluator refuses is the caller's mistake, not a rejected proof
+        if (rc != ZP_OK) return verdict(ZP_VERDICT_IDENTITY);       // zeta on the trace domain: nothing can be said at it
+        e3 lhs = e3_base(0), ap = e3_base(1);
+        for (size_t k = 0; k < pg.K; k++) { lhs = e3_add(lhs, e3_mul(ap, e3_make(cs[3 * k], cs[3 * k + 1], cs[3 * k + 2]))); ap = e3_mul(ap, alpha); }
+        const e3 zN = e3_pow2k(zeta, logn), zh = e3_make(gl_sub(zN.c[0], 1), zN.c[1], zN.c[2]);
+        const e3 zsN = e3_pow2k(e3_scale(zeta, gl_inv(vp.shift)), logn);
+        auto mul_theta = [](const e3 &a) { return e3_make(a.c[2], gl_add(a.c[0], a.c[2]), a.c[1]); };      // theta^3 = theta + 1
+        e3 q = e3_base(0), zpow = e3_base(1);
+        for (size_t j = 0; j < Q; j++) {
+            const u64 *p = &h.ev_z[3 * (Wt + 3 * j)];
+            const e3 qj = e3_add(e3_add(e3_make(p[0], p[1], p[2]), mul_theta(e3_make(p[3], p[4], p[5]))), mul_theta(mul_theta(e3_make(p[6], p[7], p[8]))));
+            q = e3_add(q, e3_mul(zpow, qj));
+            zpow = e3_mul(zpow, zsN);
+        }
+        const e3 rhs = e3_mul(q, zh);
+        if (memcmp(lhs.c, rhs.c, 24) != 0) return verdict(ZP_VERDICT_IDENTITY);
+    }
+
+    // 3. the FRI transcript
+    int cur = logm;
+    const int stop = vp.fri_final_log + logb;
+    while (cur > stop) { const int f = vp.fri_logf < cur - stop ? vp.fri_logf : cur - stop; pd->sched.push_back({cur, f}); cur -= f; }
+    const int final_log = cur;
+    const size_t n_fri = pd->sched.size();
+    if (!h.has_fri_roots || !h.has_final || h.fri_roots.size() != 4 * n_fri) return verdict(ZP_VERDICT_MALFORMED);
+    for (size_t l = 0; l < n_fri; l++) { tr.absorb(&h.fri_roots[4 * l], 4); pd->betas.push_back(tr.challenge()); }
+    if (h.final_l.size() != 3) return verdict(ZP_VERDICT_MALFORMED);
+    for (int c = 0; c < 3; c++)
+        if (h.final_l[c].size() != ((size_t)1 << final_log)) return verdict(ZP_VERDICT_MALFORMED);
+    for (int c = 0; c < 3; c++) tr.absorb(h.final_l[c].data(), h.final_l[c].size());
+    // 4. grinding
+    if (vp.pow_bits) {
+        u64 seed[4];
+        tr.squeeze(4, seed);
+        if (!h.has_nonce || h.nonce >= GL_P) return verdict(ZP_VERDICT_POW);
+        u64 s[12] = {seed[0], seed[1], seed[2], seed[3], (u64)h.nonce, 0, 0, 0, 0, 0, 0, 0};
+        H.perm(s);
+        if (s[0] >> (64 - vp.pow_bits)) return verdict(ZP_VERDICT_POW);
+        { const u64 nonce = h.nonce; tr.absorb(&nonce, 1); }
+    }
+    // 5. the indices the transcript dictates
+    pd->qidx.resize(nq);
+    tr.squeeze(nq, pd->qidx.data());
+    for (u64 &v : pd->qidx) v &= M - 1;
+    const bool header_only = (vp.flags & ZP_VERIFY_HEADER_ONLY) != 0;
+    size_t q_begin = 0, q_end = 0;
+    int32_t nq_text = 0, has_s2 = 0, nf_text = 0, widths[48], depths[48];
+    if (!header_only) {
+        if (!zp_proof_queries_scan || !zp_proof_queries_parse) return ZP_ERR_UNSUPPORTED;
+        if (!h.has_queries || zp_proof_queries_scan(text, len, &q_begin, &q_end, &nq_text, &has_s2, &nf_text, widths, depths, 48) != ZP_OK) return verdict(ZP_VERDICT_MALFORMED);
+        if ((size_t)nq_text != nq) return verdict(ZP_VERDICT_INDICES);
+        // every size below counts numbers that stand in the text; n_queries is the verifier's own
+        const int T = 2 + has_s2 + nf_text;
+        size_t nv = 0, np = 0;
+        pd->widths.assign(widths, widths + T); pd->depths.assign(depths, depths + T);
+        for (int t = 0; t < T; t++) { pd->voff.push_back(nv); pd->poff.push_back(np); nv += nq * (size_t)widths[t]; np += nq * (size_t)depths[t] * 4; }
+        pd->index.resize(nq); pd->values.resize(nv ? nv : 1); pd->paths.resize(np ? np : 1);
+        if (zp_proof_queries_parse(text, q_begin, q_end, nq_text, has_s2, nf_text, widths, depths, (uint64_t *)pd->index.data(), (uint64_t *)pd->values.data(),
+                                   (uint64_t *)pd->paths.data()) != ZP_OK)
+            return verdict(ZP_VERDICT_MALFORMED);
+        if (pd->index != pd->qidx) return verdict(ZP_VERDICT_INDICES);
+        pd->T = T;
+    }
+    // 6. the final layer has degree < 2^(final_log - logb) on its coset (the unshift scales coefficient i by s^-i: zero stays zero)
+    for (int c = 0; c < 3; c++) {
+        std::vector<u64> cf(h.final_l[c]);
+        for (u64 &v : cf) v = gl_canon(v);
+        intt_unscaled(cf, final_log, vp.root32);
+        for (size_t i = (size_t)1 << (final_log - logb); i < cf.size(); i++)
+            if (cf[i]) return verdict(ZP_VERDICT_FINAL_DEGREE);
+    }
+    if (header_only) return verdict(ZP_VERDICT_ACCEPT);
+    // the shape of the openings: trace, [stage 2], quotient, one per FRI layer
+    {
+        const bool s2 = pg.n_s2 != 0;
+        if ((has_s2 != 0) != s2 || (size_t)nf_text != n_fri) return verdict(ZP_VERDICT_MALFORMED);
+        std::vector<std::pair<size_t, int>> want_t = {{W, logm}};
+        if (s2) want_t.push_back({W2, logm});
+        want_t.push_back({3 * Q, logm});
+        for (auto &lf : pd->sched) want_t.push_back({(size_t)3 << lf.second, lf.first - lf.second});
+        for (int t = 0; t < pd->T; t++)
+            if ((size_t)widths[t] != want_t[t].first || depths[t] != want_t[t].second) return verdict(ZP_VERDICT_MALFORMED);
+    }
+    pd->roots.insert(pd->roots.end(), h.root[0].begin(), h.root[0].end());
+    if (pg.n_s2) pd->roots.insert(pd->roots.end(), h.root[1].begin(), h.root[1].end());
+    pd->roots.insert(pd->roots.end(), h.root[2].begin(), h.root[2].end());
+    pd->roots.insert(pd->roots.end(), h.fri_roots.begin(), h.fri_roots.end());
+    pd->ev_z.swap(h.ev_z); pd->ev_zw.swap(h.ev_zw);
+    for (int c = 0; c < 3; c++) pd->final_raw.insert(pd->final_raw.end(), h.final_l[c].begin(), h.final_l[c].end());
+    pd->zeta = zeta; pd->gamma = gamma; pd->final_log = final_log; pd->Wt = Wt; pd->Wall = Wt + 3 * Q;
+    pd->queries_live = true;
+    return ZP_OK;
+}
+
+// the DEEP sum and every fold of query q: arith[q][l] = layer l's opened value is the previous fold (l = n_fri: the final layer's)
+void query_arith(const Pending &pd, const VerifyParams &vp, const std::vector<e3> &gp, const std::vector<u64> &vals, size_t q, uint8_t *out) {
+    const size_t n_fri = pd.sched.size(), Wt = pd.Wt, Wall = pd.Wall;
+    const int logm = vp.logn + vp.logb, T = pd.T;
+    const u64 j = pd.index[q], wM = gl_root(vp.root32, logm), x = gl_mul(vp.shift, gl_pow(wM, j));
+    // columns in the order of the evaluations: trace, stage 2, quotient = trees 0 .. T - n_fri - 1
+    e3 A = e3_base(0), B = e3_base(0);
+    size_t k = 0;
+    for (int t = 0; t < T - (int)n_fri; t++)
+        for (int c = 0; c < pd.widths[t]; c++, k++) {
+            const u64 v = vals[pd.voff[t] + q * (size_t)pd.widths[t] + c];
+            A = e3_add(A, e3_mul(gp[k], e3_make(gl_sub(v, pd.ev_z[3 * k]), gl_neg(pd.ev_z[3 * k + 1]), gl_neg(pd.ev_z[3 * k + 2]))));
+            if (k < Wt) B = e3_add(B, e3_mul(gp[Wall + k], e3_make(gl_sub(v, pd.ev_zw[3 * k]), gl_neg(pd.ev_zw[3 * k + 1]), gl_neg(pd.ev_zw[3 * k + 2]))));
+        }
+    const e3 zeta_w = e3_scale(pd.zeta, gl_root(vp.root32, vp.logn));
+    e3 expect = e3_add(e3_mul(A, e3_inv(e3_make(gl_sub(x, pd.zeta.c[0]), gl_neg(pd.zeta.c[1]), gl_neg(pd.zeta.c[2])))),
+                       e3_mul(B, e3_inv(e3_make(gl_sub(x, zeta_w.c[0]), gl_neg(zeta_w.c[1]), gl_neg(zeta_w.c[2])))));
+    u64 pos = j, cur_shift = vp.shift;
+    for (size_t l = 0; l < n_fri; l++) {
+        const int lg = pd.sched[l].first, f = pd.sched[l].second, t = T - (int)n_fri + (int)l;
+        const size_t F = (size_t)1 << f;
+        const u64 row = pos & (((u64)1 << (lg - f)) - 1), k0 = pos >> (lg - f);
+        const u64 *raw = &pd.values[pd.voff[t] + q * 3 * F], *lv = &vals[pd.voff[t] + q * 3 * F];
+        out[l] = raw[k0] == expect.c[0] && raw[F + k0] == expect.c[1] && raw[2 * F + k0] == expect.c[2];
+        // fold: c_j = (1 / F) x^-j sum_k v_k w_F^-jk, the next value sum_j beta^j c_j
+        const u64 x_base = gl_mul(cur_shift, gl_pow(gl_root(vp.root32, lg), row)), winv = gl_inv(gl_root(vp.root32, f)), finv = gl_inv((u64)F), xinv = gl_inv(x_base);
+        u64 wp[16];                            // fri_logf <= 4
+        wp[0] = 1;
+        for (size_t i = 1; i < F; i++) wp[i] = gl_mul(wp[i - 1], winv);
+        e3 acc = e3_base(0), bp = e3_base(1);
+        u64 s = finv;
+        for (size_t jj = 0; jj < F; jj++) {
+            u64 cj[3] = {0, 0, 0};
+            for (size_t kk = 0; kk < F; kk++)
+                for (int c = 0; c < 3; c++) cj[c] = gl_add(cj[c], gl_mul(lv[c * F + kk], wp[(jj * kk) & (F - 1)]));
+            acc = e3_add(acc, e3_mul(e3_scale(e3_make(cj[0], cj[1], cj[2]), s), bp));
+            bp = e3_mul(bp, pd.betas[l]);
+            s = gl_mul(s, xinv);
+        }
+        expect = acc;
+        pos = row;
+        cur_shift = gl_pow(cur_shift, (u64)F);
+    }
+    const size_t nf = (size_t)1 << pd.final_log;
+    out[n_fri] = pd.final_raw[pos] == expect.c[0] && pd.final_raw[nf + pos] == expect.c[1] && pd.final_raw[2 * nf + pos] == expect.c[2];
+}
+
+template <class F>
+void spread(size_t n, int threads, F f) {              // f(i) for i < n over `threads` host threads (as zp_program_eval_ext spreads its columns)
+    unsigned nt = threads > 0 ? (unsigned)threads : std::thread::hardware_concurrency();
+    nt = nt < 1 ? 1 : nt > 16 ? 16 : nt;
+    if (n < 8) nt = 1;
+    auto work = [&](unsigned t) noexcept { for (size_t i = t; i < n; i += nt) f(i); };
+    std::vector<std::thread> th;
+    unsigned started = 0;
+    try { for (unsigned t = 1; t < nt; t++) { th.emplace_back(work, t); started = t; } } catch (...) {}
+    work(0);
+    for (unsigned t = started + 1; t < nt; t++) work(t);
+    for (auto &x : th) x.join();
+}
+
+// the first failing check in the protocol's order: per query the trace, quotient and stage-2 openings, then per layer its opening and its
+// consistency with the previous fold, then the last fold against the final layer
+void scan_verdict(Pending *pd, const VerifyParams &vp, bool has_s2) {
+    const size_t nq = (size_t)vp.n_queries, n_fri = pd->sched.size();
+    const int T = pd->T, tq = has_s2 ? 2 : 1;
+    for (size_t q = 0; q < nq; q++) {
+        const uint8_t *ok = &pd->open_ok[q * T], *ar = &pd->arith[q * (n_fri + 1)];
+        int v = ZP_VERDICT_ACCEPT;
+        if (!ok[0] || !ok[tq] || (has_s2 && !ok[1])) v = ZP_VERDICT_OPENING;
+        for (size_t l = 0; l < n_fri && v == ZP_VERDICT_ACCEPT; l++) v = !ok[tq + 1 + l] ? ZP_VERDICT_OPENING : !ar[l] ? ZP_VERDICT_FRI : ZP_VERDICT_ACCEPT;
+        if (v == ZP_VERDICT_ACCEPT && !ar[n_fri]) v = ZP_VERDICT_FRI;
+        if (v != ZP_VERDICT_ACCEPT) { pd->verdict = v; pd->where = (int)q; return; }
+    }
+}
+
+int32_t verify_batch_impl(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const char *const *proofs, const size_t *lens, int32_t n_proofs, VerifyParams vp,
+                          int32_t *verdicts, int32_t *where, uint64_t *h_indices) {
+    if (!h_program || !proofs || !lens || !verdicts || n_proofs < 1 || n_proofs > (1 << 20)) return ZP_ERR_ARG;
+    for (int32_t i = 0; i < n_proofs; i++)
+        if (!proofs[i]) return ZP_ERR_ARG;
+    if (vp.logn < 1 || vp.logb < 1 || vp.logn + vp.logb > 30 || vp.fri_logf < 1 || vp.fri_logf > 4 || vp.fri_final_log < 0 || vp.fri_final_log >= vp.logn || vp.n_queries < 1 ||
+        vp.n_queries > 4096 || vp.pow_bits < 0 || vp.pow_bits > 40 || (vp.flags & ~(uint32_t)(ZP_VERIFY_HEADER_ONLY | ZP_VERIFY_TRUST_OPENINGS)))
+        return ZP_ERR_ARG;
+    // the statement
+    static const unsigned char magic[8] = {'Z', 'P', 'A', 'I', 'R', '1', 0, 0};
+    if (program_words < 12 || memcmp(h_program, magic, 8) != 0 || !zpi_program_fixed_table(h_program, program_words, nullptr)) return ZP_ERR_ARG;
+    ProgramInfo pg;
+    pg.words = h_program; pg.n_words = program_words;
+    pg.W = h_program[1]; pg.W2 = h_program[2]; pg.n_pub = h_program[4]; pg.n_chal = h_program[5]; pg.K = h_program[8]; pg.n_s2 = h_program[10]; pg.Q = h_program[11];
+    if (pg.W < 1 || pg.W >= 4096 || pg.W2 >= 4096 || pg.K < 1 || pg.Q < 1 || pg.Q > 16 || (pg.n_s2 == 0) != (pg.W2 == 0) || pg.n_chal != (pg.n_s2 ? 3u : 0u)) return ZP_ERR_ARG;
+    {
+        uint8_t dg[32];
+        Sha256::digest((const uint8_t *)h_program, program_words * 8, dg);
+        for (int i = 0; i < 8; i++) snprintf(pg.digest_hex + 2 * i, 3, "%02x", dg[i]);
+        for (int i = 0; i < 4; i++) { u64 w = 0; for (int b = 7; b >= 0; b--) w = (w << 8) | dg[8 * i + b]; pg.digest_words[i] = w % GL_P; }
+    }
+    vp.root32 = ctx ? ctx->root32 : ZP_ROOT32_DEFAULT;
+    vp.shift = ctx ? ctx->coset_shift : ZP_SHIFT_DEFAULT;
+    const HostPoseidon H = {ctx ? ctx->h_rc : (const u64 *)ZP_POSEIDON_DEFAULT_RC, ctx ? ctx->h_mds : (const u64 *)ZP_POSEIDON_DEFAULT_MDS};
+    const bool has_s2 = pg.n_s2 != 0, trust = (vp.flags & ZP_VERIFY_TRUST_OPENINGS) != 0;
+    const size_t nq = (size_t)vp.n_queries;
+
+    std::vector<Pending> pend((size_t)n_proofs);
+    std::vector<int32_t> hrc((size_t)n_proofs, ZP_OK);
+    // headers: a transcript is a serial chain, proofs are independent
+    spread((size_t)n_proofs, n_proofs > 1 ? vp.threads : 1, [&](size_t i) {
+        try { VerifyParams one = vp; if (n_proofs > 1) one.threads = 1; hrc[i] = header_phase(proofs[i], lens[i], pg, one, H, &pend[i]); }
+        catch (const std::bad_alloc &) { hrc[i] = ZP_ERR_NOMEM; }
+        catch (...) { hrc[i] = ZP_ERR_INTERNAL; }
+    });
+    for (int32_t r : hrc)
+        if (r != ZP_OK) {
+            if (ctx) ctx->err = r == ZP_ERR_UNSUPPORTED ? "a proof in BN128-hash mode (or a build without the openings parser)" : "the program blob could not be evaluated at the proof's point";
+            return r;
+        }
+
+    // the openings of every proof that got this far, tree by tree (a wave of the device kernel then holds one tree shape), and their arithmetic
+    std::vector<std::vector<u64>> canon((size_t)n_proofs);
+    std::vector<ZpOpening> ops;
+    std::vector<u64> roots;
+    int Tmax = 0;
+    for (size_t i = 0; i < pend.size(); i++) {
+        Pending &pd = pend[i];
+        if (!pd.queries_live) continue;
+        canon[i] = pd.values;
+        for (u64 &v : canon[i]) v = gl_canon(v);
+        for (u64 &v : pd.paths) v = gl_canon(v);
+        pd.open_ok.assign(nq * pd.T, 1);
+        pd.arith.assign(nq * (pd.sched.size() + 1), 0);
+        Tmax = pd.T > Tmax ? pd.T : Tmax;
+    }
+    if (trust) {
+        // the opened values as given: only their range is checked (a recursion STARK vouches for the paths)
+        for (Pending &pd : pend)
+            for (int t = 0; pd.queries_live && t < pd.T; t++)
+                for (size_t q = 0; q < nq; q++)
+                    for (int c = 0; c < pd.widths[t]; c++)
+                        if (pd.values[pd.voff[t] + q * (size_t)pd.widths[t] + c] >= GL_P) pd.open_ok[q * pd.T + t] = 0;
+    } else {
+        for (int t = 0; t < Tmax; t++)
+            for (size_t i = 0; i < pend.size(); i++) {
+                Pending &pd = pend[i];
+                if (!pd.queries_live) continue;
+                if (t == 0) { pd.root0 = roots.size() / 4; roots.insert(roots.end(), pd.roots.begin(), pd.roots.end()); }
+                const int n_fri = (int)pd.sched.size(), l = t - (pd.T - n_fri);
+                for (size_t q = 0; q < nq; q++) {
+                    // the row of tree t that query q opens: a FRI layer of 2^m leaves is opened at the low m bits of the index
+                    const u64 pos = l < 0 ? pd.index[q] : pd.index[q] & (((u64)1 << (pd.sched[l].first - pd.sched[l].second)) - 1);
+                    ops.push_back({&canon[i][pd.voff[t] + q * (size_t)pd.widths[t]], &pd.paths[pd.poff[t] + q * (size_t)pd.depths[t] * 4], pos, (uint32_t)pd.widths[t],
+                                   (uint32_t)pd.depths[t], (uint32_t)(pd.root0 + t)});
+                }
+            }
+        std::vector<uint8_t> ok(ops.size() ? ops.size() : 1);
+        if (ctx && !ops.empty()) {
+            if (!zpi_merkle_verify_openings) { ctx->err = "this build has no device side"; return ZP_ERR_UNSUPPORTED; }
+            ZP_TRY(zpi_merkle_verify_openings(ctx, ops.data(), ops.size(), roots.data(), roots.size() / 4, ok.data()));
+        } else {
+            spread(ops.size(), vp.threads, [&](size_t o) { ok[o] = H.opening_ok(ops[o], &roots[4 * (size_t)ops[o].root_slot]); });
+        }
+        size_t o = 0;
+        for (int t = 0; t < Tmax; t++)
+            for (Pending &pd : pend)
+                for (size_t q = 0; pd.queries_live && q < nq; q++) pd.open_ok[q * pd.T + t] = ok[o++];
+    }
+    for (size_t i = 0; i < pend.size(); i++) {
+        Pending &pd = pend[i];
+        if (!pd.queries_live) continue;
+        std::vector<e3> gp(pd.Wall + pd.Wt);
+        e3 g = e3_base(1);
+        for (e3 &x : gp) { x = g; g = e3_mul(g, pd.gamma); }
+        spread(nq, vp.threads, [&](size_t q) { query_arith(pd, vp, gp, canon[i], q, &pd.arith[q * (pd.sched.size() + 1)]); });
+        scan_verdict(&pd, vp, has_s2);
+    }
+    for (int32_t i = 0; i < n_proofs; i++) verdicts[i] = pend[i].verdict;
+    if (where) *where = pend[0].where;
+    // the indices exist once the transcript got to them: an accepted proof, or one rejected by the check on the indices or a later one
+    if (h_indices && (pend[0].verdict == ZP_VERDICT_ACCEPT || pend[0].verdict >= ZP_VERDICT_INDICES)) memcpy(h_indices, pend[0].qidx.data(), 8 * nq);
+    return ZP_OK;
+}
+
+template <class Body>
+int32_t verify_guarded(zp_ctx *ctx, Body body) {      // no exception crosses the ABI (the guarded() of csrc/prove.hip, for a ctx that may be NULL)
+    try {
+        return body();
+    } catch (const std::bad_alloc &) {
+        try { if (ctx) ctx->err = "out of host memory while verifying"; } catch (...) {}
+        return ZP_ERR_NOMEM;
+    } catch (const std::exception &e) {
+        try { if (ctx) ctx->err = std::string("internal error: ") + e.what(); } catch (...) {}
+        return ZP_ERR_INTERNAL;
+    } catch (...) {
+        return ZP_ERR_INTERNAL;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t zp_stark_verify(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const char *proof_json, size_t proof_len, int32_t logn, int32_t logb, int32_t fri_logf,
+                        int32_t fri_final_log, int32_t n_queries, int32_t pow_bits, uint32_t flags, int32_t threads, int32_t *verdict, int32_t *where, uint64_t *h_indices) {
+    if (!verdict || !where) return ZP_ERR_ARG;
+    *verdict = ZP_VERDICT_MALFORMED;
+    *where = -1;
+    const VerifyParams vp = {logn, logb, fri_logf, fri_final_log, n_queries, pow_bits, flags, threads, 0, 0};
+    return verify_guarded(ctx, [&] { return verify_batch_impl(ctx, h_program, program_words, &proof_json, &proof_len, 1, vp, verdict, where, h_indices); });
+}
+
+int32_t zp_stark_verify_batch(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const char *const *proofs, const size_t *lens, int32_t n_proofs, int32_t logn,
+                              int32_t logb, int32_t fri_logf, int32_t fri_final_log, int32_t n_queries, int32_t pow_bits, uint32_t flags, int32_t threads, int32_t *verdicts) {
+    const VerifyParams vp = {logn, logb, fri_logf, fri_final_log, n_queries, pow_bits, flags, threads, 0, 0};
+    return verify_guarded(ctx, [&] { return verify_batch_impl(ctx, h_program, program_words, proofs, lens, n_proofs, vp, verdicts, nullptr, nullptr); });
 }
 
 }  // extern "C"

@@ -161,6 +161,11 @@ SIGNATURES = {
     "zp_ntt_host": (C.c_int32, [_vp, _u64p, C.c_int32, C.c_int32, C.c_int32]),
     "zp_lde_host": (C.c_int32, [_vp, _u64p, _u64p, C.c_int32, C.c_int32, C.c_int32, C.c_uint64]),
     "zp_merkle_commit_host": (C.c_int32, [_vp, _u64p, C.c_size_t, C.c_int32, _u64p]),
+    "zp_stark_verify": (C.c_int32, [_vp, _u64p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
+                                    C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _u64p]),
+    "zp_stark_verify_batch": (C.c_int32, [_vp, _u64p, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(C.c_int32)]),
+    "zp_merkle_verify_batch": (C.c_int32, [_vp, _u64p, C.c_size_t, _u64p, _u64p, C.c_int32, _u64p, C.c_size_t, C.POINTER(C.c_uint8)]),
     "zp_set_tuning": (C.c_int32, [_vp, C.c_char_p, C.c_int32]),
     "zp_set_profiling": (C.c_int32, [_vp, C.c_int32]),
     "zp_get_pass_timings": (C.c_int32, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int32,
@@ -340,6 +345,54 @@ def program_eval_ext(program, pubchal, logn, root32, zeta, ev_z, ev_zw, threads=
     if rc != 0:
         raise ValueError("zp_program_eval_ext: malformed program or evaluations (%d)" % rc)
     return out
+
+
+# zp_stark_verify: the verdict classes and the flags (include/zeth_prover.h)
+VERDICT_ACCEPT, VERDICT_MALFORMED, VERDICT_PARAMS, VERDICT_IDENTITY, VERDICT_POW, VERDICT_INDICES, VERDICT_FINAL_DEGREE, VERDICT_OPENING, VERDICT_FRI = range(9)
+VERIFY_HEADER_ONLY, VERIFY_TRUST_OPENINGS = 1, 2
+
+
+def _verify_params(params):
+    d = params.to_dict() if hasattr(params, "to_dict") else dict(params)
+    if d.get("hash", "gl") != "gl":
+        raise ValueError("zp_stark_verify reads Goldilocks-mode proofs")
+    return [int(d[k]) for k in ("logn", "logb", "fri_logf", "fri_final_log", "n_queries")] + [int(d.get("pow_bits", 0))]
+
+
+def _verify_error(prover, rc, what):
+    if prover is not None:
+        prover._chk(rc)
+    raise ZpError(rc, what + ": bad arguments, a malformed program blob or a proof in BN128-hash mode")
+
+
+def stark_verify(program, text, params, flags=0, prover=None, threads=0):
+    """zp_stark_verify: (verdict, where, indices) of a chunk proof TEXT (str or bytes) of the statement `program` under the verifier's own
+    `params` (StarkParams or its dict).  verdict: VERDICT_*; where: the first failing query or -1; indices: the query indices the transcript
+    dictates (None when a check before them failed).  prover = None: on the host, default tables and domain; otherwise through that ctx"""
+    prog = np.ascontiguousarray(program, dtype=np.uint64)
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    pv = _verify_params(params)
+    idx = np.zeros(pv[4], dtype=np.uint64)
+    verdict, where = C.c_int32(0), C.c_int32(-1)
+    rc = load_library().zp_stark_verify(prover.ctx if prover is not None else None, prog.ctypes.data_as(_u64p), prog.size, raw, len(raw), *pv, int(flags), threads,
+                                        C.byref(verdict), C.byref(where), idx.ctypes.data_as(_u64p))
+    if rc != 0:
+        _verify_error(prover, rc, "zp_stark_verify")
+    got = verdict.value == VERDICT_ACCEPT or verdict.value >= VERDICT_INDICES      # when the library writes the indices (include/zeth_prover.h)
+    return verdict.value, where.value, ([int(v) for v in idx] if got else None)
+
+
+def stark_verify_batch(program, texts, params, flags=0, prover=None, threads=0):
+    """zp_stark_verify_batch: the verdicts of several proof texts of one statement and parameter set (the openings of all of them in one launch)"""
+    prog = np.ascontiguousarray(program, dtype=np.uint64)
+    raws = [t.encode() if isinstance(t, str) else bytes(t) for t in texts]
+    n = len(raws)
+    ptrs, lens, out = (C.c_char_p * n)(*raws), (C.c_size_t * n)(*[len(r) for r in raws]), (C.c_int32 * n)()
+    rc = load_library().zp_stark_verify_batch(prover.ctx if prover is not None else None, prog.ctypes.data_as(_u64p), prog.size, ptrs, lens, n, *_verify_params(params),
+                                              int(flags), threads, out)
+    if rc != 0:
+        _verify_error(prover, rc, "zp_stark_verify_batch")
+    return list(out)
 
 
 def wrap_aux(openings, program, pubs, logn, root32, addr):
@@ -987,6 +1040,18 @@ class Prover:
         out = C.c_uint64(0)
         self._chk(self.lib.zp_pow_grind(self.ctx, sd, int(bits), C.byref(out)))
         return int(out.value)
+
+    def merkle_verify_batch(self, values, index, paths, root):
+        """zp_merkle_verify_batch: values u64[n][width], index u64[n], paths u64[n][depth][4] (bottom-up), root u64[4] -> uint8[n], 1 = the opening hashes to the root"""
+        v = np.ascontiguousarray(values, dtype=np.uint64)
+        ix = np.ascontiguousarray(index, dtype=np.uint64)
+        pt = np.ascontiguousarray(paths, dtype=np.uint64).reshape(len(ix), -1, 4)
+        rt = np.ascontiguousarray(root, dtype=np.uint64)
+        assert v.ndim == 2 and v.shape[0] == len(ix) and rt.size == 4
+        ok = np.zeros(max(len(ix), 1), dtype=np.uint8)
+        self._chk(self.lib.zp_merkle_verify_batch(self.ctx, v.ctypes.data_as(_u64p), v.shape[1], ix.ctypes.data_as(_u64p), pt.ctypes.data_as(_u64p) if pt.size else None,
+                                                  pt.shape[1], rt.ctypes.data_as(_u64p), len(ix), ok.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return ok[:len(ix)]
 
     def merkle_commit(self, d_cols, M, W, d_tree):
         self._chk(self.lib.zp_merkle_commit(self.ctx, _ptr(d_cols), M, W, _ptr(d_tree)))

@@ -579,6 +579,42 @@ int32_t zp_msm_bn254_g2(zp_ctx *ctx, const uint32_t *d_points, const uint32_t *d
 int32_t zp_fixed_base_mul_bn254(zp_ctx *ctx, const uint32_t *h_base, const uint32_t *h_scalars, size_t n, uint32_t *h_points, int32_t threads);
 int32_t zp_fixed_base_mul_bn254_g2(zp_ctx *ctx, const uint32_t *h_base, const uint32_t *h_scalars, size_t n, uint32_t *h_points, int32_t threads);
 
+/* ---- the STARK verifier: does a chunk proof TEXT (what zp_stark_prove wrote, what a client hands in) verify? -------------------------
+ * Goldilocks-hash mode only: a proof whose params.hash is "bn128" is ZP_ERR_UNSUPPORTED.
+ * The return value is ZP_OK whenever a verdict was reached -- a rejected proof is a verdict, not an error; negative codes are the caller's own
+ * mistakes (null pointer, a program blob that does not parse, parameters out of the prover's ranges, a HIP failure).  No exception crosses.
+ * The security parameters are the CALLER's; the root of unity and the coset shift are the ctx's (zp_set_constants), and the proof's must
+ * equal them.  *verdict = the FIRST failing check in the protocol's order: parameters / domain / statement digest / counts (PARAMS), the
+ * constraint identity at the out-of-domain point (IDENTITY), grinding (POW), the query indices against the transcript (INDICES), the degree of
+ * the final FRI layer (FINAL_DEGREE), then per query, in query order: the trace, quotient and stage-2 openings (OPENING), per FRI layer its
+ * opening (OPENING) and its value against the previous fold (FRI), the last fold against the final layer (FRI).  MALFORMED: a text outside the
+ * strict grammar of the proof texts, a missing member, a wrong width or count.  *where = the position of the first failing query, or -1.
+ * A number the protocol takes as a field element (public input, evaluation, opened value, path word) is read mod p; a number it compares
+ * (parameters, roots, indices, the nonce, an opened FRI value or final-layer value against a fold) matches nothing when it is >= p.
+ * h_indices (may be NULL) receives the n_queries indices the transcript dictates exactly when *verdict is ACCEPT or INDICES or a later class
+ * (the checks before the indices have passed); otherwise it is left as it was.
+ * flags: ZP_VERIFY_HEADER_ONLY: everything that needs no opening; "queries" is not read and the indices are not compared.
+ *        ZP_VERIFY_TRUST_OPENINGS: opened values are only range-checked (< p), paths are not hashed -- for a caller whose recursion STARK vouches for them.
+ * ctx = NULL is allowed for the two zp_stark_verify* calls: everything then runs on the host with the library's default tables and domain
+ * constants (a machine without a GPU).  With a ctx the leaf hashes and paths of ALL openings of a call are one launch (zp_merkle_verify_batch's
+ * kernels); the transcript, the identity and the arithmetic at the queries are host code on `threads` threads (<= 0: one per core, at most 16). */
+enum { ZP_VERDICT_ACCEPT = 0, ZP_VERDICT_MALFORMED = 1, ZP_VERDICT_PARAMS = 2, ZP_VERDICT_IDENTITY = 3, ZP_VERDICT_POW = 4,
+       ZP_VERDICT_INDICES = 5, ZP_VERDICT_FINAL_DEGREE = 6, ZP_VERDICT_OPENING = 7, ZP_VERDICT_FRI = 8 };
+enum { ZP_VERIFY_HEADER_ONLY = 1, ZP_VERIFY_TRUST_OPENINGS = 2 };
+int32_t zp_stark_verify(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const char *proof_json, size_t proof_len,
+                        int32_t logn, int32_t logb, int32_t fri_logf, int32_t fri_final_log, int32_t n_queries, int32_t pow_bits,
+                        uint32_t flags, int32_t threads, int32_t *verdict, int32_t *where, uint64_t *h_indices);
+/* n_proofs texts of ONE statement and parameter set: verdicts[i] as zp_stark_verify gives it; the openings of all of them in one launch */
+int32_t zp_stark_verify_batch(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const char *const *proofs, const size_t *lens,
+                              int32_t n_proofs, int32_t logn, int32_t logb, int32_t fri_logf, int32_t fri_final_log, int32_t n_queries,
+                              int32_t pow_bits, uint32_t flags, int32_t threads, int32_t *verdicts);
+/* the device primitive on its own: n openings into one binary tree of 2^depth leaves, each of `width` values (host arrays: h_values
+ * u64[n][width], h_index u64[n], h_paths u64[n][depth][4] bottom-up, h_root4 u64[4]; depth 0 is allowed; leaves of <= 4 values are their own
+ * digest, zero padded, as in zp_merkle_commit).  h_ok[o] = 1 iff opening o hashes to the root.  From "verify_lane_min" (zp_set_tuning)
+ * openings on, one lane per opening; below it the 12-lanes-per-opening walk; the same flags either way. */
+int32_t zp_merkle_verify_batch(zp_ctx *ctx, const uint64_t *h_values, size_t width, const uint64_t *h_index, const uint64_t *h_paths,
+                               int32_t depth, const uint64_t *h_root4, size_t n, uint8_t *h_ok);
+
 /* ---- host-buffer conveniences (H2D + compute + D2H + sync), the form a non-GPU-aware host uses */
 int32_t zp_ntt_host(zp_ctx *ctx, uint64_t *h_cols, int32_t logn, int32_t W, int32_t inverse);
 int32_t zp_lde_host(zp_ctx *ctx, const uint64_t *h_in, uint64_t *h_out, int32_t logn, int32_t logb,
@@ -603,7 +639,7 @@ int32_t zp_hbm_copy_probe(zp_ctx *ctx, const void *d_src, void *d_dst, size_t by
  * kernel (15), "msm_chunk_log" log2 of the points per Pippenger run (24), "msm_c" window width, "ntt_small_wave" / "fri_fold_lanes" the in-wave (DPP / ds_swizzle) forms of the
  * small transform and of the fold by 16: 0 where they measured faster, 1 always, 2 never; "ntt_logt12" 1: radix-4096 passes on 64-KiB tiles, two
  * 512-thread workgroups per CU (2: 128-KiB tiles); "p254_block" 2: the lane-per-permutation Poseidon-BN254 kernel walks its partial rounds one by
- * one instead of in blocks of four; 0 = default); not for production hosts */
+ * one instead of in blocks of four; "verify_lane_min" openings per call from which the verifier hashes one opening per lane (0 = 256: a guess, unmeasured); 0 = default); not for production hosts */
 int32_t zp_set_tuning(zp_ctx *ctx, const char *key, int32_t value);
 
 /* ---- introspection ------------------------------------------------------------------------- */
