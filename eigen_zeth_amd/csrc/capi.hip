@@ -471,7 +471,6 @@ int32_t zp_set_tuning(zp_ctx *ctx, const char *key, int32_t value) {
     else if (!strcmp(key, "g16_parallel")) ctx->tune_g16_parallel = value;
     else if (!strcmp(key, "seam_tpw")) ctx->tune_seam_tpw = value;
     else if (!strcmp(key, "lde_seam_plans")) ctx->tune_lde_seam_plans = value;
-    else if (!strcmp(key, "merkle_top_wave")) ctx->tune_merkle_top_wave = value;
     else if (!strcmp(key, "ntt_small_wave")) ctx->tune_ntt_small_wave = value;
     else if (!strcmp(key, "synth_rowwise")) ctx->tune_synth_rowwise = value;
     else if (!strcmp(key, "p254_scaled")) ctx->tune_p254_scaled = value;

@@ -6,13 +6,20 @@
 // throughput kernels walk the partial rounds three at a time (partial3_default: three S-boxes + ONE matrix product,
 // round 6) and compute only the digest rows of the last product where only a digest is read.
 //
-// Mapping: one lane = one permutation, the 12-element state lives in 24 VGPRs; round constants and
-// the MDS matrix are wave-uniform and are fetched with scalar loads.  The leaf kernel walks the
-// column-major matrix with lane = row, so every column read is a coalesced 512-byte run per wave.
+// Two mappings, each written once:
+//   * throughput -- poseidon_perm<DEFMDS, OUT4>: one lane = one permutation, the 12-element state lives in 24 VGPRs; round constants and the MDS
+//     matrix are wave-uniform and are fetched with scalar loads.  Kernels: poseidon_perm_kernel, merkle_leaves_kernel (one kernel for leaves given
+//     as columns or as rows: the layout is a template argument), merkle_level_kernel, openings_lane_kernel, pow_grind_kernel.  Each exists for
+//     the default matrix (literals) and for an injected one (LDS); launch_mds is the one place that picks between them.
+//   * latency -- spread_perm: one lane = one state WORD, 12 lanes exchange a state through a 12-word LDS row.  Kernels: poseidon_perm_small_kernel,
+//     the single-wave kernels through wave12_perm (poseidon_sponge_kernel, sponge_chains_kernel, openings_walk_kernel), merkle_leaves_coop_kernel
+//     and merkle_subtree_kernel.  Any matrix, read as data.
+// rowsum_reduce is the end of every row sum over a matrix that is data (mds_ark's general branch, spread_perm, poseidon_trace_kernel).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 #include <new>
+#include <type_traits>
 
 #include "ctx.hpp"
 // the Poseidon kernels fit 64 VGPRs (8 waves per SIMD) with the literal-table MDS: low scratch window
@@ -54,6 +61,13 @@ __host__ __device__ __forceinline__ constexpr u32 def_mds(int i, int j) {
 // spills them to VGPR lanes; LDS reads of a wave-uniform address are broadcasts).
 #include "poseidon_mds_asm.inc"   // mds_ark_default_asm: the default matrix as mad chains, 24 + 4 instructions per row
 
+// the end of a row sum over any matrix with entries < 2^28: (alo, ahi) = the sums over the low and the high 32-bit halves, value = alo + ahi 2^32
+// < 2^96  ->  weak.  Used by mds_ark's general branch, spread_perm and poseidon_trace_kernel
+__device__ __forceinline__ u64 rowsum_reduce(u64 alo, u64 ahi) {
+    const u64 mid = (alo >> 32) + ahi;  // value = (u32)alo + mid * 2^32
+    return gl_reduce96_weak(((u64)(u32)mid << 32) | (u32)alo, (u32)(mid >> 32), 0u);
+}
+
 template <bool ADDC, bool DEFMDS>
 __device__ __forceinline__ void mds_ark(u64 *s, const u32 *__restrict__ mds, const u64 *__restrict__ c) {
     if constexpr (DEFMDS) {
@@ -71,8 +85,7 @@ __device__ __forceinline__ void mds_ark(u64 *s, const u32 *__restrict__ mds, con
             alo += (u64)m * (u32)s[j];
             ahi += (u64)m * (u32)(s[j] >> 32);
         }
-        const u64 mid = (alo >> 32) + ahi;  // value = (u32)alo + mid * 2^32
-        o[i] = gl_reduce96_weak(((u64)(u32)mid << 32) | (u32)alo, (u32)(mid >> 32), 0u);
+        o[i] = rowsum_reduce(alo, ahi);
     }
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = o[i];
@@ -274,35 +287,45 @@ __global__ void __launch_bounds__(256) poseidon_perm_kernel(u64 *states, size_t 
     for (int j = 0; j < 12; j++) states[i * 12 + j] = s[j];
 }
 
-// Latency form for a handful of permutations (Fiat-Shamir transcript: one state at a time).  One lane per
-// state WORD instead of one lane per state: 12 lanes share a permutation through LDS, so a round is one
-// S-box + one 12-term row sum per lane (~150 dependent instructions) instead of ~1600 on a single lane.
+// ---- the SPREAD-STATE permutation: one lane per state WORD instead of one lane per state.  12 lanes share a permutation through a 12-word LDS
+// row, so a round is one S-box + one 12-term row sum per lane (~150 dependent instructions) instead of ~1600 on a single lane: the latency form,
+// for everything that has fewer permutations in flight than the chip has lanes.  Lane e holds word e; per round it adds its constant, applies x^7
+// (full rounds, or word 0), publishes its word, sums its matrix row over the 12 published words in two 32-bit halves and reduces.  Textbook
+// schedule; canonical out.
+//   sh: the lane's row of the exchange buffer;  rc: the 360 round constants ALREADY OFFSET to the lane's word (global memory or an LDS copy);
+//   m: the lane's 12 matrix coefficients (global mds + 12 e, or registers);  on: guards the LDS write and the row sum -- a lane that is off runs
+//   both barriers of every round, never touches sh (its row may lie past the buffer) and returns garbage.
+// Callers: poseidon_perm_small_kernel, wave12_perm (the single-wave kernels), merkle_leaves_coop_kernel, merkle_subtree_kernel.
+__device__ __forceinline__ u64 spread_perm(u64 s, int e, bool on, u64 *sh, const u64 *rc, const u32 *m) {
+    for (int r = 0; r < 30; r++) {
+        s = gl_add_weak(s, rc[r * 12]);
+        if (r < 4 || r >= 26 || e == 0) s = sbox7(s);
+        if (on) sh[e] = s;
+        __syncthreads();
+        u64 alo = 0, ahi = 0;
+        if (on) {
+#pragma unroll
+            for (int j = 0; j < 12; j++) {
+                const u64 v = sh[j];
+                alo += (u64)m[j] * (u32)v;
+                ahi += (u64)m[j] * (u32)(v >> 32);
+            }
+        }
+        __syncthreads();
+        s = rowsum_reduce(alo, ahi);
+    }
+    return gl_canon(s);
+}
+
+// A handful of permutations (count <= 64: a transcript state at a time): five states per wave, lanes 60..63 idle (q = 5 is past the buffer)
 __global__ void __launch_bounds__(64) poseidon_perm_small_kernel(u64 *states, int count, const u64 *rc, const u32 *mds) {
     __shared__ u64 sh[5][12];
     const int lane = threadIdx.x, q = lane / 12, e = lane % 12;
     const int perm = blockIdx.x * 5 + q;
     const bool on = q < 5 && perm < count;
     u64 s = on ? states[(size_t)perm * 12 + e] : 0ULL;
-    for (int r = 0; r < 30; r++) {
-        s = gl_add_weak(s, rc[r * 12 + e]);
-        if (r < 4 || r >= 26 || e == 0) s = sbox7(s);
-        if (on) sh[q][e] = s;
-        __syncthreads();
-        u64 alo = 0, ahi = 0;
-        if (on) {
-#pragma unroll
-            for (int j = 0; j < 12; j++) {
-                const u64 v = sh[q][j];
-                const u32 m = mds[e * 12 + j];
-                alo += (u64)m * (u32)v;
-                ahi += (u64)m * (u32)(v >> 32);
-            }
-        }
-        __syncthreads();
-        const u64 mid = (alo >> 32) + ahi;
-        s = gl_reduce96_weak(((u64)(u32)mid << 32) | (u32)alo, (u32)(mid >> 32), 0u);
-    }
-    if (on) states[(size_t)perm * 12 + e] = gl_canon(s);
+    s = spread_perm(s, e, on, sh[q], rc + e, mds + e * 12);
+    if (on) states[(size_t)perm * 12 + e] = s;
 }
 
 // one permutation of the state a wave holds in its lanes 0..11 (the single-wave kernels: transcript steps, recursion-witness walks)
@@ -315,59 +338,23 @@ __device__ __forceinline__ void wave12_tables(int e, bool on, const u64 *rc, con
     __syncthreads();
 }
 __device__ __forceinline__ u64 wave12_perm(u64 s, int e, bool on, u64 *sh, const u64 *rcs, const u32 *row) {
-    for (int r = 0; r < 30; r++) {
-        s = gl_add_weak(s, rcs[r * 12 + (on ? e : 0)]);
-        if (r < 4 || r >= 26 || e == 0) s = sbox7(s);
-        if (on) sh[e] = s;
-        __syncthreads();
-        u64 alo = 0, ahi = 0;
-        if (on) {
-#pragma unroll
-            for (int j = 0; j < 12; j++) {
-                const u64 v = sh[j];
-                const u32 m = row[j];
-                alo += (u64)m * (u32)v;
-                ahi += (u64)m * (u32)(v >> 32);
-            }
-        }
-        __syncthreads();
-        const u64 mid = (alo >> 32) + ahi;
-        s = gl_reduce96_weak(((u64)(u32)mid << 32) | (u32)alo, (u32)(mid >> 32), 0u);
-    }
-    return gl_canon(s);
+    return spread_perm(s, e, on, sh, rcs + (on ? e : 0), row);
 }
 
-// The Fiat-Shamir sponge as ONE launch: buf = [12 state words][nblocks x 8 block words][(1 + extra) x 8 rate words out].
+// The Fiat-Shamir sponge as ONE launch: buf = [12 state words][nblocks x 8 block words][(1 + extra) x 8 rate words out][caps out].
 // For every block: the rate (state[0..8)) is overwritten with the block, then one permutation (no block: one permutation);
 // then `extra` further permutations, the rate after each of the 1 + extra steps is written out.  Same 12-lanes-per-state form
 // as above: a transcript of k permutations costs one host round trip instead of k.
-// caps (optional): the capacity (state[8..12)) after EVERY permutation, 4 words each -- with the blocks and the rates that is the
+// caps (want_caps): the capacity (state[8..12)) after EVERY permutation, 4 words each -- with the blocks and the rates that is the
 // input state of every permutation of the step, what the verifier AIR's witness needs (stark/verifier_air.py: transcript blocks).
-__global__ void __launch_bounds__(64) poseidon_sponge_kernel(u64 *buf, int nblocks, int extra, const u64 *rc, const u32 *mds, u64 *caps) {
-    __shared__ u64 sh[12];
-    __shared__ u64 rcs[360];
-    const int e = threadIdx.x;
-    const bool on = e < 12;
-    u32 row[12];
-    wave12_tables(e, on, rc, mds, rcs, row);
-    u64 s = on ? buf[e] : 0ULL;
-    u64 *rates = buf + 12 + (size_t)nblocks * 8;
-    const int absorb = nblocks > 0 ? nblocks : 1;
-    for (int b = 0; b < absorb + extra; b++) {
-        if (b < nblocks && e < 8) s = buf[12 + (size_t)b * 8 + e];
-        s = wave12_perm(s, e, on, sh, rcs, row);
-        if (b >= absorb - 1 && e < 8) rates[(size_t)(b - (absorb - 1)) * 8 + e] = s;
-        if (caps && on && e >= 8) caps[(size_t)b * 4 + (e - 8)] = s;
-    }
-    if (on) buf[e] = s;
-}
-
-// The same step with its buffer in PAGE-LOCKED, device-visible host memory (round 5): the host writes state and blocks into the ctx's staging
-// buffer, this kernel pulls them into LDS in one coalesced sweep, walks them, and posts state, rates and capacities straight back -- one launch
-// and two stream synchronisations per transcript step instead of four launches (copy kernels in and out) and four synchronisations: a step
-// went from ~180 us to ~45 us, and a proof has 9-12 of them, a recursion witness ~24.
-__global__ void __launch_bounds__(64) poseidon_sponge_pinned_kernel(u64 *buf, int nblocks, int extra, const u64 *rc, const u32 *mds, int want_caps) {
-    extern __shared__ u64 stage[];              // [12 + nblocks * 8]
+//
+// STAGED: the buffer is PAGE-LOCKED, device-visible host memory (round 5): the host writes state and blocks into the ctx's staging buffer, the kernel
+// pulls them into LDS in one coalesced sweep, walks them, and posts state, rates and capacities straight back -- one launch and two stream
+// synchronisations per transcript step instead of four launches (copy kernels in and out) and four synchronisations: a step went from ~180 us to
+// ~45 us, and a proof has 9-12 of them, a recursion witness ~24.  Not STAGED (an input above 48 KiB): buf is device memory, read in place.
+template <bool STAGED>
+__global__ void __launch_bounds__(64) poseidon_sponge_kernel(u64 *buf, int nblocks, int extra, const u64 *rc, const u32 *mds, int want_caps) {
+    extern __shared__ u64 stage[];              // STAGED: [12 + nblocks * 8]
     __shared__ u64 sh[12];
     __shared__ u64 rcs[360];
     const int e = threadIdx.x;
@@ -375,13 +362,16 @@ __global__ void __launch_bounds__(64) poseidon_sponge_pinned_kernel(u64 *buf, in
     u32 row[12];
     wave12_tables(e, on, rc, mds, rcs, row);
     const int nin = 12 + nblocks * 8;
-    for (int i = e; i < nin; i += 64) stage[i] = buf[i];
-    __syncthreads();
-    u64 s = on ? stage[e] : 0ULL;
+    if constexpr (STAGED) {
+        for (int i = e; i < nin; i += 64) stage[i] = buf[i];
+        __syncthreads();
+    }
+    const u64 *in = STAGED ? stage : buf;
+    u64 s = on ? in[e] : 0ULL;
     u64 *rates = buf + nin, *caps = rates + (size_t)(1 + extra) * 8;
     const int absorb = nblocks > 0 ? nblocks : 1;
     for (int b = 0; b < absorb + extra; b++) {
-        if (b < nblocks && e < 8) s = stage[12 + b * 8 + e];
+        if (b < nblocks && e < 8) s = in[12 + b * 8 + e];
         s = wave12_perm(s, e, on, sh, rcs, row);
         if (b >= absorb - 1 && e < 8) rates[(size_t)(b - (absorb - 1)) * 8 + e] = s;
         if (want_caps && on && e >= 8) caps[(size_t)b * 4 + (e - 8)] = s;
@@ -570,31 +560,35 @@ __global__ void __launch_bounds__(128) poseidon_trace_kernel(const u64 *__restri
                 alo += (u64)m * (u32)y[j];
                 ahi += (u64)m * (u32)(y[j] >> 32);
             }
-            const u64 mid = (alo >> 32) + ahi;
-            s[i] = gl_canon(gl_reduce96_weak(((u64)(u32)mid << 32) | (u32)alo, (u32)(mid >> 32), 0u));
+            s[i] = gl_canon(rowsum_reduce(alo, ahi));
         }
     }
 }
 
-// leaf i = linear hash of (cols[0][i], cols[1][i], ... cols[W-1][i]);  lane = row
-template <bool DEFMDS>
-__global__ void __launch_bounds__(256) merkle_leaves_kernel(const u64 *__restrict__ cols, size_t M, int W,
+// leaf i = linear hash of its `len` values: blocks of 8 into the rate, the digest so far as the next capacity (<= 4 values are their own digest,
+// zero padded);  lane = leaf, the throughput form.  ROWS = false: `len` columns of M values (value k of leaf i at src[k M + i]; every column
+// read is a coalesced 512-byte run per wave);  ROWS = true: M contiguous rows of `len` values (src[i len + k])
+template <bool ROWS> using leaf_len_t = std::conditional_t<ROWS, size_t, int>;      // as the C ABI gives it: zp_merkle_commit's W is an int32
+template <bool DEFMDS, bool ROWS>
+__global__ void __launch_bounds__(256) merkle_leaves_kernel(const u64 *__restrict__ src, size_t M, leaf_len_t<ROWS> len,
                                                            u64 *__restrict__ tree, const u64 *rc, const u32 *mds) {
     __shared__ u32 smds[DEFMDS ? 1 : 144];
     mds = stage_mds<DEFMDS>(mds, smds);
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= M) return;
+    const u64 *row = src + i * (size_t)len;      // ROWS
+    auto at = [&](leaf_len_t<ROWS> k) { return k < len ? (ROWS ? row[k] : src[(size_t)k * M + i]) : 0ULL; };     // value k of leaf i, zero past the end
     u64 s[12];
-    if (W <= 4) {
+    if (len <= 4) {
 #pragma unroll
-        for (int j = 0; j < 4; j++) tree[i * 4 + j] = j < W ? cols[(size_t)j * M + i] : 0ULL;
+        for (int j = 0; j < 4; j++) tree[i * 4 + j] = at(j);
         return;
     }
 #pragma unroll
     for (int j = 8; j < 12; j++) s[j] = 0;
-    for (int off = 0; off < W; off += 8) {
+    for (leaf_len_t<ROWS> off = 0; off < len; off += 8) {
 #pragma unroll
-        for (int j = 0; j < 8; j++) s[j] = (off + j < W) ? cols[(size_t)(off + j) * M + i] : 0ULL;
+        for (int j = 0; j < 8; j++) s[j] = at(off + j);
         poseidon_perm<DEFMDS, true>(s, rc, mds);
 #pragma unroll
         for (int j = 0; j < 4; j++) s[8 + j] = s[j];
@@ -605,27 +599,7 @@ __global__ void __launch_bounds__(256) merkle_leaves_kernel(const u64 *__restric
 
 // Small trees (FRI layers below 2^14 leaves): 12 lanes per leaf, like merkle_subtree_kernel -- a leaf of 24 values is
 // three dependent permutations, 0.33 ms on a single lane while the chip idles, ~50 us with the state spread over lanes.
-// One permutation of the 64 states a workgroup holds, lane = (state, element); sh is the exchange buffer.
-__device__ __forceinline__ u64 coop_perm(u64 s, int node, int e, u64 (*sh)[12], const u64 *rc, const u32 *mds) {
-    for (int r = 0; r < 30; r++) {
-        s = gl_add_weak(s, rc[r * 12 + e]);
-        if (r < 4 || r >= 26 || e == 0) s = sbox7(s);
-        sh[node][e] = s;
-        __syncthreads();
-        u64 alo = 0, ahi = 0;
-#pragma unroll
-        for (int j = 0; j < 12; j++) {
-            const u64 v = sh[node][j];
-            const u32 m = mds[e * 12 + j];
-            alo += (u64)m * (u32)v;
-            ahi += (u64)m * (u32)(v >> 32);
-        }
-        __syncthreads();
-        const u64 mid = (alo >> 32) + ahi;
-        s = gl_reduce96_weak(((u64)(u32)mid << 32) | (u32)alo, (u32)(mid >> 32), 0u);
-    }
-    return gl_canon(s);
-}
+// 64 leaves per workgroup, lane = (leaf, element), one spread_perm row each; constants and matrix row from global memory (L2: 768 lanes share them).
 // stride_e / stride_i: element (row i, position k) sits at src[k * stride_e + i * stride_i]  (columns: M, 1; rows: 1, len)
 __global__ void __launch_bounds__(768) merkle_leaves_coop_kernel(const u64 *__restrict__ src, size_t M, size_t len, size_t stride_e,
                                                                 size_t stride_i, u64 *__restrict__ tree, const u64 *rc,
@@ -641,7 +615,7 @@ __global__ void __launch_bounds__(768) merkle_leaves_coop_kernel(const u64 *__re
     u64 s = 0;
     for (size_t off = 0; off < len; off += 8) {
         if (e < 8) s = (on && off + e < len) ? src[(off + e) * stride_e + i * stride_i] : 0ULL;
-        s = coop_perm(s, node, e, sh, rc, mds);
+        s = spread_perm(s, e, true, sh[node], rc + e, mds + e * 12);
         // capacity of the next block = the first four outputs
         sh[node][e] = s;
         __syncthreads();
@@ -650,34 +624,6 @@ __global__ void __launch_bounds__(768) merkle_leaves_coop_kernel(const u64 *__re
         if (e >= 8) s = cap;
         else if (off + 8 >= len && e < 4 && on) tree[i * 4 + e] = s;
     }
-}
-
-// leaves given as M contiguous rows of `len` elements
-template <bool DEFMDS>
-__global__ void __launch_bounds__(256) merkle_leaves_rows_kernel(const u64 *__restrict__ rows, size_t M, size_t len,
-                                                                u64 *__restrict__ tree, const u64 *rc, const u32 *mds) {
-    __shared__ u32 smds[DEFMDS ? 1 : 144];
-    mds = stage_mds<DEFMDS>(mds, smds);
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= M) return;
-    const u64 *row = rows + i * len;
-    u64 s[12];
-    if (len <= 4) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) tree[i * 4 + j] = (size_t)j < len ? row[j] : 0ULL;
-        return;
-    }
-#pragma unroll
-    for (int j = 8; j < 12; j++) s[j] = 0;
-    for (size_t off = 0; off < len; off += 8) {
-#pragma unroll
-        for (int j = 0; j < 8; j++) s[j] = (off + j < len) ? row[off + j] : 0ULL;
-        poseidon_perm<DEFMDS, true>(s, rc, mds);
-#pragma unroll
-        for (int j = 0; j < 4; j++) s[8 + j] = s[j];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; j++) tree[i * 4 + j] = s[8 + j];
 }
 
 // one tree level: node i = P(child[2i] || child[2i+1] || 0^4)[0..4]
@@ -712,24 +658,8 @@ __global__ void __launch_bounds__(768) merkle_subtree_kernel(u64 *prev, size_t c
         u64 *next = prev + cnt * 4;
         const bool on = (size_t)node < half;
         u64 s = (on && e < 8) ? prev[(first + 2 * (size_t)node) * 4 + e] : 0ULL;
-        for (int r = 0; r < 30; r++) {
-            s = gl_add_weak(s, rc[r * 12 + e]);
-            if (r < 4 || r >= 26 || e == 0) s = sbox7(s);
-            sh[node][e] = s;
-            __syncthreads();
-            u64 alo = 0, ahi = 0;
-#pragma unroll
-            for (int j = 0; j < 12; j++) {
-                const u64 v = sh[node][j];
-                const u32 m = mds[e * 12 + j];
-                alo += (u64)m * (u32)v;
-                ahi += (u64)m * (u32)(v >> 32);
-            }
-            __syncthreads();
-            const u64 mid = (alo >> 32) + ahi;
-            s = gl_reduce96_weak(((u64)(u32)mid << 32) | (u32)alo, (u32)(mid >> 32), 0u);
-        }
-        if (on && e < 4) next[((first >> 1) + (size_t)node) * 4 + e] = gl_canon(s);
+        s = spread_perm(s, e, true, sh[node], rc + e, mds + e * 12);     // idle nodes hash zeros in rows of their own
+        if (on && e < 4) next[((first >> 1) + (size_t)node) * 4 + e] = s;
         __threadfence_block();
         __syncthreads();
         prev = next;
@@ -739,53 +669,11 @@ __global__ void __launch_bounds__(768) merkle_subtree_kernel(u64 *prev, size_t c
     }
 }
 
-// The same subtree walk with the state exchanged by WAVE SHUFFLES instead of LDS + two workgroup barriers per round (round 5; knob
-// merkle_top_wave): a node's 12 state words sit in 12 lanes of one 16-lane row (four nodes per wave, lanes 12..15 of a row idle), a round's row
-// sum gathers them with twelve 64-bit shuffles whose source lane (row base + (e + k) mod 12) and coefficient m[e][(e + k) mod 12] are fixed per
-// lane for the whole kernel, and nothing synchronises inside a permutation -- one workgroup barrier per tree LEVEL (the next level reads what
-// other waves wrote) instead of sixty.  64 parents per 1024-thread workgroup and level, as the LDS form.  Same values (tests/test_gpu_parity.py
-// compares every node of small trees with the oracle under both knob settings).
-__global__ void __launch_bounds__(1024) merkle_subtree_wave_kernel(u64 *prev, size_t cnt, int nlev, const u64 *rc, const u32 *mds) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int node = wv * 4 + (lane >> 4), e = lane & 15, rowbase = lane & ~15;
-    const bool word = e < 12;
-    const int ee = word ? e : 11;
-    int src[12];
-    u32 m[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) {
-        const int j = (ee + k) % 12;
-        src[k] = rowbase + j;
-        m[k] = word ? mds[ee * 12 + j] : 0u;
-    }
-    size_t first = (size_t)blockIdx.x * 128;
-    size_t width = cnt < 128 ? cnt : 128;
-    for (int l = 0; l < nlev; l++) {
-        const size_t half = width >> 1;
-        u64 *next = prev + cnt * 4;
-        const bool on = (size_t)node < half && word;
-        u64 s = (on && e < 8) ? prev[(first + 2 * (size_t)node) * 4 + e] : 0ULL;
-        for (int r = 0; r < 30; r++) {
-            s = gl_add_weak(s, rc[r * 12 + ee]);
-            if (r < 4 || r >= 26 || e == 0) s = sbox7(s);
-            u64 alo = 0, ahi = 0;
-#pragma unroll
-            for (int k = 0; k < 12; k++) {
-                const u64 v = (u64)__shfl((unsigned long long)s, src[k]);
-                alo += (u64)m[k] * (u32)v;
-                ahi += (u64)m[k] * (u32)(v >> 32);
-            }
-            const u64 mid = (alo >> 32) + ahi;
-            s = gl_reduce96_weak(((u64)(u32)mid << 32) | (u32)alo, (u32)(mid >> 32), 0u);
-        }
-        if (on && e < 4) next[((first >> 1) + (size_t)node) * 4 + e] = gl_canon(s);
-        __threadfence_block();
-        __syncthreads();
-        prev = next;
-        cnt >>= 1;
-        first >>= 1;
-        width = half;
-    }
+// the one place that turns ctx->mds_is_default into a template argument: kt / kf are the <true> / <false> instantiations of one throughput
+// kernel (256 lanes per workgroup, a parameter list that ends ..., rc, mds)
+template <class K, class... A>
+void launch_mds(zp_ctx *ctx, K kt, K kf, size_t blocks, A... args) {
+    hipLaunchKernelGGL(ctx->mds_is_default ? kt : kf, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, args..., ctx->d_rc, ctx->d_mds);
 }
 
 int32_t tree_levels(zp_ctx *ctx, u64 *tree, size_t M) {
@@ -798,12 +686,8 @@ int32_t tree_levels(zp_ctx *ctx, u64 *tree, size_t M) {
             int lg = 0;
             while (((size_t)1 << lg) < cnt) lg++;
             const int nlev = lg < 7 ? lg : 7;
-            if (ctx->tune_merkle_top_wave)
-                hipLaunchKernelGGL(merkle_subtree_wave_kernel, dim3((unsigned)(cnt < 128 ? 1 : cnt / 128)), dim3(1024), 0, ctx->stream, prev, cnt, nlev,
-                                   ctx->d_rc, ctx->d_mds);
-            else
-                hipLaunchKernelGGL(merkle_subtree_kernel, dim3((unsigned)(cnt < 128 ? 1 : cnt / 128)), dim3(768), 0, ctx->stream,
-                                   prev, cnt, nlev, ctx->d_rc, ctx->d_mds);
+            hipLaunchKernelGGL(merkle_subtree_kernel, dim3((unsigned)(cnt < 128 ? 1 : cnt / 128)), dim3(768), 0, ctx->stream,
+                               prev, cnt, nlev, ctx->d_rc, ctx->d_mds);
             ZP_HIP(ctx, hipGetLastError());
             for (int l = 0; l < nlev; l++) {
                 prev += cnt * 4;
@@ -811,17 +695,26 @@ int32_t tree_levels(zp_ctx *ctx, u64 *tree, size_t M) {
             }
             continue;
         }
-        if (ctx->mds_is_default)
-            hipLaunchKernelGGL(merkle_level_kernel<true>, dim3((unsigned)((half + 255) / 256)), dim3(256), 0, ctx->stream,
-                               prev, next, half, ctx->d_rc, ctx->d_mds);
-        else
-            hipLaunchKernelGGL(merkle_level_kernel<false>, dim3((unsigned)((half + 255) / 256)), dim3(256), 0, ctx->stream,
-                               prev, next, half, ctx->d_rc, ctx->d_mds);
+        launch_mds(ctx, merkle_level_kernel<true>, merkle_level_kernel<false>, (half + 255) / 256, (const u64 *)prev, next, half);
         ZP_HIP(ctx, hipGetLastError());
         prev = next;
         cnt = half;
     }
     return ZP_OK;
+}
+
+// leaves and levels of one tree: M leaves of `len` values, as columns (ROWS = false) or as rows.  Trees of <= 2^14 hashed leaves take the
+// 12-lanes-per-leaf kernel, everything else one lane per leaf
+template <bool ROWS>
+int32_t commit_tree(zp_ctx *ctx, const u64 *src, size_t M, size_t len, u64 *tree) {
+    ZP_TRY(zpi_poseidon_sync_tables(ctx));
+    if (M <= ((size_t)1 << 14) && len > 4)
+        hipLaunchKernelGGL(merkle_leaves_coop_kernel, dim3((unsigned)((M + 63) / 64)), dim3(768), 0, ctx->stream, src, M, len,
+                           ROWS ? (size_t)1 : M, ROWS ? len : (size_t)1, tree, ctx->d_rc, ctx->d_mds);
+    else
+        launch_mds(ctx, merkle_leaves_kernel<true, ROWS>, merkle_leaves_kernel<false, ROWS>, (M + 255) / 256, src, M, (leaf_len_t<ROWS>)len, tree);
+    ZP_HIP(ctx, hipGetLastError());
+    return tree_levels(ctx, tree, M);
 }
 
 }  // namespace
@@ -945,13 +838,8 @@ int32_t zpi_merkle_verify_openings(zp_ctx *ctx, const ZpOpening *ops, size_t n, 
         u64 *d = nullptr;
         ZP_TRY(zpi_scratch(ctx, 3, total, &d));
         ZP_HIP(ctx, hipMemcpyAsync(d, buf, o_ok * 8, hipMemcpyHostToDevice, ctx->stream));
-        const dim3 grid((unsigned)((n + 255) / 256));
-        if (ctx->mds_is_default)
-            hipLaunchKernelGGL(openings_lane_kernel<true>, grid, dim3(256), 0, ctx->stream, (const VerifySeg *)d, (const u32 *)(d + o_segof), (const u32 *)(d + o_slot),
-                               d + o_idx, d + o_roots, d + o_vals, d + o_sibs, n, (unsigned char *)(d + o_ok), ctx->d_rc, ctx->d_mds);
-        else
-            hipLaunchKernelGGL(openings_lane_kernel<false>, grid, dim3(256), 0, ctx->stream, (const VerifySeg *)d, (const u32 *)(d + o_segof), (const u32 *)(d + o_slot),
-                               d + o_idx, d + o_roots, d + o_vals, d + o_sibs, n, (unsigned char *)(d + o_ok), ctx->d_rc, ctx->d_mds);
+        launch_mds(ctx, openings_lane_kernel<true>, openings_lane_kernel<false>, (n + 255) / 256, (const VerifySeg *)d, (const u32 *)(d + o_segof), (const u32 *)(d + o_slot),
+                   d + o_idx, d + o_roots, d + o_vals, d + o_sibs, n, (unsigned char *)(d + o_ok));
         ZP_HIP(ctx, hipGetLastError());
         ZP_HIP(ctx, hipMemcpyAsync(buf + o_ok, d + o_ok, n, hipMemcpyDeviceToHost, ctx->stream));
         ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1001,12 +889,7 @@ int32_t zp_poseidon_perm(zp_ctx *ctx, uint64_t *d_states, size_t count) {
         ZP_HIP(ctx, hipGetLastError());
         return ZP_OK;
     }
-    if (ctx->mds_is_default)
-        hipLaunchKernelGGL(poseidon_perm_kernel<true>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (u64 *)d_states, count, ctx->d_rc, ctx->d_mds);
-    else
-        hipLaunchKernelGGL(poseidon_perm_kernel<false>, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (u64 *)d_states, count, ctx->d_rc, ctx->d_mds);
+    launch_mds(ctx, poseidon_perm_kernel<true>, poseidon_perm_kernel<false>, (count + 255) / 256, (u64 *)d_states, count);
     ZP_HIP(ctx, hipGetLastError());
     return ZP_OK;
 }
@@ -1033,39 +916,40 @@ int32_t zp_poseidon_sponge_caps(zp_ctx *ctx, uint64_t *h_state, const uint64_t *
     for (int i = 0; i < 12; i++) ZP_ARG(ctx, h_state[i] < GL_P, "state not canonical");
     for (size_t i = 0; i < nblocks * 8; i++) ZP_ARG(ctx, h_blocks[i] < GL_P, "block not canonical");
     ZP_TRY(zpi_poseidon_sync_tables(ctx));
-    const size_t nin = 12 + nblocks * 8, nout = (1 + extra) * 8, ncap = h_caps ? ((nblocks ? nblocks : 1) + extra) * 4 : 0;
-    if (nin * 8 <= 48 * 1024) {                 // the usual case (a transcript step is a few dozen blocks): through the pinned staging buffer
+    // one buffer, [state][blocks] in and [state] ... [rates][caps] out (poseidon_sponge_kernel), packed and unpacked here once.  The usual case (a
+    // transcript step is a few dozen blocks, 48 KiB of input at the most): the ctx's pinned staging buffer, which the kernel reads and writes itself;
+    // above that a pageable copy and device scratch
+    const size_t nin = 12 + nblocks * 8, nout = (1 + extra) * 8, ncap = h_caps ? ((nblocks ? nblocks : 1) + extra) * 4 : 0, total = nin + nout + ncap;
+    const bool staged = nin * 8 <= 48 * 1024;
+    std::vector<u64> pageable(staged ? 0 : total);
+    u64 *h = pageable.data(), *d = nullptr;
+    if (staged) {
         void *stv = nullptr;
         ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));       // the staging buffer may still feed an earlier small copy
-        ZP_TRY(zpi_pinned(ctx, (nin + nout + ncap) * 8, &stv));
-        u64 *st = (u64 *)stv;
-        memcpy(st, h_state, 96);
-        if (nblocks) memcpy(st + 12, h_blocks, nblocks * 64);
-        hipLaunchKernelGGL(poseidon_sponge_pinned_kernel, dim3(1), dim3(64), nin * 8, ctx->stream, st, (int)nblocks, (int)extra, ctx->d_rc, ctx->d_mds,
+        ZP_TRY(zpi_pinned(ctx, total * 8, &stv));
+        h = (u64 *)stv;
+    } else {
+        ZP_TRY(zpi_scratch(ctx, 3, total, &d));
+    }
+    memcpy(h, h_state, 96);
+    if (nblocks) memcpy(h + 12, h_blocks, nblocks * 64);
+    if (staged) {
+        hipLaunchKernelGGL(poseidon_sponge_kernel<true>, dim3(1), dim3(64), nin * 8, ctx->stream, h, (int)nblocks, (int)extra, ctx->d_rc, ctx->d_mds,
                            h_caps ? 1 : 0);
         ZP_HIP(ctx, hipGetLastError());
         ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        memcpy(h_state, st, 96);
-        memcpy(h_rates, st + nin, nout * 8);
-        if (h_caps) memcpy(h_caps, st + nin + nout, ncap * 8);
-        return ZP_OK;
+    } else {
+        ZP_TRY(zpi_h2d_small(ctx, d, h, nin * 8));
+        hipLaunchKernelGGL(poseidon_sponge_kernel<false>, dim3(1), dim3(64), 0, ctx->stream, d, (int)nblocks, (int)extra, ctx->d_rc, ctx->d_mds,
+                           h_caps ? 1 : 0);
+        ZP_HIP(ctx, hipGetLastError());
+        // state and rates are not adjacent (the blocks sit between them): two small copies
+        ZP_TRY(zpi_d2h_small(ctx, h, d, 96));
+        ZP_TRY(zpi_d2h_small(ctx, h + nin, d + nin, (nout + ncap) * 8));
     }
-    u64 *d = nullptr;
-    ZP_TRY(zpi_scratch(ctx, 3, nin + nout + ncap, &d));
-    std::vector<u64> in(nin);
-    memcpy(in.data(), h_state, 96);
-    if (nblocks) memcpy(in.data() + 12, h_blocks, nblocks * 64);
-    ZP_TRY(zpi_h2d_small(ctx, d, in.data(), nin * 8));
-    hipLaunchKernelGGL(poseidon_sponge_kernel, dim3(1), dim3(64), 0, ctx->stream, d, (int)nblocks, (int)extra, ctx->d_rc, ctx->d_mds,
-                       h_caps ? d + nin + nout : (u64 *)nullptr);
-    ZP_HIP(ctx, hipGetLastError());
-    std::vector<u64> out(12 + nout + ncap);
-    // state and rates are not adjacent (the blocks sit between them): two small copies
-    ZP_TRY(zpi_d2h_small(ctx, out.data(), d, 96));
-    ZP_TRY(zpi_d2h_small(ctx, out.data() + 12, d + nin, (nout + ncap) * 8));
-    memcpy(h_state, out.data(), 96);
-    memcpy(h_rates, out.data() + 12, nout * 8);
-    if (h_caps) memcpy(h_caps, out.data() + 12 + nout, ncap * 8);
+    memcpy(h_state, h, 96);
+    memcpy(h_rates, h + nin, nout * 8);
+    if (h_caps) memcpy(h_caps, h + nin + nout, ncap * 8);
     return ZP_OK;
 }
 
@@ -1088,12 +972,7 @@ int32_t zp_pow_grind(zp_ctx *ctx, const uint64_t *h_seed4, int32_t bits, uint64_
     const u64 batch = 1ULL << (bits >= 16 ? 20 : bits + 4);   // expected hits per batch: 16 (fewer for bits >= 16)
     for (u64 base = 0;; base += batch) {
         ZP_ARG(ctx, base < (1ULL << 50), "no proof-of-work nonce below 2^50");
-        if (ctx->mds_is_default)
-            hipLaunchKernelGGL(pow_grind_kernel<true>, dim3((unsigned)(batch / 256)), dim3(256), 0, ctx->stream, d, (int)bits, base, d + 4,
-                               ctx->d_rc, ctx->d_mds);
-        else
-            hipLaunchKernelGGL(pow_grind_kernel<false>, dim3((unsigned)(batch / 256)), dim3(256), 0, ctx->stream, d, (int)bits, base, d + 4,
-                               ctx->d_rc, ctx->d_mds);
+        launch_mds(ctx, pow_grind_kernel<true>, pow_grind_kernel<false>, batch / 256, (const u64 *)d, (int)bits, base, d + 4);
         ZP_HIP(ctx, hipGetLastError());
         u64 best;
         ZP_TRY(zpi_d2h_small(ctx, &best, d + 4, sizeof(best)));
@@ -1107,18 +986,7 @@ int32_t zp_merkle_commit(zp_ctx *ctx, const uint64_t *d_cols, size_t M, int32_t 
     ZP_ARG(ctx, M >= 1 && (M & (M - 1)) == 0, "M must be a power of two");
     ZP_ARG(ctx, W >= 1, "W must be >= 1");
     ZP_ARG(ctx, d_cols && d_tree, "null device pointer");
-    ZP_TRY(zpi_poseidon_sync_tables(ctx));
-    if (M <= ((size_t)1 << 14) && W > 4)
-        hipLaunchKernelGGL(merkle_leaves_coop_kernel, dim3((unsigned)((M + 63) / 64)), dim3(768), 0, ctx->stream, (const u64 *)d_cols, M,
-                           (size_t)W, M, (size_t)1, (u64 *)d_tree, ctx->d_rc, ctx->d_mds);
-    else if (ctx->mds_is_default)
-        hipLaunchKernelGGL(merkle_leaves_kernel<true>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const u64 *)d_cols, M, (int)W, (u64 *)d_tree, ctx->d_rc, ctx->d_mds);
-    else
-        hipLaunchKernelGGL(merkle_leaves_kernel<false>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const u64 *)d_cols, M, (int)W, (u64 *)d_tree, ctx->d_rc, ctx->d_mds);
-    ZP_HIP(ctx, hipGetLastError());
-    return tree_levels(ctx, (u64 *)d_tree, M);
+    return commit_tree<false>(ctx, (const u64 *)d_cols, M, (size_t)W, (u64 *)d_tree);
 }
 
 int32_t zp_merkle_commit_rows(zp_ctx *ctx, const uint64_t *d_rows, size_t M, size_t len, uint64_t *d_tree) {
@@ -1127,18 +995,7 @@ int32_t zp_merkle_commit_rows(zp_ctx *ctx, const uint64_t *d_rows, size_t M, siz
     ZP_ARG(ctx, M >= 1 && (M & (M - 1)) == 0, "M must be a power of two");
     ZP_ARG(ctx, len >= 1, "len must be >= 1");
     ZP_ARG(ctx, d_rows && d_tree, "null device pointer");
-    ZP_TRY(zpi_poseidon_sync_tables(ctx));
-    if (M <= ((size_t)1 << 14) && len > 4)
-        hipLaunchKernelGGL(merkle_leaves_coop_kernel, dim3((unsigned)((M + 63) / 64)), dim3(768), 0, ctx->stream, (const u64 *)d_rows, M,
-                           len, (size_t)1, len, (u64 *)d_tree, ctx->d_rc, ctx->d_mds);
-    else if (ctx->mds_is_default)
-        hipLaunchKernelGGL(merkle_leaves_rows_kernel<true>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const u64 *)d_rows, M, len, (u64 *)d_tree, ctx->d_rc, ctx->d_mds);
-    else
-        hipLaunchKernelGGL(merkle_leaves_rows_kernel<false>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const u64 *)d_rows, M, len, (u64 *)d_tree, ctx->d_rc, ctx->d_mds);
-    ZP_HIP(ctx, hipGetLastError());
-    return tree_levels(ctx, (u64 *)d_tree, M);
+    return commit_tree<true>(ctx, (const u64 *)d_rows, M, len, (u64 *)d_tree);
 }
 
 int32_t zp_merkle_open(zp_ctx *ctx, const uint64_t *d_tree, size_t M, size_t idx, uint64_t *h_path) {

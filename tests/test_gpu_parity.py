@@ -285,7 +285,7 @@ def test_golden_merkle_through_cabi(prover, golden):
         assert tree[-1].tolist() == case["root"], (case["M"], case["W"])
 
 
-@pytest.mark.parametrize("M,W", [(1, 9), (2, 1), (8, 4), (64, 5), (1024, 8), (4096, 33), (1 << 15, 64), (1 << 12, 100)])
+@pytest.mark.parametrize("M,W", [(1, 9), (2, 1), (8, 4), (64, 5), (1024, 8), (4096, 33), (1 << 15, 64), (1 << 12, 100), (1 << 15, 13)])
 def test_merkle_matches_oracle(prover, tables, M, W):
     rc, mds = tables
     cols = O.random_field((W, M), 500 + W)
@@ -551,23 +551,31 @@ def test_pack_blocks_kernel(prover, rows, row_len, parts):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("nblocks,extra", [(0, 0), (0, 3), (1, 0), (2, 1), (7, 0), (60, 9)])
+@pytest.mark.parametrize("nblocks,extra", [(0, 0), (0, 3), (1, 0), (2, 1), (7, 0), (60, 9), (766, 1), (767, 2)])
 def test_sponge_in_one_launch_equals_permutation_by_permutation(prover, tables, nblocks, extra):
-    """zp_poseidon_sponge (the Fiat-Shamir transcript step) against the oracle's permutation applied block by block"""
+    """zp_poseidon_sponge (the Fiat-Shamir transcript step) against the oracle's permutation applied block by block.  766 blocks are the last
+    input that is staged in LDS (12 + 8 * 766 = 6 140 words <= 48 KiB), 767 the first that is read from device memory: for these two the
+    capacity after every permutation (zp_poseidon_sponge_caps) is compared too"""
     rc, mds = tables
     state = [int(v) for v in O.random_field((12,), 5 + nblocks)]
     blocks = [[int(v) for v in O.random_field((8,), 100 + i)] for i in range(nblocks)]
     if nblocks:
         blocks[0][0], blocks[-1][7] = 0, O.P - 1
     perm = lambda st: [int(v) for v in O.poseidon_perm(np.array([st], dtype=np.uint64), rc, mds)[0]]
-    st, rates = list(state), []
+    st, rates, caps = list(state), [], []
     if not blocks:
         st = perm(st)
+        caps.append(st[8:])
     for b in blocks:
         st = perm(b + st[8:])
+        caps.append(st[8:])
     rates.append(st[:8])
     for _ in range(extra):
         st = perm(st)
         rates.append(st[:8])
+        caps.append(st[8:])
     got_state, got_rates = prover.poseidon_sponge(state, blocks, extra)
     assert got_state == st and got_rates == rates
+    if nblocks >= 766:
+        got_state, got_rates, got_caps = prover.poseidon_sponge_caps(state, blocks, extra)
+        assert got_state == st and got_rates == rates and got_caps == caps

@@ -39,7 +39,7 @@ if "ntt" in src:
 if "poseidon" in src:
     d = json.load(open(src["poseidon"]))
     for k, units, label in (("poseidon_perm_kernel<true>", 1 << 22, "poseidon_perm (batch of 2^22 states)"),
-                            ("merkle_leaves_kernel<true>", 4 * (1 << 22), "merkle leaves 2^22 x 32 (4 permutations per leaf)")):
+                            ("merkle_leaves_kernel<true, false>", 4 * (1 << 22), "merkle leaves 2^22 x 32 (4 permutations per leaf)")):
         if k in d:
             v, ms = valu(d, k)
             res["stages"][label] = {"kernel": k, "valu_per_unit": v * 64 / units, "unit": "permutation", "ms_under_profiler": ms}
