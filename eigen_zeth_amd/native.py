@@ -1254,11 +1254,18 @@ class Prover:
                         pts[i, 8 * c + k] = (v >> (32 * k)) & 0xFFFFFFFF
             for k in range(8):
                 scs[i, k] = (s >> (32 * k)) & 0xFFFFFFFF
+        return self.msm_bn254_g2_arrays(pts[:n_], scs[:n_])
+
+    def msm_bn254_g2_arrays(self, pts, scs):
+        """pts u32[n][32] (x0, x1, y0, y1, eight words each; all zero = infinity), scs u32[n][8] -> ((x0, x1), (y0, y1)) or None"""
+        pts = np.ascontiguousarray(pts, dtype=np.uint32)
+        scs = np.ascontiguousarray(scs, dtype=np.uint32)
+        n_ = pts.shape[0]
         d_p = DeviceBuffer(self, max(1, pts.size // 2 + 1))
         d_s = DeviceBuffer(self, max(1, scs.size // 2 + 1))
         if n_:
-            self._chk(self.lib.zp_h2d(self.ctx, d_p.ptr, pts.ctypes.data, pts[:n_].nbytes))
-            self._chk(self.lib.zp_h2d(self.ctx, d_s.ptr, scs.ctypes.data, scs[:n_].nbytes))
+            self._chk(self.lib.zp_h2d(self.ctx, d_p.ptr, pts.ctypes.data, pts.nbytes))
+            self._chk(self.lib.zp_h2d(self.ctx, d_s.ptr, scs.ctypes.data, scs.nbytes))
         out = (C.c_uint32 * 32)()
         self._chk(self.lib.zp_msm_bn254_g2(self.ctx, d_p.ptr, d_s.ptr, n_, out))
         v = [sum(int(out[8 * c + k]) << (32 * k) for k in range(8)) for c in range(4)]

@@ -196,11 +196,28 @@ def test_fr254_host_at_corners(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------------------- on the GPU
+_LATCH = {"dead": None}       # one for the whole session: tests/test_fq254.py starts its device program through it as well
+
+
+def run_latched(key, argv, timeout=120):
+    """start a device program as a fresh child; after one dies of a signal, runs out of time or reports a HIP error nothing more is started"""
+    if _LATCH["dead"]:
+        pytest.fail("not started: " + _LATCH["dead"])
+    try:
+        out = subprocess.run(argv, capture_output=True, text=True, timeout=timeout)
+    except subprocess.TimeoutExpired:
+        _LATCH["dead"] = "%s ran out of time" % key
+        pytest.fail(_LATCH["dead"])
+    if out.returncode < 0 or out.returncode >= 2:
+        _LATCH["dead"] = "%s ended with status %d: %s" % (key, out.returncode, out.stderr[-1000:])
+        pytest.fail(_LATCH["dead"] + out.stdout[-2000:])
+    return out
+
+
 class _Device:
-    """the three programs, built once; after a child dies of a signal, runs out of time or reports a HIP error nothing more is started"""
+    """the three programs, built once; they are started through run_latched"""
 
     def __init__(self, d):
-        self.dead = None
         self.exe = {}
         flags = ["-O3", "-std=c++17", "--offload-arch=" + ARCH, "-I", CSRC]
         for window in (116, 52):
@@ -212,17 +229,7 @@ class _Device:
         self.ncases = write_fr_cases(self.cases)
 
     def run(self, key, *args):
-        if self.dead:
-            pytest.fail("not started: " + self.dead)
-        try:
-            out = subprocess.run([self.exe[key], *args], capture_output=True, text=True, timeout=120)
-        except subprocess.TimeoutExpired:
-            self.dead = "%s ran out of time" % key
-            pytest.fail(self.dead)
-        if out.returncode < 0 or out.returncode >= 2:
-            self.dead = "%s ended with status %d: %s" % (key, out.returncode, out.stderr[-1000:])
-            pytest.fail(self.dead + out.stdout[-2000:])
-        return out
+        return run_latched(key, [self.exe[key], *args])
 
 
 @pytest.fixture(scope="module")

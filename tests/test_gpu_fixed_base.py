@@ -58,3 +58,41 @@ def test_fixed_base_at_size_against_the_msm(prover):
     si = [int(a[0]) | int(a[2]) << 128 for a in sw]
     wi = [sum(int(w[i, k]) << (32 * k) for k in range(8)) for i in range(n)]
     assert got == B.mul((1, 2), sum(a * b for a, b in zip(si, wi)) % B.R)
+
+
+def _scalar_words(scal):
+    return np.array([_words(s, 8) for s in scal], dtype=np.uint32)
+
+
+def test_fixed_base_scalars_at_and_above_the_group_order(prover):
+    """s >= r: the last table addition lands on the point at infinity (s = r) or passes it; the result is (s mod r) B"""
+    scal = [B.R, B.R + 1, (1 << 256) - 1, 255 << 248]
+    p1 = prover.fixed_base_mul(G1W, _scalar_words(scal))
+    p2 = prover.fixed_base_mul(_g2_words(), _scalar_words(scal), g2=True)
+    for i, s in enumerate(scal):
+        assert _pt1(p1[i]) == B.mul((1, 2), s % B.R), i
+        assert _pt2(p2[i]) == B.mul_g2(B.G2, s % B.R), i
+    assert _pt1(p1[0]) is None and _pt2(p2[0]) is None
+
+
+def test_fixed_base_infinities_at_the_edges_of_the_inversion_runs(prover):
+    """the results are made affine with one inversion per run of 1024 points: zero scalars (infinity) at the first and last place of a run, a run of
+    nothing but infinities, and a last run of one point"""
+    n = 2049
+    rng = np.random.default_rng(7)
+    distinct = [1, 2, 255, 256, B.R - 1, (1 << 253) + 5] + [int.from_bytes(rng.bytes(32), "little") % B.R for _ in range(10)] + \
+               [int(v) for v in rng.integers(1, 1 << 20, size=16)]
+    pick = rng.integers(0, len(distinct), size=n)
+    scal = [distinct[k] for k in pick]
+    for i in [0, 1023] + list(range(1024, 2048)):
+        scal[i] = 0
+    assert scal[1] and scal[1022] and scal[2048]
+    sw = _scalar_words(scal)
+    p1 = prover.fixed_base_mul(G1W, sw)
+    p2 = prover.fixed_base_mul(_g2_words(), sw, g2=True)
+    want1 = {s: B.mul((1, 2), s) for s in distinct}
+    want2 = {s: B.mul_g2(B.G2, s) for s in distinct}
+    want1[0] = want2[0] = None
+    for i, s in enumerate(scal):
+        assert _pt1(p1[i]) == want1[s], i
+        assert _pt2(p2[i]) == want2[s], i

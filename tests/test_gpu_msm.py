@@ -156,3 +156,168 @@ def test_golden_msm_vectors_through_cabi(prover, golden):
         pts = [((int(p[0][0]), int(p[0][1])), (int(p[1][0]), int(p[1][1]))) for p in case["points"]]
         got = prover.msm_bn254_g2(pts, [int(v) for v in case["scalars"]])
         assert got == ((int(case["sum"][0][0]), int(case["sum"][0][1])), (int(case["sum"][1][0]), int(case["sum"][1][1])))
+
+
+# ---------------------------------------------------------------------------------------------------------------- the named seams
+# Every comparison below is exact; the expectation is the oracle's double-and-add per DISTINCT point of a small table (the definition plus
+# linearity, as above).  Sizes are the smallest that cross the seam.
+def _g1_rows(table):
+    return np.array([limbs(p[0]) + limbs(p[1]) for p in table], dtype=np.uint32)
+
+
+def _g2_rows(table_g2):
+    return np.array([limbs(p[0][0]) + limbs(p[0][1]) + limbs(p[1][0]) + limbs(p[1][1]) for p in table_g2], dtype=np.uint32)
+
+
+def _scalar_rows(scs):
+    return np.array([limbs(s) for s in scs], dtype=np.uint32).reshape(-1, 8)
+
+
+def _width_for(n):
+    """the window width msm_chunk picks for n points (its two loops and its floor of 6)"""
+    c = 4
+    while c < 16 and (1 << (c + 2)) <= n:
+        c += 1
+    while c < 20 and (1 << (c + 8)) <= n:
+        c += 1
+    return max(c, 6)
+
+
+def _one_bucket(n, sign, ntable):
+    """n points that all carry ONE scalar: 3 (one bucket of window 0 holds them all) or 2^(c+1) - 3, whose signed digits are (-3, +1)"""
+    c = _width_for(n)
+    assert _width_for(65 * 16384 + 1) == 16 and _width_for(1) == 6
+    s = 3 if sign == "positive" else (1 << (c + 1)) - 3
+    if sign == "negative":
+        assert recode(s, c)[:3] == [-3, 1, 0]
+    idx = np.random.default_rng(1000 + n).integers(0, ntable, size=n)
+    scs = np.zeros((n, 8), dtype=np.uint32)
+    scs[:, 0] = s
+    return idx, scs, [int(k) * s % B.R for k in np.bincount(idx, minlength=ntable)]
+
+
+def recode(s, c):
+    """the signed window digits of s at bucket-index width c, lowest window first: u = s + K, digit = u_w - 2^c  (csrc/fq254.hpp, digit_key)"""
+    cd = c + 1
+    nwin = (258 + cd - 1) // cd
+    u = s + sum(1 << (cd * w + cd - 1) for w in range(nwin))
+    assert u < 1 << (cd * nwin)
+    d = [((u >> (cd * w)) & ((1 << cd) - 1)) - (1 << c) for w in range(nwin)]
+    assert sum(x << (cd * w) for w, x in enumerate(d)) == s
+    return d
+
+
+# 255 | 256 | 257: MSM_HEAVY;  16384 | 16385 | 32769: one, two and three MSM_HCHUNK chunks;  65 * 16384 + 1: 66 chunks, the strided loop of
+# msm_heavy_combine_kernel;  1..5: the clamped prefetch indices of the two-point software pipeline
+@pytest.mark.parametrize("sign", ["positive", "negative"])
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 5, 255, 256, 257, 16384, 16385, 32769, 65 * 16384 + 1])
+def test_msm_one_bucket_of_every_seam_size(prover, table, n, sign):
+    idx, scs, per = _one_bucket(n, sign, len(table))
+    assert prover.msm_bn254_arrays(_g1_rows(table)[idx], scs) == B.msm(table, per)
+
+
+@pytest.mark.parametrize("sign", ["positive", "negative"])
+@pytest.mark.parametrize("n", [1, 2, 3, 256, 257, 16385])
+def test_msm_g2_one_bucket_of_every_seam_size(prover, table_g2, n, sign):
+    idx, scs, per = _one_bucket(n, sign, len(table_g2))
+    assert prover.msm_bn254_g2_arrays(_g2_rows(table_g2)[idx], scs) == B.msm_g2(table_g2, per)
+
+
+def signed_digit_scalars(c):
+    """scalars made from digit vectors: each of -2^c, 2^c - 1, -1, 1, 0 in window 0, in the middle window and in the last but one; every window
+    below the top at -2^c and at 2^c - 1 (carries of the bias addition across all nine words); the 256-bit extremes; 200 random ones"""
+    cd = c + 1
+    nwin = (258 + cd - 1) // cd
+    places = (0, nwin // 2, nwin - 2)
+    values = (-(1 << c), (1 << c) - 1, -1, 1, 0)
+    vectors = []
+    for w in places:
+        for v in values:
+            d = [0] * nwin
+            d[w] = v
+            vectors.append(d)
+    vectors += [[-(1 << c)] * (nwin - 1) + [0], [(1 << c) - 1] * (nwin - 1) + [0]]
+    scs = []
+    for d in vectors:
+        if sum(x << (cd * w) for w, x in enumerate(d)) < 0:
+            d[nwin - 1] = 1
+        scs.append(sum(x << (cd * w) for w, x in enumerate(d)))
+    # conditions on the inputs (not compared with the GPU): every scalar is a 256-bit value and recodes to the digits it was made from
+    assert all(0 <= s < 1 << 256 for s in scs)
+    for s, d in zip(scs, vectors):
+        assert recode(s, c) == d, (c, d)
+    for w in places:
+        for v in values:
+            assert any(recode(s, c)[w] == v for s in scs), (c, w, v)
+    assert any(all(x == -(1 << c) for x in recode(s, c)[:-1]) for s in scs) and any(all(x == (1 << c) - 1 for x in recode(s, c)[:-1]) for s in scs)
+    rnd = random.Random(600 + c)
+    return scs + [(1 << 256) - 1, 1 << 255, B.R - 1, B.R, B.R + 1] + [rnd.randrange(1 << 256) for _ in range(200)]
+
+
+def _sum_per_point(idx, scs, ntable):
+    per = [0] * ntable
+    for i, s in zip(idx, scs):
+        per[i] = (per[i] + s) % B.R
+    return per
+
+
+@pytest.mark.parametrize("c", [6, 7, 10, 11, 16, 17])
+def test_msm_signed_digit_extremes_in_every_window(prover, table, c):
+    """17 is the width of a 2^24-point run"""
+    scs = signed_digit_scalars(c)
+    rnd = random.Random(c)
+    idx = [rnd.randrange(len(table)) for _ in scs]
+    prover.set_tuning("msm_c", c)
+    try:
+        assert prover.msm_bn254_arrays(_g1_rows(table)[idx], _scalar_rows(scs)) == B.msm(table, _sum_per_point(idx, scs, len(table)))
+    finally:
+        prover.set_tuning("msm_c", 0)
+
+
+@pytest.mark.parametrize("c", [6, 11, 16])
+def test_msm_g2_signed_digit_extremes_in_every_window(prover, table_g2, c):
+    scs = signed_digit_scalars(c)
+    idx = [i % len(table_g2) for i in range(len(scs))]
+    prover.set_tuning("msm_c", c)
+    try:
+        assert prover.msm_bn254_g2_arrays(_g2_rows(table_g2)[idx], _scalar_rows(scs)) == B.msm_g2(table_g2, _sum_per_point(idx, scs, len(table_g2)))
+    finally:
+        prover.set_tuning("msm_c", 0)
+
+
+def _run_seams(msm_arrays, rows, neg_rows, tab, msm, mul, prover):
+    """runs of 2^6 points, their sums added on the host (jac_add): a last run of one point; a run that repeats the one before (the host addition
+    doubles); a run that is the negation of everything before it (the sum ends at infinity); a prefix that ends at infinity and a run added to it"""
+    rnd = random.Random(64)
+    idx = [rnd.randrange(len(tab)) for _ in range(64)]
+    scs = [rnd.randrange(1 << 256) for _ in range(64)]
+    per = _sum_per_point(idx, scs, len(tab))
+    A = msm(tab, per)
+    assert A is not None
+    S, S2 = _scalar_rows(scs), _scalar_rows([2 * s % B.R for s in scs])
+    last = rnd.randrange(len(tab))
+    prover.set_tuning("msm_chunk_log", 6)
+    try:
+        # n = 129: two runs of A and a last run of one point
+        per129 = [(2 * a + (B.R - 1 if t == last else 0)) % B.R for t, a in enumerate(per)]
+        got = msm_arrays(np.concatenate([rows[idx], rows[idx], rows[[last]]]), np.concatenate([S, S, _scalar_rows([B.R - 1])]))
+        assert got == msm(tab, per129)
+        # n = 192: A, A again, then -2 A;  its prefix n = 128 is 2 A
+        pts, sc = np.concatenate([rows[idx], rows[idx], neg_rows[idx]]), np.concatenate([S, S, S2])
+        assert msm_arrays(pts, sc) is None
+        assert msm_arrays(pts[:128], sc[:128]) == mul(A, 2)
+        # n = 192: A, -A, A;  its prefix n = 128 ends at infinity, and the third run is added to infinity
+        pts, sc = np.concatenate([rows[idx], neg_rows[idx], rows[idx]]), np.concatenate([S, S, S])
+        assert msm_arrays(pts[:128], sc[:128]) is None
+        assert msm_arrays(pts, sc) == A
+    finally:
+        prover.set_tuning("msm_chunk_log", 0)
+
+
+def test_msm_run_seams(prover, table):
+    _run_seams(prover.msm_bn254_arrays, _g1_rows(table), _g1_rows([(p[0], B.Q - p[1]) for p in table]), table, B.msm, B.mul, prover)
+
+
+def test_msm_g2_run_seams(prover, table_g2):
+    neg = [(p[0], ((-p[1][0]) % B.Q, (-p[1][1]) % B.Q)) for p in table_g2]
+    _run_seams(prover.msm_bn254_g2_arrays, _g2_rows(table_g2), _g2_rows(neg), table_g2, B.msm_g2, B.mul_g2, prover)
