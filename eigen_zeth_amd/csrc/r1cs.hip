@@ -7,6 +7,7 @@
 // comes as explicit sparse rows.  Everything runs over the template per instance (23 M multiply-adds for 1 900 instances: a second on one
 // core, instances in parallel on threads for the key scalars).  The group operations (fixed-base multiplications for the key, MSMs for a
 // proof) are the GPU's (csrc/msm.hip).  Layout of the circuit blob: eigen_zeth_amd/service/r1cs.py.
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdint>
@@ -15,6 +16,7 @@
 #include <cstring>
 #include <functional>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "ctx.hpp"
@@ -877,6 +879,10 @@ struct ZpG16Cache {
     bool hW_pinned = false;
     std::vector<uint8_t> hset;
     std::vector<uint64_t> touched;       // the wires the last proof set from outside (their flags are cleared before the next one)
+    // the wires that are internal to a gadget or arithmetic instance as disjoint ranges [first, end), ascending: the evaluator computes those,
+    // no caller sets one (zp_r1cs_eval_device)
+    std::vector<std::pair<uint64_t, uint64_t>> internal;
+    bool arith_first = false;            // a gadget input or an explicit row reads an internal wire of an arithmetic instance (eval_device)
 };
 void zpi_g16_cache_free(zp_ctx *ctx) {
     if (!ctx->g16_cache) return;
@@ -889,11 +895,26 @@ void zpi_g16_cache_free(zp_ctx *ctx) {
 
 namespace {
 
+// wire ranges [first, end): sorted, overlapping ones merged; then membership by bisection
+void merge_ranges(std::vector<std::pair<uint64_t, uint64_t>> *r) {
+    std::sort(r->begin(), r->end());
+    size_t n = 0;
+    for (const auto &x : *r) {
+        if (n && x.first <= (*r)[n - 1].second) (*r)[n - 1].second = std::max((*r)[n - 1].second, x.second);
+        else (*r)[n++] = x;
+    }
+    r->resize(n);
+}
+bool in_ranges(const std::vector<std::pair<uint64_t, uint64_t>> &r, uint64_t wire) {
+    auto it = std::upper_bound(r.begin(), r.end(), std::pair<uint64_t, uint64_t>(wire, ~(uint64_t)0));
+    return it != r.begin() && wire < (it - 1)->second;
+}
+
 // device evaluation of the parsed circuit c (its blob resident at d_blob): d_w u64[>= n_wires][4] and d_set are overwritten; d_a / d_b / d_c
 // u64[2^logm][4].  flags (host, 3 words): first violated row, first row that reads an unset wire, first wire left unset -- ~0 = none.
 int32_t eval_device(zp_ctx *ctx, const Circ &c, const uint64_t *circ, const u64 *d_blob, const u64 *d_defs, size_t n_defs, const u64 *d_idx, const u64 *d_val,
                     size_t n_set, u64 *d_w, unsigned char *d_set, u64 *d_a, u64 *d_b, u64 *d_c, unsigned long long *d_flags, unsigned long long *h_flags,
-                    const uint64_t *hW = nullptr, const std::function<int32_t()> &host_arith = nullptr) {
+                    const uint64_t *hW = nullptr, const std::function<int32_t()> &host_arith = nullptr, bool arith_first = false) {
     const size_t m = (size_t)1 << c.logm;
     ZP_HIP(ctx, hipMemsetAsync(d_w, 0, c.n_wires * 32, ctx->stream));
     ZP_HIP(ctx, hipMemsetAsync(d_set, 0, c.n_wires, ctx->stream));
@@ -903,6 +924,29 @@ int32_t eval_device(zp_ctx *ctx, const Circ &c, const uint64_t *circ, const u64 
     ZP_HIP(ctx, hipMemsetAsync(d_flags, 0xFF, 24, ctx->stream));
     hipLaunchKernelGGL(r1cs_scatter_kernel, dim3((unsigned)((n_set + 255) / 256)), dim3(256), 0, ctx->stream, d_idx, d_val, n_set, d_w, d_set);
     ZP_HIP(ctx, hipGetLastError());
+    // The internal wires of the arithmetic templates come from the host (hW): their witness programs read caller-set wires (and wires of
+    // earlier templates) only, and every instance's wires go up as one contiguous range.  THE RULE for when: the host evaluator runs the
+    // programs before anything else, so a gadget input or an explicit row may read an arithmetic wire.  A circuit in which one does
+    // (arith_first, found once per circuit by circuit_on_device) gets the programs and the upload BEFORE the first gadget wave.  In every other
+    // circuit nothing launched before the arithmetic rows kernel reads such a wire, and the programs run on the host AFTER the launches of the
+    // gadget waves and the explicit rows, while the GPU works on those (4.8 of the 13.6 ms witness step at the service's size were this host
+    // work in front of an idle GPU).
+    auto arith_wires = [&]() -> int32_t {
+        if (c.ar.empty()) return ZP_OK;
+        ZP_ARG(ctx, hW != nullptr, "internal: arithmetic templates without their host witness");
+        if (host_arith) {
+            const int32_t arc = host_arith();
+            if (arc != ZP_OK) { (void)hipStreamSynchronize(ctx->stream); return arc; }
+        }
+        for (const ArithT &t : c.ar)
+            for (uint64_t i = 0; i < t.n_inst; i++) {
+                const uint64_t base = t.inst[i * (t.n_in + 1) + t.n_in];
+                ZP_HIP(ctx, hipMemcpyAsync(d_w + 4 * base, hW + 4 * base, t.n_int * 32, hipMemcpyHostToDevice, ctx->stream));
+                ZP_HIP(ctx, hipMemsetAsync(d_set + base, 1, t.n_int, ctx->stream));
+            }
+        return ZP_OK;
+    };
+    if (arith_first) ZP_TRY(arith_wires());
     const u64 *d_inst = d_blob + (c.inst - circ);
     for (uint64_t wv = 0; wv < c.n_waves; wv++)
         ZP_TRY(zpi_r1cs_poseidon17(ctx, d_inst, c.waves[wv], c.waves[wv + 1] - c.waves[wv], d_w, d_set, d_a, d_b, d_c, d_flags, nullptr));
@@ -918,23 +962,7 @@ int32_t eval_device(zp_ctx *ctx, const Circ &c, const uint64_t *circ, const u64 
                            (u64)c.extra_base(), (const u64 *)d_w, (const unsigned char *)d_set, d_a, d_b, d_c, d_flags);
         ZP_HIP(ctx, hipGetLastError());
     }
-    // The internal wires of the arithmetic templates come from the host (hW).  Their witness programs read caller-set wires only, and nothing
-    // launched above reads an arithmetic wire: the programs run HERE, on the host, while the gadget instances and the explicit rows are on the
-    // GPU (4.8 of the 13.6 ms witness step at the service's size were this host work in front of an idle GPU); every instance's wires then go up
-    // as one contiguous range.
-    if (!c.ar.empty()) {
-        ZP_ARG(ctx, hW != nullptr, "internal: arithmetic templates without their host witness");
-        if (host_arith) {
-            const int32_t arc = host_arith();
-            if (arc != ZP_OK) { (void)hipStreamSynchronize(ctx->stream); return arc; }
-        }
-        for (const ArithT &t : c.ar)
-            for (uint64_t i = 0; i < t.n_inst; i++) {
-                const uint64_t base = t.inst[i * (t.n_in + 1) + t.n_in];
-                ZP_HIP(ctx, hipMemcpyAsync(d_w + 4 * base, hW + 4 * base, t.n_int * 32, hipMemcpyHostToDevice, ctx->stream));
-                ZP_HIP(ctx, hipMemsetAsync(d_set + base, 1, t.n_int, ctx->stream));
-            }
-    }
+    if (!arith_first) ZP_TRY(arith_wires());
     for (const ArithT &t : c.ar) {
         const ArithDev td = {t.n_in, t.n_int, t.n_rows, t.n_inst, t.first_row, d_blob + (t.coef - circ), d_blob + (t.lc_ptr - circ), d_blob + (t.lc_ent - circ),
                              d_blob + (t.rows - circ), d_blob + (t.inst - circ)};
@@ -963,6 +991,17 @@ int32_t circuit_on_device(zp_ctx *ctx, const Circ &c, const uint64_t *circ, size
     std::vector<u64> defs;
     for (uint64_t q = 0; q < c.n_extra; q++) if (c.edef[q] != ~0ull) defs.push_back(q);
     g->n_defs = defs.size();
+    for (const ArithT &t : c.ar)
+        for (uint64_t i = 0; i < t.n_inst; i++) g->internal.emplace_back(t.inst[i * (t.n_in + 1) + t.n_in], t.inst[i * (t.n_in + 1) + t.n_in] + t.n_int);
+    merge_ranges(&g->internal);
+    if (!g->internal.empty()) {          // (the arithmetic instances' ranges so far) does a gadget input or an explicit row read one of their wires?
+        for (uint64_t i = 0; i < c.n_inst && !g->arith_first; i++)
+            for (uint64_t k = 0; k < c.t; k++) if (in_ranges(g->internal, c.inst[i * (c.t + 2) + k])) { g->arith_first = true; break; }
+        for (int k = 0; k < 3 && !g->arith_first; k++)
+            for (uint64_t e = 0, nnz = c.E[k].ptr[c.n_extra]; e < nnz; e++) if (in_ranges(g->internal, c.E[k].idx[e])) { g->arith_first = true; break; }
+    }
+    for (uint64_t i = 0; i < c.n_inst; i++) g->internal.emplace_back(c.inst[i * (c.t + 2) + c.t], c.inst[i * (c.t + 2) + c.t] + n_int);
+    merge_ranges(&g->internal);
     ZP_HIP(ctx, hipMalloc((void **)&g->d_blob, words * 8));
     ZP_HIP(ctx, hipMemcpyAsync(g->d_blob, circ, words * 8, hipMemcpyHostToDevice, ctx->stream));
     if (g->n_defs) {
@@ -1039,8 +1078,11 @@ int32_t circuit_on_device(zp_ctx *ctx, const Circ &c, const uint64_t *circ, size
 extern "C" {
 
 // zp_r1cs_eval on the GPU: the n_set caller-set wires in (host), the complete witness d_w u64[n_wires][4] and A w, B w, C w (d_a, d_b, d_c
-// u64[2^logm][4]) out in HBM, the public inputs to the host.  Same results, same refusals (-20 / -21, *bad) as zp_r1cs_eval.  The gadget of the
-// circuit must be the width-17 Poseidon permutation of the installed tables (compared with the kernel once per circuit and ctx).
+// u64[2^logm][4]) out in HBM, the public inputs to the host.  Same results, same refusals (-20 / -21, *bad) as zp_r1cs_eval, with two exceptions
+// that come from taking a LIST of caller-set wires where the host takes a mask and a complete witness: a wire internal to a gadget or arithmetic
+// instance cannot be brought by the caller (the kernels compute those and would overwrite it unseen), and no wire may be named twice (the
+// scatter would keep either value) -- both are ZP_ERR_ARG.  The gadget of the circuit must be the width-17 Poseidon permutation of the installed
+// tables (compared with the kernel once per circuit and ctx).
 int32_t zp_r1cs_eval_device(zp_ctx *ctx, const uint64_t *circ, size_t words, const uint64_t *set_idx, const uint64_t *set_val, size_t n_set, uint64_t *d_w,
                             uint64_t *d_a, uint64_t *d_b, uint64_t *d_c, uint64_t *out_pub, int64_t *bad) {
     if (!ctx) return ZP_ERR_ARG;
@@ -1057,6 +1099,16 @@ int32_t zp_r1cs_eval_device(zp_ctx *ctx, const uint64_t *circ, size_t words, con
     ZP_ARG(ctx, one, "wire 0 must be set to 1");
     ZpG16Cache *g = nullptr;
     ZP_TRY(circuit_on_device(ctx, c, circ, words, &g));
+    try {
+        std::vector<uint64_t> named(set_idx, set_idx + n_set);
+        std::sort(named.begin(), named.end());
+        ZP_ARG(ctx, std::adjacent_find(named.begin(), named.end()) == named.end(), "a wire is set twice");
+        for (size_t k = 0; k < n_set; k++)
+            ZP_ARG(ctx, !in_ranges(g->internal, set_idx[k]), "a set wire is internal to a gadget or arithmetic instance: the evaluator computes those");
+    } catch (...) {
+        ctx->err = "out of host memory for the list of set wires";
+        return ZP_ERR_NOMEM;
+    }
     void *d = nullptr;
     const size_t bytes = n_set * 40 + c.n_wires + 64;
     ZP_TRY(zpi_pool_alloc(ctx, bytes, &d));
@@ -1102,7 +1154,7 @@ int32_t zp_r1cs_eval_device(zp_ctx *ctx, const uint64_t *circ, size_t words, con
         return arc;
     };
     if (rc == ZP_OK) rc = eval_device(ctx, c, circ, g->d_blob, g->d_defs, g->n_defs, d_idx, d_val, n_set, (u64 *)d_w, d_set, (u64 *)d_a, (u64 *)d_b, (u64 *)d_c, d_flags, hf,
-                                      g->hW, c.ar.empty() ? std::function<int32_t()>() : std::function<int32_t()>(host_arith));
+                                      g->hW, c.ar.empty() ? std::function<int32_t()>() : std::function<int32_t()>(host_arith), g->arith_first);
     if (rc == ZP_OK) rc = zpi_d2h_small(ctx, out_pub, (u64 *)d_w + 4, c.n_pub * 32);
     zpi_pool_release(ctx, d, bytes);
     if (rc != ZP_OK) return rc;

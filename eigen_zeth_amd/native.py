@@ -207,9 +207,12 @@ def synth_trace(kind, logn, W, seed, out=None, bind=None):
 
 
 class ZpError(RuntimeError):
-    def __init__(self, code, msg):
+    """bad: the row or wire a refusal of the R1CS evaluators names (*bad of zp_r1cs_eval / zp_r1cs_eval_device), None elsewhere"""
+
+    def __init__(self, code, msg, bad=None):
         super().__init__("libzethprover error %d: %s" % (code, msg))
         self.code = code
+        self.bad = bad
 
 
 _lib = None
@@ -309,7 +312,7 @@ def r1cs_eval(blob, witness, mask):
     if rc == -20:
         raise ValueError("the assignment does not satisfy the circuit (constraint %d): no proof for a false statement" % bad.value)
     if rc != 0:
-        raise ZpError(rc, "zp_r1cs_eval: malformed circuit or unset wire (%d)" % bad.value)
+        raise ZpError(rc, "zp_r1cs_eval: malformed circuit or unset wire (%d)" % bad.value, bad=bad.value)
     return w, ev[0], ev[1], ev[2]
 
 
@@ -1173,7 +1176,8 @@ class Prover:
                                               dc.ptr, pub.ctypes.data, C.byref(bad))
             if rc == -20:
                 raise ValueError("the assignment does not satisfy the circuit (constraint %d): no proof for a false statement" % bad.value)
-            self._chk(rc)
+            if rc != 0:
+                raise ZpError(rc, (self.lib.zp_last_error(self.ctx) or b"").decode(), bad=bad.value)
             return self.download(dw, (n, 4)), self.download(da, (m, 4)), self.download(db, (m, 4)), self.download(dc, (m, 4)), fr_ints(pub)
         finally:
             for d in (dw, da, db, dc):

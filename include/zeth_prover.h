@@ -433,8 +433,9 @@ int32_t zp_r1cs_key_scalars(const uint64_t *circ, size_t words, const uint64_t *
  * zp_r1cs_eval_device: zp_r1cs_eval on the GPU -- the n_set caller-set wires in (host), the complete witness d_w u64[n_wires][4] and A w, B w, C w
  *   (d_a, d_b, d_c u64[2^logm][4]) out in HBM, the public inputs out_pub u64[n_pub][4] to the host; an instance's wires and rows are the
  *   intermediate values of its permutation (one kernel per wave of instances), the explicit constraints go through a sparse-row kernel.  Same
- *   results and refusals (-20 / -21, *bad) as zp_r1cs_eval.  The circuit's gadget must be the width-17 Poseidon permutation of the installed tables:
- *   it is compared with the kernel on one instance, once per circuit and ctx (ZP_ERR_ARG otherwise).
+ *   results and refusals (-20 / -21, *bad) as zp_r1cs_eval, with two exceptions: set_idx names caller-set wires only -- a wire internal to a gadget
+ *   or arithmetic instance (the evaluator computes those), or a wire named twice, is ZP_ERR_ARG.  The circuit's gadget must be the width-17 Poseidon
+ *   permutation of the installed tables: it is compared with the kernel on one instance, once per circuit and ctx (ZP_ERR_ARG otherwise).
  * zp_groth16_prove: witness completion + A w, B w, C w (zp_r1cs_eval_device), the QAP quotient, five MSMs over the key's device-resident points
  *   (d_u1x: u32[n_wires + 2][16] = [u_j]_1 | alpha_1 | delta_1; d_v_wires u32[n_v]: the wires with a non-zero column in B, ascending -- the B side of
  *   the key holds only those: d_v1x u32[n_v + 2][16] = [v_j]_1 | beta_1 | delta_1, d_v2x u32[n_v + 2][32] = [v_j]_2 | beta_2 | delta_2; d_l1: u32[n_wires][16], infinity at the constant and the public inputs; d_h1: u32[2^logm - 1][16]; h_delta1 u32[16]) and the blinding
