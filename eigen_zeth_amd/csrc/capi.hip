@@ -52,6 +52,7 @@ void zp_destroy(zp_ctx *ctx) {
         if (kv.second.d_twh) (void)hipFree(kv.second.d_twh);
         if (kv.second.d_tws) (void)hipFree(kv.second.d_tws);
         if (kv.second.d_tw1) (void)hipFree(kv.second.d_tw1);
+        if (kv.second.d_itab) (void)hipFree(kv.second.d_itab);
     }
     for (auto &c : ctx->cosets) {
         if (c.d_lo) (void)hipFree(c.d_lo);
@@ -103,6 +104,7 @@ static void drop_plans(zp_ctx *ctx) {
         if (kv.second.d_twh) (void)hipFree(kv.second.d_twh);
         if (kv.second.d_tws) (void)hipFree(kv.second.d_tws);
         if (kv.second.d_tw1) (void)hipFree(kv.second.d_tw1);
+        if (kv.second.d_itab) (void)hipFree(kv.second.d_itab);
     }
     ctx->plans.clear();
 }
@@ -554,6 +556,8 @@ int32_t zp_ntt_plan_json(zp_ctx *ctx, int32_t logn, char *buf, size_t buflen) {
     }
     s += "], \"first_pass_table\": ";   // the transposing pass multiplies by the full precomputed table (MODE 3) instead of per-lane chains
     s += zpi_plan_uses_tw1(ctx, pl) ? "true" : "false";
+    s += ", \"last_pass_input_table\": ";   // the last pass applies the inter-pass twiddle of the pass before it (false once the table failed to allocate)
+    s += zpi_plan_uses_itab(pl) ? "true" : "false";
     s += ", \"small_kernel\": ";
     s += (logn <= 12) ? "true" : "false";
     if (logn + 1 <= 32) {     // the extension (blow-up 2) of columns of this size, as the provers issue it (no coefficient store since round 5)

@@ -19,6 +19,7 @@ struct NttPass {
 
 struct NttPlan {
     int logn = 0;
+    int role = 0;             // zpi_get_plan_role: 0 default, 1 ends / 2 starts in a radix-256 pass (the two sides of the seam kernel)
     bool inverse = false;     // the direction the tables below were made for: what a pass of this plan scales by
     int npass = 0;
     NttPass pass[6];
@@ -28,6 +29,8 @@ struct NttPlan {
     u64 *d_tws = nullptr;     // w_4096^e (direction matched), 4096 entries
     u64 *d_tw1 = nullptr;     // first (transposing) pass: w^(u k) at [u * R + k], all 2^logn of them (null: per-lane chains)
     bool tw1_unavailable = false;   // its allocation failed once: the per-lane chain kernel serves this plan
+    u64 *d_itab = nullptr;    // last pass of a plan of >= 3 passes, input side: ninv^inverse * w^(Pp k r) at [k * R + r], Pp and k of the pass before it (null: that pass multiplies its outputs)
+    bool itab_unavailable = false;  // its allocation failed once
     u64 w16[8];               // w_16^i (direction matched)
     u64 ninv = 1;
     int j0inv = 0;            // w_16 = (2^12)^j0 ; j0inv = j0^-1 mod 16 (0: not on the power-of-two path)
@@ -173,6 +176,7 @@ int32_t zpi_get_plan_role(zp_ctx *ctx, int logn, bool inverse, int role, NttPlan
 struct NttPassShape { int A1, A2, A3, logT; };
 NttPassShape zpi_pass_shape(const zp_ctx *ctx, int L, bool big, bool transpose, bool multiplies);
 NttPassShape zpi_plan_pass_shape(const zp_ctx *ctx, const NttPlan *pl, int i);   // pass i of a plan run on its own (no post-scale)
+bool zpi_plan_uses_itab(const NttPlan *pl);                                         // the last pass multiplies its input rows by the plan's table (d_itab), the pass before it runs plain
 bool zpi_plan_uses_tw1(const zp_ctx *ctx, const NttPlan *pl);                      // the first pass multiplies by the plan's full table (d_tw1)
 int32_t zpi_lde_plan_json(zp_ctx *ctx, int logn, int want_coef, std::string *out);           // which path zp_lde takes at this size
 int32_t zpi_get_coset(zp_ctx *ctx, int logn, u64 shift, u64 pre, CosetTable **out);
@@ -190,6 +194,7 @@ int32_t zpi_merkle_verify_openings(zp_ctx *ctx, const ZpOpening *ops, size_t n, 
 struct NttRunOpts {
     const CosetTable *post_scale = nullptr;  // multiply output i by table(i) (last pass)
     int in_valid_log = -1;                   // >=0: input columns have 2^in_valid_log elements, rest is zero
+    bool seam_last = false;                  // the passes before the last only: the last one runs inside lde_seam_kernel
 };
 // the sparse periodic fixed columns (2..n_fixed-1) of a constraint program: table behind the stage-2 table,
 // per column [lp | n_entries << 8] then n_entries x (pos | is_pub << 63, value or public index)

@@ -39,11 +39,13 @@ struct PassArgs {
     const u64 *twl, *twh;
     const u64 *tws;
     const u64 *tw1;        // transposing pass, table form: w^(u k) at [u * R + k] (MODE 3)
+    const u64 *itab;       // last pass, input side: the inter-pass twiddle the pass before it left out (times 1/N of an inverse plan) at [k * R + row]; null: none
     const u64 *csl, *csh;  // coset post-scale tables (last pass of the inverse transform in LDE)
     u64 scale;
     int logn, logPprev, lb, cslb;
     int j0inv;  // w_16(user) = (2^12)^j0, j0inv = j0^-1 mod 16; 0 = root not a power of two path (generic twiddles)
-    int flags;  // 1: inter-pass twiddle  2: multiply by `scale`  4: coset post-scale
+    int logPin;  // itab: k = u0 >> logPin, the Pprev of the pass before this one
+    int flags;  // 1: inter-pass twiddle  2: multiply by `scale`  4: coset post-scale  8: a middle pass (MODE 1 whether it multiplies or not)
     int ncols;  // MODE 3: the grid is one-dimensional, columns of one launch
 };
 
@@ -302,8 +304,14 @@ __device__ __forceinline__ void table_copy_out(u64 *v, const u64 *lds, const u64
 //    extra 8 bytes per element affordable is that they are read from HBM once per 8 columns: the grid is one-dimensional and
 //    ordered so that the columns of one tile run next to each other on ONE XCD (workgroup id % 8 picks the XCD), and the
 //    table loads are cacheable, so 7 of 8 reads are hits in that XCD's L2.
-// MODE (non-transposing passes): 0 = plain last pass, 1 = multiply by the per-tile table,
-// 2 = table and the per-lane part of a coset power (last pass of the inverse transform in an LDE)
+// MODE (non-transposing passes): 0 = last pass without an output product, 1 = a middle pass, or a last pass that multiplies by 1/N:
+// the per-tile table on the output side where flags say so (flags & 3), 2 = table and the per-lane part of a coset power (last pass of
+// the inverse transform in an LDE).
+//    Input-side table (a.itab, MODE 0): the factor w^(Pprev k s) of the pass BEFORE a last pass lands, in the last pass, on row
+//    r' = s of the tile whose columns u' = k Pprev + c share k (T <= Pprev) -- again R' entries per tile and one product per element, now
+//    applied to the loaded rows.  The pass before the last is then plain (integer work moves from a pass that is bound by instruction
+//    issue to the one that is not), and 1/N of an inverse plan rides in the same entries: no output product at all.  The entries come
+//    ready-made from the plan (itab_fill_kernel): one load per lane, a tile ahead.
 // LIMB: the register butterflies and the twiddle products that follow them on the limb form of gl_limb.hpp (16 values x 4 limbs live
 // between the rounds: 3 waves per SIMD, 168 VGPRs); the per-tile table and the LDS copies of the inter-round twiddles hold 32-byte
 // records (the balanced words of w, w 2^24, w 2^48, w 2^72).  Not for the per-lane twiddle chain of a first pass without its table.
@@ -323,6 +331,9 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
     u64 *twr1 = tab + (HAS_TAB ? R * REC : 0); // R entries:  w_R^e      (inter-round twiddles, first exchange)
     u64 *twr2 = twr1 + R * REC;                // R2 entries: w_(R2)^e   (second exchange, 3-round passes)
     constexpr bool TW1 = TRANSPOSE && MODE == 3;
+    constexpr bool CAN_IN = !TRANSPOSE && MODE == 0 && L <= 9;   // instantiations that can take the input-side table
+    u64 *itl = twr2 + (TWR_LDS ? R2 * REC : 0);                  // R entries: this tile's input-side factors (a.itab)
+    const bool in_tab = CAN_IN && a.itab != nullptr;
     static_assert(!LIMB || (TWR_LDS && (TW1 || !TRANSPOSE)), "limb form: LDS twiddle copies, no per-lane twiddle chain");
     // MODE 3: one-dimensional grid; workgroup id -> (XCD x = id % 8, j = id / 8): column = j % ncols, tile group = (j / ncols) * 8 + x
     u64 col = blockIdx.y, wg_lin = blockIdx.x;
@@ -384,13 +395,22 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
 #pragma unroll
             for (int i = 0; i < NTW; i++) { tl[i] = a.twl[e[i] & lm]; th[i] = a.twh[e[i] >> a.lb]; }
         } else {
-            if constexpr (MODE >= 1) {
-                const u64 e0 = (u0 >> logP) << logP;
+            if constexpr (MODE == 1) {
+                if (a.flags & 1) {
+                    const u64 e0 = (u0 >> logP) << logP;
 #pragma unroll
-                for (int j = 0; j < TPL; j++) {
-                    const u64 e = (a.flags & 1) ? e0 * (u64)((tid + j * NT) & (R - 1)) : 0;  // entry k = tid + j*NT (k < R used)
-                    tl[j] = a.twl[e & lm];
-                    th[j] = a.twh[e >> a.lb];
+                    for (int j = 0; j < TPL; j++) {
+                        const u64 e = e0 * (u64)((tid + j * NT) & (R - 1));  // entry k = tid + j*NT (k < R used)
+                        tl[j] = a.twl[e & lm];
+                        th[j] = a.twh[e >> a.lb];
+                    }
+                }
+            }
+            if constexpr (CAN_IN) {
+                if (in_tab) {
+                    const u64 *row = a.itab + ((u0 >> a.logPin) << L);
+#pragma unroll
+                    for (int j = 0; j < TPL; j++) tl[j] = row[(tid + j * NT) & (R - 1)];
                 }
             }
             if constexpr (MODE == 2) {
@@ -410,8 +430,10 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
     }
     const u64 tile0 = wg * tiles_per_wg;
     fetch_tile(v, twl_c, twh_c, tile0 << LOGT, threadIdx.x);
-    // once per workgroup: inter-round twiddles into LDS, tile-independent factors into registers
-    u64 kfac[TPL];
+    // once per workgroup: inter-round twiddles into LDS; an output-side table that is the same for every tile (1/N, the k-part of a
+    // coset power: a last pass, flags & 1 clear) is written here and stays
+    const bool out_tab = HAS_TAB && (MODE == 2 || (a.flags & 3) != 0);   // MODE 1 with neither flag: a plain middle pass
+    const bool tile_tab = HAS_TAB && (a.flags & 1) != 0;                 // (flags & 1 comes without 2 and 4: run_one_pass)
     {
         const int tid0 = threadIdx.x;
         if constexpr (LIMB) {
@@ -435,19 +457,31 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
                 if (tid0 < R2) twr2[tid0] = a.tws[tid0 << (12 - (A2 + A3))];
             }
         }
+        if constexpr (HAS_TAB) {
+            if (out_tab && !tile_tab) {
 #pragma unroll
-        for (int j = 0; j < TPL; j++) {
-            kfac[j] = 1;
-            if constexpr (HAS_TAB) {
-                if (a.flags & 2) kfac[j] = a.scale;
-                if constexpr (MODE == 2) {
-                    const u64 ek = (u64)((tid0 + j * NT) & (R - 1)) << logP;
-                    kfac[j] = gl_mul(kfac[j], gl_mul(a.csl[ek & ((1ULL << a.cslb) - 1)], a.csh[ek >> a.cslb]));
-                }
+                for (int j = 0; j < TPL; j++)
+                    if (tid0 + j * NT < R) {
+                        u64 w = (a.flags & 2) ? a.scale : 1;
+                        if constexpr (MODE == 2) {
+                            const u64 ek = (u64)(tid0 + j * NT) << logP;
+                            const u64 ck = gl_mul(a.csl[ek & ((1ULL << a.cslb) - 1)], a.csh[ek >> a.cslb]);
+                            w = (a.flags & 2) ? gl_mul(w, ck) : ck;
+                        }
+                        if constexpr (LIMB) w4_store((gl_w4 *)tab + tid0 + j * NT, w, gl_shl12<2>(w), gl_shl12<4>(w), gl_shl12<6>(w));
+                        else tab[tid0 + j * NT] = w;
+                    }
+            }
+        }
+        if constexpr (CAN_IN) {
+            if (in_tab) {
+#pragma unroll
+                for (int j = 0; j < TPL; j++)
+                    if (tid0 + j * NT < R) itl[tid0 + j * NT] = twl_c[j];
             }
         }
     }
-    lds_barrier();  // twr1/twr2 are read by other lanes before the first exchange barrier
+    lds_barrier();  // twr1/twr2 (and the first tile's itl) are read by other lanes before the first exchange barrier
     // drain the prologue loads here so that the loop is entered with nothing pending: the waitcnt
     // insertion then needs no vmcnt wait inside the body (one there would also drain the prefetch)
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only
@@ -463,13 +497,27 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
 
         const u64 s = TRANSPOSE ? 0 : (u0 >> logP);
         if constexpr (HAS_TAB) {
+            if (tile_tab) {
 #pragma unroll
-            for (int j = 0; j < TPL; j++)
-                if (tid + j * NT < R) {
-                    const u64 w = gl_mul(gl_mul(twl_c[j], twh_c[j]), kfac[j]);
-                    if constexpr (LIMB) w4_store((gl_w4 *)tab + tid + j * NT, w, gl_shl12<2>(w), gl_shl12<4>(w), gl_shl12<6>(w));
-                    else tab[tid + j * NT] = w;
+                for (int j = 0; j < TPL; j++)
+                    if (tid + j * NT < R) {
+                        const u64 w = gl_mul(twl_c[j], twh_c[j]);
+                        if constexpr (LIMB) w4_store((gl_w4 *)tab + tid + j * NT, w, gl_shl12<2>(w), gl_shl12<4>(w), gl_shl12<6>(w));
+                        else tab[tid + j * NT] = w;
+                    }
+            }
+        }
+        if constexpr (CAN_IN) {
+            // the rows as loaded times this tile's input-side factors (written to itl before the last barrier)
+            if (in_tab) {
+#pragma unroll
+                for (int g = 0; g < (16 >> A1); g++) {
+                    const int slot0 = slot_of((g * NT + tid) >> LOGT, 0, G::POS1, A1);
+#pragma unroll
+                    for (int j = 0; j < (1 << A1); j += 2)
+                        gl_mul2(v[g * (1 << A1) + j], itl[(j << G::POS1) + slot0], v[g * (1 << A1) + j + 1], itl[((j + 1) << G::POS1) + slot0]);
                 }
+            }
         }
         gl_l4 x[LIMB ? 16 : 1];                // LIMB: the outputs of a round (the last one: x, else v)
         if constexpr (LIMB) {
@@ -541,7 +589,7 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
                     const int ka = klow + (kja << (L - AJ)), kb = klow + (kjb << (L - AJ));
                     u64 xa, xb;
                     if constexpr (LIMB) {
-                        if constexpr (MODE >= 1) {
+                        if (out_tab) {
                             xa = gl_l4_mul(x[g * (1 << AJ) + p], w4_load((const gl_w4 *)tab + ka));
                             xb = gl_l4_mul(x[g * (1 << AJ) + p + 1], w4_load((const gl_w4 *)tab + kb));
                         } else {
@@ -551,7 +599,7 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
                     } else {
                         xa = v[g * (1 << AJ) + p];
                         xb = v[g * (1 << AJ) + p + 1];
-                        if constexpr (MODE >= 1) gl_mul2(xa, tab[ka], xb, tab[kb]);
+                        if (out_tab) gl_mul2(xa, tab[ka], xb, tab[kb]);
                     }
                     if constexpr (MODE == 2) gl_mul2(xa, cw, xb, cw);
                     u64 *const ua = sbase + ((u64)(kja << (L - AJ)) << logP), *const ub = sbase + ((u64)(kjb << (L - AJ)) << logP);   // uniform
@@ -581,7 +629,15 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
             }
         }
         if (more) {
-            lds_barrier();  // LDS (tile + table) is reused by the next tile
+            if constexpr (CAN_IN) {
+                // every lane is past this tile's exchange barrier, so past its reads of itl: the next tile's entries go in
+                if (in_tab) {
+#pragma unroll
+                    for (int j = 0; j < TPL; j++)
+                        if (tid + j * NT < R) itl[tid + j * NT] = twl_n[j];
+                }
+            }
+            lds_barrier();  // LDS (tile + tables) is reused by the next tile
 #pragma unroll
             for (int i = 0; i < 16; i++) v[i] = vn[i];
 #pragma unroll
@@ -823,6 +879,14 @@ __global__ void __launch_bounds__(256) tw1_fill_kernel(u64 *out, int logn, int L
     out[i] = tw_lookup(lo, hi, lb, (u * k) & ((1ULL << logn) - 1));
 }
 
+// the input-side table of a last pass (PassArgs::itab): out[k * R + r] = pre * w^(Pp k r mod N), k < Rprev, r < R = 2^L, Pp = 2^logPp
+__global__ void __launch_bounds__(256) itab_fill_kernel(u64 *out, u64 total, int logn, int L, int logPp, u64 pre, const u64 *lo, const u64 *hi, int lb) {
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const u64 k = i >> L, r = i & ((1ULL << L) - 1);
+    out[i] = gl_mul(pre, tw_lookup(lo, hi, lb, ((k * r) << logPp) & ((1ULL << logn) - 1)));
+}
+
 using PassKernel = void (*)(PassArgs, int);
 
 // The instantiation a launch takes.  First passes: the table form (MODE 3, never BIG, two-round shapes only) with or without limb
@@ -854,14 +918,16 @@ int32_t launch_pass2(zp_ctx *ctx, PassArgs a, bool transpose, int W) {
     dim3 grid((unsigned)(tiles / tpw), (unsigned)W), block(G::NT);
     // table form of a first pass: a one-dimensional grid, XCD-ordered (ntt_pass2_kernel, MODE 3)
     const bool table = !BIG && A3 == 0 && transpose && a.tw1 && (grid.x & 7u) == 0;
-    // MODE of a later pass: 2 = coset post-scale, 1 = per-tile table (inter-pass twiddle and / or 1/N), 0 = plain
-    const int mode = transpose ? 0 : (a.flags & 4) ? 2 : (a.flags & 3) ? 1 : 0;
+    // MODE of a later pass: 2 = coset post-scale, 1 = a middle pass or one with a table on the output side (inter-pass twiddle or 1/N),
+    // 0 = a last pass that stores what its rounds deliver
+    const int mode = transpose ? 0 : (a.flags & 4) ? 2 : (a.flags & 11) ? 1 : 0;
     // limb-form butterflies (gl_limb.hpp; knob ntt_limb): every pass with LDS twiddle copies except a first pass without its table
     // (radix 2^9 and up: tiles of 64 / 128 KiB leave no room for the 32-byte table records)
     const bool limb = !BIG && G::L <= 8 && ctx->tune_ntt_limb != 0 && (!transpose || table);
     // tile + (per-tile table: non-transposing passes with a multiplication) + (LDS copies of the inter-round twiddles, L <= 10)
     const size_t rec = limb ? 4 : 1;
-    const size_t shmem = ((size_t)G::R * G::T + (mode >= 1 ? G::R * rec : 0) + (G::L <= 10 ? (G::R + (1 << (A2 + A3))) * rec : 0)) * sizeof(u64);
+    // + (the tile's input-side factors: a last pass that takes them)
+    const size_t shmem = ((size_t)G::R * G::T + (mode >= 1 ? G::R * rec : 0) + (G::L <= 10 ? (G::R + (1 << (A2 + A3))) * rec : 0) + (a.itab ? G::R : 0)) * sizeof(u64);
     const PassKernel k = pick_pass_kernel<A1, A2, A3, LOGT, BIG>(transpose, table, a.in_valid != (1ULL << a.logn), mode, limb);
     if (shmem > 65536) ZP_HIP(ctx, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     if (table) {
@@ -878,7 +944,7 @@ constexpr int shape_key(int A1, int A2, int A3, int logT, bool big) { return (((
 // one case per shape that is built: the list of what zpi_pass_shape can return
 int32_t dispatch_pass(zp_ctx *ctx, const NttPass &p, const PassArgs &a, bool transpose, int W) {
     const bool big = a.logn > 28;
-    const NttPassShape s = zpi_pass_shape(ctx, p.L, big, transpose, (a.flags & 7) != 0);
+    const NttPassShape s = zpi_pass_shape(ctx, p.L, big, transpose, (a.flags & 7) != 0 || a.itab);
 #define ZP_PASS_SHAPE(A1, A2, A3, LOGT, BIG) case shape_key(A1, A2, A3, LOGT, BIG): return launch_pass2<A1, A2, A3, LOGT, BIG>(ctx, a, transpose, W)
     switch (shape_key(s.A1, s.A2, s.A3, s.logT, big)) {
         ZP_PASS_SHAPE(3, 2, 0, 5, false);
@@ -1005,6 +1071,7 @@ int32_t zpi_get_plan_role(zp_ctx *ctx, int logn, bool inverse, int role, NttPlan
     NttPlan pl;
     pl.logn = logn;
     pl.inverse = inverse;
+    pl.role = role;
     u64 w = gl_root(ctx->root32, logn);
     u64 w4096 = gl_root(ctx->root32, 12);
     u64 w16 = gl_root(ctx->root32, 4);
@@ -1112,6 +1179,15 @@ bool zpi_plan_uses_tw1(const zp_ctx *ctx, const NttPlan *pl) {
            pl->pass[0].L >= 7;
 }
 
+// The last pass of a plan of three passes or more multiplies its INPUT by the inter-pass twiddle of the pass before it (and by 1/N of an
+// inverse plan), which then runs plain: ntt_pass2_kernel, a.itab.  Rprev x R entries per plan (512 KiB at 2^24 rows), capped at 2 MiB;
+// radix 2^10 and up keep the output-side table of the pass before (their tiles leave the LDS no room that is worth a new shape rule).
+bool zpi_plan_uses_itab(const NttPlan *pl) {
+    const int m = pl->npass;
+    // (role 1: a plan that only ever runs in front of the seam kernel, whose built-in last pass takes no such table)
+    return m >= 3 && pl->role != 1 && !pl->itab_unavailable && pl->pass[m - 1].L <= 9 && pl->pass[m - 2].L + pl->pass[m - 1].L <= 18;
+}
+
 // pass i of a plan over w columns: cur (column stride cur_cs, in_valid real elements per column) -> nxt (column stride N)
 static int32_t run_one_pass(zp_ctx *ctx, NttPlan *pl, int i, const NttRunOpts &opts, const u64 *cur, u64 cur_cs, u64 in_valid, u64 *nxt, int w) {
     const int logn = pl->logn, m = pl->npass;
@@ -1132,13 +1208,20 @@ static int32_t run_one_pass(zp_ctx *ctx, NttPlan *pl, int i, const NttRunOpts &o
     a.logn = logn;
     a.logPprev = pl->pass[i].logPprev;
     a.j0inv = pl->j0inv;
-    a.flags = last ? 0 : 1;
-    if (last) set_output_scaling(a, pl->inverse, opts.post_scale);
+    // opts.seam_last: the plan's last pass is the seam kernel's built-in one, which takes no input-side table; neither does a last pass
+    // that multiplies by coset powers (MODE 2: the inverse side of an extension run as two transforms)
+    const bool in_tab = pl->d_itab && zpi_plan_uses_itab(pl) && !opts.seam_last && !opts.post_scale;
+    a.flags = last ? 0 : (i == m - 2 && in_tab) ? 8 : 1 | (i >= 1 ? 8 : 0);
+    if (last && in_tab) {
+        a.itab = pl->d_itab;
+        a.logPin = pl->pass[m - 2].logPprev;
+    }
+    if (last) set_output_scaling(a, pl->inverse && !in_tab, opts.post_scale);
     PassTimer timer(ctx, (i == 0) ? -pl->pass[i].L : pl->pass[i].L);
     return dispatch_pass(ctx, pl->pass[i], a, i == 0, w);
 }
 // the first pass's full table (8 bytes per element of ONE column, shared by all columns and all later calls of this size):
-// built at the first use of a plan by radix-2^7 / 2^8 two-round passes below 2^29 rows
+// built at the first use of a plan by radix-2^7 / 2^8 two-round passes below 2^29 rows; and the last pass's input-side table
 static int32_t ensure_tw1(zp_ctx *ctx, NttPlan *pl) {
     const int logn = pl->logn;
     if (!pl->d_tw1 && zpi_plan_uses_tw1(ctx, pl)) {
@@ -1151,6 +1234,20 @@ static int32_t ensure_tw1(zp_ctx *ctx, NttPlan *pl) {
         } else {
             hipLaunchKernelGGL(tw1_fill_kernel, dim3((unsigned)(((1ULL << logn) + 255) / 256)), dim3(256), 0, ctx->stream, pl->d_tw1, logn, pl->pass[0].L,
                                pl->d_twl, pl->d_twh, pl->lb);
+            ZP_HIP(ctx, hipGetLastError());
+        }
+    }
+    if (!pl->d_itab && zpi_plan_uses_itab(pl)) {
+        const int m = pl->npass, lr = pl->pass[m - 1].L;
+        const u64 total = 1ULL << (pl->pass[m - 2].L + lr);
+        if (hipMalloc((void **)&pl->d_itab, total * sizeof(u64)) != hipSuccess) {
+            // as above: without it the pass before the last multiplies on its output side, same results
+            (void)hipGetLastError();
+            pl->d_itab = nullptr;
+            pl->itab_unavailable = true;
+        } else {
+            hipLaunchKernelGGL(itab_fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, pl->d_itab, total, logn, lr,
+                               pl->pass[m - 2].logPprev, pl->inverse ? pl->ninv : 1ULL, pl->d_twl, pl->d_twh, pl->lb);
             ZP_HIP(ctx, hipGetLastError());
         }
     }
@@ -1223,13 +1320,14 @@ static int32_t lde_fused(zp_ctx *ctx, const LdeRoute &r, const CosetTable *ct, c
     ZP_TRY(zpi_scratch(ctx, 0, need, &s0));
     ZP_TRY(zpi_scratch(ctx, 1, need, &s1));
     if (mf >= 3) ZP_TRY(zpi_scratch(ctx, 2, (size_t)wf << (logn + 1), &s2));
-    NttRunOpts none;
+    NttRunOpts none, inv_side;
+    inv_side.seam_last = true;
     for (int c0 = 0; c0 < W; c0 += wc) {
         const int w = (W - c0 < wc) ? (W - c0) : wc;
         const u64 *cur = d_in + (u64)c0 * N;
         for (int i = 0; i + 1 < mi; i++) {                     // the inverse transform up to its last pass
             u64 *nxt = (i & 1) ? s1 : s0;
-            ZP_TRY(run_one_pass(ctx, pi, i, none, cur, N, N, nxt, w));
+            ZP_TRY(run_one_pass(ctx, pi, i, inv_side, cur, N, N, nxt, w));
             cur = nxt;
         }
         u64 *seam_out = (cur == s0) ? s1 : s0;
