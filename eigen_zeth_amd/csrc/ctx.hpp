@@ -4,6 +4,7 @@
 
 #include <map>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/zeth_prover.h"
@@ -160,6 +161,17 @@ struct ZpStage {
         int32_t rc_ = (expr);                                                                \
         if (rc_ != ZP_OK) return rc_;                                                        \
     } while (0)
+
+// host work over items 0 .. n - 1 on T threads: work(first, end) on the t-th of T near-equal ranges, empty ranges skipped; returns once all have ended
+template <class Work>
+void zpi_split_over_threads(size_t n, int T, Work work) {
+    std::vector<std::thread> pool;
+    for (int t = 0; t < T; t++) {
+        const size_t a = n * t / T, b = n * (t + 1) / T;
+        if (a < b) pool.emplace_back(work, a, b);
+    }
+    for (auto &th : pool) th.join();
+}
 
 // internal helpers implemented across the .hip files
 int32_t zpi_scratch(zp_ctx *ctx, int which, size_t elems, u64 **out);

@@ -1,7 +1,7 @@
 // BN254 base field F_q and the curve code of the multi-scalar multiplication (csrc/msm.hip): F_q and F_q2 in Montgomery form on nine 29-bit
-// limbs, the lazy (unreduced) forms of the G1 bucket sums, the Jacobian formulas over both fields and the signed window digits.
-// Everything is file-local (anonymous namespace): msm.hip includes it, and so does tests/native/fq254_check.hip, which runs every function
-// at the bounds its comment states.
+// limbs, the lazy (unreduced) forms of the G1 bucket sums, the Jacobian formulas over both fields, the packed affine point and the signed
+// window digits.  Everything is file-local (anonymous namespace): msm.hip, fixed_base.hip and synth.hip include it, and so does
+// tests/native/fq254_check.hip, which runs every function at the bounds its comment states.
 #pragma once
 #include <cstring>
 
@@ -529,6 +529,24 @@ FQ_HD jacT<F> jac_mul_small(const jacT<F> &p, u32 k) {  // k * p by double-and-a
     return acc;
 }
 
+// a packed affine point = 2 * FT<F>::WORDS words = NV uint4 (G1: 4, G2: 8); (0, 0) encodes the point at infinity
+#if defined(__HIPCC__)   // (uint4: the host-only build of tests/native/fq254_check.hip has no such type)
+template <class F>
+__device__ __forceinline__ void unpack_point(const uint4 *q, F &x, F &y) {
+    constexpr int NV = FT<F>::WORDS / 2;
+    u32 w[FT<F>::WORDS * 2];
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+        w[4 * k] = q[k].x;
+        w[4 * k + 1] = q[k].y;
+        w[4 * k + 2] = q[k].z;
+        w[4 * k + 3] = q[k].w;
+    }
+    x = FT<F>::from_words(w);
+    y = FT<F>::from_words(w + FT<F>::WORDS);
+}
+#endif
+
 // Signed window digits.  With K = sum_w 2^(cd w + cd - 1) the unsigned digits u_w of s + K give  s = sum_w (u_w - 2^(cd-1)) 2^(cd w):
 // digits d_w in [-2^(cd-1), 2^(cd-1)), so a window has 2^(cd-1) buckets |d| = 1 .. 2^(cd-1) (bucket index |d| - 1) and a negative
 // digit adds -P.  One more bit of window for the same bucket memory: 14 windows of 19 bits instead of 15 of 18.
@@ -567,6 +585,13 @@ fq f_inv_host(const fq &a) { return fq_inv_host(a); }
 fq2 f_inv_host(const fq2 &a) {  // (a0 - a1 u) / (a0^2 + a1^2)
     const fq d = fq_inv_host(fq_add(fq_sqr(a.c0), fq_sqr(a.c1)));
     return fq2_make(fq_mul(a.c0, d), fq_sub(fq_zero(), fq_mul(a.c1, d)));
+}
+// the affine words (standard form, x then y: the layout of the MSM entry points) of a Jacobian point with Z != 0, given zi = 1 / Z
+template <class F>
+void jac_affine_words(const jacT<F> &p, const F &zi, u32 *out) {
+    const F zi2 = f_sqr(zi);
+    FT<F>::to_words(f_from_mont(f_mul(p.X, zi2)), out);
+    FT<F>::to_words(f_from_mont(f_mul(p.Y, f_mul(zi2, zi))), out + FT<F>::WORDS);
 }
 
 }  // namespace

@@ -1,4 +1,5 @@
-// BN254 (alt_bn128) G1 multi-scalar multiplication: sum_i s_i * P_i   (SURVEY.md 8a N6).
+// BN254 (alt_bn128) multi-scalar multiplication over G1 and G2: sum_i s_i * P_i   (SURVEY.md 8a N6).  This file holds the MSM and nothing else:
+// the fixed-base multiplication of the key setup is csrc/fixed_base.hip, the synthetic input points are csrc/synth.hip.
 //
 // No reference counterpart in /root/reference: the Groth16 wrap that answers GenFinalProof
 // (proto/prover/v1/prover.proto:130-148, client src/prover/provider.rs:472-503) lives in the external
@@ -8,16 +9,15 @@
 //   3. reduction  : running sums over segments of MSM_SEG buckets, segment weights by double-and-add,
 //                   tree sum per window in LDS
 //   4. the <= 32 window results are combined on the host (254 doublings).
-// Field: F_q in Montgomery form, 9 x 29-bit limbs, product scanning with v_mad_u64_u32 (see below).  VALU only;
-// the MFMA limb-product formulation north_star mentions is not built.
+// Field and curve code: csrc/fq254.hpp (F_q in Montgomery form, 9 x 29-bit limbs).  VALU only; the MFMA limb-product formulation north_star
+// mentions is not built.
+// Written once, used by every kernel that needs it: tile_digits (the walk over a tile's window digits), wave_count (LDS counter, one atomic per
+// wave of equal keys), reserve_bins (one global reservation per bin and block), block_exclusive_scan, block_jac_sum, entry_* (the sorted entry).
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
-
 #include <cstring>
+#include <type_traits>
 #include <vector>
-
-#include <thread>
 
 #include "ctx.hpp"
 #include "fq254.hpp"
@@ -32,7 +32,7 @@ namespace {
 //   the fine stage handles with one LDS atomic per wave instead of 64 colliding ones
 //   1a. msm_coarse_hist : LDS histogram per 4096-point tile -> counts[window][coarse]
 //   1b. msm_scan        : exclusive scan per window -> coarse starts
-//   1c. msm_coarse_part : per tile, LDS ranks + one global reservation per (window, coarse bin) -> (index, fine
+//   1c. msm_coarse_part : per tile, LDS ranks + one global reservation per (window, coarse bin) -> (entry, fine
 //                         digit) pairs grouped by coarse bin (order inside a bin is arbitrary)
 //   1d. msm_fine_sort   : one workgroup per (window, coarse bin): counting sort by fine digit with LDS counters,
 //                         inside that bin's contiguous (L2-sized) region; also emits starts/counts per bucket
@@ -43,11 +43,19 @@ struct SortGeo {
     int cd;                        // digit width = c + 1 (signed digits)
     u32 K[9];                      // the recoding bias  sum_w 2^(cd w + cd - 1)
 };
-__global__ void __launch_bounds__(256) msm_coarse_hist_kernel(const u32 *scalars, u64 n, SortGeo g, int w0, u32 *ccounts) {
-    extern __shared__ u32 lh[];   // [wgroup][2^hi]
-    const int nbin = 1 << g.hi, nw = min(g.wgroup, g.nwin - w0);
-    for (int i = threadIdx.x; i < nw * nbin; i += 256) lh[i] = 0;
-    __syncthreads();
+// a digit of magnitude d >= 1 belongs to bucket d - 1 of its window: coarse bin = its low hi bits, fine digit = the lo bits above
+__device__ __forceinline__ u32 coarse_bin(const SortGeo &g, u32 d) { return (d - 1) & ((1u << g.hi) - 1); }
+__device__ __forceinline__ u32 fine_digit(const SortGeo &g, u32 d) { return (d - 1) >> g.hi; }
+__device__ __forceinline__ u64 bucket_of(const SortGeo &g, u64 w, u64 bin, u64 fine) { return (w << g.c) + (fine << g.hi) + bin; }
+// a sorted entry: the point index with the sign of its digit in bit 31 (n < 2^31)
+__device__ __forceinline__ u32 entry_make(u32 index, u32 neg) { return index | (neg << 31); }
+__device__ __forceinline__ u32 entry_index(u32 e) { return e & 0x7FFFFFFFu; }
+__device__ __forceinline__ u32 entry_neg(u32 e) { return e >> 31; }
+
+// the digit walk of one tile (block) in one pass over windows w0 .. w0 + nw - 1: fn(i, w, d, neg) for every non-zero digit -- point i, window
+// w0 + w, magnitude d, sign neg
+template <class Fn>
+__device__ __forceinline__ void tile_digits(const u32 *scalars, u64 n, const SortGeo &g, int w0, int nw, Fn fn) {
     const u64 base = (u64)blockIdx.x * MSM_TILE;
     for (int k = 0; k < MSM_TILE / 256; k++) {
         const u64 i = base + (u64)k * 256 + threadIdx.x;
@@ -59,40 +67,87 @@ __global__ void __launch_bounds__(256) msm_coarse_hist_kernel(const u32 *scalars
             add_bias9(sc, g.K, s9);
             for (int w = 0; w < nw; w++) {
                 const u32 d = digit_key(s9, w0 + w, g.cd, neg);
-                if (d) atomicAdd(&lh[w * nbin + ((d - 1) & (nbin - 1))], 1u);
+                if (d) fn(i, w, d, neg);
             }
         }
     }
+}
+// cnt[key] += 1 from every active lane, returning the lane's rank among the block's elements of that key so far.  A wave whose active lanes
+// all carry ONE key (skewed scalars) issues one LDS atomic, not 64 colliding ones.  A caller that only counts ignores the rank, and the compiler drops its computation.
+__device__ __forceinline__ u32 wave_count(u32 *cnt, u32 key) {
+    const int lane = threadIdx.x & 63;
+    const u64 act = __ballot(1);
+    if (__ballot(key == (u32)__builtin_amdgcn_readfirstlane((int)key)) == act) {
+        u32 base = 0;
+        if (lane == __ffsll((long long)act) - 1) base = atomicAdd(&cnt[key], (u32)__popcll(act));
+        base = (u32)__builtin_amdgcn_readfirstlane((int)base);
+        return base + (u32)__popcll(act & ((1ULL << lane) - 1));
+    }
+    return atomicAdd(&cnt[key], 1u);
+}
+// the reservation step of a counting sort whose blocks counted into LDS: one global atomic per bin that holds something,
+// base[b] = where this block's share of bin b starts; the counters go back to zero for the ranking pass.  256 threads.
+template <class Cursor>
+__device__ __forceinline__ void reserve_bins(u32 *cnt, u32 *base, int nbins, Cursor cursor_of) {
+    for (int b = threadIdx.x; b < nbins; b += 256) {
+        const u32 k = cnt[b];
+        base[b] = k ? atomicAdd(cursor_of(b), k) : 0u;
+        cnt[b] = 0;
+    }
+}
+// exclusive scan of count(0) .. count(n - 1) by one block of NT threads: a thread owns a run of ceil(n / NT) consecutive items, the runs'
+// totals are scanned in LDS (Hillis-Steele) and put(j, sum of the counts before j) is called for every item
+template <int NT, class Count, class Put>
+__device__ __forceinline__ void block_exclusive_scan(u32 n, Count count, Put put) {
+    __shared__ u32 part[NT];
+    const u32 t = threadIdx.x, per = (n + NT - 1) / NT;
+    const u32 lo = min(t * per, n), hi = min(lo + per, n);
+    u32 s = 0;
+    for (u32 j = lo; j < hi; j++) s += count(j);
+    part[t] = s;
+    __syncthreads();
+    for (u32 d = 1; d < NT; d <<= 1) {
+        const u32 v = t >= d ? part[t - d] : 0u;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    u32 run = part[t] - s;
+    for (u32 j = lo; j < hi; j++) {
+        put(j, run);
+        run += count(j);
+    }
+}
+// LDS tree sum of one Jacobian point per lane over the N lanes of the block; lane 0 stores the total to *out
+template <class F, int N>
+__device__ __forceinline__ void block_jac_sum(const jacT<F> &mine, jacT<F> *out) {
+    __shared__ jacT<F> sh[N];
+    sh[threadIdx.x] = mine;
+    __syncthreads();
+    for (int s = N / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] = jac_add(sh[threadIdx.x], sh[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = sh[0];
+}
+
+__global__ void __launch_bounds__(256) msm_coarse_hist_kernel(const u32 *scalars, u64 n, SortGeo g, int w0, u32 *ccounts) {
+    extern __shared__ u32 lh[];   // [wgroup][2^hi]
+    const int nbin = 1 << g.hi, nw = min(g.wgroup, g.nwin - w0);
+    for (int i = threadIdx.x; i < nw * nbin; i += 256) lh[i] = 0;
+    __syncthreads();
+    tile_digits(scalars, n, g, w0, nw, [&](u64, int w, u32 d, u32) { atomicAdd(&lh[w * nbin + coarse_bin(g, d)], 1u); });
     __syncthreads();
     for (int i = threadIdx.x; i < nw * nbin; i += 256)
-        if (lh[i]) atomicAdd(&ccounts[(u64)(w0 + i / nbin) * nbin + (i % nbin)], lh[i]);
+        if (lh[i]) atomicAdd(&ccounts[(u64)w0 * nbin + i], lh[i]);
 }
 // exclusive scan of the 2^bits counters of one window (one block per window)
 __global__ void __launch_bounds__(1024) msm_scan_kernel(const u32 *counts, u32 *starts, u32 *cursor, int bits) {
-    __shared__ u32 part[1024];
     const u64 base = (u64)blockIdx.x << bits;
-    const u32 nb = 1u << bits;
-    const u32 per = (nb + 1023) / 1024;
-    const u32 lo = min(threadIdx.x * per, nb), hi = min(lo + per, nb);
-    u32 s = 0;
-    for (u32 b = lo; b < hi; b++) s += counts[base + b];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u32 run = 0;
-        for (int t = 0; t < 1024; t++) {
-            u32 v = part[t];
-            part[t] = run;
-            run += v;
-        }
-    }
-    __syncthreads();
-    u32 run = part[threadIdx.x];
-    for (u32 b = lo; b < hi; b++) {
-        starts[base + b] = run;
-        cursor[base + b] = run;
-        run += counts[base + b];
-    }
+    block_exclusive_scan<1024>(1u << bits, [&](u32 b) { return counts[base + b]; }, [&](u32 b, u32 at) {
+        starts[base + b] = at;
+        cursor[base + b] = at;
+    });
 }
 __global__ void __launch_bounds__(256) msm_coarse_part_kernel(const u32 *scalars, u64 n, SortGeo g, int w0, u32 *ccursor,
                                                              u32 *pidx, u32 *pfine) {
@@ -101,55 +156,25 @@ __global__ void __launch_bounds__(256) msm_coarse_part_kernel(const u32 *scalars
     u32 *lbase = lh + g.wgroup * nbin;
     for (int i = threadIdx.x; i < nw * nbin; i += 256) lh[i] = 0;
     __syncthreads();
-    const u64 base = (u64)blockIdx.x * MSM_TILE;
-    for (int k = 0; k < MSM_TILE / 256; k++) {   // phase A: how many of this tile go to each (window, coarse bin)
-        const u64 i = base + (u64)k * 256 + threadIdx.x;
-        if (i < n) {
-            u32 sc[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) sc[j] = scalars[i * 8 + j];
-            u32 s9[9], neg;
-            add_bias9(sc, g.K, s9);
-            for (int w = 0; w < nw; w++) {
-                const u32 d = digit_key(s9, w0 + w, g.cd, neg);
-                if (d) atomicAdd(&lh[w * nbin + ((d - 1) & (nbin - 1))], 1u);
-            }
-        }
-    }
+    // phase A: how many of this tile go to each (window, coarse bin)
+    tile_digits(scalars, n, g, w0, nw, [&](u64, int w, u32 d, u32) { atomicAdd(&lh[w * nbin + coarse_bin(g, d)], 1u); });
     __syncthreads();
-    for (int i = threadIdx.x; i < nw * nbin; i += 256) {   // one global reservation per (window, coarse bin) of the tile
-        const u32 cnt = lh[i];
-        lbase[i] = cnt ? atomicAdd(&ccursor[(u64)(w0 + i / nbin) * nbin + (i % nbin)], cnt) : 0u;
-        lh[i] = 0;
-    }
+    reserve_bins(lh, lbase, nw * nbin, [&](int b) { return &ccursor[(u64)w0 * nbin + b]; });
     __syncthreads();
-    for (int k = 0; k < MSM_TILE / 256; k++) {   // phase B: rank inside the tile's share of the bin, write the pair
-        const u64 i = base + (u64)k * 256 + threadIdx.x;
-        if (i < n) {
-            u32 sc[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) sc[j] = scalars[i * 8 + j];
-            u32 s9[9], neg;
-            add_bias9(sc, g.K, s9);
-            for (int w = 0; w < nw; w++) {
-                const u32 d = digit_key(s9, w0 + w, g.cd, neg);
-                if (d) {
-                    const int b = w * nbin + ((d - 1) & (nbin - 1));
-                    const u32 pos = lbase[b] + atomicAdd(&lh[b], 1u);
-                    pidx[(u64)(w0 + w) * n + pos] = (u32)i | (neg << 31);   // the sign of the digit travels with the index
-                    pfine[(u64)(w0 + w) * n + pos] = (d - 1) >> g.hi;
-                }
-            }
-        }
-    }
+    // phase B: rank inside the tile's share of the bin, write the pair
+    tile_digits(scalars, n, g, w0, nw, [&](u64 i, int w, u32 d, u32 neg) {
+        const int b = w * nbin + coarse_bin(g, d);
+        const u32 pos = lbase[b] + atomicAdd(&lh[b], 1u);
+        pidx[(u64)(w0 + w) * n + pos] = entry_make((u32)i, neg);
+        pfine[(u64)(w0 + w) * n + pos] = fine_digit(g, d);
+    });
 }
 // ---- 1d. fine stage, slice-parallel: a coarse bin is cut into slices of MSM_FSLICE elements, one workgroup each, so
 // that a bin holding millions of elements (skewed scalars) is sorted by many workgroups.
 //   msm_slices      : slice list (coarse bin, slice number) per (window, coarse bin)
 //   msm_fine_hist   : LDS histogram of a slice by fine digit -> counts[bucket] (global atomics, one per digit present)
 //   msm_fine_scan   : per coarse bin: exclusive scan of its <= 1024 bucket counts -> starts[bucket], cursor[bucket]
-//   msm_fine_scatter: per slice: reserve cursor[bucket] once per digit present, rank in LDS, write the indices
-// A wave whose 64 elements carry one and the same digit (the skewed case) issues one LDS atomic, not 64 colliding ones.
+//   msm_fine_scatter: per slice: reserve cursor[bucket] once per digit present, rank in LDS, write the entries
 #define MSM_FSLICE 8192
 __global__ void __launch_bounds__(256) msm_slices_kernel(const u32 *ccounts, u32 ncoarse, u32 *slice_count, uint2 *slices) {
     const u32 i = blockIdx.x * 256 + threadIdx.x;
@@ -160,109 +185,57 @@ __global__ void __launch_bounds__(256) msm_slices_kernel(const u32 *ccounts, u32
     const u32 base = atomicAdd(slice_count, nsl);
     for (u32 s = 0; s < nsl; s++) slices[base + s] = make_uint2(i, s);
 }
-// LDS histogram of one slice by fine digit (cnt must be zero on entry, nf entries)
-__device__ __forceinline__ void slice_hist(const u32 *pf, u32 lo, u32 hi, u32 *cnt) {
-    const int lane = threadIdx.x & 63;
-    for (u32 i = lo + threadIdx.x; i < hi; i += 256) {
-        const u32 f = pf[i];
-        const u64 act = __ballot(1);
-        if (__ballot(f == (u32)__builtin_amdgcn_readfirstlane((int)f)) == act) {   // one digit in the whole wave
-            if (lane == __ffsll((long long)act) - 1) atomicAdd(&cnt[f], (u32)__popcll(act));
-        } else {
-            atomicAdd(&cnt[f], 1u);
-        }
-    }
+// what a block of the fine stage works on: elements lo .. hi - 1 of coarse bin `bin` of window w, whose region starts at element cs of the window
+struct FineSlice {
+    u64 w, bin;
+    u32 cs, lo, hi;
+};
+__device__ __forceinline__ FineSlice fine_slice(const SortGeo &g, const uint2 *slices, const u32 *cstarts, const u32 *ccounts) {
+    const uint2 sl = slices[blockIdx.x];   // (window * 2^hi + coarse bin, slice number)
+    const u32 lo = sl.y * MSM_FSLICE;
+    return FineSlice{sl.x >> g.hi, sl.x & ((1u << g.hi) - 1), cstarts[sl.x], lo, min(lo + (u32)MSM_FSLICE, ccounts[sl.x])};
+}
+// LDS histogram of the block's slice by fine digit (cnt: 2^lo entries, zeroed here)
+__device__ __forceinline__ void slice_hist(const SortGeo &g, const u32 *pf, const FineSlice &s, u32 *cnt) {
+    for (int i = threadIdx.x; i < (1 << g.lo); i += 256) cnt[i] = 0;
+    __syncthreads();
+    for (u32 i = s.lo + threadIdx.x; i < s.hi; i += 256) (void)wave_count(cnt, pf[i]);
+    __syncthreads();
 }
 __global__ void __launch_bounds__(256) msm_fine_hist_kernel(const u32 *pfine, u64 n, SortGeo g, const uint2 *slices,
                                                            const u32 *cstarts, const u32 *ccounts, u32 *counts) {
     __shared__ u32 cnt[1 << MSM_LO_MAX];
-    const int nbin = 1 << g.hi, nf = 1 << g.lo;
-    const uint2 sl = slices[blockIdx.x];
-    const u64 w = sl.x / nbin, bin = sl.x % nbin;
-    const u32 cs = cstarts[sl.x], cc = ccounts[sl.x];
-    const u32 lo = sl.y * MSM_FSLICE, hi = min(lo + (u32)MSM_FSLICE, cc);
-    for (int i = threadIdx.x; i < nf; i += 256) cnt[i] = 0;
-    __syncthreads();
-    slice_hist(pfine + w * n + cs, lo, hi, cnt);
-    __syncthreads();
-    for (int f = threadIdx.x; f < nf; f += 256)
-        if (cnt[f]) atomicAdd(&counts[(w << g.c) + ((u64)f << g.hi) + bin], cnt[f]);
+    const FineSlice s = fine_slice(g, slices, cstarts, ccounts);
+    slice_hist(g, pfine + s.w * n + s.cs, s, cnt);
+    for (int f = threadIdx.x; f < (1 << g.lo); f += 256)
+        if (cnt[f]) atomicAdd(&counts[bucket_of(g, s.w, s.bin, f)], cnt[f]);
 }
 __global__ void __launch_bounds__(1024) msm_fine_scan_kernel(SortGeo g, const u32 *cstarts, const u32 *counts, u32 *starts,
                                                             u32 *cursor) {
-    __shared__ u32 part[1024];
-    const int nbin = 1 << g.hi, nf = 1 << g.lo;
-    const u64 w = blockIdx.x / nbin, bin = blockIdx.x % nbin;
+    const u64 w = blockIdx.x >> g.hi, bin = blockIdx.x & ((1u << g.hi) - 1);
     const u32 cs = cstarts[blockIdx.x];
-    const u64 bucket = (w << g.c) + ((u64)threadIdx.x << g.hi) + bin;
-    const u32 mine = (int)threadIdx.x < nf ? counts[bucket] : 0u;
-    part[threadIdx.x] = mine;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const u32 v = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    if ((int)threadIdx.x < nf) {
-        const u32 at = cs + part[threadIdx.x] - mine;
-        starts[bucket] = at;
-        cursor[bucket] = at;
-    }
+    block_exclusive_scan<1024>(1u << g.lo, [&](u32 f) { return counts[bucket_of(g, w, bin, f)]; }, [&](u32 f, u32 at) {
+        starts[bucket_of(g, w, bin, f)] = cs + at;
+        cursor[bucket_of(g, w, bin, f)] = cs + at;
+    });
 }
 __global__ void __launch_bounds__(256) msm_fine_scatter_kernel(const u32 *pidx, const u32 *pfine, u64 n, SortGeo g,
                                                               const uint2 *slices, const u32 *cstarts, const u32 *ccounts,
                                                               u32 *cursor, u32 *sorted) {
     __shared__ u32 cnt[1 << MSM_LO_MAX], lbase[1 << MSM_LO_MAX];
-    const int nbin = 1 << g.hi, nf = 1 << g.lo;
-    const uint2 sl = slices[blockIdx.x];
-    const u64 w = sl.x / nbin, bin = sl.x % nbin;
-    const u32 cs = cstarts[sl.x], cc = ccounts[sl.x];
-    const u32 lo = sl.y * MSM_FSLICE, hi = min(lo + (u32)MSM_FSLICE, cc);
-    const u32 *pi = pidx + w * n + cs, *pf = pfine + w * n + cs;
-    for (int i = threadIdx.x; i < nf; i += 256) cnt[i] = 0;
+    const FineSlice s = fine_slice(g, slices, cstarts, ccounts);
+    const u32 *pi = pidx + s.w * n + s.cs, *pf = pfine + s.w * n + s.cs;
+    slice_hist(g, pf, s, cnt);
+    reserve_bins(cnt, lbase, 1 << g.lo, [&](int f) { return &cursor[bucket_of(g, s.w, s.bin, f)]; });
     __syncthreads();
-    slice_hist(pf, lo, hi, cnt);
-    __syncthreads();
-    for (int f = threadIdx.x; f < nf; f += 256) {   // one global reservation per digit present in the slice
-        const u32 k = cnt[f];
-        lbase[f] = k ? atomicAdd(&cursor[(w << g.c) + ((u64)f << g.hi) + bin], k) : 0u;
-        cnt[f] = 0;
-    }
-    __syncthreads();
-    u32 *out = sorted + w * n;
-    const int lane = threadIdx.x & 63;
-    for (u32 i = lo + threadIdx.x; i < hi; i += 256) {
+    u32 *out = sorted + s.w * n;
+    for (u32 i = s.lo + threadIdx.x; i < s.hi; i += 256) {
         const u32 f = pf[i];
-        const u64 act = __ballot(1);
-        u32 rank;
-        if (__ballot(f == (u32)__builtin_amdgcn_readfirstlane((int)f)) == act) {
-            u32 base = 0;
-            if (lane == __ffsll((long long)act) - 1) base = atomicAdd(&cnt[f], (u32)__popcll(act));
-            base = (u32)__builtin_amdgcn_readfirstlane((int)base);
-            rank = base + (u32)__popcll(act & ((1ULL << lane) - 1));
-        } else {
-            rank = atomicAdd(&cnt[f], 1u);
-        }
+        const u32 rank = wave_count(cnt, f);
         out[lbase[f] + rank] = pi[i];
     }
 }
 
-// a packed affine point = 2 * FT<F>::WORDS words = NV uint4 (G1: 4, G2: 8); (0, 0) encodes the point at infinity
-template <class F>
-__device__ __forceinline__ void unpack_point(const uint4 *q, F &x, F &y) {
-    constexpr int NV = FT<F>::WORDS / 2;
-    u32 w[FT<F>::WORDS * 2];
-#pragma unroll
-    for (int k = 0; k < NV; k++) {
-        w[4 * k] = q[k].x;
-        w[4 * k + 1] = q[k].y;
-        w[4 * k + 2] = q[k].z;
-        w[4 * k + 3] = q[k].w;
-    }
-    x = FT<F>::from_words(w);
-    y = FT<F>::from_words(w + FT<F>::WORDS);
-}
 // ---- 2a. one-time conversion of the affine inputs to Montgomery form (16-byte vector accesses); stored packed
 template <class F>
 __global__ void __launch_bounds__(256) msm_to_mont_kernel(const uint4 *points, u64 n, uint4 *mont) {
@@ -316,22 +289,18 @@ struct HeavyLists {
 //   msm_order_scan : exclusive scan from the largest bin down (one block)
 //   msm_order_fill : rank inside the block (LDS), one reservation per bin and block, order[pos] = id
 #define MSM_OBINS (MSM_HEAVY + 2)
+__device__ __forceinline__ u32 order_bin(u32 count) { return count > MSM_HEAVY ? MSM_HEAVY + 1 : count; }
 __global__ void __launch_bounds__(256) msm_order_hist_kernel(const u32 *counts, u64 nb, u32 *hist) {
     __shared__ u32 h[MSM_OBINS];
     for (int i = threadIdx.x; i < MSM_OBINS; i += 256) h[i] = 0;
     __syncthreads();
-    for (u64 id = (u64)blockIdx.x * 256 + threadIdx.x; id < nb; id += (u64)gridDim.x * 256) {
-        const u32 cnt = counts[id];
-        atomicAdd(&h[cnt > MSM_HEAVY ? MSM_HEAVY + 1 : cnt], 1u);
-    }
+    for (u64 id = (u64)blockIdx.x * 256 + threadIdx.x; id < nb; id += (u64)gridDim.x * 256) atomicAdd(&h[order_bin(counts[id])], 1u);
     __syncthreads();
     for (int i = threadIdx.x; i < MSM_OBINS; i += 256)
         if (h[i]) atomicAdd(&hist[i], h[i]);
 }
-__global__ void __launch_bounds__(64) msm_order_scan_kernel(const u32 *hist, u32 *cursor) {
-    if (threadIdx.x) return;
-    u32 run = 0;
-    for (int b = MSM_OBINS - 1; b >= 0; b--) { cursor[b] = run; run += hist[b]; }
+__global__ void __launch_bounds__(64) msm_order_scan_kernel(const u32 *hist, u32 *cursor) {   // item j of the scan is bin MSM_OBINS - 1 - j
+    block_exclusive_scan<64>(MSM_OBINS, [&](u32 j) { return hist[MSM_OBINS - 1 - j]; }, [&](u32 j, u32 at) { cursor[MSM_OBINS - 1 - j] = at; });
 }
 __global__ void __launch_bounds__(256) msm_order_fill_kernel(const u32 *counts, u64 nb, u32 *cursor, u32 *order) {
     __shared__ u32 h[MSM_OBINS], base[MSM_OBINS];
@@ -340,13 +309,11 @@ __global__ void __launch_bounds__(256) msm_order_fill_kernel(const u32 *counts, 
     __syncthreads();
     u32 bin = 0, rank = 0;
     if (id < nb) {
-        const u32 cnt = counts[id];
-        bin = cnt > MSM_HEAVY ? MSM_HEAVY + 1 : cnt;
+        bin = order_bin(counts[id]);
         rank = atomicAdd(&h[bin], 1u);
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < MSM_OBINS; i += 256)
-        if (h[i]) base[i] = atomicAdd(&cursor[i], h[i]);
+    reserve_bins(h, base, MSM_OBINS, [&](int b) { return &cursor[b]; });
     __syncthreads();
     if (id < nb) order[base[bin] + rank] = (u32)id;
 }
@@ -371,24 +338,24 @@ __global__ void __launch_bounds__(256) msm_bucket_kernel(const uint4 *mont, u64 
     if (cnt) {
         const u32 last = cnt - 1;
         uint4 A[NV], B[NV];
-        u32 va = idx[0];                     // bit 31: sign of the digit, bits 0..30: point index
-        u64 pa = va & 0x7FFFFFFFu;
+        u32 va = idx[0];
+        u64 pa = entry_index(va);
 #pragma unroll
         for (int j = 0; j < NV; j++) A[j] = mont[pa * NV + j];
         u32 ia = idx[last < 1 ? last : 1];
         for (u32 k = 0; k < cnt; k += 2) {
             const u32 vb = ia;
-            const u64 pb = vb & 0x7FFFFFFFu;
+            const u64 pb = entry_index(vb);
 #pragma unroll
             for (int j = 0; j < NV; j++) B[j] = mont[pb * NV + j];
             const u32 ib = idx[k + 2 < last ? k + 2 : last];
-            acc = madd_packed<F>(acc, A, va >> 31);
+            acc = madd_packed<F>(acc, A, entry_neg(va));
             va = ib;
-            pa = va & 0x7FFFFFFFu;
+            pa = entry_index(va);
 #pragma unroll
             for (int j = 0; j < NV; j++) A[j] = mont[pa * NV + j];
             ia = idx[k + 3 < last ? k + 3 : last];
-            if (k + 1 < cnt) acc = madd_packed<F>(acc, B, vb >> 31);
+            if (k + 1 < cnt) acc = madd_packed<F>(acc, B, entry_neg(vb));
         }
     }
     buckets[id] = jac_canon(acc);
@@ -398,7 +365,6 @@ template <class F>
 __global__ void __launch_bounds__(256) msm_heavy_kernel(const uint4 *mont, u64 n, int c, const u32 *starts, const u32 *counts,
                                                        const u32 *sorted, HeavyLists hl, jacT<F> *partial) {
     constexpr int NV = FT<F>::WORDS / 2;
-    __shared__ jacT<F> sh[256];
     const uint2 ch = hl.chunks[blockIdx.x];
     const u64 id = ch.x, w = id >> c;
     const u32 cnt = counts[id];
@@ -406,35 +372,22 @@ __global__ void __launch_bounds__(256) msm_heavy_kernel(const uint4 *mont, u64 n
     const u32 *idx = sorted + w * n + starts[id];
     jacT<F> acc = jac_inf<F>();
     for (u32 k = lo + threadIdx.x; k < hi; k += 256) {
-        const u32 vi = idx[k];
-        const u64 pi = vi & 0x7FFFFFFFu;
+        const u32 e = idx[k];
+        const u64 pi = entry_index(e);
         uint4 q[NV];
 #pragma unroll
         for (int j = 0; j < NV; j++) q[j] = mont[pi * NV + j];
-        acc = madd_packed<F>(acc, q, vi >> 31);
+        acc = madd_packed<F>(acc, q, entry_neg(e));
     }
-    sh[threadIdx.x] = jac_canon(acc);
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] = jac_add(sh[threadIdx.x], sh[threadIdx.x + s]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+    block_jac_sum<F, 256>(jac_canon(acc), &partial[blockIdx.x]);
 }
 // one wave per heavy bucket: lane t adds chunk sums t, t+64, ..., LDS tree over the lanes
 template <class F>
-__global__ void __launch_bounds__(64) msm_heavy_combine_kernel(HeavyLists hl, u32 nheavy, const jacT<F> *partial, jacT<F> *buckets) {
-    __shared__ jacT<F> sh[64];
+__global__ void __launch_bounds__(64) msm_heavy_combine_kernel(HeavyLists hl, const jacT<F> *partial, jacT<F> *buckets) {
     const uint4 h = hl.heavy[blockIdx.x];
     jacT<F> acc = jac_inf<F>();
     for (u32 k = threadIdx.x; k < h.z; k += 64) acc = jac_add(acc, partial[h.y + k]);
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 32; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] = jac_add(sh[threadIdx.x], sh[threadIdx.x + s]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) buckets[h.x] = sh[0];
+    block_jac_sum<F, 64>(acc, &buckets[h.x]);
 }
 // ---- 3a. per segment of SEG buckets: sum_{b in seg} (b + 1) * B_b   (bucket index b holds the points of digit magnitude b + 1)
 // (round 6: 16 instead of 64 -- the kernel is one dependent chain of additions per lane with fewer lanes than the chip has SIMD slots:
@@ -460,22 +413,46 @@ __global__ void __launch_bounds__(64) msm_segment_kernel(const jacT<F> *buckets,
 // ---- 3b. tree sum of the segment results of one window (one block per window)
 template <class F>
 __global__ void __launch_bounds__(256) msm_window_kernel(const jacT<F> *segs, int nseg, jacT<F> *wins) {
-    __shared__ jacT<F> sh[256];
     const jacT<F> *S = segs + (u64)blockIdx.x * nseg;
     jacT<F> acc = jac_inf<F>();
     for (int k = threadIdx.x; k < nseg; k += 256) acc = jac_add(acc, S[k]);
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] = jac_add(sh[threadIdx.x], sh[threadIdx.x + s]);
-        __syncthreads();
+    block_jac_sum<F, 256>(acc, &wins[blockIdx.x]);
+}
+
+// ---- host side of one Pippenger run, top to bottom: window width -> sort geometry -> arena plan -> three enqueue stages -> Horner
+// window width (bucket-index bits c) for a run of n points; `knob` > 0 dictates it (zp_set_tuning "msm_c")
+int msm_window_bits(size_t n, int knob) {
+    int c = 4;
+    while (c < 16 && (1ULL << (c + 2)) <= n) c++;   // ~4 points per bucket up to c = 16
+    while (c < 20 && (1ULL << (c + 8)) <= n) c++;   // wider windows only while buckets keep >= 128 points (signed digits: profiles/r2_msm_c_sweep.txt)
+    if (knob > 0) c = knob;                          // experiment knob
+    if (c < 6) c = 6;                                // segments of MSM_SEG buckets (and the sort geometry) need c >= 6
+    if (c > 22) c = 22;
+    return c;
+}
+// c = bucket-index bits of a window; digits are signed and one bit wider (cd = c + 1).  s + K must stay below 2^(cd nwin)
+// for any 256-bit scalar (the BN254 group order has 254 bits): cd * nwin >= 258
+SortGeo msm_sort_geo(int c) {
+    SortGeo g;
+    g.c = c;
+    g.cd = c + 1;
+    g.nwin = (258 + g.cd - 1) / g.cd;
+    g.lo = c < MSM_LO_MAX ? c : MSM_LO_MAX;
+    g.hi = c - g.lo;
+    for (int j = 0; j < 9; j++) g.K[j] = 0;
+    for (int w = 0; w < g.nwin; w++) {
+        const int bit = g.cd * w + g.cd - 1;        // < 288
+        g.K[bit >> 5] |= 1u << (bit & 31);
     }
-    if (threadIdx.x == 0) wins[blockIdx.x] = sh[0];
+    // windows per pass of the tile kernels: counters and bases of a pass, 2 * wgroup * 2^hi words, within 48 KiB of LDS
+    g.wgroup = g.nwin;
+    while ((size_t)g.wgroup * ((size_t)2 << g.hi) * sizeof(u32) > 48 * 1024 && g.wgroup > 1) g.wgroup = (g.wgroup + 1) / 2;
+    return g;
 }
 
 // All scratch of a run comes from ONE ctx-owned arena that only grows: hipMalloc/hipFree of gigabytes per call cost
 // up to 45 ms (more than the 2^22-point run itself) once the process holds other large allocations.
-static int32_t msm_arena(zp_ctx *ctx, size_t bytes, char **out) {
+int32_t msm_arena(zp_ctx *ctx, size_t bytes, char **out) {
     if (ctx->msm_arena_bytes < bytes) {
         if (ctx->msm_arena) {
             ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -489,134 +466,157 @@ static int32_t msm_arena(zp_ctx *ctx, size_t bytes, char **out) {
     *out = (char *)ctx->msm_arena;
     return ZP_OK;
 }
+// carves pieces off one allocation, each at its type's alignment; over a null base it only measures (`at` ends as the size)
+struct Bump {
+    char *base;
+    size_t at = 0;
+    void align(size_t a) { at = (at + a - 1) & ~(a - 1); }
+    template <class T>
+    void take(T *&p, size_t count) {
+        align(alignof(T));
+        p = base ? (T *)(base + at) : nullptr;
+        at += count * sizeof(T);
+    }
+};
+// the arena of one run: ONE list of pieces gives the size (null base) and the pointers.  Six groups, each starting on a 256-byte boundary.
+template <class F>
+struct MsmPlan {
+    size_t n, nb, ncoarse, nseg, max_slices, max_heavy, max_chunks;
+    uint2 *slices;                                   // fine-stage slice list
+    u32 *counts, *starts, *fcursor, *order;          // per bucket: point count, start in `sorted`, scatter cursor | bucket ids by size
+    u32 *ohist;                                      // MSM_OBINS histogram bins of the size ordering, then as many cursors
+    u32 *ccounts, *cstarts, *ccursor, *slice_count;  // per (window, coarse bin), then the length of the slice list: cleared by one memset
+    u32 *sorted, *pidx, *pfine;                      // sorted entries | coarse-partitioned (entry, fine digit) pairs
+    uint4 *mont;                                     // the points in Montgomery form
+    jacT<F> *buckets, *segs, *wins;
+    HeavyLists hl;
+    jacT<F> *partial;                                // chunk sums of the heavy buckets
+    size_t bytes;
+
+    MsmPlan(size_t n_, const SortGeo &g, char *base) : n(n_) {
+        constexpr int NV = FT<F>::WORDS / 2;
+        nb = (size_t)g.nwin << g.c;
+        ncoarse = (size_t)g.nwin << g.hi;
+        nseg = ((size_t)1 << g.c) / MSM_SEG;
+        max_slices = (size_t)g.nwin * n / MSM_FSLICE + ncoarse + 1;
+        max_heavy = (size_t)g.nwin * n / MSM_HEAVY + 1;
+        max_chunks = (size_t)g.nwin * n / MSM_HCHUNK + max_heavy + 1;
+        Bump b{base};
+        b.take(slices, max_slices);                  // the 8-byte piece first: the words behind it need no padding
+        b.take(counts, nb);
+        b.take(starts, nb);
+        b.take(fcursor, nb);
+        b.take(order, nb);
+        b.take(ohist, 2 * MSM_OBINS);
+        b.take(ccounts, ncoarse);
+        b.take(cstarts, ncoarse);
+        b.take(ccursor, ncoarse);
+        b.take(slice_count, 8);                      // (one word used)
+        b.align(256);
+        b.take(sorted, (size_t)g.nwin * n);
+        b.take(pidx, (size_t)g.nwin * n);
+        b.take(pfine, (size_t)g.nwin * n);
+        b.align(256);
+        b.take(mont, n * NV);
+        b.align(256);
+        b.take(buckets, nb);
+        b.take(segs, g.nwin * nseg);
+        b.take(wins, g.nwin);
+        b.align(256);
+        b.take(hl.counters, 4);
+        b.take(hl.heavy, max_heavy);
+        b.take(hl.chunks, max_chunks);
+        b.align(256);
+        b.take(partial, max_chunks);
+        b.align(256);
+        bytes = b.at;
+    }
+};
+
+// The enqueue stages return the first HIP error and launch nothing after it; msm_chunk drains the stream whatever they return.
+#define MSM_HIP(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
+#define MSM_LAUNCH(kernel, grid, block, lds, stream, ...) \
+    do { hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, stream, __VA_ARGS__); MSM_HIP(hipGetLastError()); } while (0)
+inline unsigned blocks_of(size_t items, size_t per_block) { return (unsigned)((items + per_block - 1) / per_block); }
+
+// stage 1: points to Montgomery form; sorted entries, starts and counts per bucket; bucket ids ordered by size
+template <class F>
+hipError_t msm_enqueue_sort(hipStream_t st, const uint32_t *d_points, const u32 *d_scalars, const SortGeo &g, const MsmPlan<F> &p) {
+    const u64 n = p.n;
+    MSM_HIP(hipMemsetAsync(p.ccounts, 0, (size_t)((char *)(p.slice_count + 4) - (char *)p.ccounts), st));   // coarse counters + slice count
+    MSM_LAUNCH(msm_to_mont_kernel<F>, blocks_of(n, 256), 256, 0, st, (const uint4 *)d_points, n, p.mont);
+    const unsigned tiles = blocks_of(n, MSM_TILE);
+    const size_t lds1 = (size_t)g.wgroup * ((size_t)1 << g.hi) * sizeof(u32);
+    for (int w0 = 0; w0 < g.nwin; w0 += g.wgroup) MSM_LAUNCH(msm_coarse_hist_kernel, tiles, 256, lds1, st, d_scalars, n, g, w0, p.ccounts);
+    MSM_LAUNCH(msm_scan_kernel, g.nwin, 1024, 0, st, p.ccounts, p.cstarts, p.ccursor, g.hi);
+    for (int w0 = 0; w0 < g.nwin; w0 += g.wgroup)
+        MSM_LAUNCH(msm_coarse_part_kernel, tiles, 256, 2 * lds1, st, d_scalars, n, g, w0, p.ccursor, p.pidx, p.pfine);
+    // fine stage: slice list on the device, its length read back (one of the two host round trips of a run)
+    MSM_LAUNCH(msm_slices_kernel, blocks_of(p.ncoarse, 256), 256, 0, st, p.ccounts, (u32)p.ncoarse, p.slice_count, p.slices);
+    u32 nslices = 0;
+    MSM_HIP(hipMemcpyAsync(&nslices, p.slice_count, 4, hipMemcpyDeviceToHost, st));
+    MSM_HIP(hipStreamSynchronize(st));
+    MSM_HIP(hipMemsetAsync(p.counts, 0, p.nb * 4, st));
+    if (nslices) MSM_LAUNCH(msm_fine_hist_kernel, nslices, 256, 0, st, p.pfine, n, g, p.slices, p.cstarts, p.ccounts, p.counts);
+    MSM_LAUNCH(msm_fine_scan_kernel, (unsigned)p.ncoarse, 1024, 0, st, g, p.cstarts, p.counts, p.starts, p.fcursor);
+    if (nslices)
+        MSM_LAUNCH(msm_fine_scatter_kernel, nslices, 256, 0, st, p.pidx, p.pfine, n, g, p.slices, p.cstarts, p.ccounts, p.fcursor, p.sorted);
+    MSM_HIP(hipMemsetAsync(p.ohist, 0, 2 * MSM_OBINS * 4, st));
+    MSM_LAUNCH(msm_order_hist_kernel, 256, 256, 0, st, p.counts, p.nb, p.ohist);
+    MSM_LAUNCH(msm_order_scan_kernel, 1, 64, 0, st, p.ohist, p.ohist + MSM_OBINS);
+    MSM_LAUNCH(msm_order_fill_kernel, blocks_of(p.nb, 256), 256, 0, st, p.counts, p.nb, p.ohist + MSM_OBINS, p.order);
+    return hipSuccess;
+}
+// stage 2: bucket sums; the heavy buckets' lists are read back (the second host round trip) and summed by workgroups
+template <class F>
+hipError_t msm_enqueue_buckets(hipStream_t st, const SortGeo &g, const MsmPlan<F> &p) {
+    const u64 n = p.n;
+    MSM_HIP(hipMemsetAsync(p.hl.counters, 0, 16, st));
+    MSM_LAUNCH(msm_bucket_kernel<F>, blocks_of(p.nb, 256), 256, 0, st, p.mont, n, g.c, g.nwin, p.starts, p.counts, p.sorted, p.order, p.buckets, p.hl);
+    u32 hcnt[2] = {0, 0};   // chunks, heavy buckets
+    MSM_HIP(hipMemcpyAsync(hcnt, p.hl.counters, 8, hipMemcpyDeviceToHost, st));
+    MSM_HIP(hipStreamSynchronize(st));
+    if (hcnt[0]) {
+        MSM_LAUNCH(msm_heavy_kernel<F>, hcnt[0], 256, 0, st, p.mont, n, g.c, p.starts, p.counts, p.sorted, p.hl, p.partial);
+        MSM_LAUNCH(msm_heavy_combine_kernel<F>, hcnt[1], 64, 0, st, p.hl, p.partial, p.buckets);
+    }
+    return hipSuccess;
+}
+// stage 3: segment sums, one tree sum per window, the window results to the host (read after the caller's synchronise)
+template <class F>
+hipError_t msm_enqueue_reduce(hipStream_t st, const SortGeo &g, const MsmPlan<F> &p, jacT<F> *h_wins) {
+    MSM_LAUNCH(msm_segment_kernel<F>, blocks_of(g.nwin * p.nseg, 64), 64, 0, st, p.buckets, g.c, g.nwin, p.segs);
+    MSM_LAUNCH(msm_window_kernel<F>, g.nwin, 256, 0, st, p.segs, (int)p.nseg, p.wins);
+    MSM_HIP(hipMemcpyAsync(h_wins, p.wins, g.nwin * sizeof(jacT<F>), hipMemcpyDeviceToHost, st));
+    return hipSuccess;
+}
+// host: sum_w 2^(cd w) * W_w  (Horner from the top window)
+template <class F>
+jacT<F> msm_horner(const std::vector<jacT<F>> &wins, int cd) {
+    jacT<F> acc = jac_inf<F>();
+    for (size_t w = wins.size(); w-- > 0;) {
+        for (int k = 0; k < cd; k++) acc = jac_dbl(acc);
+        acc = jac_add(acc, wins[w]);
+    }
+    return acc;
+}
 
 // one Pippenger run over n points (n <= 2^24 from the entry points): result as a Jacobian point in *out
 template <class F>
 int32_t msm_chunk(zp_ctx *ctx, const uint32_t *d_points, const uint32_t *d_scalars, size_t n, jacT<F> *out) {
-    constexpr int NV = FT<F>::WORDS / 2;
-    using J = jacT<F>;
-    int c = 4;
-    while (c < 16 && (1ULL << (c + 2)) <= n) c++;   // ~4 points per bucket up to c = 16
-    while (c < 20 && (1ULL << (c + 8)) <= n) c++;   // wider windows only while buckets keep >= 128 points (signed digits: profiles/r2_msm_c_sweep.txt)
-    if (ctx->tune_msm_c > 0) c = ctx->tune_msm_c;    // experiment knob
-    if (c < 6) c = 6;                                // segments of MSM_SEG buckets (and the sort geometry) need c >= 6
-    if (c > 22) c = 22;
-    // c = bucket-index bits of a window; digits are signed and one bit wider (cd = c + 1).  s + K must stay below 2^(cd nwin)
-    // for any 256-bit scalar (the BN254 group order has 254 bits): cd * nwin >= 258
-    const int cd = c + 1;
-    const int nwin = (258 + cd - 1) / cd;
-    const u64 nb = (u64)nwin << c;
-    u32 *d_counts = nullptr, *d_starts = nullptr, *d_sorted = nullptr;
-    J *d_buckets = nullptr, *d_segs = nullptr, *d_wins = nullptr;
-    uint4 *d_mont = nullptr;
-    const u64 nseg = (1ULL << c) / MSM_SEG;
-    SortGeo g;
-    g.c = c;
-    g.lo = c < MSM_LO_MAX ? c : MSM_LO_MAX;
-    g.hi = c - g.lo;
-    g.nwin = nwin;
-    g.cd = cd;
-    for (int j = 0; j < 9; j++) g.K[j] = 0;
-    for (int w = 0; w < nwin; w++) {
-        const int bit = cd * w + cd - 1;            // < 288
-        g.K[bit >> 5] |= 1u << (bit & 31);
-    }
-    g.wgroup = nwin;
-    while ((size_t)g.wgroup * ((size_t)2 << g.hi) * sizeof(u32) > 48 * 1024 && g.wgroup > 1) g.wgroup = (g.wgroup + 1) / 2;
-    const u64 ncoarse = (u64)nwin << g.hi;
+    const SortGeo g = msm_sort_geo(msm_window_bits(n, ctx->tune_msm_c));
     ZP_HIP(ctx, hipSetDevice(ctx->device));
-    // arena layout (256-byte aligned pieces): per-bucket counts/starts/cursor | coarse counts/starts/cursor | slice list |
-    // sorted indices + coarse-partitioned (index, fine) pairs | Montgomery points | buckets/segments/windows | heavy lists | chunk sums
-    const u64 max_slices = (u64)nwin * n / MSM_FSLICE + ncoarse + 1;
-    const u64 max_heavy = (u64)nwin * n / MSM_HEAVY + 1, max_chunks = (u64)nwin * n / MSM_HCHUNK + max_heavy + 1;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t sz_counts = al((nb * 4 + 2 * MSM_OBINS + ncoarse * 3 + 8 + max_slices * 2) * 4), sz_sorted = al((u64)nwin * n * 4 * 3),
-                 sz_mont = al((u64)n * NV * 16), sz_buckets = al((nb + nwin * nseg + nwin) * sizeof(J)),
-                 sz_hl = al(16 + max_chunks * sizeof(uint2) + max_heavy * sizeof(uint4)), sz_partial = al(max_chunks * sizeof(J));
     char *arena = nullptr;
-    ZP_TRY(msm_arena(ctx, sz_counts + sz_sorted + sz_mont + sz_buckets + sz_hl + sz_partial, &arena));
-    d_counts = (u32 *)arena;
-    d_sorted = (u32 *)(arena + sz_counts);
-    d_mont = (uint4 *)(arena + sz_counts + sz_sorted);
-    d_buckets = (J *)(arena + sz_counts + sz_sorted + sz_mont);
-    u32 *d_hl = (u32 *)(arena + sz_counts + sz_sorted + sz_mont + sz_buckets);
-    J *d_partial = (J *)(arena + sz_counts + sz_sorted + sz_mont + sz_buckets + sz_hl);
-    d_starts = d_counts + nb;
-    u32 *d_fcursor = d_starts + nb;
-    u32 *d_order = d_fcursor + nb, *d_ohist = d_order + nb;     // bucket ids sorted by size | MSM_OBINS histogram bins, then as many cursors
-    u32 *d_ccounts = d_ohist + 2 * MSM_OBINS, *d_cstarts = d_ccounts + ncoarse, *d_ccursor = d_cstarts + ncoarse;
-    u32 *d_slice_count = d_ccursor + ncoarse;
-    uint2 *d_slices = (uint2 *)(((uintptr_t)(d_slice_count + 4) + 7) & ~(uintptr_t)7);
-    u32 *d_pidx = d_sorted + (u64)nwin * n, *d_pfine = d_pidx + (u64)nwin * n;
-    d_segs = d_buckets + nb;
-    d_wins = d_segs + nwin * nseg;
-    ZP_HIP(ctx, hipMemsetAsync(d_ccounts, 0, (ncoarse * 3 + 4) * 4, ctx->stream));   // coarse counters + slice count
-    const unsigned gb = (unsigned)((n + 255) / 256), gt = (unsigned)((n + MSM_TILE - 1) / MSM_TILE);
-    hipLaunchKernelGGL(msm_to_mont_kernel<F>, dim3(gb), dim3(256), 0, ctx->stream, (const uint4 *)d_points, (u64)n, d_mont);
-    const size_t lds1 = (size_t)g.wgroup * ((size_t)1 << g.hi) * sizeof(u32);
-    for (int w0 = 0; w0 < nwin; w0 += g.wgroup)
-        hipLaunchKernelGGL(msm_coarse_hist_kernel, dim3(gt), dim3(256), lds1, ctx->stream, (const u32 *)d_scalars, (u64)n, g, w0, d_ccounts);
-    hipLaunchKernelGGL(msm_scan_kernel, dim3(nwin), dim3(1024), 0, ctx->stream, d_ccounts, d_cstarts, d_ccursor, g.hi);
-    for (int w0 = 0; w0 < nwin; w0 += g.wgroup)
-        hipLaunchKernelGGL(msm_coarse_part_kernel, dim3(gt), dim3(256), 2 * lds1, ctx->stream, (const u32 *)d_scalars, (u64)n, g, w0,
-                           d_ccursor, d_pidx, d_pfine);
-    // fine stage: slice list on the device, its length read back (one of the two host round trips of a run)
-    hipLaunchKernelGGL(msm_slices_kernel, dim3((unsigned)((ncoarse + 255) / 256)), dim3(256), 0, ctx->stream, d_ccounts, (u32)ncoarse,
-                       d_slice_count, d_slices);
-    u32 nslices = 0;
-    hipError_t he = hipMemcpyAsync(&nslices, d_slice_count, 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
-    if (he == hipSuccess) he = hipMemsetAsync(d_counts, 0, nb * 4, ctx->stream);
-    if (he == hipSuccess && nslices)
-        hipLaunchKernelGGL(msm_fine_hist_kernel, dim3(nslices), dim3(256), 0, ctx->stream, d_pfine, (u64)n, g, d_slices, d_cstarts,
-                           d_ccounts, d_counts);
-    if (he == hipSuccess)
-        hipLaunchKernelGGL(msm_fine_scan_kernel, dim3((unsigned)ncoarse), dim3(1024), 0, ctx->stream, g, d_cstarts, d_counts, d_starts,
-                           d_fcursor);
-    if (he == hipSuccess && nslices)
-        hipLaunchKernelGGL(msm_fine_scatter_kernel, dim3(nslices), dim3(256), 0, ctx->stream, d_pidx, d_pfine, (u64)n, g, d_slices,
-                           d_cstarts, d_ccounts, d_fcursor, d_sorted);
-    if (he == hipSuccess) he = hipMemsetAsync(d_ohist, 0, 2 * MSM_OBINS * 4, ctx->stream);
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(msm_order_hist_kernel, dim3(256), dim3(256), 0, ctx->stream, (const u32 *)d_counts, nb, d_ohist);
-        hipLaunchKernelGGL(msm_order_scan_kernel, dim3(1), dim3(64), 0, ctx->stream, (const u32 *)d_ohist, d_ohist + MSM_OBINS);
-        hipLaunchKernelGGL(msm_order_fill_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, ctx->stream, (const u32 *)d_counts, nb, d_ohist + MSM_OBINS, d_order);
-    }
-    HeavyLists hl;
-    hl.counters = d_hl;
-    hl.heavy = (uint4 *)(d_hl + 4);
-    hl.chunks = (uint2 *)(hl.heavy + max_heavy);
-    ZP_HIP(ctx, hipMemsetAsync(d_hl, 0, 16, ctx->stream));
-    hipLaunchKernelGGL(msm_bucket_kernel<F>, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const uint4 *)d_mont, (u64)n, c, nwin, d_starts, d_counts, d_sorted, (const u32 *)d_order, d_buckets, hl);
-    u32 hcnt[2] = {0, 0};
-    if (he == hipSuccess) he = hipMemcpyAsync(hcnt, d_hl, 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
-    if (he == hipSuccess && hcnt[0]) {
-        {
-            hipLaunchKernelGGL(msm_heavy_kernel<F>, dim3(hcnt[0]), dim3(256), 0, ctx->stream, (const uint4 *)d_mont, (u64)n, c, d_starts,
-                               d_counts, d_sorted, hl, d_partial);
-            hipLaunchKernelGGL(msm_heavy_combine_kernel<F>, dim3(hcnt[1]), dim3(64), 0, ctx->stream, hl, hcnt[1], d_partial,
-                               d_buckets);
-        }
-    }
-    hipLaunchKernelGGL(msm_segment_kernel<F>, dim3((unsigned)((nwin * nseg + 63) / 64)), dim3(64), 0, ctx->stream, d_buckets, c, nwin, d_segs);
-    hipLaunchKernelGGL(msm_window_kernel<F>, dim3(nwin), dim3(256), 0, ctx->stream, d_segs, (int)nseg, d_wins);
-    hipError_t le = hipGetLastError();
-    std::vector<J> wins(nwin);
-    hipError_t ce = hipMemcpyAsync(wins.data(), d_wins, nwin * sizeof(J), hipMemcpyDeviceToHost, ctx->stream);
-    hipError_t se = hipStreamSynchronize(ctx->stream);
-    ZP_HIP(ctx, he);
-    ZP_HIP(ctx, le);
-    ZP_HIP(ctx, ce);
-    ZP_HIP(ctx, se);
-    // host: sum_w 2^(cd*w) * W_w  (Horner from the top window)
-    J acc = jac_inf<F>();
-    for (int w = nwin - 1; w >= 0; w--) {
-        for (int k = 0; k < cd; k++) acc = jac_dbl(acc);
-        acc = jac_add(acc, wins[w]);
-    }
-    *out = acc;
+    ZP_TRY(msm_arena(ctx, MsmPlan<F>(n, g, nullptr).bytes, &arena));
+    const MsmPlan<F> plan(n, g, arena);
+    std::vector<jacT<F>> wins(g.nwin);
+    hipError_t enqueue = msm_enqueue_sort<F>(ctx->stream, d_points, d_scalars, g, plan);
+    if (enqueue == hipSuccess) enqueue = msm_enqueue_buckets<F>(ctx->stream, g, plan);
+    if (enqueue == hipSuccess) enqueue = msm_enqueue_reduce<F>(ctx->stream, g, plan, wins.data());
+    const hipError_t drain = hipStreamSynchronize(ctx->stream);   // also after a failure: the next call reuses the arena
+    ZP_HIP(ctx, enqueue);
+    ZP_HIP(ctx, drain);
+    *out = msm_horner<F>(wins, g.cd);
     return ZP_OK;
 }
 
@@ -627,13 +627,7 @@ int32_t msm_chunk(zp_ctx *ctx, const uint32_t *d_points, const uint32_t *d_scala
 // a Jacobian sum as affine words in the layout of the entry points (standard form; infinity leaves h_out as it is: the callers zero it)
 template <class F>
 void jac_to_words(const jacT<F> &acc, uint32_t *h_out) {
-    if (f_is_zero(acc.Z)) return;  // infinity: all-zero output
-    F zi = f_inv_host(acc.Z);
-    F zi2 = f_sqr(zi);
-    F x = f_from_mont(f_mul(acc.X, zi2));
-    F y = f_from_mont(f_mul(acc.Y, f_mul(zi2, zi)));
-    FT<F>::to_words(x, h_out);
-    FT<F>::to_words(y, h_out + FT<F>::WORDS);
+    if (!f_is_zero(acc.Z)) jac_affine_words(acc, f_inv_host(acc.Z), h_out);
 }
 
 template <class F>
@@ -739,242 +733,4 @@ extern "C" int32_t zp_msm_bn254_sharded(zp_comm *comm, const uint32_t *d_points_
 
 extern "C" int32_t zp_msm_bn254_g2_sharded(zp_comm *comm, const uint32_t *d_points_local, const uint32_t *d_scalars_local, size_t n_total, uint32_t *h_out) {
     return msm_sharded<fq2>(comm, d_points_local, d_scalars_local, n_total, h_out);
-}
-
-// ---- fixed-base multiplication: out_i = s_i * B for ONE base B -- the group elements of a Groth16 key ([u_j(tau)]_1, [v_j(tau)]_2, ...: millions of
-// scalars times the generator; zp_r1cs_key_scalars makes the scalars).  An MSM sums; this does not.  Table T[w][d] = d 2^(8w) B (32 windows of
-// 8 bits, 255 entries each, affine, Montgomery form, built on the host with one batched inversion), lane = scalar: 32 table additions
-// (Jacobian += affine), result stored in Jacobian form; the host turns the results affine with batched inversions on threads (one field
-// inversion per 1 024 points) and writes them in the layout zp_msm_bn254 / _g2 read.  Setup work: run once per key, not per proof.
-namespace {
-
-template <class F>
-__global__ void __launch_bounds__(256) fixed_base_kernel(const uint4 *__restrict__ table, const u32 *__restrict__ scalars, u64 n, jacT<F> *__restrict__ out) {
-    constexpr int NV = FT<F>::WORDS / 2;
-    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    u32 sc[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) sc[k] = scalars[i * 8 + k];
-    jacT<F> acc = jac_inf<F>();
-    for (int w = 0; w < 32; w++) {
-        const u32 d = (sc[w >> 2] >> (8 * (w & 3))) & 255u;
-        if (d == 0) continue;
-        uint4 q[NV];
-        const uint4 *src = table + ((size_t)w * 256 + d) * NV;
-#pragma unroll
-        for (int k = 0; k < NV; k++) q[k] = src[k];
-        F x, y;
-        unpack_point<F>(q, x, y);
-        acc = jac_madd(acc, x, y);
-    }
-    out[i] = acc;
-}
-
-// Jacobian -> affine, standard form, packed words ((0, 0) for the point at infinity): Montgomery's trick over runs of `run` points
-template <class F>
-void batch_to_affine_host(const jacT<F> *pts, size_t n, u32 *out_words, int threads) {
-    constexpr int W2 = 2 * FT<F>::WORDS;
-    const size_t run = 1024, nrun = (n + run - 1) / run;
-    int T = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
-    if (T < 1) T = 1;
-    if (T > 32) T = 32;
-    if ((size_t)T > nrun) T = (int)(nrun ? nrun : 1);
-    auto work = [&](size_t r0, size_t r1) {
-        std::vector<F> pre(run);
-        for (size_t r = r0; r < r1; r++) {
-            const size_t a = r * run, b = a + run < n ? a + run : n;
-            F acc = FT<F>::one();
-            for (size_t i = a; i < b; i++) {
-                pre[i - a] = acc;
-                if (!f_is_zero(pts[i].Z)) acc = f_mul(acc, pts[i].Z);
-            }
-            F inv = f_inv_host(acc);
-            for (size_t i = b; i-- > a;) {
-                u32 *o = out_words + i * W2;
-                if (f_is_zero(pts[i].Z)) { memset(o, 0, W2 * 4); continue; }
-                const F zi = f_mul(inv, pre[i - a]);          // 1 / Z_i
-                inv = f_mul(inv, pts[i].Z);
-                const F zi2 = f_sqr(zi);
-                FT<F>::to_words(f_from_mont(f_mul(pts[i].X, zi2)), o);
-                FT<F>::to_words(f_from_mont(f_mul(pts[i].Y, f_mul(zi2, zi))), o + FT<F>::WORDS);
-            }
-        }
-    };
-    std::vector<std::thread> pool;
-    for (int t = 0; t < T; t++) {
-        const size_t r0 = nrun * t / T, r1 = nrun * (t + 1) / T;
-        if (r0 < r1) pool.emplace_back(work, r0, r1);
-    }
-    for (auto &th : pool) th.join();
-}
-
-template <class F>
-int32_t fixed_base_run(zp_ctx *ctx, const uint32_t *h_base, const uint32_t *h_scalars, size_t n, uint32_t *h_points, int32_t threads) {
-    constexpr int NV = FT<F>::WORDS / 2, W2 = 2 * FT<F>::WORDS;
-    ZP_ARG(ctx, h_base && (n == 0 || (h_scalars && h_points)), "null pointer");
-    if (n == 0) return ZP_OK;
-    F bx = f_to_mont(FT<F>::from_words(h_base)), by = f_to_mont(FT<F>::from_words(h_base + FT<F>::WORDS));
-    ZP_ARG(ctx, !(f_is_zero(bx) && f_is_zero(by)), "the base is the point at infinity");
-    // the table in Jacobian form on the host: T[w][d] = T[w][d - 1] + B_w, B_(w+1) = 256 B_w
-    std::vector<jacT<F>> tab((size_t)32 * 256);
-    jacT<F> bw;
-    bw.X = bx; bw.Y = by; bw.Z = FT<F>::one();
-    for (int w = 0; w < 32; w++) {
-        tab[(size_t)w * 256] = jac_inf<F>();
-        for (int d = 1; d < 256; d++) tab[(size_t)w * 256 + d] = jac_add(tab[(size_t)w * 256 + d - 1], bw);
-        bw = jac_add(tab[(size_t)w * 256 + 255], bw);
-    }
-    std::vector<u32> tw(tab.size() * W2), tm(tab.size() * W2);
-    batch_to_affine_host<F>(tab.data(), tab.size(), tw.data(), threads);
-    for (size_t e = 0; e < tab.size(); e++) {       // back to Montgomery form, the kernel's input (infinity stays (0, 0))
-        FT<F>::to_words(f_to_mont(FT<F>::from_words(&tw[e * W2])), &tm[e * W2]);
-        FT<F>::to_words(f_to_mont(FT<F>::from_words(&tw[e * W2 + FT<F>::WORDS])), &tm[e * W2 + FT<F>::WORDS]);
-    }
-    void *d_tab = nullptr, *d_sc = nullptr, *d_out = nullptr;
-    int32_t rc = zp_dev_alloc(ctx, tm.size() * 4, &d_tab);
-    if (rc == ZP_OK) rc = zp_dev_alloc(ctx, n * 32, &d_sc);
-    if (rc == ZP_OK) rc = zp_dev_alloc(ctx, n * sizeof(jacT<F>), &d_out);
-    if (rc == ZP_OK) rc = zp_h2d(ctx, d_tab, tm.data(), tm.size() * 4);
-    if (rc == ZP_OK) rc = zp_h2d(ctx, d_sc, h_scalars, n * 32);
-    std::vector<jacT<F>> res;
-    if (rc == ZP_OK) {
-        hipLaunchKernelGGL(fixed_base_kernel<F>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint4 *)d_tab, (const u32 *)d_sc, (u64)n,
-                           (jacT<F> *)d_out);
-        if (hipGetLastError() != hipSuccess) { ctx->err = "fixed_base_kernel launch failed"; rc = ZP_ERR_HIP; }
-        (void)NV;
-    }
-    if (rc == ZP_OK) {
-        res.resize(n);
-        rc = zp_d2h(ctx, res.data(), d_out, n * sizeof(jacT<F>));
-    }
-    if (d_tab) (void)zp_dev_free(ctx, d_tab);
-    if (d_sc) (void)zp_dev_free(ctx, d_sc);
-    if (d_out) (void)zp_dev_free(ctx, d_out);
-    if (rc != ZP_OK) return rc;
-    batch_to_affine_host<F>(res.data(), n, h_points, threads);
-    return ZP_OK;
-}
-
-}  // namespace
-
-extern "C" int32_t zp_fixed_base_mul_bn254(zp_ctx *ctx, const uint32_t *h_base, const uint32_t *h_scalars, size_t n, uint32_t *h_points, int32_t threads) {
-    if (!ctx) return ZP_ERR_ARG;
-    ZpStage stage_(ctx, "fixed_base_mul_bn254");
-    try {
-        return fixed_base_run<fq>(ctx, h_base, h_scalars, n, h_points, threads);
-    } catch (...) {
-        ctx->err = "out of host memory";
-        return ZP_ERR_NOMEM;
-    }
-}
-
-extern "C" int32_t zp_fixed_base_mul_bn254_g2(zp_ctx *ctx, const uint32_t *h_base, const uint32_t *h_scalars, size_t n, uint32_t *h_points, int32_t threads) {
-    if (!ctx) return ZP_ERR_ARG;
-    ZpStage stage_(ctx, "fixed_base_mul_bn254_g2");
-    try {
-        return fixed_base_run<fq2>(ctx, h_base, h_scalars, n, h_points, threads);
-    } catch (...) {
-        ctx->err = "out of host memory";
-        return ZP_ERR_NOMEM;
-    }
-}
-
-// ---- synthetic MSM inputs: n DISTINCT points P_i = (start + i) * G of BN254 G1 (host code, this file's own field
-// arithmetic).  Like zp_synth_trace it stands in for data the offline build cannot obtain (a real proving key); distinct
-// points make an MSM benchmark read 64 B per point from HBM instead of hitting a small table in cache, and the known
-// discrete logs give a checkable answer: sum_i s_i P_i = (sum_i s_i (start + i) mod r) * G.
-// Affine chord additions P_base + j*G against a table of 1024 multiples, one batched inversion per block.
-namespace {
-struct affp { fq x, y; };
-affp aff_add_host(const affp &p, const affp &q) {   // p != -q
-    fq num, den;
-    if (fq_eq(p.x, q.x)) {
-        const fq t = fq_sqr(p.x);
-        num = fq_add(fq_add(t, t), t);
-        den = fq_add(p.y, p.y);
-    } else {
-        num = fq_sub(q.y, p.y);
-        den = fq_sub(q.x, p.x);
-    }
-    const fq lam = fq_mul(num, fq_inv_host(den));
-    affp r;
-    r.x = fq_sub(fq_sub(fq_sqr(lam), p.x), q.x);
-    r.y = fq_sub(fq_mul(lam, fq_sub(p.x, r.x)), p.y);
-    return r;
-}
-affp aff_mul_g_host(const affp &g, u64 k) {   // k >= 1
-    affp acc = g, base = g;
-    bool started = false;
-    for (int i = 0; i < 64 && (k >> i); i++) {
-        if ((k >> i) & 1) {
-            acc = started ? aff_add_host(acc, base) : base;
-            started = true;
-        }
-        base = aff_add_host(base, base);
-    }
-    return acc;
-}
-void aff_store(uint32_t *out, const affp &p) {
-    fq_to_words(fq_from_mont(p.x), out);
-    fq_to_words(fq_from_mont(p.y), out + 8);
-}
-}  // namespace
-
-#include <thread>
-extern "C" int32_t zp_synth_g1_points(uint64_t start, size_t n, uint32_t *h_points, int32_t threads) {
-    constexpr int BLK = 1024;
-    if (!h_points || start <= (uint64_t)BLK || start + n < start) return ZP_ERR_ARG;
-    if (n == 0) return ZP_OK;
-    affp g;
-    {
-        fq one = fq_zero(), two = fq_zero();
-        one.l[0] = 1;
-        two.l[0] = 2;
-        g.x = fq_to_mont(one);
-        g.y = fq_to_mont(two);
-    }
-    std::vector<affp> tab(BLK + 1);   // tab[j] = j*G
-    tab[1] = g;
-    for (int j = 2; j <= BLK; j++) tab[j] = aff_add_host(tab[j - 1], g);
-    const size_t nblk = (n + BLK - 1) / BLK;
-    int T = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
-    if (T < 1) T = 1;
-    if ((size_t)T > nblk) T = (int)nblk;
-    auto work = [&](size_t b0, size_t b1) {
-        std::vector<fq> den(BLK), pre(BLK);
-        affp base = aff_mul_g_host(g, start + b0 * BLK);
-        for (size_t b = b0; b < b1; b++) {
-            const size_t cnt = (b + 1) * BLK <= n ? BLK : n - b * BLK;
-            uint32_t *o = h_points + b * BLK * 16;
-            aff_store(o, base);
-            fq acc = fq_one();
-            for (int j = 1; j <= BLK; j++) {
-                den[j - 1] = fq_sub(tab[j].x, base.x);
-                pre[j - 1] = acc;
-                acc = fq_mul(acc, den[j - 1]);
-            }
-            fq inv = fq_inv_host(acc);
-            affp next = base;
-            for (int j = BLK; j >= 1; j--) {
-                const fq dinv = fq_mul(inv, pre[j - 1]);
-                inv = fq_mul(inv, den[j - 1]);
-                if ((size_t)j >= cnt && j != BLK) continue;
-                const fq lam = fq_mul(fq_sub(tab[j].y, base.y), dinv);
-                affp r;
-                r.x = fq_sub(fq_sub(fq_sqr(lam), base.x), tab[j].x);
-                r.y = fq_sub(fq_mul(lam, fq_sub(base.x, r.x)), base.y);
-                if (j == BLK) next = r;
-                if ((size_t)j < cnt) aff_store(o + (size_t)j * 16, r);
-            }
-            base = next;
-        }
-    };
-    std::vector<std::thread> pool;
-    for (int t = 0; t < T; t++) {
-        const size_t b0 = nblk * t / T, b1 = nblk * (t + 1) / T;
-        if (b0 < b1) pool.emplace_back(work, b0, b1);
-    }
-    for (auto &th : pool) th.join();
-    return ZP_OK;
 }

@@ -1,4 +1,4 @@
-"""zp_fixed_base_mul_bn254(_g2) -- the group elements of a Groth16 key from its scalars (csrc/msm.hip: 8-bit window table of one base point,
+"""zp_fixed_base_mul_bn254(_g2) -- the group elements of a Groth16 key from its scalars (csrc/fixed_base.hip: 8-bit window table of one base point,
 32 table additions per scalar on the GPU, batched inversions on host threads) -- against the double-and-add definition
 (oracle/naive_bn254.py) and, at size, against the library's own MSM: sum_i w_i (s_i G) = (sum_i w_i s_i) G."""
 import numpy as np

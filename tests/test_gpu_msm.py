@@ -174,7 +174,7 @@ def _scalar_rows(scs):
 
 
 def _width_for(n):
-    """the window width msm_chunk picks for n points (its two loops and its floor of 6)"""
+    """the window width msm_window_bits (csrc/msm.hip) picks for n points (its two loops and its floor of 6)"""
     c = 4
     while c < 16 and (1 << (c + 2)) <= n:
         c += 1
@@ -261,9 +261,10 @@ def _sum_per_point(idx, scs, ntable):
     return per
 
 
-@pytest.mark.parametrize("c", [6, 7, 10, 11, 16, 17])
+@pytest.mark.parametrize("c", [6, 7, 10, 11, 16, 17, 19, 20])
 def test_msm_signed_digit_extremes_in_every_window(prover, table, c):
-    """17 is the width of a 2^24-point run"""
+    """17 is the width of a 2^24-point run;  19 | 20: the 13 windows no longer fit the LDS budget of the tile kernels and are walked in passes of
+    wgroup windows -- 7 and a ragged 6 at c = 19 (hi = 9), 4, 4, 4 and 1 at c = 20 (hi = 10)"""
     scs = signed_digit_scalars(c)
     rnd = random.Random(c)
     idx = [rnd.randrange(len(table)) for _ in scs]
