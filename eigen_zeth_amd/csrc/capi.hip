@@ -485,6 +485,7 @@ int32_t zp_set_tuning(zp_ctx *ctx, const char *key, int32_t value) {
     else if (!strcmp(key, "merkle_coop_log")) ctx->tune_merkle_coop_log = value;
     else if (!strcmp(key, "p254_bulk_log")) ctx->tune_p254_bulk_log = value;
     else if (!strcmp(key, "verify_lane_min")) ctx->tune_verify_lane_min = value;
+    else if (!strcmp(key, "verify16_lane_min")) ctx->tune_verify16_lane_min = value;
     else { ctx->err = "unknown tuning key"; return ZP_ERR_ARG; }
     return ZP_OK;
 }

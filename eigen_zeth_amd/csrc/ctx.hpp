@@ -99,6 +99,7 @@ struct zp_ctx {
     int tune_p254_bulk_log = 0;   // 0 = 14: Poseidon-BN254 t = 17 launches of >= 2^14 permutations use the lane-per-permutation kernel (31 = never)
     int tune_msm_c = 0;           // 0 = window width chosen from n
     int tune_verify_lane_min = 0;   // 0 = 256: zp_merkle_verify_batch / zp_stark_verify* use the lane-per-opening kernel from this many openings per call on (fewer: the 12-lane walk kernel).  256 (four full waves) is A GUESS until tools/verify_measure.py has run on the device: unmeasured
+    int tune_verify16_lane_min = 0; // 0 = 2^14 JOBS (one permutation chain each): zp_merkle16_verify_batch_bn254 / zp_stark_verify*_bn128 hash one job per lane (state in LDS) from this many jobs per call on (fewer: 17 lanes per job).  2^14 is where the lane form wins for commitments: for openings A GUESS until tools/verify_bn128_measure.py has run on the device: unmeasured
     int tune_msm_chunk_log = 0;   // 0 = default (2^24 points per Pippenger run)
     // zp_stark_prove: device buffers kept between proofs (chunk after chunk has the same shapes; hipMalloc / hipFree of ~20 buffers
     // cost milliseconds per proof) and the LDE of the two boundary selectors per (logn, logb, shift, root)
@@ -198,10 +199,17 @@ int32_t zpi_poseidon_openings_walk(zp_ctx *ctx, const u64 *d_op, const u64 *d_va
                                    size_t count, u64 *d_inputs, u64 *d_digests);
 // one Merkle opening a verifier checks: `width` leaf values, `depth` siblings of four words (bottom-up), the leaf's position, and which of the
 // caller's roots it must hash to.  Host pointers; the words are canonical (the caller reduces what it read from a text)
-struct ZpOpening { const u64 *values, *path; u64 index; uint32_t width, depth, root_slot; };
+// A 16-ary Poseidon-BN254 opening (csrc/poseidon_bn254.hip) uses the same record: `path` is [depth][16][4] raw words (the whole group of every level),
+// `depth` the number of levels above `leaves` leaves (which need not be a power of 16), the root one element of four words
+struct ZpOpening { const u64 *values, *path; u64 index; uint32_t width, depth, root_slot; u64 leaves; };
 // ok[o] = 1 iff opening o hashes to roots[4 * root_slot ..): every opening of a call in ONE launch (csrc/poseidon.hip).  Openings of one
 // (width, depth) should be adjacent: a wave then walks one tree shape
 int32_t zpi_merkle_verify_openings(zp_ctx *ctx, const ZpOpening *ops, size_t n, const u64 *h_roots, size_t n_roots, uint8_t *ok);
+// the same for 16-ary Poseidon-BN254 openings: every hash of every opening is one JOB (a leaf chain, or one level's group), all jobs of a call in ONE
+// launch; ok[o] = the AND of opening o's jobs.  Widths, level counts and indices are validated here, before the launch
+int32_t zpi_merkle16_verify_openings_bn254(zp_ctx *ctx, const ZpOpening *ops, size_t n, const u64 *h_roots, size_t n_roots, uint8_t *ok);
+// the t = 17 tables installed on the ctx's device as the host verifier takes them: Montgomery limbs, rc [(8 + rp) * 17][9], mds [17 * 17][9]
+int32_t zpi_p254_host_tables(zp_ctx *ctx, std::vector<u32> *rc, std::vector<u32> *mds, int *rp);
 // run the transform on W columns; in/out column strides are 2^logn (or in_valid for zero-padded input)
 struct NttRunOpts {
     const CosetTable *post_scale = nullptr;  // multiply output i by table(i) (last pass)

@@ -252,3 +252,18 @@ GL_HD bool fr_is_canonical_u64(const u64 *w) {   // value < r
     }
     return false;
 }
+// One sponge block of a 16-ary tree's leaf absorbs up to 56 Goldilocks values in its 16 rate elements: element k holds values base + 3k .. 3k+2 in
+// bits 0..191 and, in bits 192..223, 32-bit half number k of values base + 48 .. base + 55 (half 2i = low word of value 48 + i, half
+// 2i + 1 = its high word).  Below 2^224 < r.  Rows of at most 48 values pack as three per element.  (oracle/naive.py: pack_leaf_block)
+// The ONE statement of the rule: the committing kernels read row i of cols[W][M], a verifier the row it was handed (M = 1, i = 0), on the
+// device (csrc/poseidon_bn254.hip) and on the host (csrc/verify.hip).
+GL_HD void leaf_block_element(const u64 *__restrict__ cols, size_t M, size_t i, int W, int base, int k, u64 *w) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) w[c] = (base + 3 * k + c < W) ? cols[(size_t)(base + 3 * k + c) * M + i] : 0ULL;
+    const int x = base + 48 + (k >> 1);
+    w[3] = 0;
+    if (x < W) {
+        const u64 v = cols[(size_t)x * M + i];
+        w[3] = (k & 1) ? (v >> 32) : (v & 0xFFFFFFFFULL);
+    }
+}

@@ -53,6 +53,25 @@ struct Cur {
         *out = v;
         return digits > 0;
     }
+    // a field element of a BN128-mode text: a QUOTED decimal in the strict grammar its prover writes (one or more digits, no sign, no leading
+    // zero except "0") into four little-endian words.  A string of any length is read to its end: a value >= 2^256 becomes all ones, which
+    // is >= r and so equals nothing
+    bool dec256(uint64_t w[4]) {
+        ws();
+        if (p >= end || *p != '"') { ok = false; return false; }
+        const char *b = ++p;
+        bool over = false;
+        w[0] = w[1] = w[2] = w[3] = 0;
+        for (; p < end && *p >= '0' && *p <= '9'; p++) {
+            unsigned __int128 c = (unsigned)(*p - '0');
+            for (int k = 0; k < 4; k++) { c += (unsigned __int128)w[k] * 10; w[k] = (uint64_t)c; c >>= 64; }
+            over |= c != 0;
+        }
+        if (p == b || (p - b > 1 && *b == '0') || p >= end || *p != '"') { ok = false; return false; }
+        p++;
+        if (over) w[0] = w[1] = w[2] = w[3] = ~(uint64_t)0;
+        return true;
+    }
     void skip_value(int depth = 0) {          // any JSON value
         ws();
         if (!ok || p >= end || depth > 64) { ok = false; return; }

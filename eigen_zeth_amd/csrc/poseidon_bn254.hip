@@ -245,20 +245,7 @@ __device__ __forceinline__ fr perm_coop(fr s, int q, int e, bool on, u32 (*sh)[T
 }
 
 // ---- bulk form, t = 17: ONE LANE PER PERMUTATION (launches of >= 2^14 permutations: the Merkle commitments of the final STARK).
-// One sponge block of a leaf absorbs up to 56 Goldilocks values in its 16 rate elements: element k holds values base + 3k .. 3k+2 in
-// bits 0..191 and, in bits 192..223, 32-bit half number k of values base + 48 .. base + 55 (half 2i = low word of value 48 + i, half
-// 2i + 1 = its high word).  Below 2^224 < r.  Rows of at most 48 values pack as three per element.  (oracle/naive.py: pack_leaf_block)
-__device__ __forceinline__ void leaf_block_element(const u64 *__restrict__ cols, size_t M, size_t i, int W, int base, int k, u64 *w) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) w[c] = (base + 3 * k + c < W) ? cols[(size_t)(base + 3 * k + c) * M + i] : 0ULL;
-    const int x = base + 48 + (k >> 1);
-    w[3] = 0;
-    if (x < W) {
-        const u64 v = cols[(size_t)x * M + i];
-        w[3] = (k & 1) ? (v >> 32) : (v & 0xFFFFFFFFULL);
-    }
-}
-
+// (the packing of a leaf's sponge block -- 56 Goldilocks values in 16 rate elements -- is leaf_block_element of csrc/fr254.hpp)
 // The cooperative form above gives a wave three permutations (51 of 64 lanes) and makes the whole wave walk the three dependent
 // products of the ONE S-box of a partial round: 5 product steps per lane and round for 36 field products per permutation.  Here every
 // lane does exactly the products of its own permutation.  The 17-element state lives in LDS ([element][limb][lane]: conflict-free,
@@ -667,6 +654,96 @@ __global__ void __launch_bounds__(256) merkle16_paths_kernel(const u64 *__restri
     out[i] = c < n ? tree[(off + c) * 4 + word] : 0ULL;
 }
 
+// ---- the openings of a verifier (zp_merkle16_verify_batch_bn254, zp_stark_verify*_bn128): a 16-ary path carries the whole group of every level, so
+// the hashes of one opening are INDEPENDENT -- level l's permutation reads only the text's group l, and its digest is compared with the text's entry of
+// group l + 1 (or the root).  A call is flattened into JOBS: per opening one leaf chain (ceil(width / 56) permutations, the digest as the next
+// capacity) and one job per level; every job of every opening, tree, query and proof of the call runs in ONE launch, and the flag of an opening
+// is the AND of its jobs (a failing job clears it; the host set it).  A job checks: every word of its group < r, children beyond the level's
+// size zero (nvalid), and its digest against its target -- the slot match of the next level, or the root comparison.  The host sized and validated
+// every field of a job record: no loop bound here comes from a text.
+struct Verify16Job {
+    u64 src;          // leaf chain: first value in vals;  level: group number in grps
+    u64 target;       // the element (four words) the digest must equal: in grps, or with to_root in roots
+    u32 width;        // leaf chain: values in the leaf (>= 1);  level: 0
+    u32 nvalid;       // level: children the level has in this group (1 .. 16)
+    u32 opening, to_root;
+};
+// element k (0 .. 15) of block b of a job as four standard words, and whether the checks on it hold (a failing element hashes as zero)
+__device__ __forceinline__ bool verify16_element(const Verify16Job &jb, int b, int k, const u64 *__restrict__ vals, const u64 *__restrict__ grps, u64 *w) {
+    if (jb.width) {
+        leaf_block_element(vals + jb.src, 1, 0, (int)jb.width, 56 * b, k, w);
+        return true;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) w[i] = grps[(jb.src * 16 + k) * 4 + i];
+    const bool good = fr_is_canonical_u64(w) && (k < (int)jb.nvalid || (w[0] | w[1] | w[2] | w[3]) == 0);
+    if (!good) w[0] = w[1] = w[2] = w[3] = 0;
+    return good;
+}
+__device__ __forceinline__ bool verify16_digest_ok(const Verify16Job &jb, const fr &mont, const u64 *__restrict__ grps, const u64 *__restrict__ roots) {
+    u64 w[4];
+    fr_to_u64(fr_from_mont(mont), w);
+    const u64 *t = (jb.to_root ? roots : grps) + jb.target * 4;
+    return w[0] == t[0] && w[1] == t[1] && w[2] == t[2] && w[3] == t[3];
+}
+__device__ __forceinline__ int verify16_blocks(u32 width) { return width ? (int)((width + 55) / 56) : 1; }
+
+// 17 lanes per job, three jobs per wave (perm_coop): the latency form.  perm_coop holds barriers, so the three jobs of a workgroup walk the longest
+// chain among them together (the host puts the leaf chains first, tree by tree: neighbours have one length)
+__global__ void __launch_bounds__(64) verify16_coop_kernel(const Verify16Job *__restrict__ jobs, size_t njobs, const u64 *__restrict__ vals, const u64 *__restrict__ grps,
+                                                           const u64 *__restrict__ roots, u32 *__restrict__ ok, P254Dev d) {
+    constexpr int T = 17, PPW = 3;
+    __shared__ u32 sh[PPW][T][9];
+    const int q = threadIdx.x / T, e = threadIdx.x % T;
+    const size_t j0 = (size_t)blockIdx.x * PPW, j = j0 + q;
+    const bool on = q < PPW && j < njobs;
+    int nblk = 1;
+    for (int k = 0; k < PPW; k++)
+        if (j0 + k < njobs) { const int nb = verify16_blocks(jobs[j0 + k].width); nblk = nb > nblk ? nb : nblk; }
+    const Verify16Job jb = jobs[on ? j : j0];
+    const int mine = verify16_blocks(jb.width);
+    fr s = fr_zero();                                  // capacity 0
+    bool good = true;
+    for (int b = 0; b < nblk; b++) {
+        const bool act = on && b < mine;
+        if (act && e >= 1) {
+            u64 w[4];
+            good &= verify16_element(jb, b, e - 1, vals, grps, w);
+            s = fr_to_mont(fr_from_u64(w));
+        }
+        s = perm_coop<T>(s, q, e, act, sh, d);          // lane e = 0 keeps the digest: the capacity of the next block
+    }
+    if (on && e == 0) good = verify16_digest_ok(jb, s, grps, roots);
+    if (on && !good) atomicAnd(&ok[jb.opening], 0u);
+}
+
+// one lane per job, the state in LDS (bulk_perm17: 39 KiB per 64-lane workgroup, four workgroups per CU -- the form's occupancy limit, which this
+// kernel adds nothing to): the throughput form.  No barriers: a lane walks its own chain
+__global__ void __launch_bounds__(64) verify16_bulk_kernel(const Verify16Job *__restrict__ jobs, size_t njobs, const u64 *__restrict__ vals, const u64 *__restrict__ grps,
+                                                           const u64 *__restrict__ roots, u32 *__restrict__ ok, P254Dev d) {
+    __shared__ u32 st_mem[P254_BULK_LDS];
+    lu32 *const st = (lu32 *)st_mem;
+    const int lane = threadIdx.x;
+    const size_t j = (size_t)blockIdx.x * 64 + lane;
+    if (j >= njobs) return;
+    const Verify16Job jb = jobs[j];
+    const int nblk = verify16_blocks(jb.width);
+    bool good = true;
+    lds_put(st, 0, lane, fr_zero());
+#pragma unroll 1
+    for (int b = 0; b < nblk; b++) {
+#pragma unroll 1
+        for (int e = 1; e < 17; e++) {
+            u64 w[4];
+            good &= verify16_element(jb, b, e - 1, vals, grps, w);
+            lds_put(st, e, lane, fr_to_mont(fr_from_u64(w)));
+        }
+        bulk_perm17<true>(st, lane, d);                 // the digest (element 0) stays as the capacity of the next block
+    }
+    good &= verify16_digest_ok(jb, lds_get(st, 0, lane), grps, roots);
+    if (!good) atomicAnd(&ok[jb.opening], 0u);
+}
+
 int32_t table_for(zp_ctx *ctx, int t, const P254Table **out) {
     ZP_ARG(ctx, t == 3 || t == 17, "Poseidon-BN254 width must be 3 or 17");
     const P254Table *tb = table_of(ctx, t == 3 ? 0 : 1);
@@ -1011,6 +1088,28 @@ int32_t zp_merkle16_open_batch_bn254(zp_ctx *ctx, const uint64_t *d_tree, size_t
     return ZP_OK;
 }
 
+// the device primitive of the BN128-mode verifier on its own: n openings into ONE 16-ary tree of M leaves (zp_merkle16_commit_bn254's)
+int32_t zp_merkle16_verify_batch_bn254(zp_ctx *ctx, const uint64_t *h_values, size_t width, const uint64_t *h_index, const uint64_t *h_paths, size_t M,
+                                       const uint64_t *h_root4, size_t n, uint8_t *h_ok) {
+    if (!ctx) return ZP_ERR_ARG;
+    ZpStage stage_(ctx, "merkle16_verify_batch_bn254");
+    ZP_ARG(ctx, h_values && h_index && h_root4 && h_ok && M >= 1 && width >= 1 && width < (1u << 16) && n < (1u << 24), "bad arguments");
+    uint32_t levels = 0;
+    for (size_t m = M; m > 1; m = (m + 15) / 16) levels++;
+    ZP_ARG(ctx, h_paths || !levels || !n, "null paths");
+    try {
+        std::vector<ZpOpening> ops(n);
+        for (size_t o = 0; o < n; o++) ops[o] = {(const u64 *)h_values + o * width, levels ? (const u64 *)h_paths + o * levels * 64 : nullptr, h_index[o] < M ? h_index[o] : 0, (uint32_t)width, levels, 0u, (u64)M};
+        ZP_TRY(zpi_merkle16_verify_openings_bn254(ctx, ops.data(), n, (const u64 *)h_root4, 1, h_ok));
+        for (size_t o = 0; o < n; o++)
+            if (h_index[o] >= M) h_ok[o] = 0;              // an index beyond the tree is no opening of it
+        return ZP_OK;
+    } catch (const std::bad_alloc &) {
+        ctx->err = "out of host memory";
+        return ZP_ERR_NOMEM;
+    }
+}
+
 }  // extern "C"
 
 // the levels above n digests that already lie at the head of d_tree (u64[zp_merkle16_nodes(n)][4]): what zp_merkle16_commit_bn254 runs after its
@@ -1032,6 +1131,80 @@ int32_t zpi_merkle16_levels_bn254(zp_ctx *ctx, u64 *d_tree, size_t n) {
         off += n;
         n = nn;
     }
+    return ZP_OK;
+}
+
+// the installed t = 17 tables for the host side of the BN128-mode verifier (csrc/verify.hip): the Montgomery words zp_set_poseidon_bn254 kept
+int32_t zpi_p254_host_tables(zp_ctx *ctx, std::vector<u32> *rc, std::vector<u32> *mds, int *rp) {
+    const P254Table *tb;
+    ZP_TRY(table_for(ctx, 17, &tb));
+    std::lock_guard<std::mutex> lk(g_tables_mu);
+    const std::vector<u32> &key = g_installed[ctx->device][1];       // rc | mds | rp
+    const size_t nm = (size_t)17 * 17 * 9;
+    *rp = (int)key.back();
+    rc->assign(key.begin(), key.end() - 1 - nm);
+    mds->assign(key.end() - 1 - nm, key.end() - 1);
+    return ZP_OK;
+}
+
+// Every hash of every opening of a call in one launch (the kernels above).  From `verify16_lane_min` JOBS on the lane-per-job kernel, below it 17 lanes
+// per job; the same flags either way (tests/test_gpu_stark_verify_bn128.py forces each through the knob).  One buffer, one upload, one launch, one
+// download: [jobs][roots][values][groups][flags (u32 per opening, set here, cleared by a failing job)].
+int32_t zpi_merkle16_verify_openings_bn254(zp_ctx *ctx, const ZpOpening *ops, size_t n, const u64 *h_roots, size_t n_roots, uint8_t *ok) {
+    if (!n) return ZP_OK;
+    const P254Table *tb;
+    ZP_TRY(table_for(ctx, 17, &tb));
+    ZP_ARG(ctx, ops && h_roots && ok && n < (1u << 24) && n_roots >= 1 && n_roots < (1u << 24), "bad openings");
+    size_t nv = 0, ng = 0, njobs = 0;
+    for (size_t o = 0; o < n; o++) {
+        int levels = 0;
+        for (u64 m = ops[o].leaves; m > 1; m = (m + 15) / 16) levels++;
+        ZP_ARG(ctx, ops[o].values && (ops[o].path || !ops[o].depth) && ops[o].width >= 1 && ops[o].width < (1u << 16) && ops[o].leaves >= 1 &&
+                        ops[o].leaves <= ((u64)1 << 40) && ops[o].index < ops[o].leaves && ops[o].depth == (u32)levels && ops[o].root_slot < n_roots,
+               "opening out of range");
+        nv += ops[o].width; ng += ops[o].depth; njobs += 1 + ops[o].depth;
+    }
+    static_assert(sizeof(Verify16Job) == 32, "job records are four words");
+    const size_t o_roots = 4 * njobs, o_vals = o_roots + 4 * n_roots, o_grps = o_vals + nv, o_ok = o_grps + 64 * ng, total = o_ok + (n + 1) / 2;
+    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (an earlier small copy may still read the staging buffer)
+    void *stv = nullptr;
+    ZP_TRY(zpi_pinned(ctx, total * 8, &stv));
+    u64 *buf = (u64 *)stv;
+    Verify16Job *jobs = (Verify16Job *)buf;
+    u32 *flags = (u32 *)(buf + o_ok);
+    memcpy(buf + o_roots, h_roots, 32 * n_roots);
+    // leaf chains first, in the caller's order (tree by tree: neighbours have one width), then the levels
+    size_t v_at = 0, g_at = 0, lj = n;
+    for (size_t o = 0; o < n; o++) {
+        const ZpOpening &op = ops[o];
+        memcpy(buf + o_vals + v_at, op.values, 8 * (size_t)op.width);
+        if (op.depth) memcpy(buf + o_grps + 64 * g_at, op.path, 512 * (size_t)op.depth);
+        flags[o] = 1;
+        // the digest of the leaf, then of level l, must sit at slot pos_l % 16 of group l, the last one be the root
+        jobs[o] = {(u64)v_at, op.depth ? (g_at * 16 + op.index % 16) : (u64)op.root_slot, op.width, 0u, (u32)o, op.depth ? 0u : 1u};
+        u64 m = op.leaves, pos = op.index;
+        for (u32 l = 0; l < op.depth; l++, m = (m + 15) / 16, pos /= 16) {
+            const u64 g0 = (pos / 16) * 16, have = m - g0 < 16 ? m - g0 : 16;
+            const bool last = l + 1 == op.depth;
+            jobs[lj++] = {(u64)(g_at + l), last ? (u64)op.root_slot : ((g_at + l + 1) * 16 + (pos / 16) % 16), 0u, (u32)have, (u32)o, last ? 1u : 0u};
+        }
+        v_at += op.width; g_at += op.depth;
+    }
+    if (n & 1) flags[n] = 0;
+    u64 *dbuf = nullptr;
+    ZP_TRY(zpi_scratch(ctx, 3, total, &dbuf));
+    ZP_HIP(ctx, hipMemcpyAsync(dbuf, buf, total * 8, hipMemcpyHostToDevice, ctx->stream));
+    const bool lane_form = njobs >= (size_t)(ctx->tune_verify16_lane_min > 0 ? ctx->tune_verify16_lane_min : (1 << 14));      // 2^14: unmeasured for openings (ctx.hpp)
+    if (lane_form)
+        hipLaunchKernelGGL(verify16_bulk_kernel, dim3((unsigned)((njobs + 63) / 64)), dim3(64), 0, ctx->stream, (const Verify16Job *)dbuf, njobs, dbuf + o_vals, dbuf + o_grps,
+                           dbuf + o_roots, (u32 *)(dbuf + o_ok), dev_of(ctx, tb));
+    else
+        hipLaunchKernelGGL(verify16_coop_kernel, dim3((unsigned)((njobs + 2) / 3)), dim3(64), 0, ctx->stream, (const Verify16Job *)dbuf, njobs, dbuf + o_vals, dbuf + o_grps,
+                           dbuf + o_roots, (u32 *)(dbuf + o_ok), dev_of(ctx, tb));
+    ZP_HIP(ctx, hipGetLastError());
+    ZP_HIP(ctx, hipMemcpyAsync(buf + o_ok, dbuf + o_ok, (total - o_ok) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t o = 0; o < n; o++) ok[o] = flags[o] ? 1 : 0;
     return ZP_OK;
 }
 

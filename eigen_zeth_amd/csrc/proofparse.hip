@@ -19,10 +19,12 @@ using zpjson::each_member;
 
 constexpr int MAX_TREES = 48;
 
-struct Sizes { int n_queries = 0, has_stage2 = 0, n_fri = 0, w[MAX_TREES] = {}, d[MAX_TREES] = {}; };
+struct Sizes { int n_queries = 0, has_stage2 = 0, n_fri = 0, w[MAX_TREES] = {}, d[MAX_TREES] = {}; bool bn = false; };
 
-// one opening {"values":[..],"path":[[4]..]}: counts (vals == nullptr) or writes
-bool opening(Cur &c, int *w, int *depth, uint64_t *vals, uint64_t *path) {
+// one opening {"values":[..],"path":[[4]..]}: counts (vals == nullptr) or writes.  bn (BN128-hash mode): a path entry is the group of a level of the
+// 16-ary tree, 16 quoted field elements of four words each ([levels][16][4] in the output)
+bool opening(Cur &c, bool bn, int *w, int *depth, uint64_t *vals, uint64_t *path) {
+    const int per = bn ? 16 : 4, ew = bn ? 4 : 1;
     int nw = 0, nd = 0;
     bool got_v = false, got_p = false;
     each_member(c, [&](const char *b, const char *e) {
@@ -47,11 +49,11 @@ bool opening(Cur &c, int *w, int *depth, uint64_t *vals, uint64_t *path) {
             if (!c.eat(']'))
                 for (;;) {
                     if (!c.need('[')) return;
-                    for (int k = 0; k < 4; k++) {
-                        uint64_t v;
-                        if (!c.u64v(&v)) return;
-                        if (path) { if (nd >= *depth) { c.ok = false; return; } path[4 * nd + k] = v; }
-                        if (k < 3 && !c.need(',')) return;
+                    for (int k = 0; k < per; k++) {
+                        uint64_t v[4];
+                        if (!(bn ? c.dec256(v) : c.u64v(v))) return;
+                        if (path) { if (nd >= *depth) { c.ok = false; return; } memcpy(path + ((size_t)per * nd + k) * ew, v, 8 * (size_t)ew); }
+                        if (k < per - 1 && !c.need(',')) return;
                     }
                     if (!c.need(']')) return;
                     nd++;
@@ -81,9 +83,9 @@ bool query(Cur &c, Sizes &sz, bool first, uint64_t *index, uint64_t **vals, uint
                 // write mode: only the trees the caller sized exist (their pointers are the only initialised ones)
                 if (t >= 2 + sz.has_stage2 + sz.n_fri) { c.ok = false; return; }
                 int w = sz.w[t], d = sz.d[t];
-                opening(c, &w, &d, vals[t], paths[t]);
+                opening(c, sz.bn, &w, &d, vals[t], paths[t]);
             }
-            else opening(c, &me.w[t], &me.d[t], nullptr, nullptr);
+            else opening(c, sz.bn, &me.w[t], &me.d[t], nullptr, nullptr);
         };
         const int tq = vals ? 1 + sz.has_stage2 : 2;        // while sizing, slot 1 is kept free for a stage-2 opening (compacted below)
         auto once = [&](bool &got) { if (got) c.ok = false; got = true; return c.ok; };   // a repeated key is an error in both passes
@@ -130,6 +132,11 @@ bool query(Cur &c, Sizes &sz, bool first, uint64_t *index, uint64_t **vals, uint
 
 }  // namespace
 
+int32_t zpi_proof_queries_scan(const char *text, size_t len, size_t *q_begin, size_t *q_end, int32_t *n_queries, int32_t *has_stage2, int32_t *n_fri,
+                               int32_t *widths, int32_t *depths, int32_t max_trees, bool bn);
+int32_t zpi_proof_queries_parse(const char *text, size_t q_begin, size_t q_end, int32_t n_queries, int32_t has_stage2, int32_t n_fri,
+                                const int32_t *widths, const int32_t *depths, uint64_t *index, uint64_t *values, uint64_t *paths, bool bn);
+
 extern "C" {
 
 // [begin, end) of the VALUE of member `key` of the JSON object that starts at text[0 ..): ZP_OK, or ZP_ERR_ARG when the text is not an
@@ -153,11 +160,28 @@ int32_t zp_json_key_span(const char *text, size_t len, const char *key, size_t *
 // this grammar.
 int32_t zp_proof_queries_scan(const char *text, size_t len, size_t *q_begin, size_t *q_end, int32_t *n_queries, int32_t *has_stage2, int32_t *n_fri,
                               int32_t *widths, int32_t *depths, int32_t max_trees) {
+    return zpi_proof_queries_scan(text, len, q_begin, q_end, n_queries, has_stage2, n_fri, widths, depths, max_trees, false);
+}
+
+// The openings themselves.  index u64[nq]; values: per tree t a block u64[nq][w_t], blocks one after the other; paths: per tree a block
+// u64[nq][d_t][4].  The sizes are those zp_proof_queries_scan reported for this text.
+int32_t zp_proof_queries_parse(const char *text, size_t q_begin, size_t q_end, int32_t n_queries, int32_t has_stage2, int32_t n_fri,
+                               const int32_t *widths, const int32_t *depths, uint64_t *index, uint64_t *values, uint64_t *paths) {
+    return zpi_proof_queries_parse(text, q_begin, q_end, n_queries, has_stage2, n_fri, widths, depths, index, values, paths, false);
+}
+
+}  // extern "C"
+
+// The two passes with the hash mode as a parameter (csrc/verify.hip reads both modes through these).  bn: the paths are those of the 16-ary
+// Poseidon-BN254 trees -- per level the 16 quoted field elements of the group -- and a path block is u64[nq][d_t][16][4].
+int32_t zpi_proof_queries_scan(const char *text, size_t len, size_t *q_begin, size_t *q_end, int32_t *n_queries, int32_t *has_stage2, int32_t *n_fri,
+                               int32_t *widths, int32_t *depths, int32_t max_trees, bool bn) {
     if (!text || !q_begin || !q_end || !n_queries || !has_stage2 || !n_fri || !widths || !depths) return ZP_ERR_ARG;
     size_t b = 0, e = 0;
     if (zp_json_key_span(text, len, "queries", &b, &e) != ZP_OK) return ZP_ERR_ARG;
     Cur c{text + b, text + e};
     Sizes sz;
+    sz.bn = bn;
     int nq = 0;
     if (!c.need('[')) return ZP_ERR_ARG;
     if (!c.eat(']'))
@@ -175,15 +199,14 @@ int32_t zp_proof_queries_scan(const char *text, size_t len, size_t *q_begin, siz
     return ZP_OK;
 }
 
-// The openings themselves.  index u64[nq]; values: per tree t a block u64[nq][w_t], blocks one after the other; paths: per tree a block
-// u64[nq][d_t][4].  The sizes are those zp_proof_queries_scan reported for this text.
-int32_t zp_proof_queries_parse(const char *text, size_t q_begin, size_t q_end, int32_t n_queries, int32_t has_stage2, int32_t n_fri,
-                               const int32_t *widths, const int32_t *depths, uint64_t *index, uint64_t *values, uint64_t *paths) {
+int32_t zpi_proof_queries_parse(const char *text, size_t q_begin, size_t q_end, int32_t n_queries, int32_t has_stage2, int32_t n_fri,
+                                const int32_t *widths, const int32_t *depths, uint64_t *index, uint64_t *values, uint64_t *paths, bool bn) {
+    const size_t pw = bn ? 64 : 4;                         // words per path entry
     if (!text || !widths || !depths || !index || !values || !paths || n_queries < 1 || q_end <= q_begin || n_fri < 0) return ZP_ERR_ARG;
     const int T = 2 + (has_stage2 ? 1 : 0) + n_fri;
     if (T > MAX_TREES) return ZP_ERR_ARG;
     Sizes sz;
-    sz.n_queries = n_queries; sz.has_stage2 = has_stage2 ? 1 : 0; sz.n_fri = n_fri;
+    sz.n_queries = n_queries; sz.has_stage2 = has_stage2 ? 1 : 0; sz.n_fri = n_fri; sz.bn = bn;
     uint64_t *vb[MAX_TREES] = {}, *pb[MAX_TREES] = {};
     size_t vo = 0, po = 0;
     for (int t = 0; t < T; t++) {
@@ -191,17 +214,15 @@ int32_t zp_proof_queries_parse(const char *text, size_t q_begin, size_t q_end, i
         sz.w[t] = widths[t]; sz.d[t] = depths[t];
         vb[t] = values + vo; pb[t] = paths + po;
         vo += (size_t)n_queries * widths[t];
-        po += (size_t)n_queries * depths[t] * 4;
+        po += (size_t)n_queries * depths[t] * pw;
     }
     Cur c{text + q_begin, text + q_end};
     if (!c.need('[')) return ZP_ERR_ARG;
     for (int q = 0; q < n_queries; q++) {
         uint64_t *v[MAX_TREES] = {}, *p[MAX_TREES] = {};
-        for (int t = 0; t < T; t++) { v[t] = vb[t] + (size_t)q * sz.w[t]; p[t] = pb[t] + (size_t)q * sz.d[t] * 4; }
+        for (int t = 0; t < T; t++) { v[t] = vb[t] + (size_t)q * sz.w[t]; p[t] = pb[t] + (size_t)q * sz.d[t] * pw; }
         if (!query(c, sz, false, index + q, v, p)) return ZP_ERR_ARG;
         if (q + 1 < n_queries && !c.need(',')) return ZP_ERR_ARG;
     }
     return c.need(']') ? ZP_OK : ZP_ERR_ARG;
 }
-
-}  // extern "C"

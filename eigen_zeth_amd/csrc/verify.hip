@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "fr254.hpp"
 #include "jsoncur.hpp"
 #include "sha256.hpp"
 #include "poseidon_default_table.inc"      // ctx = NULL verifies with the library's default tables
@@ -24,13 +25,13 @@
 // What the verifier takes from other translation units, as WEAK references: this file is also built on its own as plain C++ under the host
 // sanitizers (tests/test_verify_fuzz.py, tests/test_r1cs_fuzz.py link it without the rest of the library).  The openings of a text are read by
 // csrc/proofparse.hip (absent: only ZP_VERIFY_HEADER_ONLY can be served); the device side is csrc/poseidon.hip (absent: only ctx = NULL).
-extern "C" {
-int32_t zp_proof_queries_scan(const char *text, size_t len, size_t *q_begin, size_t *q_end, int32_t *n_queries, int32_t *has_stage2, int32_t *n_fri, int32_t *widths,
-                              int32_t *depths, int32_t max_trees) __attribute__((weak));
-int32_t zp_proof_queries_parse(const char *text, size_t q_begin, size_t q_end, int32_t n_queries, int32_t has_stage2, int32_t n_fri, const int32_t *widths,
-                               const int32_t *depths, uint64_t *index, uint64_t *values, uint64_t *paths) __attribute__((weak));
-}
+extern int32_t zpi_proof_queries_scan(const char *text, size_t len, size_t *q_begin, size_t *q_end, int32_t *n_queries, int32_t *has_stage2, int32_t *n_fri, int32_t *widths,
+                                      int32_t *depths, int32_t max_trees, bool bn) __attribute__((weak));
+extern int32_t zpi_proof_queries_parse(const char *text, size_t q_begin, size_t q_end, int32_t n_queries, int32_t has_stage2, int32_t n_fri, const int32_t *widths,
+                                       const int32_t *depths, uint64_t *index, uint64_t *values, uint64_t *paths, bool bn) __attribute__((weak));
 extern int32_t zpi_merkle_verify_openings(zp_ctx *ctx, const ZpOpening *ops, size_t n, const u64 *h_roots, size_t n_roots, uint8_t *ok) __attribute__((weak));
+extern int32_t zpi_merkle16_verify_openings_bn254(zp_ctx *ctx, const ZpOpening *ops, size_t n, const u64 *h_roots, size_t n_roots, uint8_t *ok) __attribute__((weak));
+extern int32_t zpi_p254_host_tables(zp_ctx *ctx, std::vector<u32> *rc, std::vector<u32> *mds, int *rp) __attribute__((weak));
 
 namespace {
 
@@ -252,8 +253,12 @@ int32_t zp_program_fixed_eval_ext(const uint64_t *h_program, size_t program_word
 }  // extern "C"
 
 // ================================================================================================================================
-// The STARK verifier (Goldilocks-hash mode) behind zp_stark_verify / zp_stark_verify_batch: what a host that was handed a chunk proof as
-// TEXT asks before it spends anything on it.  The protocol is stark/prover.py's; the checks and their order are restated here from the
+// The STARK verifier behind zp_stark_verify / zp_stark_verify_batch (Goldilocks-hash mode) and zp_stark_verify_bn128 / zp_stark_verify_batch_bn128
+// (BN128-hash mode: the final STARK of GenFinalProof): what a host that was handed a proof as TEXT asks before it spends anything on it.
+// The hash mode is a PARAMETER of the one header phase and the one query phase below.  What BN128 mode changes: roots and path words are quoted
+// field elements of F_r (a root >= r is MALFORMED, a path word >= r equals nothing), the transcript is the width-17 sponge (HostSponge254), a long
+// public-input vector is committed by the 16-ary tree over rows of 48, a committed leaf holds 2^g rows, and an opening carries the whole group of
+// every level (HostPoseidon254::opening_ok; on a ctx csrc/poseidon_bn254.hip: zpi_merkle16_verify_openings_bn254).  No grinding in that mode.  The protocol is stark/prover.py's; the checks and their order are restated here from the
 // protocol (the CPU checker's independent statement of the same is oracle/stark_verify.py -- the tests run the two side by side).
 // Everything in this file is host code: the header of the text, the transcript (a textbook-schedule Poseidon, the only host one in the
 // product), the identity at zeta, the final layer's degree, the DEEP sum and every fold at every query.  The one O(openings) part -- the
@@ -315,14 +320,23 @@ struct HostPoseidon {
 
 // stark/transcript.py: absorb queues; a squeeze first absorbs the queue in blocks of 8 that overwrite the rate (one permutation when nothing is
 // queued), then hands out the rate
-struct HostSponge {
+struct Transcript {                            // what the header phase asks of either mode's sponge
+    virtual void absorb(const u64 *v, size_t n) = 0;
+    virtual void absorb_root(const u64 *root4) = 0;      // Goldilocks mode: four elements; BN128 mode: one element of F_r in four words, < r
+    virtual void squeeze(size_t n, u64 *out) = 0;
+    virtual ~Transcript() {}
+    e3 challenge() { u64 c[3]; squeeze(3, c); return e3_make(c[0], c[1], c[2]); }
+};
+
+struct HostSponge : Transcript {
     const HostPoseidon &H;
     u64 st[12] = {0};
     std::vector<u64> q;
     int pos = 8;
     explicit HostSponge(const HostPoseidon &h) : H(h) {}
-    void absorb(const u64 *v, size_t n) { for (size_t i = 0; i < n; i++) q.push_back(gl_canon(v[i])); pos = 8; }
-    void squeeze(size_t n, u64 *out) {
+    void absorb(const u64 *v, size_t n) override { for (size_t i = 0; i < n; i++) q.push_back(gl_canon(v[i])); pos = 8; }
+    void absorb_root(const u64 *root4) override { absorb(root4, 4); }
+    void squeeze(size_t n, u64 *out) override {
         for (size_t k = 0; k < n; k++) {
             if (!q.empty() || pos == 8) {
                 if (q.empty()) H.perm(st);
@@ -336,8 +350,128 @@ struct HostSponge {
             out[k] = st[pos++];
         }
     }
-    e3 challenge() { u64 c[3]; squeeze(3, c); return e3_make(c[0], c[1], c[2]); }
 };
+
+// ---- BN128-hash mode on the host: the product's only host Poseidon-BN254 (t = 17), a textbook-schedule permutation over csrc/fr254.hpp (the device
+// kernels walk the sparse form of the same map: csrc/poseidon_bn254.hip); tables in Montgomery limbs, as zp_set_poseidon_bn254 keeps them
+inline int levels16(u64 n) { int l = 0; for (; n > 1; n = (n + 15) / 16) l++; return l; }
+struct HostPoseidon254 {
+    int rp = 0;
+    std::vector<u32> rc, mds;                  // [(8 + rp) * 17][9], [17 * 17][9]
+    static fr limbs(const u32 *p) { fr x; memcpy(x.l, p, 36); return x; }
+    void perm(fr *s) const {                   // ARK -> S-box -> matrix (a row: 6 + 6 + 5 products, one reduction each), 4 + rp + 4 rounds
+        for (int r = 0; r < 8 + rp; r++) {
+            const bool full = r < 4 || r >= 4 + rp;
+            for (int i = 0; i < 17; i++) {
+                fr x = fr_add(s[i], limbs(&rc[((size_t)r * 17 + i) * 9]));
+                if (full || i == 0) { const fr x2 = fr_sqr(x), x4 = fr_sqr(x2); x = fr_mul(x4, x); }
+                s[i] = x;
+            }
+            fr o[17];
+            for (int i = 0; i < 17; i++) {
+                const u32 *row = &mds[(size_t)i * 17 * 9];
+                o[i] = fr_add(fr_add(fr_dotc<6>(s, row), fr_dotc<6>(s + 6, row + 6 * 9)), fr_dotc<5>(s + 12, row + 12 * 9));
+            }
+            memcpy(s, o, sizeof o);
+        }
+    }
+    // the digest of [0 | 16 elements of four standard words each, < r]
+    void node(const u64 *grp64, u64 *out4) const {
+        fr s[17];
+        s[0] = fr_zero();
+        for (int k = 0; k < 16; k++) s[1 + k] = fr_to_mont(fr_from_u64(grp64 + 4 * k));
+        perm(s);
+        fr_to_u64(fr_from_mont(s[0]), out4);
+    }
+    // the leaf hash of zp_merkle16_commit_bn254: a sponge over blocks of 56 values (leaf_block_element), the digest so far as the next capacity
+    void leaf(const u64 *v, size_t w, u64 *out4) const {
+        fr s[17];
+        s[0] = fr_zero();
+        for (size_t base = 0; base < w || base == 0; base += 56) {
+            for (int k = 0; k < 16; k++) {
+                u64 x[4];
+                leaf_block_element(v, 1, 0, (int)w, (int)base, k, x);
+                s[1 + k] = fr_to_mont(fr_from_u64(x));
+            }
+            perm(s);
+        }
+        fr_to_u64(fr_from_mont(s[0]), out4);
+    }
+    // per level: every word of the group < r, the digest so far at the group's slot pos % 16, children beyond the level's size zero, the next digest
+    // the permutation of [0, group]; after the last level the digest is the root.  (width, depth = level count and index were validated by the caller)
+    bool opening_ok(const ZpOpening &op, const u64 *root4) const {
+        u64 cur[4];
+        leaf(op.values, op.width, cur);
+        u64 n = op.leaves, pos = op.index;
+        for (uint32_t l = 0; l < op.depth; l++, n = (n + 15) / 16, pos /= 16) {
+            const u64 *grp = op.path + 64 * (size_t)l, g0 = (pos / 16) * 16;
+            for (int c = 0; c < 16; c++) {
+                if (!fr_is_canonical_u64(grp + 4 * c)) return false;
+                if (g0 + c >= n && (grp[4 * c] | grp[4 * c + 1] | grp[4 * c + 2] | grp[4 * c + 3])) return false;
+            }
+            if (memcmp(grp + 4 * (pos % 16), cur, 32) != 0) return false;
+            node(grp, cur);
+        }
+        return memcmp(cur, root4, 32) == 0;
+    }
+};
+
+// oracle/stark_verify.py SpongeBN128 (stark/transcript.py TranscriptBN128): element 0 = capacity, 1..16 = rate.  Goldilocks values go three to an
+// element (each absorb padded separately), a root is one element; a squeeze absorbs the queue in blocks of 16 that overwrite the rate (one permutation
+// when nothing is queued) and hands out the three low 64-bit words of each rate element mod p
+struct HostSponge254 : Transcript {
+    const HostPoseidon254 &H;
+    fr st[17];
+    std::vector<u64> q;                        // four words per queued element
+    u64 avail[48];
+    int pos = 48;
+    explicit HostSponge254(const HostPoseidon254 &h) : H(h) { for (fr &x : st) x = fr_zero(); }
+    void absorb(const u64 *v, size_t n) override {
+        for (size_t i = 0; i < n; i += 3) {
+            for (size_t c = 0; c < 3; c++) q.push_back(i + c < n ? gl_canon(v[i + c]) : 0);
+            q.push_back(0);
+        }
+        pos = 48;
+    }
+    void absorb_root(const u64 *root4) override { q.insert(q.end(), root4, root4 + 4); pos = 48; }
+    void squeeze(size_t n, u64 *out) override {
+        for (size_t k = 0; k < n; k++) {
+            if (!q.empty() || pos == 48) {
+                if (q.empty()) H.perm(st);
+                for (size_t off = 0; off < q.size(); off += 64) {
+                    for (size_t j = 0; j < 16; j++) st[1 + j] = off + 4 * j < q.size() ? fr_to_mont(fr_from_u64(&q[off + 4 * j])) : fr_zero();
+                    H.perm(st);
+                }
+                q.clear();
+                for (int e = 0; e < 16; e++) {
+                    u64 w[4];
+                    fr_to_u64(fr_from_mont(st[1 + e]), w);
+                    for (int c = 0; c < 3; c++) avail[3 * e + c] = gl_canon(w[c]);
+                }
+                pos = 0;
+            }
+            out[k] = avail[pos++];
+        }
+    }
+};
+
+// the same commitment in BN128 mode (publics_rows: rows of 48 values, three to an element, >= 1 row; the 16-ary tree of zp_merkle16_commit_bn254)
+void publics_digest_host254(const HostPoseidon254 &H, const std::vector<u64> &pubs, u64 *out4) {
+    size_t n = (pubs.size() + 47) / 48;
+    n = n ? n : 1;
+    std::vector<u64> lvl(4 * n), row(48);
+    for (size_t r = 0; r < n; r++) {
+        for (size_t j = 0; j < 48; j++) row[j] = 48 * r + j < pubs.size() ? pubs[48 * r + j] : 0;
+        H.leaf(row.data(), 48, &lvl[4 * r]);
+    }
+    for (; n > 1; n = (n + 15) / 16)
+        for (size_t r = 0; r < (n + 15) / 16; r++) {
+            u64 grp[64] = {0};
+            memcpy(grp, &lvl[64 * r], 32 * (16 * r + 16 <= n ? 16 : n - 16 * r));
+            H.node(grp, &lvl[4 * r]);
+        }
+    memcpy(out4, lvl.data(), 32);
+}
 
 // the commitment a long public-input vector enters the transcript as (stark/prover.py publics_rows: rows of 8, zero padded, 2^k >= 2 rows)
 void publics_digest_host(const HostPoseidon &H, const std::vector<u64> &pubs, u64 *out4) {
@@ -365,7 +499,7 @@ struct ProofHeader {
     std::string hash = "gl", digest;
     std::vector<u64> pubs, root[3], ev_z, ev_zw, fri_roots;
     std::vector<std::vector<u64>> final_l;
-    bool rows_ok = true;                       // every row of the evaluations has 3 words, every root 4
+    bool rows_ok = true;                       // every row of the evaluations has 3 words, every root 4 (BN128 mode: one quoted element, kept as its 4 words)
 };
 const char *const PARAM_KEYS[ProofHeader::NPARAM] = {"logn", "logb", "fri_logf", "fri_final_log", "n_queries", "pow_bits"};
 
@@ -382,6 +516,24 @@ bool u64_list(Cur &c, std::vector<u64> *out) {
         return c.need(']');
     }
 }
+// BN128 mode: a root, ["<decimal>"] -- one quoted element, kept as four words (anything else in the list clears *rows_ok; a plain number is read so
+// that a Goldilocks-mode text reaches the check of its hash mode)
+bool fr_root(Cur &c, std::vector<u64> *out, bool *rows_ok) {
+    if (!c.need('[')) return false;
+    size_t count = 0;
+    if (!c.eat(']'))
+        for (;;) {
+            uint64_t w[4] = {0, 0, 0, 0};
+            if (c.peek('"')) { if (!c.dec256(w)) return false; }
+            else { if (!c.u64v(w)) return c.ok = false; *rows_ok = false; }
+            if (count++ == 0) out->insert(out->end(), w, w + 4);
+            if (c.eat(',')) continue;
+            if (!c.need(']')) return false;
+            break;
+        }
+    if (count != 1) { *rows_ok = false; out->resize(out->size() + (count ? 0 : 4), 0); }
+    return true;
+}
 // [[..],[..]]: rows of `row` words each, flattened (another row length clears *rows_ok)
 bool u64_rows(Cur &c, size_t row, std::vector<u64> *out, bool *rows_ok) {
     if (!c.need('[')) return false;
@@ -395,7 +547,7 @@ bool u64_rows(Cur &c, size_t row, std::vector<u64> *out, bool *rows_ok) {
     }
 }
 
-bool parse_header(const char *text, size_t len, ProofHeader *h) {
+bool parse_header(const char *text, size_t len, bool bn, ProofHeader *h) {
     Cur c{text, text + len};
     const bool ok = each_member(c, [&](const char *b, const char *e) {
         if (c.key_is(b, e, "params")) {
@@ -422,7 +574,9 @@ bool parse_header(const char *text, size_t len, ProofHeader *h) {
             each_member(c, [&](const char *kb, const char *ke) {
                 const int t = c.key_is(kb, ke, "trace") ? 0 : c.key_is(kb, ke, "stage2") ? 1 : c.key_is(kb, ke, "quotient") ? 2 : -1;
                 if (t < 0) { c.skip_value(); return; }
-                if (once(c, h->has_root[t]) && u64_list(c, &h->root[t]) && h->root[t].size() != 4) h->rows_ok = false;
+                if (!once(c, h->has_root[t])) return;
+                if (bn) fr_root(c, &h->root[t], &h->rows_ok);
+                else if (u64_list(c, &h->root[t]) && h->root[t].size() != 4) h->rows_ok = false;
             });
         } else if (c.key_is(b, e, "evals")) {
             each_member(c, [&](const char *kb, const char *ke) {
@@ -432,7 +586,17 @@ bool parse_header(const char *text, size_t len, ProofHeader *h) {
             });
         } else if (c.key_is(b, e, "fri")) {
             each_member(c, [&](const char *kb, const char *ke) {
-                if (c.key_is(kb, ke, "roots")) { if (once(c, h->has_fri_roots)) u64_rows(c, 4, &h->fri_roots, &h->rows_ok); }
+                if (c.key_is(kb, ke, "roots")) {
+                    if (!once(c, h->has_fri_roots)) return;
+                    if (!bn) { u64_rows(c, 4, &h->fri_roots, &h->rows_ok); return; }
+                    if (!c.need('[') || c.eat(']')) return;
+                    for (;;) {
+                        if (!fr_root(c, &h->fri_roots, &h->rows_ok)) return;
+                        if (c.eat(',')) continue;
+                        c.need(']');
+                        return;
+                    }
+                }
                 else if (c.key_is(kb, ke, "final")) {
                     if (!once(c, h->has_final) || !c.need('[')) return;
                     if (c.eat(']')) return;
@@ -477,7 +641,7 @@ void intt_unscaled(std::vector<u64> &a, int lg, u64 root32) {
     }
 }
 
-struct VerifyParams { int logn, logb, fri_logf, fri_final_log, n_queries, pow_bits; uint32_t flags; int threads; u64 root32, shift; };
+struct VerifyParams { int logn, logb, fri_logf, fri_final_log, n_queries, pow_bits; uint32_t flags; int threads; u64 root32, shift; const HostPoseidon254 *H254; };      // H254: BN128-hash mode
 struct ProgramInfo { const uint64_t *words; size_t n_words; size_t W, W2, n_pub, n_chal, K, Q, n_s2; char digest_hex[17]; u64 digest_words[4]; };
 
 // one proof between the header checks and the verdict: what the query phase needs
@@ -485,7 +649,8 @@ struct Pending {
     int verdict = ZP_VERDICT_ACCEPT, where = -1;
     bool queries_live = false;                 // the header passed and there are openings to check
     std::vector<u64> qidx, index, values, paths, roots;      // roots: 4 words per tree (raw: a word >= p matches no digest)
-    std::vector<int32_t> widths, depths;
+    std::vector<int32_t> widths, depths, grp;  // per tree: leaf width, path entries, log2 of the rows a leaf holds (BN128 mode groups the committed trees' leaves)
+    std::vector<u64> leaves;                   // per tree: its leaf count (a power of two)
     std::vector<size_t> voff, poff;            // where tree t's block starts in values / paths
     std::vector<std::pair<int, int>> sched;    // (log size of the layer, log fold factor)
     std::vector<u64> ev_z, ev_zw, final_raw;   // canonical evaluations; the final layer as the text has it, plane-major
@@ -500,14 +665,15 @@ struct Pending {
 int32_t header_phase(const char *text, size_t len, const ProgramInfo &pg, const VerifyParams &vp, const HostPoseidon &H, Pending *pd) {
     auto verdict = [&](int v) { pd->verdict = v; return ZP_OK; };
     ProofHeader h;
-    if (!parse_header(text, len, &h)) return verdict(ZP_VERDICT_MALFORMED);
+    const bool bn = vp.H254 != nullptr;
+    if (!parse_header(text, len, bn, &h)) return verdict(ZP_VERDICT_MALFORMED);
     // 1. parameters, domain, statement, counts
     const u64 want[ProofHeader::NPARAM] = {(u64)vp.logn, (u64)vp.logb, (u64)vp.fri_logf, (u64)vp.fri_final_log, (u64)vp.n_queries, (u64)vp.pow_bits};
     if (!h.has_params) return verdict(ZP_VERDICT_MALFORMED);
     for (int i = 0; i < ProofHeader::NPARAM; i++)
         if (!h.has_param[i] || h.param[i] != want[i]) return verdict(ZP_VERDICT_PARAMS);
-    if (h.hash == "bn128") return ZP_ERR_UNSUPPORTED;
-    if (h.hash != "gl") return verdict(ZP_VERDICT_PARAMS);
+    if (!bn && h.hash == "bn128") return ZP_ERR_UNSUPPORTED;
+    if (h.hash != (bn ? "bn128" : "gl")) return verdict(ZP_VERDICT_PARAMS);
     if (!h.has_root32 || !h.has_shift || !h.has_digest || !h.has_pubs) return verdict(ZP_VERDICT_MALFORMED);
     if (h.root32 != vp.root32 || h.shift != vp.shift) return verdict(ZP_VERDICT_PARAMS);
     if (h.digest != pg.digest_hex) return verdict(ZP_VERDICT_PARAMS);
@@ -517,27 +683,36 @@ int32_t header_phase(const char *text, size_t len, const ProgramInfo &pg, const 
     const size_t W = pg.W, W2 = pg.W2, Wt = W + W2, Q = pg.Q, nq = (size_t)vp.n_queries;
     const u64 M = (u64)1 << logm;
     for (u64 &v : h.pubs) v = gl_canon(v);
-    // the transcript
-    HostSponge tr(H);
+    // the transcript (head and inline public inputs are ONE absorb: BN128 mode packs three values to an element per absorb)
+    HostSponge tr_gl(H);
+    static const HostPoseidon254 no_tables;
+    HostSponge254 tr_bn(bn ? *vp.H254 : no_tables);
+    Transcript &tr = bn ? (Transcript &)tr_bn : (Transcript &)tr_gl;
+    auto root_ok = [&](const u64 *r) { return !bn || fr_is_canonical_u64(r); };      // "malformed BN128 root"
     {
         std::vector<u64> head = {(u64)logn, (u64)logb, (u64)W, (u64)W2, (u64)vp.fri_logf, (u64)vp.fri_final_log, (u64)vp.n_queries, (u64)vp.pow_bits, vp.root32, vp.shift,
                                  pg.digest_words[0], pg.digest_words[1], pg.digest_words[2], pg.digest_words[3], (u64)h.pubs.size()};
+        if (h.pubs.size() <= 64) head.insert(head.end(), h.pubs.begin(), h.pubs.end());      // PUBLICS_INLINE
         tr.absorb(head.data(), head.size());
-        if (h.pubs.size() <= 64) tr.absorb(h.pubs.data(), h.pubs.size());      // PUBLICS_INLINE
-        else { u64 dg[4]; publics_digest_host(H, h.pubs, dg); tr.absorb(dg, 4); }
+        if (h.pubs.size() > 64) {
+            u64 dg[4];
+            if (bn) publics_digest_host254(*vp.H254, h.pubs, dg); else publics_digest_host(H, h.pubs, dg);
+            tr.absorb_root(dg);
+        }
     }
     if (!h.has_root[0] || !h.has_root[2] || !h.rows_ok) return verdict(ZP_VERDICT_MALFORMED);
-    tr.absorb(h.root[0].data(), 4);
+    if (!root_ok(h.root[0].data()) || !root_ok(h.root[2].data()) || (pg.n_s2 && h.has_root[1] && !root_ok(h.root[1].data()))) return verdict(ZP_VERDICT_MALFORMED);
+    tr.absorb_root(h.root[0].data());
     std::vector<u64> pubchal = h.pubs;
     if (pg.n_s2) {
         if (!h.has_root[1]) return verdict(ZP_VERDICT_MALFORMED);
         u64 ch[3];
         tr.squeeze(3, ch);
         pubchal.insert(pubchal.end(), ch, ch + 3);
-        tr.absorb(h.root[1].data(), 4);
+        tr.absorb_root(h.root[1].data());
     }
     const e3 alpha = tr.challenge();
-    tr.absorb(h.root[2].data(), 4);
+    tr.absorb_root(h.root[2].data());
     const e3 zeta = tr.challenge();
     if (!h.has_z || !h.has_zw || h.ev_z.size() != 3 * (Wt + 3 * Q) || h.ev_zw.size() != 3 * Wt) return verdict(ZP_VERDICT_MALFORMED);
     for (u64 &v : h.ev_z) v = gl_canon(v);
@@ -578,7 +753,9 @@ int32_t header_phase(const char *text, size_t len, const ProgramInfo &pg, const 
     const int final_log = cur;
     const size_t n_fri = pd->sched.size();
     if (!h.has_fri_roots || !h.has_final || h.fri_roots.size() != 4 * n_fri) return verdict(ZP_VERDICT_MALFORMED);
-    for (size_t l = 0; l < n_fri; l++) { tr.absorb(&h.fri_roots[4 * l], 4); pd->betas.push_back(tr.challenge()); }
+    for (size_t l = 0; l < n_fri; l++)
+        if (!root_ok(&h.fri_roots[4 * l])) return verdict(ZP_VERDICT_MALFORMED);
+    for (size_t l = 0; l < n_fri; l++) { tr.absorb_root(&h.fri_roots[4 * l]); pd->betas.push_back(tr.challenge()); }
     if (h.final_l.size() != 3) return verdict(ZP_VERDICT_MALFORMED);
     for (int c = 0; c < 3; c++)
         if (h.final_l[c].size() != ((size_t)1 << final_log)) return verdict(ZP_VERDICT_MALFORMED);
@@ -601,17 +778,17 @@ int32_t header_phase(const char *text, size_t len, const ProgramInfo &pg, const 
     size_t q_begin = 0, q_end = 0;
     int32_t nq_text = 0, has_s2 = 0, nf_text = 0, widths[48], depths[48];
     if (!header_only) {
-        if (!zp_proof_queries_scan || !zp_proof_queries_parse) return ZP_ERR_UNSUPPORTED;
-        if (!h.has_queries || zp_proof_queries_scan(text, len, &q_begin, &q_end, &nq_text, &has_s2, &nf_text, widths, depths, 48) != ZP_OK) return verdict(ZP_VERDICT_MALFORMED);
+        if (!zpi_proof_queries_scan || !zpi_proof_queries_parse) return ZP_ERR_UNSUPPORTED;
+        if (!h.has_queries || zpi_proof_queries_scan(text, len, &q_begin, &q_end, &nq_text, &has_s2, &nf_text, widths, depths, 48, bn) != ZP_OK) return verdict(ZP_VERDICT_MALFORMED);
         if ((size_t)nq_text != nq) return verdict(ZP_VERDICT_INDICES);
         // every size below counts numbers that stand in the text; n_queries is the verifier's own
         const int T = 2 + has_s2 + nf_text;
         size_t nv = 0, np = 0;
         pd->widths.assign(widths, widths + T); pd->depths.assign(depths, depths + T);
-        for (int t = 0; t < T; t++) { pd->voff.push_back(nv); pd->poff.push_back(np); nv += nq * (size_t)widths[t]; np += nq * (size_t)depths[t] * 4; }
+        for (int t = 0; t < T; t++) { pd->voff.push_back(nv); pd->poff.push_back(np); nv += nq * (size_t)widths[t]; np += nq * (size_t)depths[t] * (bn ? 64 : 4); }
         pd->index.resize(nq); pd->values.resize(nv ? nv : 1); pd->paths.resize(np ? np : 1);
-        if (zp_proof_queries_parse(text, q_begin, q_end, nq_text, has_s2, nf_text, widths, depths, (uint64_t *)pd->index.data(), (uint64_t *)pd->values.data(),
-                                   (uint64_t *)pd->paths.data()) != ZP_OK)
+        if (zpi_proof_queries_parse(text, q_begin, q_end, nq_text, has_s2, nf_text, widths, depths, (uint64_t *)pd->index.data(), (uint64_t *)pd->values.data(),
+                                    (uint64_t *)pd->paths.data(), bn) != ZP_OK)
             return verdict(ZP_VERDICT_MALFORMED);
         if (pd->index != pd->qidx) return verdict(ZP_VERDICT_INDICES);
         pd->T = T;
@@ -625,16 +802,27 @@ int32_t header_phase(const char *text, size_t len, const ProgramInfo &pg, const 
             if (cf[i]) return verdict(ZP_VERDICT_FINAL_DEGREE);
     }
     if (header_only) return verdict(ZP_VERDICT_ACCEPT);
-    // the shape of the openings: trace, [stage 2], quotient, one per FRI layer
+    // the shape of the openings: trace, [stage 2], quotient, one per FRI layer.  BN128 mode: a committed leaf holds 2^g rows (stark/prover.py
+    // bn128_rows_per_leaf_log: the largest g with width 2^g <= 56 values that leaves the tree 16 leaves), FRI leaves are not grouped, and a path has
+    // ceil(log16) entries.  Checked before anything is hashed
     {
         const bool s2 = pg.n_s2 != 0;
         if ((has_s2 != 0) != s2 || (size_t)nf_text != n_fri) return verdict(ZP_VERDICT_MALFORMED);
-        std::vector<std::pair<size_t, int>> want_t = {{W, logm}};
-        if (s2) want_t.push_back({W2, logm});
-        want_t.push_back({3 * Q, logm});
-        for (auto &lf : pd->sched) want_t.push_back({(size_t)3 << lf.second, lf.first - lf.second});
-        for (int t = 0; t < pd->T; t++)
-            if ((size_t)widths[t] != want_t[t].first || depths[t] != want_t[t].second) return verdict(ZP_VERDICT_MALFORMED);
+        auto committed = [&](size_t w) {
+            int g = 0;
+            while (bn && (w << (g + 1)) <= 56 && g + 1 <= logm - 4) g++;
+            pd->grp.push_back(g); pd->leaves.push_back(M >> g);
+            return w << g;
+        };
+        std::vector<size_t> want_w = {committed(W)};
+        if (s2) want_w.push_back(committed(W2));
+        want_w.push_back(committed(3 * Q));
+        for (auto &lf : pd->sched) { want_w.push_back((size_t)3 << lf.second); pd->grp.push_back(0); pd->leaves.push_back((u64)1 << (lf.first - lf.second)); }
+        for (int t = 0; t < pd->T; t++) {
+            int lg = 0;
+            while (((u64)1 << lg) < pd->leaves[t]) lg++;
+            if ((size_t)widths[t] != want_w[t] || depths[t] != (bn ? levels16(pd->leaves[t]) : lg)) return verdict(ZP_VERDICT_MALFORMED);
+        }
     }
     pd->roots.insert(pd->roots.end(), h.root[0].begin(), h.root[0].end());
     if (pg.n_s2) pd->roots.insert(pd->roots.end(), h.root[1].begin(), h.root[1].end());
@@ -656,8 +844,9 @@ void query_arith(const Pending &pd, const VerifyParams &vp, const std::vector<e3
     e3 A = e3_base(0), B = e3_base(0);
     size_t k = 0;
     for (int t = 0; t < T - (int)n_fri; t++)
-        for (int c = 0; c < pd.widths[t]; c++, k++) {
-            const u64 v = vals[pd.voff[t] + q * (size_t)pd.widths[t] + c];
+        for (int c = 0, g = pd.grp[t]; c < pd.widths[t] >> g; c++, k++) {
+            // the queried row out of the 2^g rows of the leaf: column c of row j sits at c 2^g + j / (M / 2^g)  (g = 0: the leaf is the row)
+            const u64 v = vals[pd.voff[t] + q * (size_t)pd.widths[t] + ((size_t)c << g) + (size_t)(j >> (logm - g))];
             A = e3_add(A, e3_mul(gp[k], e3_make(gl_sub(v, pd.ev_z[3 * k]), gl_neg(pd.ev_z[3 * k + 1]), gl_neg(pd.ev_z[3 * k + 2]))));
             if (k < Wt) B = e3_add(B, e3_mul(gp[Wall + k], e3_make(gl_sub(v, pd.ev_zw[3 * k]), gl_neg(pd.ev_zw[3 * k + 1]), gl_neg(pd.ev_zw[3 * k + 2]))));
         }
@@ -747,7 +936,7 @@ int32_t verify_batch_impl(zp_ctx *ctx, const uint64_t *h_program, size_t program
     vp.root32 = ctx ? ctx->root32 : ZP_ROOT32_DEFAULT;
     vp.shift = ctx ? ctx->coset_shift : ZP_SHIFT_DEFAULT;
     const HostPoseidon H = {ctx ? ctx->h_rc : (const u64 *)ZP_POSEIDON_DEFAULT_RC, ctx ? ctx->h_mds : (const u64 *)ZP_POSEIDON_DEFAULT_MDS};
-    const bool has_s2 = pg.n_s2 != 0, trust = (vp.flags & ZP_VERIFY_TRUST_OPENINGS) != 0;
+    const bool has_s2 = pg.n_s2 != 0, trust = (vp.flags & ZP_VERIFY_TRUST_OPENINGS) != 0, bn = vp.H254 != nullptr;
     const size_t nq = (size_t)vp.n_queries;
 
     std::vector<Pending> pend((size_t)n_proofs);
@@ -760,7 +949,7 @@ int32_t verify_batch_impl(zp_ctx *ctx, const uint64_t *h_program, size_t program
     });
     for (int32_t r : hrc)
         if (r != ZP_OK) {
-            if (ctx) ctx->err = r == ZP_ERR_UNSUPPORTED ? "a proof in BN128-hash mode (or a build without the openings parser)" : "the program blob could not be evaluated at the proof's point";
+            if (ctx) ctx->err = r == ZP_ERR_UNSUPPORTED ? "a proof in BN128-hash mode handed to the Goldilocks-mode call (or a build without the openings parser)" : "the program blob could not be evaluated at the proof's point";
             return r;
         }
 
@@ -774,7 +963,7 @@ int32_t verify_batch_impl(zp_ctx *ctx, const uint64_t *h_program, size_t program
         if (!pd.queries_live) continue;
         canon[i] = pd.values;
         for (u64 &v : canon[i]) v = gl_canon(v);
-        for (u64 &v : pd.paths) v = gl_canon(v);
+        if (!bn) for (u64 &v : pd.paths) v = gl_canon(v);      // (a BN128 path word is compared, never reduced: one >= r equals nothing)
         pd.open_ok.assign(nq * pd.T, 1);
         pd.arith.assign(nq * (pd.sched.size() + 1), 0);
         Tmax = pd.T > Tmax ? pd.T : Tmax;
@@ -792,20 +981,24 @@ int32_t verify_batch_impl(zp_ctx *ctx, const uint64_t *h_program, size_t program
                 Pending &pd = pend[i];
                 if (!pd.queries_live) continue;
                 if (t == 0) { pd.root0 = roots.size() / 4; roots.insert(roots.end(), pd.roots.begin(), pd.roots.end()); }
-                const int n_fri = (int)pd.sched.size(), l = t - (pd.T - n_fri);
                 for (size_t q = 0; q < nq; q++) {
-                    // the row of tree t that query q opens: a FRI layer of 2^m leaves is opened at the low m bits of the index
-                    const u64 pos = l < 0 ? pd.index[q] : pd.index[q] & (((u64)1 << (pd.sched[l].first - pd.sched[l].second)) - 1);
-                    ops.push_back({&canon[i][pd.voff[t] + q * (size_t)pd.widths[t]], &pd.paths[pd.poff[t] + q * (size_t)pd.depths[t] * 4], pos, (uint32_t)pd.widths[t],
-                                   (uint32_t)pd.depths[t], (uint32_t)(pd.root0 + t)});
+                    // the leaf of tree t that query q opens: a tree of 2^m leaves (a FRI layer, a grouped commitment) is opened at the low m bits of the index.
+                    // BN128 mode hashes the opened values as the text has them (the checker packs them unreduced)
+                    const std::vector<u64> &hv = bn ? pd.values : canon[i];
+                    ops.push_back({&hv[pd.voff[t] + q * (size_t)pd.widths[t]], &pd.paths[pd.poff[t] + q * (size_t)pd.depths[t] * (bn ? 64 : 4)], pd.index[q] & (pd.leaves[t] - 1),
+                                   (uint32_t)pd.widths[t], (uint32_t)pd.depths[t], (uint32_t)(pd.root0 + t), pd.leaves[t]});
                 }
             }
         std::vector<uint8_t> ok(ops.size() ? ops.size() : 1);
         if (ctx && !ops.empty()) {
-            if (!zpi_merkle_verify_openings) { ctx->err = "this build has no device side"; return ZP_ERR_UNSUPPORTED; }
-            ZP_TRY(zpi_merkle_verify_openings(ctx, ops.data(), ops.size(), roots.data(), roots.size() / 4, ok.data()));
+            const auto device = bn ? zpi_merkle16_verify_openings_bn254 : zpi_merkle_verify_openings;
+            if (!device) { ctx->err = "this build has no device side"; return ZP_ERR_UNSUPPORTED; }
+            ZP_TRY(device(ctx, ops.data(), ops.size(), roots.data(), roots.size() / 4, ok.data()));
         } else {
-            spread(ops.size(), vp.threads, [&](size_t o) { ok[o] = H.opening_ok(ops[o], &roots[4 * (size_t)ops[o].root_slot]); });
+            spread(ops.size(), vp.threads, [&](size_t o) {
+                const u64 *root = &roots[4 * (size_t)ops[o].root_slot];
+                ok[o] = bn ? vp.H254->opening_ok(ops[o], root) : H.opening_ok(ops[o], root);
+            });
         }
         size_t o = 0;
         for (int t = 0; t < Tmax; t++)
@@ -843,6 +1036,28 @@ int32_t verify_guarded(zp_ctx *ctx, Body body) {      // no exception crosses th
     }
 }
 
+// the t = 17 tables of a BN128-mode call: with a ctx the ones installed on its device (zp_set_poseidon_bn254; none: the error zp_stark_prove_bn128
+// gives), with ctx = NULL the caller's, in the layout of zp_set_poseidon_bn254
+int32_t tables254(zp_ctx *ctx, int32_t rp, const uint64_t *h_rc, const uint64_t *h_mds, HostPoseidon254 *H) {
+    if (ctx) {
+        ZP_ARG(ctx, !h_rc && !h_mds, "with a ctx the installed t = 17 tables are used: pass h_rc and h_mds as NULL");
+        if (!zpi_p254_host_tables) { ctx->err = "this build has no device side"; return ZP_ERR_UNSUPPORTED; }
+        return zpi_p254_host_tables(ctx, &H->rc, &H->mds, &H->rp);
+    }
+    if (rp < 1 || rp > 128 || !h_rc || !h_mds) return ZP_ERR_ARG;
+    const size_t nrc = (size_t)(8 + rp) * 17, nm = 17 * 17;
+    H->rp = rp;
+    H->rc.resize(nrc * 9); H->mds.resize(nm * 9);
+    for (size_t i = 0; i < nrc + nm; i++) {
+        const uint64_t *src = i < nrc ? h_rc + 4 * i : h_mds + 4 * (i - nrc);
+        const u64 w[4] = {src[0], src[1], src[2], src[3]};
+        if (!fr_is_canonical_u64(w)) return ZP_ERR_ARG;
+        const fr m = fr_to_mont(fr_from_u64(w));
+        memcpy(i < nrc ? &H->rc[9 * i] : &H->mds[9 * (i - nrc)], m.l, 36);
+    }
+    return ZP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -852,14 +1067,39 @@ int32_t zp_stark_verify(zp_ctx *ctx, const uint64_t *h_program, size_t program_w
     if (!verdict || !where) return ZP_ERR_ARG;
     *verdict = ZP_VERDICT_MALFORMED;
     *where = -1;
-    const VerifyParams vp = {logn, logb, fri_logf, fri_final_log, n_queries, pow_bits, flags, threads, 0, 0};
+    const VerifyParams vp = {logn, logb, fri_logf, fri_final_log, n_queries, pow_bits, flags, threads, 0, 0, nullptr};
     return verify_guarded(ctx, [&] { return verify_batch_impl(ctx, h_program, program_words, &proof_json, &proof_len, 1, vp, verdict, where, h_indices); });
 }
 
 int32_t zp_stark_verify_batch(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const char *const *proofs, const size_t *lens, int32_t n_proofs, int32_t logn,
                               int32_t logb, int32_t fri_logf, int32_t fri_final_log, int32_t n_queries, int32_t pow_bits, uint32_t flags, int32_t threads, int32_t *verdicts) {
-    const VerifyParams vp = {logn, logb, fri_logf, fri_final_log, n_queries, pow_bits, flags, threads, 0, 0};
+    const VerifyParams vp = {logn, logb, fri_logf, fri_final_log, n_queries, pow_bits, flags, threads, 0, 0, nullptr};
     return verify_guarded(ctx, [&] { return verify_batch_impl(ctx, h_program, program_words, proofs, lens, n_proofs, vp, verdicts, nullptr, nullptr); });
+}
+
+int32_t zp_stark_verify_bn128(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const char *proof_json, size_t proof_len, int32_t logn, int32_t logb,
+                              int32_t fri_logf, int32_t fri_final_log, int32_t n_queries, int32_t rp, const uint64_t *h_rc, const uint64_t *h_mds, uint32_t flags,
+                              int32_t threads, int32_t *verdict, int32_t *where, uint64_t *h_indices) {
+    if (!verdict || !where) return ZP_ERR_ARG;
+    *verdict = ZP_VERDICT_MALFORMED;
+    *where = -1;
+    return verify_guarded(ctx, [&] {
+        HostPoseidon254 H254;
+        ZP_TRY(tables254(ctx, rp, h_rc, h_mds, &H254));
+        const VerifyParams vp = {logn, logb, fri_logf, fri_final_log, n_queries, 0, flags, threads, 0, 0, &H254};
+        return verify_batch_impl(ctx, h_program, program_words, &proof_json, &proof_len, 1, vp, verdict, where, h_indices);
+    });
+}
+
+int32_t zp_stark_verify_batch_bn128(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const char *const *proofs, const size_t *lens, int32_t n_proofs,
+                                    int32_t logn, int32_t logb, int32_t fri_logf, int32_t fri_final_log, int32_t n_queries, int32_t rp, const uint64_t *h_rc,
+                                    const uint64_t *h_mds, uint32_t flags, int32_t threads, int32_t *verdicts) {
+    return verify_guarded(ctx, [&] {
+        HostPoseidon254 H254;
+        ZP_TRY(tables254(ctx, rp, h_rc, h_mds, &H254));
+        const VerifyParams vp = {logn, logb, fri_logf, fri_final_log, n_queries, 0, flags, threads, 0, 0, &H254};
+        return verify_batch_impl(ctx, h_program, program_words, proofs, lens, n_proofs, vp, verdicts, nullptr, nullptr);
+    });
 }
 
 }  // extern "C"

@@ -166,6 +166,11 @@ SIGNATURES = {
     "zp_stark_verify_batch": (C.c_int32, [_vp, _u64p, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(C.c_int32)]),
     "zp_merkle_verify_batch": (C.c_int32, [_vp, _u64p, C.c_size_t, _u64p, _u64p, C.c_int32, _u64p, C.c_size_t, C.POINTER(C.c_uint8)]),
+    "zp_stark_verify_bn128": (C.c_int32, [_vp, _u64p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _u64p, _u64p,
+                                          C.c_uint32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _u64p]),
+    "zp_stark_verify_batch_bn128": (C.c_int32, [_vp, _u64p, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                C.c_int32, C.c_int32, C.c_int32, _u64p, _u64p, C.c_uint32, C.c_int32, C.POINTER(C.c_int32)]),
+    "zp_merkle16_verify_batch_bn254": (C.c_int32, [_vp, _u64p, C.c_size_t, _u64p, _u64p, C.c_size_t, _u64p, C.c_size_t, C.POINTER(C.c_uint8)]),
     "zp_set_tuning": (C.c_int32, [_vp, C.c_char_p, C.c_int32]),
     "zp_set_profiling": (C.c_int32, [_vp, C.c_int32]),
     "zp_get_pass_timings": (C.c_int32, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int32,
@@ -395,6 +400,52 @@ def stark_verify_batch(program, texts, params, flags=0, prover=None, threads=0):
                                               int(flags), threads, out)
     if rc != 0:
         _verify_error(prover, rc, "zp_stark_verify_batch")
+    return list(out)
+
+
+def _verify_params_bn128(params, prover, bn_tables):
+    """[logn, logb, fri_logf, fri_final_log, n_queries, rp, h_rc, h_mds] of a BN128-mode call, and what keeps the tables alive"""
+    d = params.to_dict() if hasattr(params, "to_dict") else dict(params)
+    pv = [int(d[k]) for k in ("logn", "logb", "fri_logf", "fri_final_log", "n_queries")]
+    if prover is not None:
+        return pv + [0, None, None], None
+    if bn_tables is None:
+        raise ValueError("zp_stark_verify_bn128 without a ctx needs the t = 17 tables: bn_tables = (rc, mds, rp)")
+    rc, mds, rp = bn_tables
+    flat = [v for row in mds for v in row] if isinstance(mds[0], (list, tuple)) else list(mds)
+    keep = (Prover._fr_words(rc), Prover._fr_words(flat))
+    return pv + [int(rp), keep[0].ctypes.data_as(_u64p), keep[1].ctypes.data_as(_u64p)], keep
+
+
+def stark_verify_bn128(program, text, params, flags=0, prover=None, threads=0, bn_tables=None):
+    """zp_stark_verify_bn128: (verdict, where, indices) of a BN128-hash-mode proof TEXT, as stark_verify gives them.  prover = None: on the host with
+    bn_tables = (rc, mds, rp) of the t = 17 instance (poseidon_constants.bn254_poseidon_params(17)); otherwise through that ctx and the tables
+    installed on it (install_poseidon_bn254(17))"""
+    prog = np.ascontiguousarray(program, dtype=np.uint64)
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    pv, keep = _verify_params_bn128(params, prover, bn_tables)
+    idx = np.zeros(pv[4], dtype=np.uint64)
+    verdict, where = C.c_int32(0), C.c_int32(-1)
+    rc = load_library().zp_stark_verify_bn128(prover.ctx if prover is not None else None, prog.ctypes.data_as(_u64p), prog.size, raw, len(raw), *pv, int(flags), threads,
+                                              C.byref(verdict), C.byref(where), idx.ctypes.data_as(_u64p))
+    del keep
+    if rc != 0:
+        _verify_error(prover, rc, "zp_stark_verify_bn128")
+    got = verdict.value == VERDICT_ACCEPT or verdict.value >= VERDICT_INDICES
+    return verdict.value, where.value, ([int(v) for v in idx] if got else None)
+
+
+def stark_verify_batch_bn128(program, texts, params, flags=0, prover=None, threads=0, bn_tables=None):
+    """zp_stark_verify_batch_bn128: the verdicts of several BN128-mode proof texts of one statement and parameter set (every hash of every opening in one launch)"""
+    prog = np.ascontiguousarray(program, dtype=np.uint64)
+    raws = [t.encode() if isinstance(t, str) else bytes(t) for t in texts]
+    n = len(raws)
+    pv, keep = _verify_params_bn128(params, prover, bn_tables)
+    ptrs, lens, out = (C.c_char_p * n)(*raws), (C.c_size_t * n)(*[len(r) for r in raws]), (C.c_int32 * n)()
+    rc = load_library().zp_stark_verify_batch_bn128(prover.ctx if prover is not None else None, prog.ctypes.data_as(_u64p), prog.size, ptrs, lens, n, *pv, int(flags), threads, out)
+    del keep
+    if rc != 0:
+        _verify_error(prover, rc, "zp_stark_verify_batch_bn128")
     return list(out)
 
 
@@ -1043,6 +1094,20 @@ class Prover:
         out = C.c_uint64(0)
         self._chk(self.lib.zp_pow_grind(self.ctx, sd, int(bits), C.byref(out)))
         return int(out.value)
+
+    def merkle16_verify_batch_bn254(self, values, index, paths, M, root):
+        """zp_merkle16_verify_batch_bn254: values u64[n][width], index u64[n], paths u64[n][levels][16][4] (merkle16_open_batch_bn254's words), the tree's
+        leaf count M, root u64[4] -> uint8[n], 1 = the opening hashes into the root"""
+        v = np.ascontiguousarray(values, dtype=np.uint64)
+        ix = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1)
+        pt = np.ascontiguousarray(paths, dtype=np.uint64).reshape(-1)
+        rt = np.ascontiguousarray(root, dtype=np.uint64).reshape(4)
+        n = ix.size
+        assert v.ndim == 2 and v.shape[0] == n
+        ok = np.zeros(max(n, 1), dtype=np.uint8)
+        self._chk(self.lib.zp_merkle16_verify_batch_bn254(self.ctx, v.ctypes.data_as(_u64p), v.shape[1], ix.ctypes.data_as(_u64p), pt.ctypes.data_as(_u64p) if pt.size else None,
+                                                          int(M), rt.ctypes.data_as(_u64p), n, ok.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return ok[:n]
 
     def merkle_verify_batch(self, values, index, paths, root):
         """zp_merkle_verify_batch: values u64[n][width], index u64[n], paths u64[n][depth][4] (bottom-up), root u64[4] -> uint8[n], 1 = the opening hashes to the root"""

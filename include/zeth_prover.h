@@ -581,7 +581,7 @@ int32_t zp_fixed_base_mul_bn254(zp_ctx *ctx, const uint32_t *h_base, const uint3
 int32_t zp_fixed_base_mul_bn254_g2(zp_ctx *ctx, const uint32_t *h_base, const uint32_t *h_scalars, size_t n, uint32_t *h_points, int32_t threads);
 
 /* ---- the STARK verifier: does a chunk proof TEXT (what zp_stark_prove wrote, what a client hands in) verify? -------------------------
- * Goldilocks-hash mode only: a proof whose params.hash is "bn128" is ZP_ERR_UNSUPPORTED.
+ * Goldilocks-hash mode: a proof whose params.hash is "bn128" is ZP_ERR_UNSUPPORTED here and is read by zp_stark_verify_bn128 below.
  * The return value is ZP_OK whenever a verdict was reached -- a rejected proof is a verdict, not an error; negative codes are the caller's own
  * mistakes (null pointer, a program blob that does not parse, parameters out of the prover's ranges, a HIP failure).  No exception crosses.
  * The security parameters are the CALLER's; the root of unity and the coset shift are the ctx's (zp_set_constants), and the proof's must
@@ -616,6 +616,32 @@ int32_t zp_stark_verify_batch(zp_ctx *ctx, const uint64_t *h_program, size_t pro
 int32_t zp_merkle_verify_batch(zp_ctx *ctx, const uint64_t *h_values, size_t width, const uint64_t *h_index, const uint64_t *h_paths,
                                int32_t depth, const uint64_t *h_root4, size_t n, uint8_t *h_ok);
 
+/* ---- the same verifier in BN128-hash mode: the final STARK of GenFinalProof, the text zp_stark_prove_bn128 / zp_stark_prove_sharded_bn128 write
+ * (16-ary Poseidon-BN254 trees, transcript over F_r).  Verdict classes, their order, *where, h_indices, the two flags, `threads` and the rule
+ * "a verdict is ZP_OK, an error is the caller's mistake" are zp_stark_verify's.  What this mode changes:
+ *  - no pow_bits argument: the mode has no grinding; a text whose params.pow_bits is not 0, or whose params.hash is not "bn128", is PARAMS.
+ *  - roots ([one element]) and path entries ([levels][16]) are QUOTED decimals: one or more digits, no sign, no leading zero except "0";
+ *    anything else is MALFORMED.  A root >= r is MALFORMED; a path word >= r equals nothing (OPENING).  Strings of any length are read.
+ *  - a trace / stage-2 / quotient leaf holds 2^g rows (the largest g with width 2^g <= 56 that leaves the tree 16 leaves); widths and level
+ *    counts (ceil(log16) of the leaf count) are checked before anything is hashed (MALFORMED).  Opened values are hashed as the text has them.
+ *  - tables: with a ctx the t = 17 tables installed by zp_set_poseidon_bn254 (pass rp = 0, h_rc = h_mds = NULL; none installed: the error
+ *    zp_stark_prove_bn128 gives); all hashes of all openings of the call are ONE launch.  With ctx = NULL everything runs on the host: rp, h_rc
+ *    ((8 + rp) * 17 elements) and h_mds (17 * 17) are required, in zp_set_poseidon_bn254's layout; the domain constants are the library defaults. */
+int32_t zp_stark_verify_bn128(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const char *proof_json, size_t proof_len,
+                              int32_t logn, int32_t logb, int32_t fri_logf, int32_t fri_final_log, int32_t n_queries,
+                              int32_t rp, const uint64_t *h_rc, const uint64_t *h_mds,
+                              uint32_t flags, int32_t threads, int32_t *verdict, int32_t *where, uint64_t *h_indices);
+int32_t zp_stark_verify_batch_bn128(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const char *const *proofs, const size_t *lens,
+                                    int32_t n_proofs, int32_t logn, int32_t logb, int32_t fri_logf, int32_t fri_final_log, int32_t n_queries,
+                                    int32_t rp, const uint64_t *h_rc, const uint64_t *h_mds, uint32_t flags, int32_t threads, int32_t *verdicts);
+/* the device primitive on its own: n openings into ONE 16-ary tree of M leaves (zp_merkle16_commit_bn254's; M need not be a power of 16), each
+ * leaf of `width` values: h_values u64[n][width], h_index u64[n], h_paths u64[n][levels][16][4] (zp_merkle16_open_batch_bn254's layout, raw words),
+ * h_root4 u64[4].  h_ok[o] = 1 iff the leaf hashes into slot index % 16 of its group, every level's digest into the next group's slot, the last
+ * into the root, every group word is < r and the children beyond a level's size are zero; an index >= M gives 0.  Every permutation chain of the
+ * call is a job of one launch: from "verify16_lane_min" (zp_set_tuning) jobs on one lane per job, below it 17 lanes per job; the same flags. */
+int32_t zp_merkle16_verify_batch_bn254(zp_ctx *ctx, const uint64_t *h_values, size_t width, const uint64_t *h_index, const uint64_t *h_paths,
+                                       size_t M, const uint64_t *h_root4, size_t n, uint8_t *h_ok);
+
 /* ---- host-buffer conveniences (H2D + compute + D2H + sync), the form a non-GPU-aware host uses */
 int32_t zp_ntt_host(zp_ctx *ctx, uint64_t *h_cols, int32_t logn, int32_t W, int32_t inverse);
 int32_t zp_lde_host(zp_ctx *ctx, const uint64_t *h_in, uint64_t *h_out, int32_t logn, int32_t logb,
@@ -640,7 +666,8 @@ int32_t zp_hbm_copy_probe(zp_ctx *ctx, const void *d_src, void *d_dst, size_t by
  * kernel (15), "msm_chunk_log" log2 of the points per Pippenger run (24), "msm_c" window width, "ntt_small_wave" / "fri_fold_lanes" the in-wave (DPP / ds_swizzle) forms of the
  * small transform and of the fold by 16: 0 where they measured faster, 1 always, 2 never; "ntt_logt12" 1: radix-4096 passes on 64-KiB tiles, two
  * 512-thread workgroups per CU (2: 128-KiB tiles); "p254_block" 2: the lane-per-permutation Poseidon-BN254 kernel walks its partial rounds one by
- * one instead of in blocks of four; "verify_lane_min" openings per call from which the verifier hashes one opening per lane (0 = 256: a guess, unmeasured); 0 = default); not for production hosts */
+ * one instead of in blocks of four; "verify_lane_min" openings per call from which the verifier hashes one opening per lane (0 = 256: a guess, unmeasured);
+ * "verify16_lane_min" hash jobs per call from which the BN128-mode verifier hashes one job per lane (0 = 2^14: a guess, unmeasured); 0 = default); not for production hosts */
 int32_t zp_set_tuning(zp_ctx *ctx, const char *key, int32_t value);
 
 /* ---- introspection ------------------------------------------------------------------------- */
