@@ -209,7 +209,7 @@ static int32_t program_eval_ext_impl(const uint64_t *h_program, size_t program_w
                 case 3: if (idx >= n_fixed) { ok = false; return e3_base(0); } return fixed[idx];
                 case 4: if (idx >= (size_t)n_pubchal) { ok = false; return e3_base(0); } return e3_base(h_pubchal[idx]);
                 case 5: if (idx >= n_const) { ok = false; return e3_base(0); } return e3_base(consts[idx] % GL_P);
-                case 6: return xml;
+                case 6: if (idx != 0) { ok = false; return e3_base(0); } return xml;     // one such factor: index 0, as the prover's interpreter checks it
                 default: ok = false; return e3_base(0);
             }
         };

@@ -223,7 +223,9 @@ int32_t zp_fri_fold(zp_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, int32_t 
  * zp_deep_quotient: on x = shift*w_M^r, r < 2^logm,
  *   F(x) = sum_{k<Wa+Wb} g^k (p_k(x)-e_k)/(x-z) + sum_{k<n_next} g^(Wa+Wb+k) (p_k(x)-e'_k)/(x-zw)
  *   p_k = columns of d_cols_a (k<Wa) then d_cols_b; e = h_ev_z[Wa+Wb][3], e' = h_ev_zw[n_next][3];
- *   d_out u64[3][2^logm].
+ *   d_out u64[3][2^logm].  A row whose x equals z (or, with n_next > 0, zw) -- a point ON the domain, which a protocol
+ *   excludes -- receives 0 in all three planes (the kernel inverts the product of the row's denominators); every other row,
+ *   the other row of its lane pair included, is unaffected.
  * zp_gather_rows: h_out[nq][W] = row h_idx[q] of the column-major matrix (query openings).
  * zp_merkle_open_batch: h_paths[nq][log2 M][4], bottom-up siblings for every queried leaf.        */
 int32_t zp_poly_eval_ext(zp_ctx *ctx, const uint64_t *d_coef, int32_t logn, int32_t W, const uint64_t z[3],
@@ -306,7 +308,7 @@ int32_t zp_domain_tables(zp_ctx *ctx, int32_t logm, const uint64_t **d_lo, const
  * zp_eval_quotient evaluates the program on every row of the LDE domain (M = 2^logm rows, x = shift*w_M^r), combines
  * constraint k with alpha^k in F_{p^3} (h_alpha_pows [K][3]), multiplies by h_zhinv[r mod 2^logb] and writes the three
  * planes d_out u64[3][M].  d_cols u64[W+W2][M], d_fixed u64[2][M]; h_pub = publics then challenges (n_pub values).
- * A malformed program (bad magic, lengths, operand or slot out of range, more than 24 slots) is ZP_ERR_ARG.        */
+ * A malformed program (bad magic, lengths, operand or slot out of range, more than 32 slots) is ZP_ERR_ARG.        */
 int32_t zp_eval_quotient(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const uint64_t *d_cols,
                          const uint64_t *d_fixed, int32_t logm, int32_t logb, const uint64_t *h_pub, int32_t n_pub,
                          const uint64_t *h_alpha_pows, const uint64_t *h_zhinv, uint64_t shift, uint64_t w_last,

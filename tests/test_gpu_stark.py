@@ -77,7 +77,7 @@ def test_ood_eval_from_values_matches_the_coefficient_definition(prover, logn, l
         d.free()
 
 
-@pytest.mark.parametrize("logm,Wa,Wb,nn", [(6, 3, 0, 0), (10, 5, 3, 5), (12, 4, 3, 2)])
+@pytest.mark.parametrize("logm,Wa,Wb,nn", [(6, 3, 0, 0), (10, 5, 3, 5), (12, 4, 3, 2), (0, 1, 0, 0), (1, 1, 0, 1), (6, 3, 0, 3), (7, 1, 2, 1)])
 def test_deep_quotient_matches_oracle(prover, logm, Wa, Wb, nn):
     a = O.random_field((Wa, 1 << logm), 50)
     b = O.random_field((max(Wb, 1), 1 << logm), 51)
@@ -89,6 +89,69 @@ def test_deep_quotient_matches_oracle(prover, logm, Wa, Wb, nn):
     d_out = prover.alloc(3 << logm)
     prover.deep_quotient(prover.upload(a), Wa, prover.upload(b) if Wb else None, Wb, logm, nn, z, zw, g, ez, ezw, 49, d_out)
     assert (prover.download(d_out, (3, 1 << logm)) == ref).all()
+
+
+@pytest.mark.parametrize("nrows,Wa,Wb,nn,stride,base", [(1, 1, 0, 1, 1, 0), (255, 3, 2, 2, 256, 0), (257, 3, 2, 3, 258, 0), (257, 3, 0, 3, 259, 0), (257, 3, 2, 1, 258, 1)])
+def test_deep_quotient_rows_odd_windows_strides_and_bases(prover, nrows, Wa, Wb, nn, stride, base):
+    """zp_deep_quotient_rows against orc_deep_quotient_rows: windows of 1, 255 and 257 rows (a lane holds two rows: an odd count ends on
+    half a lane), on even strides and 16-byte-aligned bases (each lane loads its row pair at once), on the odd column stride 259 and on a
+    column base moved by one word (both turn the pair loads off)"""
+    logm, row0 = 10, 301
+    a = O.random_field((Wa, stride), 930 + nrows)
+    b = O.random_field((max(Wb, 1), stride), 931 + nrows)
+    z, zw, g = (O.random_field((3,), 932 + i).tolist() for i in range(3))
+    ez, ezw = O.random_field((Wa + Wb, 3), 935), O.random_field((max(nn, 1), 3), 936)
+    so = nrows + 1
+    ref = np.zeros((3, so), dtype=np.uint64)
+    O.lib().orc_deep_quotient_rows(O._p(a), Wa, stride, O._p(b), Wb, stride, logm, row0, nrows, nn, O._p(O._arr(z)), O._p(O._arr(zw)), O._p(O._arr(g)),
+                                   O._p(ez), O._p(ezw), 49, O.ROOT32_DEFAULT, O._p(ref), so)
+    pad = np.zeros(base, dtype=np.uint64)
+    d_a, d_b = prover.upload(np.concatenate([pad, a.reshape(-1)])), prover.upload(np.concatenate([pad, b.reshape(-1)]))
+    d_o = prover.alloc(3 * so)
+    prover.memset(d_o, 0, 3 * so * 8)
+    prover.deep_quotient_rows(d_a.offset(base), Wa, stride, d_b.offset(base) if Wb else None, Wb, stride, logm, row0, nrows, nn, z, zw, g, ez, ezw, 49, d_o, so)
+    assert (prover.download(d_o, (3, so)) == ref).all()      # the word behind each plane's window stays 0
+
+
+@pytest.mark.parametrize("r", [36, 37])
+def test_deep_quotient_row_whose_denominator_vanishes(prover, r):
+    """z = the domain's own point of row r (a protocol excludes it): include/zeth_prover.h says what the call leaves there -- row r is 0 in
+    all three planes, where the checker keeps the term over x - zw -- and every other row, its lane partner r ^ 1 included, is exact"""
+    logm, Wa, Wb, nn = 7, 1, 2, 1
+    M = 1 << logm
+    a, b = O.random_field((Wa, M), 940), O.random_field((Wb, M), 941)
+    z = [49 * pow(NV.root(logm), r, P) % P, 0, 0]
+    zw, g = (O.random_field((3,), 942 + i).tolist() for i in range(2))
+    ez, ezw = O.random_field((Wa + Wb, 3), 944), O.random_field((nn, 3), 945)
+    ref = O.deep_quotient(a, b, nn, z, zw, g, ez, ezw)
+    d_out = prover.alloc(3 * M)
+    prover.deep_quotient(prover.upload(a), Wa, prover.upload(b), Wb, logm, nn, z, zw, g, ez, ezw, 49, d_out)
+    got = prover.download(d_out, (3, M))
+    others = np.arange(M) != r
+    assert (got[:, others] == ref[:, others]).all()
+    assert got[:, r].tolist() == [0, 0, 0] and ref[:, r].tolist() != [0, 0, 0]
+
+
+def test_stage2_columns_with_a_zero_denominator_match_the_checker(prover):
+    """a base-field challenge g = (g0, 0, 0) that meets b[i] = -g0 (grand product) or a[i] = -g0 (LogUp) at i = 4096 + 5, in the second of
+    three blocks: both sides read 1/0 as 0, so Z is 0 from row i + 1 on and h1[i] = 0; word for word against the checker"""
+    n, i, g = 2 * 4096 + 17, 4096 + 5, [0x1234567, 0, 0]
+    a = O.random_field((n,), 950)
+    b = O.random_field((n,), 951)
+    t_, m = O.random_field((n,), 952), np.random.default_rng(953).integers(0, 5, size=n, dtype=np.uint64)
+    b[i] = P - g[0]
+    assert (P - g[0]) not in a.tolist() + t_.tolist() and b.tolist().count(P - g[0]) == 1      # the one zero denominator is the planted one
+    d_out = prover.alloc(3 * n)
+    prover.grand_product(prover.upload(a), prover.upload(b), n, g, d_out)
+    got = prover.download(d_out, (3, n))
+    assert (got == O.grand_product(a, b, g)).all()
+    assert not got[:, i + 1:].any() and got[:, i].any()
+    a[i] = P - g[0]
+    d_out = prover.alloc(9 * n)
+    prover.logup_columns(prover.upload(a), prover.upload(t_), prover.upload(m), n, g, d_out)
+    got = prover.download(d_out, (9, n))
+    assert (got == O.logup_columns(a, t_, m, g)).all()
+    assert got[0:3, i].tolist() == [0, 0, 0]
 
 
 def test_gather_and_batch_open(prover, tables):
@@ -108,7 +171,12 @@ def test_gather_and_batch_open(prover, tables):
         prover.gather_rows(d, M, W, [M])
 
 
-@pytest.mark.parametrize("n", [1, 2, 17, 4096, 4097, (1 << 16) + 5, 1 << 20])
+# rows the large stage-2 cases sample: the first blocks, the middle, the end, and both sides of block 256 -- where the scan of the block
+# totals starts its second chunk with a carry (n = 2^20 + 4097 is 258 blocks of 4096; 2^20 is exactly one chunk of 256)
+STAGE2_ROWS = [0, 1, 4095, 4096, (1 << 20) - 1, 1 << 20, (1 << 20) + 4095, (1 << 20) + 4096]
+
+
+@pytest.mark.parametrize("n", [1, 2, 17, 4096, 4097, (1 << 16) + 5, 1 << 20, (1 << 20) + 4097])
 def test_grand_product_matches_oracle(prover, n):
     a = O.random_field((n,), 80)
     b = a[np.random.default_rng(81).permutation(n)]
@@ -120,14 +188,14 @@ def test_grand_product_matches_oracle(prover, n):
         assert (got == O.grand_product(a, b, g)).all()
     else:   # size-independent properties: Z[0] = 1 and the recurrence at sampled rows
         assert got[:, 0].tolist() == [1, 0, 0]
-        for i in [0, 1, 4095, 4096, n // 2, n - 2]:
+        for i in [i for i in STAGE2_ROWS if i < n - 2] + [n // 2, n - 2]:
             zi = [int(got[c, i]) for c in range(3)]
             zn = [int(got[c, i + 1]) for c in range(3)]
             lhs = NV.e3_mul(zn, [(int(b[i]) + g[0]) % P, g[1], g[2]])
             assert lhs == NV.e3_mul(zi, [(int(a[i]) + g[0]) % P, g[1], g[2]])
 
 
-@pytest.mark.parametrize("n", [1, 2, 17, 4096, 4097, (1 << 16) + 5, 1 << 20])
+@pytest.mark.parametrize("n", [1, 2, 17, 4096, 4097, (1 << 16) + 5, 1 << 20, (1 << 20) + 4097])
 def test_logup_columns_match_oracle(prover, n):
     rng = np.random.default_rng(90)
     k = max(1, min(12, n.bit_length() - 1))
@@ -142,7 +210,7 @@ def test_logup_columns_match_oracle(prover, n):
         assert (got == O.logup_columns(a, t_, m, g)).all()
     else:   # definitions at sampled rows: h1 (a+g) = 1, h2 (t+g) = m, S' = S + h1 - h2, S[0] = 0
         assert got[6:9, 0].tolist() == [0, 0, 0]
-        for i in [0, 1, 4095, 4096, n // 2, n - 2]:
+        for i in [i for i in STAGE2_ROWS if i < n - 2] + [n // 2, n - 2]:
             h1 = [int(got[c, i]) for c in range(3)]
             h2 = [int(got[3 + c, i]) for c in range(3)]
             assert NV.e3_mul(h1, [(int(a[i]) + g[0]) % P, g[1], g[2]]) == [1, 0, 0]
