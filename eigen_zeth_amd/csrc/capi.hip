@@ -64,6 +64,7 @@ void zp_destroy(zp_ctx *ctx) {
     for (auto &kv : ctx->prove_fixed) (void)hipFree(kv.second);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     zpi_g16_cache_free(ctx);
+    zpi_fixed_eval_cache_free(ctx);
     for (zp_ctx *&h : ctx->msm_helpers) {
         if (h) zp_destroy(h);
         h = nullptr;
@@ -486,6 +487,7 @@ int32_t zp_set_tuning(zp_ctx *ctx, const char *key, int32_t value) {
     else if (!strcmp(key, "p254_bulk_log")) ctx->tune_p254_bulk_log = value;
     else if (!strcmp(key, "verify_lane_min")) ctx->tune_verify_lane_min = value;
     else if (!strcmp(key, "verify16_lane_min")) ctx->tune_verify16_lane_min = value;
+    else if (!strcmp(key, "fixed_eval_dev_min")) ctx->tune_fixed_eval_dev_min = value < 0 ? 1 << 15 : value;
     else { ctx->err = "unknown tuning key"; return ZP_ERR_ARG; }
     return ZP_OK;
 }

@@ -44,6 +44,7 @@ struct CosetTable {  // shift^i * pre, i < 2^logn, two-level
 };
 
 struct ZpG16Cache;
+struct ZpFixedEvalCache;
 struct zp_ctx {
     int device = 0;
     hipStream_t stream = nullptr;      // where every launch of this ctx goes
@@ -73,6 +74,7 @@ struct zp_ctx {
     size_t pinned_bytes = 0;
     zp_ctx *msm_helpers[4] = {nullptr, nullptr, nullptr, nullptr};   // zp_groth16_prove: ctxs (streams, MSM arenas) of the MSMs that run beside the first one
     ZpG16Cache *g16_cache = nullptr;   // zp_r1cs_eval_device: the circuit last used, in HBM (csrc/r1cs.hip; freed by zpi_g16_cache_free)
+    ZpFixedEvalCache *fixed_eval_cache = nullptr;   // zp_program_fixed_eval_ext_batch: per-entry tables of the programs last used, in HBM (csrc/fixed_eval.hip; freed by zpi_fixed_eval_cache_free)
     int num_cu = 256;
     // experiment knobs (zp_set_tuning): not part of the stable surface
     void *msm_arena = nullptr;    // scratch of zp_msm_bn254*: grows to the largest run, freed by zp_destroy
@@ -101,6 +103,7 @@ struct zp_ctx {
     int tune_verify_lane_min = 0;   // 0 = 256: zp_merkle_verify_batch / zp_stark_verify* use the lane-per-opening kernel from this many openings per call on (fewer: the 12-lane walk kernel).  256 (four full waves) is A GUESS until tools/verify_measure.py has run on the device: unmeasured
     int tune_verify16_lane_min = 0; // 0 = 2^14 JOBS (one permutation chain each): zp_merkle16_verify_batch_bn254 / zp_stark_verify*_bn128 hash one job per lane (state in LDS) from this many jobs per call on (fewer: 17 lanes per job).  2^14 is where the lane form wins for commitments: for openings A GUESS until tools/verify_bn128_measure.py has run on the device: unmeasured
     int tune_msm_chunk_log = 0;   // 0 = default (2^24 points per Pippenger run)
+    int tune_fixed_eval_dev_min = 1 << 15;   // zp_program_fixed_eval_ext_batch with a ctx: calls of fewer (points x sparse entries) run on the host (0: always the device; < 0 restores this default).  2^15: from ~12.5 ns per entry on 16 host threads against ~0.5 ms per device call (profiles/r12_fixed_eval_batch.json: every size measured there is above it and the device wins, 10x at one point of 4.4 x 10^5 entries); not measured AT the crossover
     // zp_stark_prove: device buffers kept between proofs (chunk after chunk has the same shapes; hipMalloc / hipFree of ~20 buffers
     // cost milliseconds per proof) and the LDE of the two boundary selectors per (logn, logb, shift, root)
     std::multimap<size_t, void *> prove_pool;
@@ -229,6 +232,11 @@ int32_t zpi_pool_alloc(zp_ctx *ctx, size_t bytes, void **out);
 void zpi_pool_release(zp_ctx *ctx, void *p, size_t bytes);
 void zpi_sha256(const uint8_t *data, size_t len, uint8_t *out32);
 void zpi_g16_cache_free(zp_ctx *ctx);
+void zpi_fixed_eval_cache_free(zp_ctx *ctx);
+// the sparse fixed columns of a validated program at n_points points in two launches (csrc/fixed_eval.hip): h_sparse u64[n_points][cols.size()][3];
+// h_on_domain[i] = 1 (and zero rows) where a denominator of point i vanished.  Inputs canonical, every lp <= logn: csrc/verify.hip checks before it calls
+int32_t zpi_fixed_eval_device(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const std::vector<ZpFixedCol> &cols, const uint64_t *h_pubchal,
+                              int32_t n_pubchal, int32_t logn, uint64_t root32, const uint64_t *h_zeta, int32_t n_points, uint64_t *h_sparse, uint8_t *h_on_domain);
 int32_t zpi_r1cs_poseidon17(zp_ctx *ctx, const u64 *d_inst, size_t i0, size_t count, u64 *d_w, unsigned char *d_set, u64 *d_a, u64 *d_b, u64 *d_c,
                             unsigned long long *d_flags, int *rp_out);
 int32_t zpi_merkle16_levels_bn254(zp_ctx *ctx, u64 *d_tree, size_t n);   // the levels above n digests at the head of a 16-ary tree buffer (csrc/poseidon_bn254.hip)

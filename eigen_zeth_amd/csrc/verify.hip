@@ -24,13 +24,17 @@
 
 // What the verifier takes from other translation units, as WEAK references: this file is also built on its own as plain C++ under the host
 // sanitizers (tests/test_verify_fuzz.py, tests/test_r1cs_fuzz.py link it without the rest of the library).  The openings of a text are read by
-// csrc/proofparse.hip (absent: only ZP_VERIFY_HEADER_ONLY can be served); the device side is csrc/poseidon.hip (absent: only ctx = NULL).
+// csrc/proofparse.hip (absent: only ZP_VERIFY_HEADER_ONLY can be served); the device side is csrc/poseidon.hip (absent: only ctx = NULL) and, for the
+// fixed columns at many points, csrc/fixed_eval.hip (absent: the host loop).
 extern int32_t zpi_proof_queries_scan(const char *text, size_t len, size_t *q_begin, size_t *q_end, int32_t *n_queries, int32_t *has_stage2, int32_t *n_fri, int32_t *widths,
                                       int32_t *depths, int32_t max_trees, bool bn) __attribute__((weak));
 extern int32_t zpi_proof_queries_parse(const char *text, size_t q_begin, size_t q_end, int32_t n_queries, int32_t has_stage2, int32_t n_fri, const int32_t *widths,
                                        const int32_t *depths, uint64_t *index, uint64_t *values, uint64_t *paths, bool bn) __attribute__((weak));
 extern int32_t zpi_merkle_verify_openings(zp_ctx *ctx, const ZpOpening *ops, size_t n, const u64 *h_roots, size_t n_roots, uint8_t *ok) __attribute__((weak));
 extern int32_t zpi_merkle16_verify_openings_bn254(zp_ctx *ctx, const ZpOpening *ops, size_t n, const u64 *h_roots, size_t n_roots, uint8_t *ok) __attribute__((weak));
+extern int32_t zpi_fixed_eval_device(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const std::vector<ZpFixedCol> &cols, const uint64_t *h_pubchal,
+                                     int32_t n_pubchal, int32_t logn, uint64_t root32, const uint64_t *h_zeta, int32_t n_points, uint64_t *h_sparse, uint8_t *h_on_domain)
+    __attribute__((weak));            // csrc/fixed_eval.hip (absent: zp_program_fixed_eval_ext_batch runs on the host whatever the ctx)
 extern int32_t zpi_p254_host_tables(zp_ctx *ctx, std::vector<u32> *rc, std::vector<u32> *mds, int *rp) __attribute__((weak));
 
 namespace {
@@ -82,6 +86,17 @@ int fixed_col_at(const uint64_t *prog, const ZpFixedCol &fc, const uint64_t *pub
     return FIXED_OK;
 }
 
+// fixed columns 0 / 1 at zeta: the Lagrange basis polynomials of the first and the last row, Z_H(zeta) / (N (zeta - 1)) and Z_H(zeta) w^(N-1) / (N (zeta - w^(N-1)));
+// false: zeta is one of the two rows
+bool selectors_at(const e3 &zeta, const e3 &zh, u64 wlast, u64 ninv, e3 *first, e3 *last) {
+    u64 d0, d1;
+    const e3 a0 = e3_adj(e3_make(gl_sub(zeta.c[0], 1), zeta.c[1], zeta.c[2]), &d0), a1 = e3_adj(e3_make(gl_sub(zeta.c[0], wlast), zeta.c[1], zeta.c[2]), &d1);
+    if (d0 == 0 || d1 == 0) return false;
+    *first = e3_mul(e3_scale(zh, ninv), e3_scale(a0, gl_inv(d0)));
+    *last = e3_mul(e3_scale(zh, gl_mul(ninv, wlast)), e3_scale(a1, gl_inv(d1)));
+    return true;
+}
+
 }  // namespace
 
 // The table of sparse periodic fixed columns behind a program's stage-2 table (layout: stark/air.py compile_program): validates the whole-blob
@@ -130,7 +145,7 @@ extern "C" {
 // others: to a verifier it is a property of the proof, not a mistake of its caller).  threads <= 0: one per core, at most 16.
 static int32_t program_eval_ext_impl(const uint64_t *h_program, size_t program_words, const uint64_t *h_pubchal, int32_t n_pubchal, int32_t logn, uint64_t root32,
                                      const uint64_t zeta3[3], const uint64_t *h_ev_z, const uint64_t *h_ev_zw, int32_t n_cols, uint64_t *h_out, int32_t n_out,
-                                     int32_t threads, uint64_t *h_fixed_out, int32_t n_fixed_out, bool *zeta_on_domain = nullptr) {
+                                     int32_t threads, uint64_t *h_fixed_out, int32_t n_fixed_out, bool *zeta_on_domain = nullptr, const uint64_t *fixed_in = nullptr) {
     if (zeta_on_domain) *zeta_on_domain = false;
     const bool only_fixed = h_fixed_out != nullptr;
     try {
@@ -159,38 +174,36 @@ static int32_t program_eval_ext_impl(const uint64_t *h_program, size_t program_w
         const u64 N = 1ULL << logn, wN = gl_root(root32, logn), wlast = gl_pow(wN, N - 1), ninv = gl_inv(N % GL_P);
         const e3 zN = e3_pow2k(zeta, logn), zh = e3_make(gl_sub(zN.c[0], 1), zN.c[1], zN.c[2]);
         std::vector<e3> fixed(n_fixed);
-        {
-            u64 d0, d1;
-            const e3 a0 = e3_adj(e3_make(gl_sub(zeta.c[0], 1), zeta.c[1], zeta.c[2]), &d0), a1 = e3_adj(e3_make(gl_sub(zeta.c[0], wlast), zeta.c[1], zeta.c[2]), &d1);
-            if (d0 == 0 || d1 == 0) { if (zeta_on_domain) *zeta_on_domain = true; return ZP_ERR_ARG; }
-            fixed[0] = e3_mul(e3_scale(zh, ninv), e3_scale(a0, gl_inv(d0)));
-            fixed[1] = e3_mul(e3_scale(zh, gl_mul(ninv, wlast)), e3_scale(a1, gl_inv(d1)));
+        if (fixed_in) {                        // u64[n_fixed][3] made by zp_program_fixed_eval_ext_batch for this very (program, public inputs, zeta)
+            for (size_t k = 0; k < n_fixed; k++) fixed[k] = e3_make(fixed_in[3 * k], fixed_in[3 * k + 1], fixed_in[3 * k + 2]);
+        } else {
+            if (!selectors_at(zeta, zh, wlast, ninv, &fixed[0], &fixed[1])) { if (zeta_on_domain) *zeta_on_domain = true; return ZP_ERR_ARG; }
+            // the sparse columns over threads (columns differ a lot in length: hand them out one at a time)
+            unsigned nt = threads > 0 ? (unsigned)threads : std::thread::hardware_concurrency();
+            nt = nt < 1 ? 1 : nt > 16 ? 16 : nt;
+            if (fxc.size() < 8) nt = 1;
+            std::vector<int> bad(nt, 0);
+            auto work = [&](unsigned t) noexcept {
+                try {
+                    for (size_t k = t; k < fxc.size(); k += nt)
+                        if (const int r = fixed_col_at(h_program, fxc[k], h_pubchal, logn, root32, zeta, zh, &fixed[2 + k])) { bad[t] = r; return; }
+                } catch (...) { bad[t] = FIXED_NOMEM; }
+            };
+            {
+                std::vector<std::thread> th;
+                unsigned started = 0;
+                try { for (unsigned t = 1; t < nt; t++) { th.emplace_back(work, t); started = t; } } catch (...) {}
+                work(0);
+                for (unsigned t = started + 1; t < nt; t++) work(t);      // threads that could not be started: their share runs here
+                for (auto &x : th) x.join();
+            }
+            for (int b : bad)
+                if (b == FIXED_NOMEM) return ZP_ERR_NOMEM;
+            for (int b : bad)
+                if (b == FIXED_BAD) return ZP_ERR_ARG;
+            for (int b : bad)
+                if (b) { if (zeta_on_domain) *zeta_on_domain = true; return ZP_ERR_ARG; }
         }
-        // the sparse columns over threads (columns differ a lot in length: hand them out one at a time)
-        unsigned nt = threads > 0 ? (unsigned)threads : std::thread::hardware_concurrency();
-        nt = nt < 1 ? 1 : nt > 16 ? 16 : nt;
-        if (fxc.size() < 8) nt = 1;
-        std::vector<int> bad(nt, 0);
-        auto work = [&](unsigned t) noexcept {
-            try {
-                for (size_t k = t; k < fxc.size(); k += nt)
-                    if (const int r = fixed_col_at(h_program, fxc[k], h_pubchal, logn, root32, zeta, zh, &fixed[2 + k])) { bad[t] = r; return; }
-            } catch (...) { bad[t] = FIXED_NOMEM; }
-        };
-        {
-            std::vector<std::thread> th;
-            unsigned started = 0;
-            try { for (unsigned t = 1; t < nt; t++) { th.emplace_back(work, t); started = t; } } catch (...) {}
-            work(0);
-            for (unsigned t = started + 1; t < nt; t++) work(t);      // threads that could not be started: their share runs here
-            for (auto &x : th) x.join();
-        }
-        for (int b : bad)
-            if (b == FIXED_NOMEM) return ZP_ERR_NOMEM;
-        for (int b : bad)
-            if (b == FIXED_BAD) return ZP_ERR_ARG;
-        for (int b : bad)
-            if (b) { if (zeta_on_domain) *zeta_on_domain = true; return ZP_ERR_ARG; }
         if (only_fixed) {
             for (size_t k = 0; k < n_fixed; k++) memcpy(h_fixed_out + 3 * k, fixed[k].c, 24);
             return ZP_OK;
@@ -248,6 +261,67 @@ int32_t zp_program_fixed_eval_ext(const uint64_t *h_program, size_t program_word
                                   const uint64_t zeta3[3], uint64_t *h_fixed, int32_t n_fixed, int32_t threads) {
     if (!h_fixed) return ZP_ERR_ARG;
     return program_eval_ext_impl(h_program, program_words, h_pubchal, n_pubchal, logn, root32, zeta3, nullptr, nullptr, 0, nullptr, 0, threads, h_fixed, n_fixed);
+}
+
+// The same at n_points points, each with its own public inputs: h_pubchal u64[n_points][n_pubchal], h_zeta u64[n_points][3], h_fixed u64[n_points][n_fixed][3].
+// Point by point the results and refusals of zp_program_fixed_eval_ext, but for a zeta on the trace domain or on the domain of one column: that sets
+// h_on_domain[i], leaves the point's rows zero and fails nothing (to a verifier a property of one proof).  ctx = NULL, or fewer (points x sparse
+// entries) than the knob "fixed_eval_dev_min": the host code above in a loop.  Otherwise the sparse columns of all points in one pass of
+// csrc/fixed_eval.hip (the two selectors stay here); F_{p^3} arithmetic is exact, so the two paths give the same words.
+int32_t zp_program_fixed_eval_ext_batch(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const uint64_t *h_pubchal, int32_t n_pubchal, int32_t logn,
+                                        uint64_t root32, const uint64_t *h_zeta, int32_t n_points, uint64_t *h_fixed, int32_t n_fixed, uint8_t *h_on_domain, int32_t threads) {
+    try {
+        if (!h_program || n_points < 0 || (n_points && (!h_zeta || !h_fixed || !h_on_domain)) || program_words < 12 || logn < 1 || logn > 32 || n_pubchal < 0 ||
+            (n_pubchal && n_points && !h_pubchal))
+            return ZP_ERR_ARG;
+        // the refusals of program_eval_ext_impl that do not depend on the point, once (n_points = 0 is refused like any other count)
+        static const unsigned char magic[8] = {'Z', 'P', 'A', 'I', 'R', '1', 0, 0};
+        if (memcmp(h_program, magic, 8) != 0) return ZP_ERR_ARG;
+        const size_t W = h_program[1], W2 = h_program[2], n_pub = h_program[4], n_chal = h_program[5], K = h_program[8], n_slots = h_program[9];
+        std::vector<ZpFixedCol> fxc;
+        if (!zpi_program_fixed_table(h_program, program_words, &fxc) || W < 1 || W >= 4096 || W2 >= 4096 || n_slots > (1u << 16) || K < 1 ||
+            (size_t)n_pubchal != n_pub + n_chal || root32 == 0 || root32 >= GL_P || n_fixed < 0 || (size_t)n_fixed != h_program[3])
+            return ZP_ERR_ARG;
+        size_t entries = 0;
+        for (const ZpFixedCol &fc : fxc) {
+            if (fc.lp > logn) return ZP_ERR_ARG;
+            entries += fc.n_entries;
+        }
+        const size_t np = (size_t)n_points, row = (size_t)n_fixed * 3;
+        for (size_t i = 0; i < np * 3; i++)
+            if (h_zeta[i] >= GL_P) return ZP_ERR_ARG;
+        for (size_t i = 0; i < np * (size_t)n_pubchal; i++)
+            if (h_pubchal[i] >= GL_P) return ZP_ERR_ARG;
+        if (np) { memset(h_on_domain, 0, np); memset(h_fixed, 0, np * row * 8); }
+        const bool on_device = ctx && zpi_fixed_eval_device && !fxc.empty() && np && entries &&
+                               (ctx->tune_fixed_eval_dev_min <= 0 || np >= ((size_t)ctx->tune_fixed_eval_dev_min + entries - 1) / entries);
+        if (!on_device) {
+            for (size_t i = 0; i < np; i++) {
+                bool on_domain = false;
+                const int32_t rc = program_eval_ext_impl(h_program, program_words, n_pubchal ? h_pubchal + i * (size_t)n_pubchal : nullptr, n_pubchal, logn, root32, h_zeta + 3 * i,
+                                                         nullptr, nullptr, 0, nullptr, 0, threads, h_fixed + i * row, n_fixed, &on_domain);
+                if (rc != ZP_OK && !on_domain) return rc;
+                if (rc != ZP_OK) { h_on_domain[i] = 1; memset(h_fixed + i * row, 0, row * 8); }
+            }
+            return ZP_OK;
+        }
+        std::vector<u64> sparse(np * fxc.size() * 3);
+        ZP_TRY(zpi_fixed_eval_device(ctx, h_program, program_words, fxc, h_pubchal, n_pubchal, logn, root32, h_zeta, n_points, (uint64_t *)sparse.data(), h_on_domain));
+        const u64 N = 1ULL << logn, wlast = gl_pow(gl_root(root32, logn), N - 1), ninv = gl_inv(N % GL_P);
+        for (size_t i = 0; i < np; i++) {
+            const e3 zeta = e3_make(h_zeta[3 * i], h_zeta[3 * i + 1], h_zeta[3 * i + 2]);
+            const e3 zN = e3_pow2k(zeta, logn), zh = e3_make(gl_sub(zN.c[0], 1), zN.c[1], zN.c[2]);
+            e3 sel[2];
+            if (!selectors_at(zeta, zh, wlast, ninv, &sel[0], &sel[1])) h_on_domain[i] = 1;
+            if (h_on_domain[i]) continue;              // the point's rows stay zero
+            memcpy(h_fixed + i * row, sel[0].c, 24);
+            memcpy(h_fixed + i * row + 3, sel[1].c, 24);
+            memcpy(h_fixed + i * row + 6, &sparse[i * fxc.size() * 3], fxc.size() * 24);
+        }
+        return ZP_OK;
+    } catch (...) {
+        return ZP_ERR_NOMEM;
+    }
 }
 
 }  // extern "C"
@@ -349,6 +423,45 @@ struct HostSponge : Transcript {
             }
             out[k] = st[pos++];
         }
+    }
+};
+
+// The sponge above with NO hashing (restated from the protocol of stark/verifier_air.py; the checker's: oracle/stark_verify.py PublicSponge): a
+// verifier-AIR STARK vouches for every permutation of an inner proof's transcript, and its public inputs list, in protocol order, the values each
+// permutation absorbs (a last block is NOT padded) and the rate after every permutation the protocol reads.  Absorbing compares, squeezing reads;
+// anything else than the stream dictates is a TranscriptMismatch.  One stream serves all inner proofs of a node: reset() between them.
+struct TranscriptMismatch {};
+struct PublicSponge : Transcript {
+    const u64 *s;
+    size_t n, pos = 0;
+    std::vector<u64> q;
+    u64 avail[8];
+    int apos = 8;
+    PublicSponge(const u64 *stream, size_t len) : s(stream), n(len) {}
+    const u64 *take(size_t k) { if (k > n - pos) throw TranscriptMismatch{}; pos += k; return s + pos - k; }
+    void reset() { q.clear(); apos = 8; }
+    void absorb(const u64 *v, size_t k) override { for (size_t i = 0; i < k; i++) q.push_back(gl_canon(v[i])); apos = 8; }
+    void absorb_root(const u64 *root4) override { absorb(root4, 4); }
+    void squeeze(size_t k, u64 *out) override {
+        for (size_t i = 0; i < k; i++) {
+            if (!q.empty() || apos == 8) {
+                for (size_t off = 0; off < q.size(); off += 8) {
+                    const size_t len = q.size() - off < 8 ? q.size() - off : 8;
+                    if (memcmp(take(len), &q[off], 8 * len) != 0) throw TranscriptMismatch{};
+                }
+                q.clear();
+                memcpy(avail, take(8), 64);
+                for (u64 v : avail) if (v >= GL_P) throw TranscriptMismatch{};      // a rate is a permutation's output: canonical
+                apos = 0;
+            }
+            out[i] = avail[apos++];
+        }
+    }
+    // the grinding hash, the last permutation of a proof's public transcript: seed || nonce in, the rate out
+    u64 pow_digest0(const u64 *seed4, u64 nonce) {
+        const u64 *in = take(5);
+        if (memcmp(in, seed4, 32) != 0 || in[4] != nonce) throw TranscriptMismatch{};
+        return take(8)[0];
     }
 };
 
@@ -660,9 +773,44 @@ struct Pending {
     size_t Wt = 0, Wall = 0;
     std::vector<uint8_t> open_ok, arith;       // per (query, tree): the opening hashes to its root; per (query, 0..n_fri): layer l's value / the final value is consistent
     size_t root0 = 0;                          // the slot of its first root in the batch's list
+    // zp_aggregate_verify: the identity at zeta waits for the fixed columns of every header of the tree (one zp_program_fixed_eval_ext_batch per program)
+    bool defer_identity = false, id_pending = false;
+    std::vector<u64> id_pubchal;
+    e3 id_alpha;
 };
 
-int32_t header_phase(const char *text, size_t len, const ProgramInfo &pg, const VerifyParams &vp, const HostPoseidon &H, Pending *pd) {
+// the constraint identity at zeta: sum_k alpha^k C_k(zeta) = q(zeta) Z_H(zeta).  *v: ZP_VERDICT_ACCEPT or ZP_VERDICT_IDENTITY; the return code is
+// not ZP_OK for a blob the evaluator refuses (the caller's mistake, not a rejected proof).  fixed_in: the fixed columns at zeta, when made elsewhere
+int32_t identity_at_zeta(const ProgramInfo &pg, const VerifyParams &vp, const std::vector<u64> &pubchal, const e3 &alpha, const e3 &zeta, const std::vector<u64> &ev_z,
+                         const std::vector<u64> &ev_zw, const uint64_t *fixed_in, int threads, int *v) {
+    const int logn = vp.logn;
+    const size_t Wt = pg.W + pg.W2, Q = pg.Q;
+    std::vector<u64> cs(3 * pg.K);
+    bool on_domain = false;
+    *v = ZP_VERDICT_IDENTITY;
+    const int32_t rc = program_eval_ext_impl(pg.words, pg.n_words, (const uint64_t *)pubchal.data(), (int32_t)(pg.n_pub + pg.n_chal), logn, vp.root32, (const uint64_t *)zeta.c,
+                                             (const uint64_t *)ev_z.data(), (const uint64_t *)ev_zw.data(), (int32_t)Wt, (uint64_t *)cs.data(), (int32_t)pg.K, threads, nullptr, 0, &on_domain,
+                                             fixed_in);
+    if (rc != ZP_OK && !on_domain) return rc;
+    if (rc != ZP_OK) return ZP_OK;             // zeta on the trace domain: nothing can be said at it
+    e3 lhs = e3_base(0), ap = e3_base(1);
+    for (size_t k = 0; k < pg.K; k++) { lhs = e3_add(lhs, e3_mul(ap, e3_make(cs[3 * k], cs[3 * k + 1], cs[3 * k + 2]))); ap = e3_mul(ap, alpha); }
+    const e3 zN = e3_pow2k(zeta, logn), zh = e3_make(gl_sub(zN.c[0], 1), zN.c[1], zN.c[2]);
+    const e3 zsN = e3_pow2k(e3_scale(zeta, gl_inv(vp.shift)), logn);
+    auto mul_theta = [](const e3 &a) { return e3_make(a.c[2], gl_add(a.c[0], a.c[2]), a.c[1]); };      // theta^3 = theta + 1
+    e3 q = e3_base(0), zpow = e3_base(1);
+    for (size_t j = 0; j < Q; j++) {
+        const u64 *p = &ev_z[3 * (Wt + 3 * j)];
+        const e3 qj = e3_add(e3_add(e3_make(p[0], p[1], p[2]), mul_theta(e3_make(p[3], p[4], p[5]))), mul_theta(mul_theta(e3_make(p[6], p[7], p[8]))));
+        q = e3_add(q, e3_mul(zpow, qj));
+        zpow = e3_mul(zpow, zsN);
+    }
+    const e3 rhs = e3_mul(q, zh);
+    if (memcmp(lhs.c, rhs.c, 24) == 0) *v = ZP_VERDICT_ACCEPT;
+    return ZP_OK;
+}
+
+int32_t header_phase(const char *text, size_t len, const ProgramInfo &pg, const VerifyParams &vp, const HostPoseidon &H, Pending *pd, PublicSponge *ps = nullptr) {
     auto verdict = [&](int v) { pd->verdict = v; return ZP_OK; };
     ProofHeader h;
     const bool bn = vp.H254 != nullptr;
@@ -687,7 +835,7 @@ int32_t header_phase(const char *text, size_t len, const ProgramInfo &pg, const 
     HostSponge tr_gl(H);
     static const HostPoseidon254 no_tables;
     HostSponge254 tr_bn(bn ? *vp.H254 : no_tables);
-    Transcript &tr = bn ? (Transcript &)tr_bn : (Transcript &)tr_gl;
+    Transcript &tr = ps ? (Transcript &)*ps : bn ? (Transcript &)tr_bn : (Transcript &)tr_gl;      // ps: the transcript is READ (an inner header of an aggregated proof)
     auto root_ok = [&](const u64 *r) { return !bn || fr_is_canonical_u64(r); };      // "malformed BN128 root"
     {
         std::vector<u64> head = {(u64)logn, (u64)logb, (u64)W, (u64)W2, (u64)vp.fri_logf, (u64)vp.fri_final_log, (u64)vp.n_queries, (u64)vp.pow_bits, vp.root32, vp.shift,
@@ -721,29 +869,16 @@ int32_t header_phase(const char *text, size_t len, const ProgramInfo &pg, const 
     tr.absorb(h.ev_zw.data(), h.ev_zw.size());
     const e3 gamma = tr.challenge();
 
-    // 2. the constraint identity at zeta: sum_k alpha^k C_k(zeta) = q(zeta) Z_H(zeta)
-    {
-        std::vector<u64> cs(3 * pg.K);
-        if (pubchal.empty()) pubchal.push_back(0);
-        bool on_domain = false;
-        const int32_t rc = program_eval_ext_impl(pg.words, pg.n_words, (const uint64_t *)pubchal.data(), (int32_t)(pg.n_pub + pg.n_chal), logn, vp.root32, (const uint64_t *)zeta.c,
-                                                 (const uint64_t *)h.ev_z.data(), (const uint64_t *)h.ev_zw.data(), (int32_t)Wt, (uint64_t *)cs.data(), (int32_t)pg.K, vp.threads, nullptr, 0, &on_domain);
-        if (rc != ZP_OK && !on_domain) return rc;                   // a blob the evaluator refuses is the caller's mistake, not a rejected proof
-        if (rc != ZP_OK) return verdict(ZP_VERDICT_IDENTITY);       // zeta on the trace domain: nothing can be said at it
-        e3 lhs = e3_base(0), ap = e3_base(1);
-        for (size_t k = 0; k < pg.K; k++) { lhs = e3_add(lhs, e3_mul(ap, e3_make(cs[3 * k], cs[3 * k + 1], cs[3 * k + 2]))); ap = e3_mul(ap, alpha); }
-        const e3 zN = e3_pow2k(zeta, logn), zh = e3_make(gl_sub(zN.c[0], 1), zN.c[1], zN.c[2]);
-        const e3 zsN = e3_pow2k(e3_scale(zeta, gl_inv(vp.shift)), logn);
-        auto mul_theta = [](const e3 &a) { return e3_make(a.c[2], gl_add(a.c[0], a.c[2]), a.c[1]); };      // theta^3 = theta + 1
-        e3 q = e3_base(0), zpow = e3_base(1);
-        for (size_t j = 0; j < Q; j++) {
-            const u64 *p = &h.ev_z[3 * (Wt + 3 * j)];
-            const e3 qj = e3_add(e3_add(e3_make(p[0], p[1], p[2]), mul_theta(e3_make(p[3], p[4], p[5]))), mul_theta(mul_theta(e3_make(p[6], p[7], p[8]))));
-            q = e3_add(q, e3_mul(zpow, qj));
-            zpow = e3_mul(zpow, zsN);
-        }
-        const e3 rhs = e3_mul(q, zh);
-        if (memcmp(lhs.c, rhs.c, 24) != 0) return verdict(ZP_VERDICT_IDENTITY);
+    // 2. the constraint identity at zeta: sum_k alpha^k C_k(zeta) = q(zeta) Z_H(zeta) -- now, or once the caller has the fixed columns of all its headers
+    pd->zeta = zeta; pd->gamma = gamma;
+    if (pubchal.empty()) pubchal.push_back(0);
+    if (pd->defer_identity) {
+        pd->id_pending = true; pd->id_pubchal = pubchal; pd->id_alpha = alpha; pd->ev_z = h.ev_z; pd->ev_zw = h.ev_zw;
+    } else {
+        int v;
+        const int32_t rc = identity_at_zeta(pg, vp, pubchal, alpha, zeta, h.ev_z, h.ev_zw, nullptr, vp.threads, &v);
+        if (rc != ZP_OK) return rc;
+        if (v != ZP_VERDICT_ACCEPT) return verdict(v);
     }
 
     // 3. the FRI transcript
@@ -751,6 +886,7 @@ int32_t header_phase(const char *text, size_t len, const ProgramInfo &pg, const 
     const int stop = vp.fri_final_log + logb;
     while (cur > stop) { const int f = vp.fri_logf < cur - stop ? vp.fri_logf : cur - stop; pd->sched.push_back({cur, f}); cur -= f; }
     const int final_log = cur;
+    pd->final_log = final_log;
     const size_t n_fri = pd->sched.size();
     if (!h.has_fri_roots || !h.has_final || h.fri_roots.size() != 4 * n_fri) return verdict(ZP_VERDICT_MALFORMED);
     for (size_t l = 0; l < n_fri; l++)
@@ -761,19 +897,28 @@ int32_t header_phase(const char *text, size_t len, const ProgramInfo &pg, const 
         if (h.final_l[c].size() != ((size_t)1 << final_log)) return verdict(ZP_VERDICT_MALFORMED);
     for (int c = 0; c < 3; c++) tr.absorb(h.final_l[c].data(), h.final_l[c].size());
     // 4. grinding
+    u64 pow_seed[4] = {0, 0, 0, 0};
     if (vp.pow_bits) {
         u64 seed[4];
         tr.squeeze(4, seed);
+        memcpy(pow_seed, seed, 32);
         if (!h.has_nonce || h.nonce >= GL_P) return verdict(ZP_VERDICT_POW);
         u64 s[12] = {seed[0], seed[1], seed[2], seed[3], (u64)h.nonce, 0, 0, 0, 0, 0, 0, 0};
-        H.perm(s);
-        if (s[0] >> (64 - vp.pow_bits)) return verdict(ZP_VERDICT_POW);
+        if (!ps) {
+            H.perm(s);
+            if (s[0] >> (64 - vp.pow_bits)) return verdict(ZP_VERDICT_POW);
+        }
         { const u64 nonce = h.nonce; tr.absorb(&nonce, 1); }
     }
     // 5. the indices the transcript dictates
     pd->qidx.resize(nq);
     tr.squeeze(nq, pd->qidx.data());
     for (u64 &v : pd->qidx) v &= M - 1;
+    if (ps && vp.pow_bits) {                   // the grinding hash is the last permutation of a public transcript
+        u64 seed[4];
+        memcpy(seed, pow_seed, 32);
+        if (ps->pow_digest0(seed, h.nonce) >> (64 - vp.pow_bits)) return verdict(ZP_VERDICT_POW);
+    }
     const bool header_only = (vp.flags & ZP_VERIFY_HEADER_ONLY) != 0;
     size_t q_begin = 0, q_end = 0;
     int32_t nq_text = 0, has_s2 = 0, nf_text = 0, widths[48], depths[48];
@@ -912,49 +1057,32 @@ void scan_verdict(Pending *pd, const VerifyParams &vp, bool has_s2) {
     }
 }
 
-int32_t verify_batch_impl(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const char *const *proofs, const size_t *lens, int32_t n_proofs, VerifyParams vp,
-                          int32_t *verdicts, int32_t *where, uint64_t *h_indices) {
-    if (!h_program || !proofs || !lens || !verdicts || n_proofs < 1 || n_proofs > (1 << 20)) return ZP_ERR_ARG;
-    for (int32_t i = 0; i < n_proofs; i++)
-        if (!proofs[i]) return ZP_ERR_ARG;
-    if (vp.logn < 1 || vp.logb < 1 || vp.logn + vp.logb > 30 || vp.fri_logf < 1 || vp.fri_logf > 4 || vp.fri_final_log < 0 || vp.fri_final_log >= vp.logn || vp.n_queries < 1 ||
-        vp.n_queries > 4096 || vp.pow_bits < 0 || vp.pow_bits > 40 || (vp.flags & ~(uint32_t)(ZP_VERIFY_HEADER_ONLY | ZP_VERIFY_TRUST_OPENINGS)))
-        return ZP_ERR_ARG;
-    // the statement
+// the verifier's own parameters, and a statement: what the header phase needs to know of a program blob (false: not a program a STARK here is over)
+bool params_in_range(const VerifyParams &vp) {
+    return !(vp.logn < 1 || vp.logb < 1 || vp.logn + vp.logb > 30 || vp.fri_logf < 1 || vp.fri_logf > 4 || vp.fri_final_log < 0 || vp.fri_final_log >= vp.logn || vp.n_queries < 1 ||
+             vp.n_queries > 4096 || vp.pow_bits < 0 || vp.pow_bits > 40 || (vp.flags & ~(uint32_t)(ZP_VERIFY_HEADER_ONLY | ZP_VERIFY_TRUST_OPENINGS)));
+}
+bool program_info(const uint64_t *h_program, size_t program_words, ProgramInfo *out) {
     static const unsigned char magic[8] = {'Z', 'P', 'A', 'I', 'R', '1', 0, 0};
-    if (program_words < 12 || memcmp(h_program, magic, 8) != 0 || !zpi_program_fixed_table(h_program, program_words, nullptr)) return ZP_ERR_ARG;
-    ProgramInfo pg;
+    if (program_words < 12 || memcmp(h_program, magic, 8) != 0 || !zpi_program_fixed_table(h_program, program_words, nullptr)) return false;
+    ProgramInfo &pg = *out;
     pg.words = h_program; pg.n_words = program_words;
     pg.W = h_program[1]; pg.W2 = h_program[2]; pg.n_pub = h_program[4]; pg.n_chal = h_program[5]; pg.K = h_program[8]; pg.n_s2 = h_program[10]; pg.Q = h_program[11];
-    if (pg.W < 1 || pg.W >= 4096 || pg.W2 >= 4096 || pg.K < 1 || pg.Q < 1 || pg.Q > 16 || (pg.n_s2 == 0) != (pg.W2 == 0) || pg.n_chal != (pg.n_s2 ? 3u : 0u)) return ZP_ERR_ARG;
-    {
-        uint8_t dg[32];
-        Sha256::digest((const uint8_t *)h_program, program_words * 8, dg);
-        for (int i = 0; i < 8; i++) snprintf(pg.digest_hex + 2 * i, 3, "%02x", dg[i]);
-        for (int i = 0; i < 4; i++) { u64 w = 0; for (int b = 7; b >= 0; b--) w = (w << 8) | dg[8 * i + b]; pg.digest_words[i] = w % GL_P; }
-    }
-    vp.root32 = ctx ? ctx->root32 : ZP_ROOT32_DEFAULT;
-    vp.shift = ctx ? ctx->coset_shift : ZP_SHIFT_DEFAULT;
-    const HostPoseidon H = {ctx ? ctx->h_rc : (const u64 *)ZP_POSEIDON_DEFAULT_RC, ctx ? ctx->h_mds : (const u64 *)ZP_POSEIDON_DEFAULT_MDS};
-    const bool has_s2 = pg.n_s2 != 0, trust = (vp.flags & ZP_VERIFY_TRUST_OPENINGS) != 0, bn = vp.H254 != nullptr;
+    if (pg.W < 1 || pg.W >= 4096 || pg.W2 >= 4096 || pg.K < 1 || pg.Q < 1 || pg.Q > 16 || (pg.n_s2 == 0) != (pg.W2 == 0) || pg.n_chal != (pg.n_s2 ? 3u : 0u)) return false;
+    uint8_t dg[32];
+    Sha256::digest((const uint8_t *)h_program, program_words * 8, dg);
+    for (int i = 0; i < 8; i++) snprintf(pg.digest_hex + 2 * i, 3, "%02x", dg[i]);
+    for (int i = 0; i < 4; i++) { u64 w = 0; for (int b = 7; b >= 0; b--) w = (w << 8) | dg[8 * i + b]; pg.digest_words[i] = w % GL_P; }
+    return true;
+}
+
+// The query phase of every proof whose header passed: the openings of all of them in ONE launch on a ctx (here on the host without one), the DEEP sum
+// and the folds at every query, then the first failing check per proof
+int32_t queries_phase(zp_ctx *ctx, const VerifyParams &vp, const HostPoseidon &H, std::vector<Pending> &pend, bool has_s2) {
+    const bool trust = (vp.flags & ZP_VERIFY_TRUST_OPENINGS) != 0, bn = vp.H254 != nullptr;
     const size_t nq = (size_t)vp.n_queries;
-
-    std::vector<Pending> pend((size_t)n_proofs);
-    std::vector<int32_t> hrc((size_t)n_proofs, ZP_OK);
-    // headers: a transcript is a serial chain, proofs are independent
-    spread((size_t)n_proofs, n_proofs > 1 ? vp.threads : 1, [&](size_t i) {
-        try { VerifyParams one = vp; if (n_proofs > 1) one.threads = 1; hrc[i] = header_phase(proofs[i], lens[i], pg, one, H, &pend[i]); }
-        catch (const std::bad_alloc &) { hrc[i] = ZP_ERR_NOMEM; }
-        catch (...) { hrc[i] = ZP_ERR_INTERNAL; }
-    });
-    for (int32_t r : hrc)
-        if (r != ZP_OK) {
-            if (ctx) ctx->err = r == ZP_ERR_UNSUPPORTED ? "a proof in BN128-hash mode handed to the Goldilocks-mode call (or a build without the openings parser)" : "the program blob could not be evaluated at the proof's point";
-            return r;
-        }
-
     // the openings of every proof that got this far, tree by tree (a wave of the device kernel then holds one tree shape), and their arithmetic
-    std::vector<std::vector<u64>> canon((size_t)n_proofs);
+    std::vector<std::vector<u64>> canon(pend.size());
     std::vector<ZpOpening> ops;
     std::vector<u64> roots;
     int Tmax = 0;
@@ -1014,6 +1142,37 @@ int32_t verify_batch_impl(zp_ctx *ctx, const uint64_t *h_program, size_t program
         spread(nq, vp.threads, [&](size_t q) { query_arith(pd, vp, gp, canon[i], q, &pd.arith[q * (pd.sched.size() + 1)]); });
         scan_verdict(&pd, vp, has_s2);
     }
+    return ZP_OK;
+}
+
+int32_t verify_batch_impl(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const char *const *proofs, const size_t *lens, int32_t n_proofs, VerifyParams vp,
+                          int32_t *verdicts, int32_t *where, uint64_t *h_indices) {
+    if (!h_program || !proofs || !lens || !verdicts || n_proofs < 1 || n_proofs > (1 << 20)) return ZP_ERR_ARG;
+    for (int32_t i = 0; i < n_proofs; i++)
+        if (!proofs[i]) return ZP_ERR_ARG;
+    if (!params_in_range(vp)) return ZP_ERR_ARG;
+    ProgramInfo pg;
+    if (!program_info(h_program, program_words, &pg)) return ZP_ERR_ARG;
+    vp.root32 = ctx ? ctx->root32 : ZP_ROOT32_DEFAULT;
+    vp.shift = ctx ? ctx->coset_shift : ZP_SHIFT_DEFAULT;
+    const HostPoseidon H = {ctx ? ctx->h_rc : (const u64 *)ZP_POSEIDON_DEFAULT_RC, ctx ? ctx->h_mds : (const u64 *)ZP_POSEIDON_DEFAULT_MDS};
+    const size_t nq = (size_t)vp.n_queries;
+
+    std::vector<Pending> pend((size_t)n_proofs);
+    std::vector<int32_t> hrc((size_t)n_proofs, ZP_OK);
+    // headers: a transcript is a serial chain, proofs are independent
+    spread((size_t)n_proofs, n_proofs > 1 ? vp.threads : 1, [&](size_t i) {
+        try { VerifyParams one = vp; if (n_proofs > 1) one.threads = 1; hrc[i] = header_phase(proofs[i], lens[i], pg, one, H, &pend[i]); }
+        catch (const std::bad_alloc &) { hrc[i] = ZP_ERR_NOMEM; }
+        catch (...) { hrc[i] = ZP_ERR_INTERNAL; }
+    });
+    for (int32_t r : hrc)
+        if (r != ZP_OK) {
+            if (ctx) ctx->err = r == ZP_ERR_UNSUPPORTED ? "a proof in BN128-hash mode handed to the Goldilocks-mode call (or a build without the openings parser)" : "the program blob could not be evaluated at the proof's point";
+            return r;
+        }
+
+    ZP_TRY(queries_phase(ctx, vp, H, pend, pg.n_s2 != 0));
     for (int32_t i = 0; i < n_proofs; i++) verdicts[i] = pend[i].verdict;
     if (where) *where = pend[0].where;
     // the indices exist once the transcript got to them: an accepted proof, or one rejected by the check on the indices or a later one
@@ -1055,6 +1214,379 @@ int32_t tables254(zp_ctx *ctx, int32_t rp, const uint64_t *h_rc, const uint64_t 
         const fr m = fr_to_mont(fr_from_u64(w));
         memcpy(i < nrc ? &H->rc[9 * i] : &H->mds[9 * (i - nrc)], m.l, 36);
     }
+    return ZP_OK;
+}
+
+// ================================================================================================================================
+// The verifier of AGGREGATED proofs behind zp_aggregate_verify / zp_aggregate_verify_batch: what GenAggregatedProof returns and GenFinalProof takes.
+//   text = {"shape"?, "inner": [header ...], "children"?: [node ...], "stark": proof}      node = {"shape", "inner", "children"?}
+// A node's "inner" are HEADERS (no "queries").  A STARK over the verifier AIR of the node's shape vouches for them: the outer "stark" for the top
+// node, header i of the parent for child i -- its public inputs are then facts.  Accepting means every chunk proof at the leaves verifies:
+//   the outer STARK verifies under the statement of the top shape (header and query phases above; Goldilocks-hash mode);
+//   per node, natively, what needs no opening: every header passes the header phase with its transcript READ off the vouching public inputs
+//   (PublicSponge; the stream used up exactly), and those public inputs are exactly, in order: roots | leaf index of every (slot, proof, tree) |
+//   transcripts | the arithmetic constants per proof | the final-layer value at every slot's position.
+// The protocol is stark/verifier_air.py's and stark/prover.py's; the checker's independent statement is oracle/aggregate_verify.py (verify_tree).
+// Order of the checks (the first failing one decides): the grammar of the whole text; its depth (more than AGG_MAX_DEPTH levels of nodes: TREE); the outer STARK (header, identity, queries); then the nodes
+// depth-first in text order (pre-order number 0 = the top node), per node: its structure (TREE / PARAMS), its headers in order (each: header phase,
+// identity), the length of the transcript section (TRANSCRIPT), the other sections (PUBLICS).
+// The identity at zeta of EVERY header of every text of a call takes its fixed columns from one zp_program_fixed_eval_ext_batch per distinct
+// statement: the challenges come from the public stream, so all (program, public inputs, zeta) are known before anything is evaluated.
+enum { SHAPE_KEYS = 13, AGG_MAX_DEPTH = 8 };
+const char *const SHAPE_KEY[SHAPE_KEYS] = {"logn", "logb", "W", "W2", "Wq", "n_queries", "fri_logf", "fri_final_log", "n_proofs", "n_pub_inner", "pow_bits", "root32", "shift"};
+const u64 SHAPE_MAX[SHAPE_KEYS] = {30, 8, 4096, 4096, 64, 4096, 4, 16, 64, 1u << 24, 64, GL_P - 1, GL_P - 1};
+
+// a shape dictionary (stark/verifier_air.py Shape.from_dict: every member bounded before it sizes anything).  The return value is the GRAMMAR
+// (an object of exactly these members, each a non-negative integer < 2^64, each once); *in_range the bounds
+bool parse_shape(Cur &c, u64 *v, bool *in_range) {
+    bool got[SHAPE_KEYS] = {};
+    const bool ok = each_member(c, [&](const char *b, const char *e) {
+        for (int i = 0; i < SHAPE_KEYS; i++)
+            if (c.key_is(b, e, SHAPE_KEY[i])) { if (once(c, got[i])) { uint64_t x = 0; c.u64v(&x); v[i] = x; } return; }
+        c.ok = false;
+    });
+    if (!ok || !c.ok) return false;
+    *in_range = true;
+    for (int i = 0; i < SHAPE_KEYS; i++)
+        if (!got[i] || v[i] > SHAPE_MAX[i]) *in_range = false;
+    if (v[0] < 1 || v[1] < 1 || v[2] < 1 || v[4] < 1 || v[5] < 1 || v[6] < 1 || v[8] < 1 || v[0] + v[1] > 32 || v[11] < 2 || v[12] < 1) *in_range = false;
+    if (v[0] + v[1] <= v[7] + v[1] || v[0] + v[1] < 2) *in_range = false;      // no committed FRI layer
+    return true;
+}
+
+struct Span { const char *p; size_t n; };
+struct AggNode {
+    bool has_shape = false, shape_ok = false, has_inner = false, has_children = false, has_stark = false, too_deep = false;
+    u64 shape[SHAPE_KEYS] = {};
+    std::vector<Span> inner;
+    std::vector<AggNode> kids;
+    Span stark = {nullptr, 0};
+};
+
+bool object_span(Cur &c, Span *out) {
+    c.ws();
+    const char *b = c.p;
+    if (!c.peek('{')) return c.ok = false;
+    c.skip_value();
+    *out = {b, (size_t)(c.p - b)};
+    return c.ok;
+}
+
+// depth: 1 for the top node.  A node at AGG_MAX_DEPTH that has children is marked too_deep and its children are skipped, not walked
+bool parse_node(Cur &c, AggNode *nd, int depth) {
+    const bool ok = each_member(c, [&](const char *b, const char *e) {
+        if (c.key_is(b, e, "shape")) { if (once(c, nd->has_shape)) parse_shape(c, nd->shape, &nd->shape_ok); }
+        else if (c.key_is(b, e, "stark")) { if (once(c, nd->has_stark)) object_span(c, &nd->stark); }
+        else if (c.key_is(b, e, "inner")) {
+            if (!once(c, nd->has_inner) || !c.need('[') || c.eat(']')) return;
+            for (;;) {
+                Span sp;
+                if (!object_span(c, &sp)) return;
+                nd->inner.push_back(sp);
+                if (c.eat(',')) continue;
+                c.need(']');
+                return;
+            }
+        } else if (c.key_is(b, e, "children")) {
+            if (!once(c, nd->has_children) || !c.need('[') || c.eat(']')) return;
+            for (;;) {
+                if (depth >= AGG_MAX_DEPTH) { Span sp; nd->too_deep = true; if (!object_span(c, &sp)) return; }
+                else { nd->kids.emplace_back(); if (!parse_node(c, &nd->kids.back(), depth + 1)) { c.ok = false; return; } }
+                if (c.eat(',')) continue;
+                c.need(']');
+                return;
+            }
+        } else c.skip_value();
+    });
+    return ok && c.ok;
+}
+
+bool too_deep(const AggNode &nd) {
+    if (nd.too_deep) return true;
+    for (const AggNode &k : nd.kids)
+        if (too_deep(k)) return true;
+    return false;
+}
+
+struct AggStmt { bool leaf = false; u64 shape[SHAPE_KEYS] = {}; ProgramInfo pg; VerifyParams vp; size_t n_slots = 0; };
+
+int find_stmt(const std::vector<AggStmt> &st, const u64 *shape) {      // shape = NULL: the leaf statement
+    for (size_t i = 0; i < st.size(); i++)
+        if (shape ? !st[i].leaf && memcmp(st[i].shape, shape, sizeof st[i].shape) == 0 : st[i].leaf) return (int)i;
+    return -1;
+}
+
+struct HeaderJob {
+    Span text = {nullptr, 0};
+    int stmt = -1;
+    ProofHeader raw;                           // the header as the text has it (public inputs, roots, final layer: compared unreduced)
+    Pending pd;
+    int id_verdict = ZP_VERDICT_ACCEPT;
+    int32_t rc = ZP_OK;
+};
+struct NodeJob {
+    const AggNode *nd = nullptr;
+    int stmt_own = -1, stmt_inner = -1;
+    const std::vector<u64> *pubs = nullptr;    // the vouching STARK's public inputs
+    std::vector<HeaderJob> hdr;
+    int verdict = ZP_VERDICT_ACCEPT;           // decided while planning (structure): the node is not run
+    int post_verdict = ZP_VERDICT_ACCEPT;      // after its headers: the sections of the public inputs
+    int32_t rc = ZP_OK;
+};
+struct TextJob {
+    AggNode top;
+    int verdict = ZP_VERDICT_ACCEPT, where = -1, top_stmt = -1;
+    HeaderJob outer;
+    std::vector<NodeJob *> nodes;              // pre-order
+    ~TextJob() { for (NodeJob *n : nodes) delete n; }
+    TextJob() = default;
+    TextJob(const TextJob &) = delete;
+    TextJob &operator=(const TextJob &) = delete;
+};
+
+void fri_schedule(const VerifyParams &vp, std::vector<std::pair<int, int>> *sched, int *final_log) {
+    int cur = vp.logn + vp.logb;
+    const int stop = vp.fri_final_log + vp.logb;
+    while (cur > stop) { const int f = vp.fri_logf < cur - stop ? vp.fri_logf : cur - stop; sched->push_back({cur, f}); cur -= f; }
+    *final_log = cur;
+}
+
+// the structure of a node and of everything below it, pre-order; nothing is hashed or evaluated here
+void plan_node(TextJob *tj, const AggNode &nd, const std::vector<u64> *pubs, const std::vector<AggStmt> &st, bool top) {
+    NodeJob *nj = new NodeJob;
+    tj->nodes.push_back(nj);
+    nj->nd = &nd; nj->pubs = pubs;
+    auto stop = [&](int v) { nj->verdict = v; };
+    if (!nd.has_inner) return stop(ZP_VERDICT_MALFORMED);
+    if (nd.has_shape && !nd.shape_ok) return stop(ZP_VERDICT_MALFORMED);
+    if (nd.inner.empty() || (!nd.has_shape && !top)) return stop(ZP_VERDICT_TREE);
+    nj->hdr.resize(nd.inner.size());
+    for (size_t i = 0; i < nd.inner.size(); i++) {
+        nj->hdr[i].text = nd.inner[i];
+        if (!parse_header(nd.inner[i].p, nd.inner[i].n, false, &nj->hdr[i].raw)) return stop(ZP_VERDICT_MALFORMED);
+    }
+    for (const HeaderJob &h : nj->hdr)
+        if (h.raw.has_queries) return stop(ZP_VERDICT_TREE);      // an aggregated proof carries no openings of its inner proofs
+    if (!nd.kids.empty()) {
+        if (nd.kids.size() != nd.inner.size()) return stop(ZP_VERDICT_TREE);
+        for (const AggNode &k : nd.kids) {
+            if (k.has_shape && !k.shape_ok) return stop(ZP_VERDICT_MALFORMED);
+            if (!k.has_shape || memcmp(k.shape, nd.kids[0].shape, sizeof k.shape) != 0) return stop(ZP_VERDICT_TREE);
+        }
+    }
+    // the statement of this node's shape gives the query slots of the vouching trace; a node without a shape (a level-1 text) takes the first
+    // statement of the table that is not the leaf's
+    if (nd.has_shape) nj->stmt_own = find_stmt(st, nd.shape);
+    else for (size_t i = 0; i < st.size() && nj->stmt_own < 0; i++) if (!st[i].leaf) nj->stmt_own = (int)i;
+    nj->stmt_inner = nd.kids.empty() ? find_stmt(st, nullptr) : find_stmt(st, nd.kids[0].shape);
+    if (nj->stmt_own < 0 || nj->stmt_inner < 0) return stop(ZP_VERDICT_PARAMS);
+    for (HeaderJob &h : nj->hdr) h.stmt = nj->stmt_inner;
+    for (size_t i = 0; i < nd.kids.size(); i++) plan_node(tj, nd.kids[i], &nj->hdr[i].raw.pubs, st, false);
+}
+
+// what the verifier AIR takes as public per inner proof for its arithmetic constraints (stark/verifier_air.py arith_publics): g^1..g^8 with
+// g = 1 / gamma; gamma^(Wall-1); gamma^(Wall+Wt-1); E_z; E_zw; zeta; zeta w; beta_l^j (1 <= j < 2^f) for every committed layer
+void arithmetic_publics(const Pending &pd, const ProgramInfo &pg, const VerifyParams &vp, std::vector<u64> *out) {
+    auto put = [&](const e3 &x) { out->insert(out->end(), x.c, x.c + 3); };
+    const e3 g = e3_inv(pd.gamma);
+    e3 cur = e3_base(1);
+    for (int i = 0; i < 8; i++) { cur = e3_mul(cur, g); put(cur); }
+    const size_t Wt = pg.W + pg.W2, Wall = Wt + 3 * pg.Q;
+    std::vector<e3> gp(Wall + Wt);
+    cur = e3_base(1);
+    for (e3 &x : gp) { x = cur; cur = e3_mul(cur, pd.gamma); }
+    e3 eza = e3_base(0), ezb = e3_base(0);
+    for (size_t k = 0; k < Wall; k++) eza = e3_add(eza, e3_mul(gp[k], e3_make(pd.ev_z[3 * k], pd.ev_z[3 * k + 1], pd.ev_z[3 * k + 2])));
+    for (size_t k = 0; k < Wt; k++) ezb = e3_add(ezb, e3_mul(gp[Wall + k], e3_make(pd.ev_zw[3 * k], pd.ev_zw[3 * k + 1], pd.ev_zw[3 * k + 2])));
+    put(gp[Wall - 1]); put(gp[Wall + Wt - 1]); put(eza); put(ezb); put(pd.zeta); put(e3_scale(pd.zeta, gl_root(vp.root32, vp.logn)));
+    for (size_t l = 0; l < pd.sched.size(); l++) {
+        cur = e3_base(1);
+        for (int j = 1; j < (1 << pd.sched[l].second); j++) { cur = e3_mul(cur, pd.betas[l]); put(cur); }
+    }
+}
+
+// the headers of one node against the vouching public inputs; identities are left pending
+void run_node(NodeJob *nj, const std::vector<AggStmt> &st, const HostPoseidon &H) {
+    const AggStmt &S = st[nj->stmt_inner];
+    const std::vector<u64> &pubs = *nj->pubs;
+    std::vector<std::pair<int, int>> sched;
+    int final_log = 0;
+    fri_schedule(S.vp, &sched, &final_log);
+    if (sched.empty()) { nj->verdict = ZP_VERDICT_PARAMS; return; }      // inner proofs without a committed FRI layer are not aggregated
+    const size_t n_in = nj->hdr.size(), n_slots = st[nj->stmt_own].n_slots, T = 2 + (S.pg.W2 ? 1 : 0) + sched.size(), nq = (size_t)S.vp.n_queries;
+    size_t n_arith = 42;
+    for (auto &lf : sched) n_arith += 3 * (((size_t)1 << lf.second) - 1);
+    const size_t n_merkle = n_in * T * 4 + n_slots * n_in * T, n_tail = n_in * n_arith + n_slots * n_in * 3;
+    if (pubs.size() < n_merkle + n_tail) { nj->verdict = ZP_VERDICT_PUBLICS; return; }
+    PublicSponge ps(pubs.data() + n_merkle, pubs.size() - n_merkle - n_tail);
+    VerifyParams vp = S.vp;
+    vp.flags = ZP_VERIFY_HEADER_ONLY;
+    vp.threads = 1;
+    for (HeaderJob &h : nj->hdr) {
+        ps.reset();                            // a fresh queue per proof on the one stream
+        h.pd.defer_identity = true;
+        try { h.rc = header_phase(h.text.p, h.text.n, S.pg, vp, H, &h.pd, &ps); }
+        catch (const TranscriptMismatch &) { h.pd.verdict = ZP_VERDICT_TRANSCRIPT; }
+        if (h.rc == ZP_ERR_UNSUPPORTED) { h.rc = ZP_OK; h.pd.verdict = ZP_VERDICT_PARAMS; }      // an inner header that names the BN128 hash
+        if (h.rc != ZP_OK) { nj->rc = h.rc; return; }
+        if (h.pd.verdict != ZP_VERDICT_ACCEPT) return;      // the stream position means nothing behind a header that failed
+    }
+    if (ps.pos != ps.n) { nj->post_verdict = ZP_VERDICT_TRANSCRIPT; return; }
+    // roots, then the leaf index of every (slot, proof, tree): the index of query slot mod n_queries, cut to the tree's depth
+    const int logm = S.vp.logn + S.vp.logb;
+    std::vector<int> depths = {logm};
+    if (S.pg.W2) depths.push_back(logm);
+    depths.push_back(logm);
+    for (auto &lf : sched) depths.push_back(lf.first - lf.second);
+    std::vector<u64> want;
+    want.reserve(n_merkle > n_tail ? n_merkle : n_tail);
+    for (const HeaderJob &h : nj->hdr) {
+        want.insert(want.end(), h.raw.root[0].begin(), h.raw.root[0].end());
+        if (S.pg.W2) want.insert(want.end(), h.raw.root[1].begin(), h.raw.root[1].end());
+        want.insert(want.end(), h.raw.root[2].begin(), h.raw.root[2].end());
+        want.insert(want.end(), h.raw.fri_roots.begin(), h.raw.fri_roots.end());
+    }
+    for (size_t g = 0; g < n_slots; g++)
+        for (const HeaderJob &h : nj->hdr)
+            for (int d : depths) want.push_back(h.pd.qidx[g % nq] & (((u64)1 << d) - 1));
+    if (want.size() != n_merkle || memcmp(want.data(), pubs.data(), 8 * n_merkle) != 0) { nj->post_verdict = ZP_VERDICT_PUBLICS; return; }
+    want.clear();
+    for (const HeaderJob &h : nj->hdr) arithmetic_publics(h.pd, S.pg, S.vp, &want);
+    const u64 mask = ((u64)1 << final_log) - 1;
+    for (size_t g = 0; g < n_slots; g++)
+        for (const HeaderJob &h : nj->hdr)
+            for (int c = 0; c < 3; c++) want.push_back(h.raw.final_l[c][h.pd.qidx[g % nq] & mask]);
+    if (want.size() != n_tail || memcmp(want.data(), pubs.data() + pubs.size() - n_tail, 8 * n_tail) != 0) nj->post_verdict = ZP_VERDICT_PUBLICS;
+}
+
+int32_t aggregate_verify_impl(zp_ctx *ctx, const zp_agg_statement *stmts, int32_t n_stmts, const char *const *texts, const size_t *lens, int32_t n_texts, uint32_t flags,
+                              int32_t threads, int32_t *verdicts, int32_t *where) {
+    if (!stmts || n_stmts < 1 || n_stmts > 64 || !texts || !lens || !verdicts || n_texts < 1 || n_texts > (1 << 20) || (flags & ~(uint32_t)ZP_VERIFY_HEADER_ONLY)) return ZP_ERR_ARG;
+    for (int32_t i = 0; i < n_texts; i++)
+        if (!texts[i]) return ZP_ERR_ARG;
+    // the table of statements
+    std::vector<AggStmt> st((size_t)n_stmts);
+    int leaves = 0;
+    for (int32_t i = 0; i < n_stmts; i++) {
+        const zp_agg_statement &a = stmts[i];
+        AggStmt &S = st[i];
+        S.vp = {a.logn, a.logb, a.fri_logf, a.fri_final_log, a.n_queries, a.pow_bits, flags, 1, ctx ? ctx->root32 : ZP_ROOT32_DEFAULT, ctx ? ctx->coset_shift : ZP_SHIFT_DEFAULT, nullptr};
+        if (!a.h_program || !params_in_range(S.vp) || !program_info(a.h_program, a.program_words, &S.pg)) return ZP_ERR_ARG;
+        S.leaf = a.shape_json == nullptr;
+        leaves += S.leaf;
+        if (!S.leaf) {
+            Cur c{a.shape_json, a.shape_json + strlen(a.shape_json)};
+            bool in_range = false;
+            if (!parse_shape(c, S.shape, &in_range) || !in_range) return ZP_ERR_ARG;
+            c.ws();
+            if (c.p != c.end || a.n_slots < 1 || a.n_slots > (1 << 20)) return ZP_ERR_ARG;
+            S.n_slots = (size_t)a.n_slots;
+        }
+    }
+    if (leaves > 1) return ZP_ERR_ARG;
+    const HostPoseidon H = {ctx ? ctx->h_rc : (const u64 *)ZP_POSEIDON_DEFAULT_RC, ctx ? ctx->h_mds : (const u64 *)ZP_POSEIDON_DEFAULT_MDS};
+    const bool header_only = (flags & ZP_VERIFY_HEADER_ONLY) != 0;
+
+    // 1. grammar and structure of every text
+    std::vector<TextJob> tj((size_t)n_texts);
+    struct Unit { TextJob *t; NodeJob *n; };   // n = NULL: the outer STARK's header
+    std::vector<Unit> units;
+    for (int32_t i = 0; i < n_texts; i++) {
+        TextJob &t = tj[i];
+        Cur c{texts[i], texts[i] + lens[i]};
+        const bool ok = parse_node(c, &t.top, 1);
+        c.ws();
+        if (!ok || !c.ok || c.p != c.end || !t.top.has_stark || !t.top.has_inner) { t.verdict = ZP_VERDICT_MALFORMED; continue; }
+        if (t.top.has_shape && !t.top.shape_ok) { t.verdict = ZP_VERDICT_MALFORMED; continue; }
+        if (too_deep(t.top)) { t.verdict = ZP_VERDICT_TREE; continue; }
+        if (t.top.has_shape) t.top_stmt = find_stmt(st, t.top.shape);
+        else for (size_t k = 0; k < st.size() && t.top_stmt < 0; k++) if (!st[k].leaf) t.top_stmt = (int)k;
+        if (t.top_stmt < 0) { t.verdict = ZP_VERDICT_PARAMS; continue; }
+        t.outer.text = t.top.stark; t.outer.stmt = t.top_stmt;
+        if (!parse_header(t.top.stark.p, t.top.stark.n, false, &t.outer.raw)) { t.verdict = ZP_VERDICT_MALFORMED; continue; }
+        units.push_back({&t, nullptr});
+        plan_node(&t, t.top, &t.outer.raw.pubs, st, true);
+        for (NodeJob *n : t.nodes)
+            if (n->verdict == ZP_VERDICT_ACCEPT) units.push_back({&t, n});
+    }
+    // 2. every header phase (a transcript is a serial chain; nodes and texts are independent)
+    spread(units.size(), threads, [&](size_t u) {
+        TextJob &t = *units[u].t;
+        int32_t *rc = units[u].n ? &units[u].n->rc : &t.outer.rc;
+        try {
+            if (units[u].n) { run_node(units[u].n, st, H); return; }
+            t.outer.pd.defer_identity = true;
+            *rc = header_phase(t.outer.text.p, t.outer.text.n, st[t.top_stmt].pg, st[t.top_stmt].vp, H, &t.outer.pd);
+        } catch (const std::bad_alloc &) { *rc = ZP_ERR_NOMEM; }
+        catch (...) { *rc = ZP_ERR_INTERNAL; }
+    });
+    for (const Unit &u : units) {
+        const int32_t rc = u.n ? u.n->rc : u.t->outer.rc;
+        if (rc != ZP_OK) {
+            if (ctx) ctx->err = rc == ZP_ERR_UNSUPPORTED ? "an outer STARK in BN128-hash mode (or a build without the openings parser)" : "a program blob could not be evaluated at a proof's point";
+            return rc;
+        }
+    }
+    // 3. the fixed columns of every pending identity, one call per statement; then the constraint programs
+    std::vector<std::vector<HeaderJob *>> by_stmt(st.size());
+    for (const Unit &u : units) {
+        if (!u.n) { if (u.t->outer.pd.id_pending) by_stmt[u.t->top_stmt].push_back(&u.t->outer); continue; }
+        for (HeaderJob &h : u.n->hdr)
+            if (h.pd.id_pending) by_stmt[h.stmt].push_back(&h);
+    }
+    for (size_t k = 0; k < st.size(); k++) {
+        std::vector<HeaderJob *> &jobs = by_stmt[k];
+        if (jobs.empty()) continue;
+        const AggStmt &S = st[k];
+        const size_t n = jobs.size(), npc = S.pg.n_pub + S.pg.n_chal, n_fixed = (size_t)S.pg.words[3];
+        std::vector<u64> pc(n * npc + 1), zeta(n * 3), fixed(n * n_fixed * 3);
+        std::vector<uint8_t> on_domain(n);
+        for (size_t i = 0; i < n; i++) {
+            if (npc) memcpy(&pc[i * npc], jobs[i]->pd.id_pubchal.data(), 8 * npc);
+            memcpy(&zeta[3 * i], jobs[i]->pd.zeta.c, 24);
+        }
+        const int32_t rc = zp_program_fixed_eval_ext_batch(ctx, S.pg.words, S.pg.n_words, (const uint64_t *)pc.data(), (int32_t)npc, S.vp.logn, S.vp.root32, (const uint64_t *)zeta.data(),
+                                                           (int32_t)n, (uint64_t *)fixed.data(), (int32_t)n_fixed, on_domain.data(), threads);
+        if (rc != ZP_OK) { if (ctx && ctx->err.empty()) ctx->err = "a program blob could not be evaluated at a proof's point"; return rc; }
+        std::vector<int32_t> rcs(n, ZP_OK);
+        spread(n, threads, [&](size_t i) {
+            HeaderJob &h = *jobs[i];
+            if (on_domain[i]) { h.id_verdict = ZP_VERDICT_IDENTITY; return; }
+            try { rcs[i] = identity_at_zeta(S.pg, S.vp, h.pd.id_pubchal, h.pd.id_alpha, h.pd.zeta, h.pd.ev_z, h.pd.ev_zw, (const uint64_t *)&fixed[i * n_fixed * 3], 1, &h.id_verdict); }
+            catch (...) { rcs[i] = ZP_ERR_NOMEM; }
+        });
+        for (int32_t r : rcs)
+            if (r != ZP_OK) return r;
+    }
+    // 4. the query phase of the outer STARKs that got this far, statement by statement (one launch each on a ctx)
+    for (size_t k = 0; k < st.size() && !header_only; k++) {
+        std::vector<TextJob *> live;
+        for (TextJob &t : tj)
+            if (t.verdict == ZP_VERDICT_ACCEPT && t.top_stmt == (int)k && t.outer.id_verdict == ZP_VERDICT_ACCEPT && t.outer.pd.queries_live) live.push_back(&t);
+        if (live.empty()) continue;
+        std::vector<Pending> pend(live.size());
+        for (size_t i = 0; i < live.size(); i++) pend[i] = std::move(live[i]->outer.pd);
+        VerifyParams vp = st[k].vp;
+        vp.threads = threads;
+        const int32_t rc = queries_phase(ctx, vp, H, pend, st[k].pg.n_s2 != 0);
+        for (size_t i = 0; i < live.size(); i++) live[i]->outer.pd = std::move(pend[i]);
+        if (rc != ZP_OK) return rc;
+    }
+    // 5. the first failing check in the documented order
+    for (int32_t i = 0; i < n_texts; i++) {
+        TextJob &t = tj[i];
+        auto header_verdict = [](const HeaderJob &h) { return h.pd.id_pending && h.id_verdict != ZP_VERDICT_ACCEPT ? h.id_verdict : h.pd.verdict; };
+        if (t.verdict == ZP_VERDICT_ACCEPT) t.verdict = header_verdict(t.outer);
+        for (size_t k = 0; k < t.nodes.size() && t.verdict == ZP_VERDICT_ACCEPT; k++) {
+            const NodeJob &n = *t.nodes[k];
+            int v = n.verdict;
+            for (size_t j = 0; j < n.hdr.size() && v == ZP_VERDICT_ACCEPT; j++) v = header_verdict(n.hdr[j]);
+            if (v == ZP_VERDICT_ACCEPT) v = n.post_verdict;
+            if (v != ZP_VERDICT_ACCEPT) { t.verdict = v; t.where = (int)k; }
+        }
+        verdicts[i] = t.verdict;
+    }
+    if (where) *where = tj[0].where;
     return ZP_OK;
 }
 
@@ -1100,6 +1632,19 @@ int32_t zp_stark_verify_batch_bn128(zp_ctx *ctx, const uint64_t *h_program, size
         const VerifyParams vp = {logn, logb, fri_logf, fri_final_log, n_queries, 0, flags, threads, 0, 0, &H254};
         return verify_batch_impl(ctx, h_program, program_words, proofs, lens, n_proofs, vp, verdicts, nullptr, nullptr);
     });
+}
+
+int32_t zp_aggregate_verify(zp_ctx *ctx, const zp_agg_statement *stmts, int32_t n_stmts, const char *text, size_t len, uint32_t flags, int32_t threads, int32_t *verdict,
+                            int32_t *where) {
+    if (!verdict || !where) return ZP_ERR_ARG;
+    *verdict = ZP_VERDICT_MALFORMED;
+    *where = -1;
+    return verify_guarded(ctx, [&] { return aggregate_verify_impl(ctx, stmts, n_stmts, &text, &len, 1, flags, threads, verdict, where); });
+}
+
+int32_t zp_aggregate_verify_batch(zp_ctx *ctx, const zp_agg_statement *stmts, int32_t n_stmts, const char *const *texts, const size_t *lens, int32_t n_texts, uint32_t flags,
+                                  int32_t threads, int32_t *verdicts) {
+    return verify_guarded(ctx, [&] { return aggregate_verify_impl(ctx, stmts, n_stmts, texts, lens, n_texts, flags, threads, verdicts, nullptr); });
 }
 
 }  // extern "C"

@@ -33,6 +33,12 @@ _u64p = C.POINTER(C.c_uint64)
 _vp = C.c_void_p
 
 # every symbol include/zeth_prover.h declares: (restype, argtypes)
+class AggStatement(C.Structure):
+    """zp_agg_statement: one kind of proof that can occur in an aggregated proof's tree"""
+    _fields_ = [("shape_json", C.c_char_p), ("h_program", C.POINTER(C.c_uint64)), ("program_words", C.c_size_t), ("logn", C.c_int32), ("logb", C.c_int32),
+                ("fri_logf", C.c_int32), ("fri_final_log", C.c_int32), ("n_queries", C.c_int32), ("pow_bits", C.c_int32), ("n_slots", C.c_int32)]
+
+
 SIGNATURES = {
     "zp_create": (C.c_int32, [C.POINTER(_vp), C.c_int32]),
     "zp_destroy": (None, [_vp]),
@@ -97,6 +103,11 @@ SIGNATURES = {
     "zp_poly_eval_ext": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, _u64p, _u64p]),
     "zp_program_eval_ext": (C.c_int32, [_u64p, C.c_size_t, _u64p, C.c_int32, C.c_int32, C.c_uint64, _u64p, _u64p, _u64p, C.c_int32, _u64p, C.c_int32, C.c_int32]),
     "zp_program_fixed_eval_ext": (C.c_int32, [_u64p, C.c_size_t, _u64p, C.c_int32, C.c_int32, C.c_uint64, _u64p, _u64p, C.c_int32, C.c_int32]),
+    "zp_aggregate_verify": (C.c_int32, [_vp, C.POINTER(AggStatement), C.c_int32, C.c_char_p, C.c_size_t, C.c_uint32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "zp_aggregate_verify_batch": (C.c_int32, [_vp, C.POINTER(AggStatement), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int32, C.c_uint32, C.c_int32,
+                                              C.POINTER(C.c_int32)]),
+    "zp_program_fixed_eval_ext_batch": (C.c_int32, [_vp, _u64p, C.c_size_t, _u64p, C.c_int32, C.c_int32, C.c_uint64, _u64p, C.c_int32, _u64p, C.c_int32,
+                                                    C.POINTER(C.c_uint8), C.c_int32]),
     "zp_ood_eval": (C.c_int32, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_int32, C.c_int32, C.c_uint64, _u64p, C.c_int32, _u64p, _u64p]),
     "zp_deep_quotient": (C.c_int32, [_vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _u64p, _u64p, _u64p,
                                      _u64p, _u64p, C.c_uint64, _vp]),
@@ -358,6 +369,8 @@ def program_eval_ext(program, pubchal, logn, root32, zeta, ev_z, ev_zw, threads=
 # zp_stark_verify: the verdict classes and the flags (include/zeth_prover.h)
 VERDICT_ACCEPT, VERDICT_MALFORMED, VERDICT_PARAMS, VERDICT_IDENTITY, VERDICT_POW, VERDICT_INDICES, VERDICT_FINAL_DEGREE, VERDICT_OPENING, VERDICT_FRI = range(9)
 VERIFY_HEADER_ONLY, VERIFY_TRUST_OPENINGS = 1, 2
+VERDICT_TRANSCRIPT, VERDICT_PUBLICS, VERDICT_TREE = 9, 10, 11      # zp_aggregate_verify* only
+
 
 
 def _verify_params(params):
@@ -449,6 +462,49 @@ def stark_verify_batch_bn128(program, texts, params, flags=0, prover=None, threa
     return list(out)
 
 
+def agg_statements(entries):
+    """the zp_agg_statement table of zp_aggregate_verify* from (shape dict or None, program, params, n_slots) tuples: shape None is the leaf statement
+    (chunk proofs; n_slots ignored), otherwise the dictionary a node carries under "shape" with the verifier AIR's program for inner proofs of that shape,
+    the verifier's StarkParams (or its dict) of a STARK over it and the query slots of its trace.  Returns (table, what keeps its pointers alive)"""
+    import json
+    table, keep = (AggStatement * len(entries))(), []
+    for st, (shape, program, params, n_slots) in zip(table, entries):
+        prog = np.ascontiguousarray(program, dtype=np.uint64)
+        text = None if shape is None else json.dumps(shape).encode()
+        keep += [prog, text]
+        st.shape_json, st.h_program, st.program_words = text, prog.ctypes.data_as(C.POINTER(C.c_uint64)), prog.size
+        st.logn, st.logb, st.fri_logf, st.fri_final_log, st.n_queries, st.pow_bits = _verify_params(params)
+        st.n_slots = int(n_slots or 0)
+    return table, keep
+
+
+def aggregate_verify(statements, text, flags=0, prover=None, threads=0):
+    """zp_aggregate_verify: (verdict, where) of an aggregated proof TEXT (str or bytes) of any level under the statements `statements` (tuples as
+    agg_statements takes them).  verdict: VERDICT_*; where: the pre-order number of the failing node, -1 for the outer STARK.  prover = None: on the host"""
+    table, keep = agg_statements(statements)
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    verdict, where = C.c_int32(-1), C.c_int32(-1)
+    rc = load_library().zp_aggregate_verify(prover.ctx if prover is not None else None, table, len(table), raw, len(raw), int(flags), threads, C.byref(verdict), C.byref(where))
+    del keep
+    if rc != 0:
+        _verify_error(prover, rc, "zp_aggregate_verify")
+    return verdict.value, where.value
+
+
+def aggregate_verify_batch(statements, texts, flags=0, prover=None, threads=0):
+    """zp_aggregate_verify_batch: the verdicts of several aggregated proof texts under one table of statements: the fixed columns of every header of
+    every text in one evaluation per statement, the openings of the outer STARKs in one launch per statement"""
+    table, keep = agg_statements(statements)
+    raws = [t.encode() if isinstance(t, str) else bytes(t) for t in texts]
+    n = len(raws)
+    ptrs, lens, out = (C.c_char_p * n)(*raws), (C.c_size_t * n)(*[len(r) for r in raws]), (C.c_int32 * n)()
+    rc = load_library().zp_aggregate_verify_batch(prover.ctx if prover is not None else None, table, len(table), ptrs, lens, n, int(flags), threads, out)
+    del keep
+    if rc != 0:
+        _verify_error(prover, rc, "zp_aggregate_verify_batch")
+    return list(out)
+
+
 def wrap_aux(openings, program, pubs, logn, root32, addr):
     """zp_wrap_aux: ([addr, packed sparse fixed columns at zeta ...] as ints, zeta) for a stage B-2 wrap"""
     openings = np.ascontiguousarray(openings, dtype=np.uint64)
@@ -477,6 +533,35 @@ def program_fixed_eval_ext(program, pubchal, logn, root32, zeta, threads=0):
     if rc != 0:
         raise ValueError("zp_program_fixed_eval_ext: malformed program or point (%d)" % rc)
     return out
+
+
+def program_fixed_eval_ext_batch(program, pubchal, logn, root32, zetas, prover=None, threads=0):
+    """zp_program_fixed_eval_ext_batch: the fixed columns of a program at many points, each with its own public inputs (and challenges).
+    pubchal: n_points rows of n_pub + n_chal values; zetas: n_points rows of 3.  Returns (u64[n_points][n_fixed][3], on_domain bool[n_points]): a point on
+    the trace domain or on a column's domain is flagged and its rows are zero.  prover=None: host code; with a Prover the sparse columns of all points
+    run on the device from the knob "fixed_eval_dev_min" (points x entries) on -- the same words either way.  ValueError: malformed input"""
+    prog = np.ascontiguousarray(program, dtype=np.uint64)
+    as_rows = lambda a: a.astype(np.uint64) if isinstance(a, np.ndarray) else np.array([[int(v) for v in row] for row in a], dtype=np.uint64)
+    z = np.ascontiguousarray(as_rows(zetas).reshape(-1, 3))
+    n = z.shape[0]
+    if len(pubchal) != n or any(len(r) != len(pubchal[0]) for r in pubchal):
+        raise ValueError("zp_program_fixed_eval_ext_batch: one row of public inputs per point, all of one length")
+    n_pubchal = len(pubchal[0]) if n else 0
+    pc = np.ascontiguousarray(as_rows(pubchal).reshape(-1)) if n and n_pubchal else np.zeros(1, dtype=np.uint64)
+    n_fixed = int(prog[3]) if prog.size > 3 and int(prog[3]) <= 4096 else 0
+    out = np.zeros((n, n_fixed, 3), dtype=np.uint64)
+    flags = np.zeros(max(n, 1), dtype=np.uint8)
+    p = lambda a: a.ctypes.data_as(_u64p)
+    rc = load_library().zp_program_fixed_eval_ext_batch(prover.ctx if prover is not None else None, p(prog), prog.size, p(pc), n_pubchal, logn, int(root32),
+                                                        p(z if n else np.zeros(3, dtype=np.uint64)), n, p(out if out.size else np.zeros(3, dtype=np.uint64)), n_fixed,
+                                                        flags.ctypes.data_as(C.POINTER(C.c_uint8)), threads)
+    if rc == -1:
+        raise ValueError("zp_program_fixed_eval_ext_batch: malformed program or point (%d)" % rc)
+    if rc != 0:
+        if prover is not None:
+            prover._chk(rc)
+        raise ZpError(rc, "zp_program_fixed_eval_ext_batch")
+    return out, flags[:n].astype(bool)
 
 
 def sha256(data):

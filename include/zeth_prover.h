@@ -244,6 +244,18 @@ int32_t zp_program_eval_ext(const uint64_t *h_program, size_t program_words, con
  * (service/wrap_arith.py), a reader of its public input recomputes them.  Same arguments and refusals as zp_program_eval_ext.                       */
 int32_t zp_program_fixed_eval_ext(const uint64_t *h_program, size_t program_words, const uint64_t *h_pubchal, int32_t n_pubchal, int32_t logn,
                                   uint64_t root32, const uint64_t zeta3[3], uint64_t *h_fixed, int32_t n_fixed, int32_t threads);
+/* The same at n_points points, each with its own public inputs -- what a verifier of an aggregated proof asks for the headers of a whole tree, all
+ * over one verifier AIR: h_pubchal u64[n_points][n_pubchal], h_zeta u64[n_points][3], h_fixed u64[n_points][n_fixed][3], h_on_domain u8[n_points].
+ * Point by point the results and refusals of zp_program_fixed_eval_ext (malformed blob, non-canonical input, n_fixed that is not the program's:
+ * ZP_ERR_ARG for the call), with one difference: a zeta on the trace domain, or on the domain of one column at a nonzero entry, sets h_on_domain[i],
+ * leaves that point's rows zero and does not fail the call -- to a verifier it is a property of one proof, not a mistake of its caller.
+ * ctx = NULL: the host code, point after point.  With a ctx and at least "fixed_eval_dev_min" (zp_set_tuning) (points x sparse entries) the sparse
+ * columns of all points run on the device (csrc/fixed_eval.hip: a workgroup per (point, 1024 entries of a column) sums fractions in F_{p^3}, one
+ * inversion per (point, column)); the per-entry tables of the last four (program, logn, root32) stay on the ctx.  F_{p^3} arithmetic is exact: both
+ * paths give the same words, the knob changes speed only.  The call returns synchronised.                                                         */
+int32_t zp_program_fixed_eval_ext_batch(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const uint64_t *h_pubchal, int32_t n_pubchal,
+                                        int32_t logn, uint64_t root32, const uint64_t *h_zeta, int32_t n_points, uint64_t *h_fixed, int32_t n_fixed,
+                                        uint8_t *h_on_domain, int32_t threads);
 /* Out-of-domain evaluations FROM VALUES (barycentric form; round 5: the provers keep no coefficient buffers for this any more).
  * Column c is a polynomial p_c of degree < 2^logn given by its values on the coset shift*<w>, w of order 2^logn:
  *   d_cols[c * col_stride + i * row_stride] = p_c(shift * w^i)      (row_stride = 2^logb reads the 2^logn-point sub-coset of an
@@ -602,7 +614,9 @@ int32_t zp_fixed_base_mul_bn254_g2(zp_ctx *ctx, const uint32_t *h_base, const ui
  * constants (a machine without a GPU).  With a ctx the leaf hashes and paths of ALL openings of a call are one launch (zp_merkle_verify_batch's
  * kernels); the transcript, the identity and the arithmetic at the queries are host code on `threads` threads (<= 0: one per core, at most 16). */
 enum { ZP_VERDICT_ACCEPT = 0, ZP_VERDICT_MALFORMED = 1, ZP_VERDICT_PARAMS = 2, ZP_VERDICT_IDENTITY = 3, ZP_VERDICT_POW = 4,
-       ZP_VERDICT_INDICES = 5, ZP_VERDICT_FINAL_DEGREE = 6, ZP_VERDICT_OPENING = 7, ZP_VERDICT_FRI = 8 };
+       ZP_VERDICT_INDICES = 5, ZP_VERDICT_FINAL_DEGREE = 6, ZP_VERDICT_OPENING = 7, ZP_VERDICT_FRI = 8,
+       /* zp_aggregate_verify* only */
+       ZP_VERDICT_TRANSCRIPT = 9, ZP_VERDICT_PUBLICS = 10, ZP_VERDICT_TREE = 11 };
 enum { ZP_VERIFY_HEADER_ONLY = 1, ZP_VERIFY_TRUST_OPENINGS = 2 };
 int32_t zp_stark_verify(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const char *proof_json, size_t proof_len,
                         int32_t logn, int32_t logb, int32_t fri_logf, int32_t fri_final_log, int32_t n_queries, int32_t pow_bits,
@@ -669,7 +683,9 @@ int32_t zp_hbm_copy_probe(zp_ctx *ctx, const void *d_src, void *d_dst, size_t by
  * small transform and of the fold by 16: 0 where they measured faster, 1 always, 2 never; "ntt_logt12" 1: radix-4096 passes on 64-KiB tiles, two
  * 512-thread workgroups per CU (2: 128-KiB tiles); "p254_block" 2: the lane-per-permutation Poseidon-BN254 kernel walks its partial rounds one by
  * one instead of in blocks of four; "verify_lane_min" openings per call from which the verifier hashes one opening per lane (0 = 256: a guess, unmeasured);
- * "verify16_lane_min" hash jobs per call from which the BN128-mode verifier hashes one job per lane (0 = 2^14: a guess, unmeasured); 0 = default); not for production hosts */
+ * "verify16_lane_min" hash jobs per call from which the BN128-mode verifier hashes one job per lane (0 = 2^14: a guess, unmeasured); 0 = default;
+ * "fixed_eval_dev_min" (points x sparse entries) from which zp_program_fixed_eval_ext_batch uses the device -- the VALUE is the bound: 0 always the
+ * device, < 0 restores the default 2^15 (derived from profiles/r12_fixed_eval_batch.json, not measured at that size)); not for production hosts */
 int32_t zp_set_tuning(zp_ctx *ctx, const char *key, int32_t value);
 
 /* ---- introspection ------------------------------------------------------------------------- */
@@ -677,6 +693,40 @@ int32_t zp_set_tuning(zp_ctx *ctx, const char *key, int32_t value);
 int32_t zp_ntt_plan_json(zp_ctx *ctx, int32_t logn, char *buf, size_t buflen);
 /* name of the dominant kernel symbol of zp_ntt for this size (for matching rocprof output) */
 int32_t zp_device_info_json(zp_ctx *ctx, char *buf, size_t buflen);
+
+/* ---- aggregated proofs (csrc/verify.hip) ------------------------------------------------------
+ * What GenAggregatedProof returns and GenFinalProof takes, judged natively:
+ *   text = {"shape"?, "inner": [header ...], "children"?: [node ...], "stark": proof}      node = {"shape", "inner", "children"?}
+ * "inner" are the HEADERS of the proofs a node aggregates (no "queries"); a STARK over the verifier AIR of the node's "shape" vouches for them -- the
+ * outer "stark" for the top node, header i of the parent for child i.  A level-1 text may leave "shape" out: it is then judged under the first
+ * statement of the table that is not the leaf's.
+ * stmts: every kind of proof that can occur in the tree.  shape_json = NULL: the leaf statement (chunk proofs: at most one per table); otherwise the
+ * shape dictionary a node carries under "shape" (the thirteen members of stark/verifier_air.py Shape, compared member by member -- order and
+ * whitespace do not matter), with the verifier AIR's program for inner proofs of that shape, the VERIFIER's parameters of a STARK over it and the
+ * query slots of its trace.  The domain (2^32-th root, coset shift) and the Poseidon tables are the ctx's, or the defaults with ctx = NULL.
+ * Checks, the first failing one decides: the grammar of the text (MALFORMED; shape members are range-checked before they size anything); its depth (TREE: more than 8 levels of nodes); the outer
+ * STARK under the top shape's statement, as zp_stark_verify judges it (PARAMS: no such statement; BN128-hash mode: ZP_ERR_UNSUPPORTED); then the
+ * nodes depth-first in text order, per node: its structure (TREE: a header with openings, children that are missing a shape, not one per header
+ * or of mixed shapes; PARAMS: a shape that is in no statement), its headers in order -- the header phase with the Fiat-Shamir
+ * transcript READ off the vouching public inputs (TRANSCRIPT: they absorb other values than the header's, or end early) and the identity at zeta --,
+ * the length of the transcript section (TRANSCRIPT) and the other sections: roots, leaf indices, arithmetic constants, final-layer values (PUBLICS).
+ * *where: the pre-order number of the failing node (0 = the top node), -1 for the outer STARK, the grammar and ACCEPT.
+ * The fixed columns at zeta of every header of the call come from ONE zp_program_fixed_eval_ext_batch per statement (on the device with a ctx).
+ * flags: ZP_VERIFY_HEADER_ONLY skips the outer STARK's openings (GenFinalProof: its final STARK proves them).  ctx = NULL: host alone.
+ * ZP_OK: a verdict was reached; negative: the caller's mistake (null pointer, a statement that is no program or out of range).                      */
+typedef struct zp_agg_statement {
+    const char *shape_json;
+    const uint64_t *h_program;
+    size_t program_words;
+    int32_t logn, logb, fri_logf, fri_final_log, n_queries, pow_bits;
+    int32_t n_slots;
+} zp_agg_statement;
+int32_t zp_aggregate_verify(zp_ctx *ctx, const zp_agg_statement *stmts, int32_t n_stmts, const char *text, size_t len, uint32_t flags,
+                            int32_t threads, int32_t *verdict, int32_t *where);
+/* the same for n_texts texts under one table: the header phases spread over threads, the fixed columns of all texts in one call per statement, the
+ * openings of all outer STARKs of one statement in one launch; verdicts[n_texts]                                                                */
+int32_t zp_aggregate_verify_batch(zp_ctx *ctx, const zp_agg_statement *stmts, int32_t n_stmts, const char *const *texts, const size_t *lens,
+                                  int32_t n_texts, uint32_t flags, int32_t threads, int32_t *verdicts);
 
 #ifdef __cplusplus
 }
