@@ -30,6 +30,27 @@
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) int zp_i32x4;
+typedef __attribute__((address_space(1))) u64 zp_gu64;     // global memory, said so: an address that went through sgpr_opaque has lost what the compiler inferred
+typedef __attribute__((address_space(1))) char zp_gchar;
+
+// A wave-uniform value the compiler may not look through: what is computed from it is computed where it is used (in scalar registers), not
+// ahead of the loop and kept.  No instruction.
+template <bool ON>
+__device__ __forceinline__ u64 sgpr_opaque(u64 x) {
+    if constexpr (!ON) return x;
+    u32 lo = (u32)x, hi = (u32)(x >> 32);   // (as two halves: a 64-bit scalar operand does not get through instruction selection)
+    asm("" : "+s"(lo), "+s"(hi));
+    return ((u64)hi << 32) | lo;
+}
+template <bool ON>
+__device__ __forceinline__ int sgpr_opaque_once(int x) {   // of a loop-invariant value: once per evaluation, not once per kernel
+    if constexpr (!ON) return x;
+    asm volatile("" : "+s"(x));
+    return x;
+}
+
+// the per-tile table of a pass of ntt_pass2_kernel, fixed by the plan for every launch
+constexpr int TAB_NONE = 0, TAB_FIXED = 1 /* output side, the same for every tile */, TAB_TILE = 2 /* output side, per tile */, TAB_IN = 3 /* input side */;
 
 struct PassArgs {
     const u64 *in;
@@ -290,6 +311,13 @@ __device__ __forceinline__ void table_copy_out(u64 *v, const u64 *lds, const u64
 //    top of iteration i and consumed in iteration i+1; the body of an iteration touches only
 //    registers and LDS, and barriers order LDS only.  vmcnt is an in-order counter, so this is what
 //    keeps HBM loads (and the previous tile's stores) in flight under the integer work.
+//  * The loop holds two tiles a trip: the register set that receives the prefetch in one body is the current tile of the other, so no
+//    register is copied from tile to tile (tiles_per_wg odd, 1 included, leaves after the first body).  Which table a pass has (TAB) is a
+//    template argument, so a loop holds its own case only; uniform row and k-step addresses are walked by scalar adds where they are used
+//    (sgpr_opaque) and every load and store takes a scalar base beside a 32-bit lane offset.  Before, sixteen load bases, sixteen store
+//    bases and the k_j of every round were loop invariants that did not fit beside the butterflies' carry pairs and came back through
+//    v_readlane.  Static counts and counters: profiles/r12_ntt_isa_breakdown.txt, r12_pmc_sq_ntt.json.  (LEAN below: the limb form and
+//    the per-lane twiddle chain keep one tile a trip with a hand-over -- two bodies cost them spills.)
 //  * butterflies use the canonical 16-th root 2^12 (shifts only); the user's root enters through
 //    j0inv as a renaming of outputs.
 //  * TRANSPOSE=false (passes 2..m, Pprev >= T): the tile shares s; the inter-pass twiddle w^(e0*k)
@@ -305,9 +333,9 @@ __device__ __forceinline__ void table_copy_out(u64 *v, const u64 *lds, const u64
 //    ordered so that the columns of one tile run next to each other on ONE XCD (workgroup id % 8 picks the XCD), and the
 //    table loads are cacheable, so 7 of 8 reads are hits in that XCD's L2.
 // MODE (non-transposing passes): 0 = last pass without an output product, 1 = a middle pass, or a last pass that multiplies by 1/N:
-// the per-tile table on the output side where flags say so (flags & 3), 2 = table and the per-lane part of a coset power (last pass of
-// the inverse transform in an LDE).
-//    Input-side table (a.itab, MODE 0): the factor w^(Pprev k s) of the pass BEFORE a last pass lands, in the last pass, on row
+// the per-tile table on the output side where TAB says so (TAB_TILE: the inter-pass twiddle, flags & 1; TAB_FIXED: 1/N, flags & 2; TAB_NONE:
+// a plain middle pass), 2 = table (TAB_FIXED) and the per-lane part of a coset power (last pass of the inverse transform in an LDE).
+//    Input-side table (a.itab, MODE 0, TAB_IN): the factor w^(Pprev k s) of the pass BEFORE a last pass lands, in the last pass, on row
 //    r' = s of the tile whose columns u' = k Pprev + c share k (T <= Pprev) -- again R' entries per tile and one product per element, now
 //    applied to the loaded rows.  The pass before the last is then plain (integer work moves from a pass that is bound by instruction
 //    issue to the one that is not), and 1/N of an inverse plan rides in the same entries: no output product at all.  The entries come
@@ -315,7 +343,7 @@ __device__ __forceinline__ void table_copy_out(u64 *v, const u64 *lds, const u64
 // LIMB: the register butterflies and the twiddle products that follow them on the limb form of gl_limb.hpp (16 values x 4 limbs live
 // between the rounds: 3 waves per SIMD, 168 VGPRs); the per-tile table and the LDS copies of the inter-round twiddles hold 32-byte
 // records (the balanced words of w, w 2^24, w 2^48, w 2^72).  Not for the per-lane twiddle chain of a first pass without its table.
-template <int A1, int A2, int A3, int LOGT, bool TRANSPOSE, bool PADDED, int MODE, bool BIG = false, bool LIMB = false>
+template <int A1, int A2, int A3, int LOGT, bool TRANSPOSE, bool PADDED, int MODE, int TAB, bool BIG = false, bool LIMB = false>
 __global__ void __launch_bounds__((1 << (A1 + A2 + A3 + LOGT)) / 16, LIMB ? 3 : 4)   // 4 waves per SIMD: 128 VGPRs, of which v116..v127 are the scratch window of gl_asm.hpp
 ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
     using G = Geo<A1, A2, A3, LOGT>;
@@ -333,7 +361,13 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
     constexpr bool TW1 = TRANSPOSE && MODE == 3;
     constexpr bool CAN_IN = !TRANSPOSE && MODE == 0 && L <= 9;   // instantiations that can take the input-side table
     u64 *itl = twr2 + (TWR_LDS ? R2 * REC : 0);                  // R entries: this tile's input-side factors (a.itab)
-    const bool in_tab = CAN_IN && a.itab != nullptr;
+    // The two-tile loop and the scalar address walks (below) are for the forms that gain registers by them.  The limb form's 168 registers
+    // and the per-lane twiddle chain of a first pass without its table have no room for two bodies with swapped roles: they spill.
+    constexpr bool LEAN = !LIMB && !(TRANSPOSE && MODE == 1);
+    constexpr bool in_tab = TAB == TAB_IN;
+    constexpr bool out_tab = TAB == TAB_FIXED || TAB == TAB_TILE;   // MODE 1 with TAB_NONE: a plain middle pass
+    constexpr bool tile_tab = TAB == TAB_TILE;
+    static_assert((!in_tab || CAN_IN) && (!out_tab || (HAS_TAB && (MODE == 1 || !tile_tab))) && (MODE != 2 || out_tab), "a table the pass has no place for");
     static_assert(!LIMB || (TWR_LDS && (TW1 || !TRANSPOSE)), "limb form: LDS twiddle copies, no per-lane twiddle chain");
     // MODE 3: one-dimensional grid; workgroup id -> (XCD x = id % 8, j = id / 8): column = j % ncols, tile group = (j / ncols) * 8 + x
     u64 col = blockIdx.y, wg_lin = blockIdx.x;
@@ -357,7 +391,9 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
     // 64-bit address arithmetic -- three VALU instructions per load when written naively -- is scalar work.  The byte
     // offset fits 32 bits up to 2^28 rows; larger transforms are the BIG instantiation with 64-bit lane offsets.
     constexpr bool small_n = !BIG;
-    auto fetch_tile = [&](u64 *r, u64 *tl, u64 *th, u64 u0, int tid) {
+    // The uniform part walks from row to row by one scalar add (sgpr_opaque keeps it a chain: sixteen bases computed ahead and held
+    // across the butterflies' carry pairs do not fit the SGPR file and end up in VGPR lanes).
+    auto fetch_tile = [&](u64 *r, u64 *tl, u64 *th, u64 u0, int tid) __attribute__((always_inline)) {
         constexpr int GR = 16 >> A1;
         const u64 valid_rows = a.in_valid >> logNR;     // PADDED: rows >= valid_rows read as zero (in_valid is a multiple of N/R)
 #pragma unroll
@@ -367,11 +403,13 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
             const u32 slot0 = (u32)slot_of(o, 0, G::POS1, A1);
             const u32 lane_bytes = (((u32)slot0 << logNR) + (u32)t) << 3;
             const u64 lane_el = ((u64)slot0 << logNR) + (u64)t;
+            u64 row_at = sgpr_opaque<LEAN>((u64)(src + u0));                             // wave-uniform: row j starts at src + (j << POS1 rows) + u0
 #pragma unroll
             for (int j = 0; j < (1 << A1); j++) {
-                const u64 *rowp = src + (((u64)j << G::POS1) << logNR) + u0;      // wave-uniform
-                const u64 *ptr;
-                if constexpr (small_n) ptr = (const u64 *)((const char *)rowp + lane_bytes);
+                const zp_gu64 *rowp = (const zp_gu64 *)row_at;
+                row_at = sgpr_opaque<LEAN>(row_at + ((8ULL << G::POS1) << logNR));
+                const zp_gu64 *ptr;
+                if constexpr (small_n) ptr = (const zp_gu64 *)((const zp_gchar *)rowp + lane_bytes);
                 else ptr = rowp + lane_el;
                 // short runs (T < 16) want the L2 to merge neighbouring tiles' pieces of a line: plain, cacheable loads
                 u64 val;
@@ -396,7 +434,7 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
             for (int i = 0; i < NTW; i++) { tl[i] = a.twl[e[i] & lm]; th[i] = a.twh[e[i] >> a.lb]; }
         } else {
             if constexpr (MODE == 1) {
-                if (a.flags & 1) {
+                if constexpr (tile_tab) {
                     const u64 e0 = (u0 >> logP) << logP;
 #pragma unroll
                     for (int j = 0; j < TPL; j++) {
@@ -407,7 +445,7 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
                 }
             }
             if constexpr (CAN_IN) {
-                if (in_tab) {
+                if constexpr (in_tab) {
                     const u64 *row = a.itab + ((u0 >> a.logPin) << L);
 #pragma unroll
                     for (int j = 0; j < TPL; j++) tl[j] = row[(tid + j * NT) & (R - 1)];
@@ -432,8 +470,6 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
     fetch_tile(v, twl_c, twh_c, tile0 << LOGT, threadIdx.x);
     // once per workgroup: inter-round twiddles into LDS; an output-side table that is the same for every tile (1/N, the k-part of a
     // coset power: a last pass, flags & 1 clear) is written here and stays
-    const bool out_tab = HAS_TAB && (MODE == 2 || (a.flags & 3) != 0);   // MODE 1 with neither flag: a plain middle pass
-    const bool tile_tab = HAS_TAB && (a.flags & 1) != 0;                 // (flags & 1 comes without 2 and 4: run_one_pass)
     {
         const int tid0 = threadIdx.x;
         if constexpr (LIMB) {
@@ -458,7 +494,7 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
             }
         }
         if constexpr (HAS_TAB) {
-            if (out_tab && !tile_tab) {
+            if constexpr (TAB == TAB_FIXED) {
 #pragma unroll
                 for (int j = 0; j < TPL; j++)
                     if (tid0 + j * NT < R) {
@@ -474,7 +510,7 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
             }
         }
         if constexpr (CAN_IN) {
-            if (in_tab) {
+            if constexpr (in_tab) {
 #pragma unroll
                 for (int j = 0; j < TPL; j++)
                     if (tid0 + j * NT < R) itl[tid0 + j * NT] = twl_c[j];
@@ -485,19 +521,25 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
     // drain the prologue loads here so that the loop is entered with nothing pending: the waitcnt
     // insertion then needs no vmcnt wait inside the body (one there would also drain the prefetch)
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only
-#pragma clang loop unroll(disable)
-    for (int it = 0; it < tiles_per_wg; it++) {
+    // One tile: v, twl_c, twh_c hold tile `it`, the next tile's loads go to vn, twl_n, twh_n.  The loop below calls it twice per trip with the
+    // two register sets in swapped roles, so nothing is copied from tile to tile.
+    auto tile_step = [&](u64 *v, u64 *twl_c, u64 *twh_c, u64 *vn, u64 *twl_n, u64 *twh_n, int it) __attribute__((always_inline)) {
         const u64 u0 = (tile0 + it) << LOGT;
         const bool more = it + 1 < tiles_per_wg;
         // opaque copy of the lane id: keeps the compiler from hoisting every per-lane address of the
         // loop body out of the loop (that costs > 100 VGPRs and spills)
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
+        // ... and of what the uniform addresses and output renamings are made from: sixteen store bases, the k_j of every round and their
+        // LDS slots are a few scalar instructions each where they are used; made ahead of the loop they outnumber the SGPRs that the
+        // butterflies' carry pairs leave, and come back through v_readlane
+        const int j0inv = sgpr_opaque_once<LEAN>(a.j0inv);
+        const int logP = sgpr_opaque_once<LEAN>(a.logPprev);
         if (more) fetch_tile(vn, twl_n, twh_n, u0 + T, tid);
 
         const u64 s = TRANSPOSE ? 0 : (u0 >> logP);
         if constexpr (HAS_TAB) {
-            if (tile_tab) {
+            if constexpr (tile_tab) {
 #pragma unroll
                 for (int j = 0; j < TPL; j++)
                     if (tid + j * NT < R) {
@@ -509,7 +551,7 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
         }
         if constexpr (CAN_IN) {
             // the rows as loaded times this tile's input-side factors (written to itl before the last barrier)
-            if (in_tab) {
+            if constexpr (in_tab) {
 #pragma unroll
                 for (int g = 0; g < (16 >> A1); g++) {
                     const int slot0 = slot_of((g * NT + tid) >> LOGT, 0, G::POS1, A1);
@@ -523,22 +565,22 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
         if constexpr (LIMB) {
 #pragma unroll
             for (int g = 0; g < (16 >> A1); g++) dif_shift_l4<A1>(v + g * (1 << A1), x + g * (1 << A1));
-            exchange2_l4<G, A1, G::POS1, A2, G::POS2>(x, v, lds, (const gl_w4 *)twr1, a.j0inv, tid);
+            exchange2_l4<G, A1, G::POS1, A2, G::POS2>(x, v, lds, (const gl_w4 *)twr1, j0inv, tid);
 #pragma unroll
             for (int g = 0; g < (16 >> A2); g++) dif_shift_l4<A2>(v + g * (1 << A2), x + g * (1 << A2));
             if constexpr (G::J >= 3) {
-                exchange2_l4<G, A2, G::POS2, A3, 0>(x, v, lds, (const gl_w4 *)twr2, a.j0inv, tid);
+                exchange2_l4<G, A2, G::POS2, A3, 0>(x, v, lds, (const gl_w4 *)twr2, j0inv, tid);
 #pragma unroll
                 for (int g = 0; g < (16 >> A3); g++) dif_shift_l4<A3>(v + g * (1 << A3), x + g * (1 << A3));
             }
         } else {
 #pragma unroll
         for (int g = 0; g < (16 >> A1); g++) dif_shift<A1>(v + g * (1 << A1));
-        exchange2<G, A1, G::POS1, A2, G::POS2, TWR_LDS ? 0 : 12 - L>(v, lds, TWR_LDS ? twr1 : a.tws, a.j0inv, tid);
+        exchange2<G, A1, G::POS1, A2, G::POS2, TWR_LDS ? 0 : 12 - L>(v, lds, TWR_LDS ? twr1 : a.tws, j0inv, tid);
 #pragma unroll
         for (int g = 0; g < (16 >> A2); g++) dif_shift<A2>(v + g * (1 << A2));
         if constexpr (G::J >= 3) {
-            exchange2<G, A2, G::POS2, A3, 0, TWR_LDS ? 0 : 12 - (A2 + A3)>(v, lds, TWR_LDS ? twr2 : a.tws, a.j0inv, tid);
+            exchange2<G, A2, G::POS2, A3, 0, TWR_LDS ? 0 : 12 - (A2 + A3)>(v, lds, TWR_LDS ? twr2 : a.tws, j0inv, tid);
 #pragma unroll
             for (int g = 0; g < (16 >> A3); g++) dif_shift<A3>(v + g * (1 << A3));
         }
@@ -549,7 +591,7 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
             const int t = gamma & (T - 1), o = gamma >> LOGT;
             const int klow = G::kof(o << AJ);
             if constexpr (TW1) {
-                const int jr = a.j0inv & ((1 << AJ) - 1);
+                const int jr = j0inv & ((1 << AJ) - 1);
 #pragma unroll
                 for (int i = 0; i < (1 << AJ); i++) {
                     const int kj = (jr * i) & ((1 << AJ) - 1);
@@ -557,7 +599,7 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
                     else lds[G::lpos(slot_of(o, kj, 0, AJ), t)] = v[g * (1 << AJ) + brev(i, AJ)];
                 }
             } else if constexpr (TRANSPOSE) {
-                const int jr = a.j0inv & ((1 << AJ) - 1);  // odd, < 2^AJ: floor(jr*i/2^AJ) steps by 0 or 1
+                const int jr = j0inv & ((1 << AJ) - 1);  // odd, < 2^AJ: floor(jr*i/2^AJ) steps by 0 or 1
                 u64 w = gl_mul(twl_c[g], twh_c[g]);
                 const u64 hj = gl_mul(twl_c[GRJ], twh_c[GRJ]);
                 const u64 hjd = gl_mul(hj, gl_mul(twl_c[GRJ + 1], twh_c[GRJ + 1]));
@@ -585,11 +627,11 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
                 if constexpr (MODE == 2) cw = gl_mul(twl_c[TPL], twh_c[TPL]);  // shift^c, c < Pprev
 #pragma unroll
                 for (int p = 0; p < (1 << AJ); p += 2) {
-                    const int kja = (a.j0inv * brev(p, AJ)) & ((1 << AJ) - 1), kjb = (a.j0inv * brev(p + 1, AJ)) & ((1 << AJ) - 1);
+                    const int kja = (j0inv * brev(p, AJ)) & ((1 << AJ) - 1), kjb = (j0inv * brev(p + 1, AJ)) & ((1 << AJ) - 1);
                     const int ka = klow + (kja << (L - AJ)), kb = klow + (kjb << (L - AJ));
                     u64 xa, xb;
                     if constexpr (LIMB) {
-                        if (out_tab) {
+                        if constexpr (out_tab) {
                             xa = gl_l4_mul(x[g * (1 << AJ) + p], w4_load((const gl_w4 *)tab + ka));
                             xb = gl_l4_mul(x[g * (1 << AJ) + p + 1], w4_load((const gl_w4 *)tab + kb));
                         } else {
@@ -599,12 +641,14 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
                     } else {
                         xa = v[g * (1 << AJ) + p];
                         xb = v[g * (1 << AJ) + p + 1];
-                        if (out_tab) gl_mul2(xa, tab[ka], xb, tab[kb]);
+                        if constexpr (out_tab) gl_mul2(xa, tab[ka], xb, tab[kb]);
                     }
                     if constexpr (MODE == 2) gl_mul2(xa, cw, xb, cw);
-                    u64 *const ua = sbase + ((u64)(kja << (L - AJ)) << logP), *const ub = sbase + ((u64)(kjb << (L - AJ)) << logP);   // uniform
-                    u64 *pa, *pb;
-                    if constexpr (small_n) { pa = (u64 *)((char *)ua + lane_sb); pb = (u64 *)((char *)ub + lane_sb); }
+                    // uniform, and through sgpr_opaque a scalar base of its own: the store takes it beside the 32-bit lane offset
+                    zp_gu64 *const ua = (zp_gu64 *)sgpr_opaque<LEAN>((u64)(sbase + ((u64)(kja << (L - AJ)) << logP)));
+                    zp_gu64 *const ub = (zp_gu64 *)sgpr_opaque<LEAN>((u64)(sbase + ((u64)(kjb << (L - AJ)) << logP)));
+                    zp_gu64 *pa, *pb;
+                    if constexpr (small_n) { pa = (zp_gu64 *)((zp_gchar *)ua + lane_sb); pb = (zp_gu64 *)((zp_gchar *)ub + lane_sb); }
                     else { pa = ua + lane_se; pb = ub + lane_se; }
                     if constexpr (LOGT < 4) {
                         *pa = xa;
@@ -631,20 +675,39 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
         if (more) {
             if constexpr (CAN_IN) {
                 // every lane is past this tile's exchange barrier, so past its reads of itl: the next tile's entries go in
-                if (in_tab) {
+                if constexpr (in_tab) {
 #pragma unroll
                     for (int j = 0; j < TPL; j++)
                         if (tid + j * NT < R) itl[tid + j * NT] = twl_n[j];
                 }
             }
             lds_barrier();  // LDS (tile + tables) is reused by the next tile
+        }
+    };
+    if constexpr (!LEAN) {
+        // one tile per trip, and the hand-over
+#pragma clang loop unroll(disable)
+        for (int it = 0; it < tiles_per_wg; it++) {
+            tile_step(v, twl_c, twh_c, vn, twl_n, twh_n, it);
+            if (it + 1 < tiles_per_wg) {
 #pragma unroll
-            for (int i = 0; i < 16; i++) v[i] = vn[i];
+                for (int i = 0; i < 16; i++) v[i] = vn[i];
 #pragma unroll
-            for (int i = 0; i < NTW; i++) { twl_c[i] = twl_n[i]; twh_c[i] = twh_n[i]; }
+                for (int i = 0; i < NTW; i++) { twl_c[i] = twl_n[i]; twh_c[i] = twh_n[i]; }
+            }
+        }
+    } else {
+        // two tiles per trip; an odd count (1 included) leaves after the first
+#pragma clang loop unroll(disable)
+        for (int it = 0;; it += 2) {
+            tile_step(v, twl_c, twh_c, vn, twl_n, twh_n, it);
+            if (it + 1 >= tiles_per_wg) break;
+            tile_step(vn, twl_n, twh_n, v, twl_c, twh_c, it + 1);
+            if (it + 2 >= tiles_per_wg) break;
         }
     }
 }
+
 
 // ---- the seam of an extension (blow-up 2): the LAST pass of the inverse transform and the FIRST pass of the zero-padded forward transform
 // in one kernel.  The inverse's last radix-256 pass delivers a tile of coefficients { k N/256 + c : k < 256, c in 16 consecutive } -- and
@@ -654,7 +717,7 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
 // tiles = the 4 096 elements of the inverse tile), each lane picks up its 2 x 8 non-zero inputs, and the two forward tiles go through
 // the first-pass body (first butterfly level of a half-zero register file: a copy and a shift).  Per column this saves the write and
 // the read of the coefficient buffer (16 N of 136 N bytes; 8 N when the caller wants the coefficients: `coef`), and one launch.
-// Inverse side = ntt_pass2_kernel<4,4,0,4,false,false,2>, forward side = <4,4,0,4,true,true,3>: the same values, bit for bit.
+// Inverse side = ntt_pass2_kernel<4,4,0,4,false,false,2,TAB_FIXED>, forward side = <4,4,0,4,true,true,3,TAB_NONE>: the same values, bit for bit.
 struct SeamArgs {
     const u64 *in;          // input of the inverse transform's last pass, columns of N
     u64 *out;               // output of the forward transform's first pass, columns of 2N
@@ -890,21 +953,30 @@ __global__ void __launch_bounds__(256) itab_fill_kernel(u64 *out, u64 total, int
 using PassKernel = void (*)(PassArgs, int);
 
 // The instantiation a launch takes.  First passes: the table form (MODE 3, never BIG, two-round shapes only) with or without limb
-// butterflies, or the per-lane chain (MODE 1); either reads a zero-padded input or a full one.  Later passes: `mode` 0..2, limb or not.
+// butterflies, or the per-lane chain (MODE 1); either reads a zero-padded input or a full one.  Later passes: `mode` 0..2 with the table
+// that run_one_pass gives that mode (the list below is all it can ask for), limb or not.  Null: not built.
+template <int A1, int A2, int A3, int LOGT, bool BIG, bool LIMB>
+PassKernel pick_later_pass(int mode, int tab) {
+    if (mode == 2) return tab == TAB_FIXED ? ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 2, TAB_FIXED, BIG, LIMB> : nullptr;   // coset powers, with or without 1/N
+    if (mode == 1)
+        return tab == TAB_TILE    ? ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 1, TAB_TILE, BIG, LIMB>    // a middle pass with its inter-pass twiddle
+               : tab == TAB_FIXED ? ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 1, TAB_FIXED, BIG, LIMB>   // a last pass that multiplies by 1/N
+               : tab == TAB_NONE  ? ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 1, TAB_NONE, BIG, LIMB>    // the plain pass before a last pass with TAB_IN
+                                  : nullptr;
+    if constexpr (A1 + A2 + A3 <= 9) {
+        if (tab == TAB_IN) return ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 0, TAB_IN, BIG, LIMB>;
+    }
+    return tab == TAB_NONE ? ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 0, TAB_NONE, BIG, LIMB> : nullptr;
+}
 template <int A1, int A2, int A3, int LOGT, bool BIG>
-PassKernel pick_pass_kernel(bool transpose, bool table, bool padded, int mode, bool limb) {
+PassKernel pick_pass_kernel(bool transpose, bool table, bool padded, int mode, int tab, bool limb) {
     constexpr bool CAN_TABLE = !BIG && A3 == 0, CAN_LIMB = !BIG && A1 + A2 + A3 <= 8;
     if constexpr (CAN_TABLE) {
-        if (table && limb) return padded ? ntt_pass2_kernel<A1, A2, A3, LOGT, true, true, 3, false, CAN_LIMB> : ntt_pass2_kernel<A1, A2, A3, LOGT, true, false, 3, false, CAN_LIMB>;
-        if (table) return padded ? ntt_pass2_kernel<A1, A2, A3, LOGT, true, true, 3, false> : ntt_pass2_kernel<A1, A2, A3, LOGT, true, false, 3, false>;
+        if (table && limb) return padded ? ntt_pass2_kernel<A1, A2, A3, LOGT, true, true, 3, TAB_NONE, false, CAN_LIMB> : ntt_pass2_kernel<A1, A2, A3, LOGT, true, false, 3, TAB_NONE, false, CAN_LIMB>;
+        if (table) return padded ? ntt_pass2_kernel<A1, A2, A3, LOGT, true, true, 3, TAB_NONE, false> : ntt_pass2_kernel<A1, A2, A3, LOGT, true, false, 3, TAB_NONE, false>;
     }
-    if (transpose) return padded ? ntt_pass2_kernel<A1, A2, A3, LOGT, true, true, 1, BIG> : ntt_pass2_kernel<A1, A2, A3, LOGT, true, false, 1, BIG>;
-    if (limb) return mode == 2 ? ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 2, BIG, CAN_LIMB>
-                   : mode == 1 ? ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 1, BIG, CAN_LIMB>
-                               : ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 0, BIG, CAN_LIMB>;
-    return mode == 2 ? ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 2, BIG>
-         : mode == 1 ? ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 1, BIG>
-                     : ntt_pass2_kernel<A1, A2, A3, LOGT, false, false, 0, BIG>;
+    if (transpose) return padded ? ntt_pass2_kernel<A1, A2, A3, LOGT, true, true, 1, TAB_NONE, BIG> : ntt_pass2_kernel<A1, A2, A3, LOGT, true, false, 1, TAB_NONE, BIG>;
+    return limb ? pick_later_pass<A1, A2, A3, LOGT, BIG, CAN_LIMB>(mode, tab) : pick_later_pass<A1, A2, A3, LOGT, BIG, false>(mode, tab);
 }
 
 template <int A1, int A2, int A3, int LOGT, bool BIG = false>
@@ -928,7 +1000,13 @@ int32_t launch_pass2(zp_ctx *ctx, PassArgs a, bool transpose, int W) {
     const size_t rec = limb ? 4 : 1;
     // + (the tile's input-side factors: a last pass that takes them)
     const size_t shmem = ((size_t)G::R * G::T + (mode >= 1 ? G::R * rec : 0) + (G::L <= 10 ? (G::R + (1 << (A2 + A3))) * rec : 0) + (a.itab ? G::R : 0)) * sizeof(u64);
-    const PassKernel k = pick_pass_kernel<A1, A2, A3, LOGT, BIG>(transpose, table, a.in_valid != (1ULL << a.logn), mode, limb);
+    // ... and the table of that pass, a template argument like the mode: the tile loop of a kernel holds its own case only
+    const int tab = transpose ? TAB_NONE : a.itab ? TAB_IN : (a.flags & 1) ? TAB_TILE : (a.flags & 6) ? TAB_FIXED : TAB_NONE;
+    const PassKernel k = pick_pass_kernel<A1, A2, A3, LOGT, BIG>(transpose, table, a.in_valid != (1ULL << a.logn), mode, tab, limb);
+    if (!k) {
+        ctx->err = "pass kernel not built for this combination of output scaling and tables";
+        return ZP_ERR_UNSUPPORTED;
+    }
     if (shmem > 65536) ZP_HIP(ctx, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     if (table) {
         a.ncols = W;
