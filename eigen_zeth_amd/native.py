@@ -189,6 +189,10 @@ SIGNATURES = {
     "zp_stage_timings": (C.c_int32, [_vp, C.c_char_p, C.c_size_t]),
     "zp_ntt_plan_json": (C.c_int32, [_vp, C.c_int32, C.c_char_p, C.c_size_t]),
     "zp_device_info_json": (C.c_int32, [_vp, C.c_char_p, C.c_size_t]),
+    "zp_pairing_bn254": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.c_int32, _vp, _vp]),
+    "zp_pairing_check_bn254": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.c_int32, C.POINTER(C.c_int32)]),
+    "zp_groth16_verify": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.POINTER(C.c_int32)]),
+    "zp_groth16_verify_batch": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, C.c_int32, _vp]),
 }
 
 
@@ -369,7 +373,8 @@ def program_eval_ext(program, pubchal, logn, root32, zeta, ev_z, ev_zw, threads=
 # zp_stark_verify: the verdict classes and the flags (include/zeth_prover.h)
 VERDICT_ACCEPT, VERDICT_MALFORMED, VERDICT_PARAMS, VERDICT_IDENTITY, VERDICT_POW, VERDICT_INDICES, VERDICT_FINAL_DEGREE, VERDICT_OPENING, VERDICT_FRI = range(9)
 VERIFY_HEADER_ONLY, VERIFY_TRUST_OPENINGS = 1, 2
-VERDICT_TRANSCRIPT, VERDICT_PUBLICS, VERDICT_TREE = 9, 10, 11      # zp_aggregate_verify* only
+VERDICT_TRANSCRIPT, VERDICT_PUBLICS, VERDICT_TREE = 9, 10, 11      # zp_aggregate_verify*; PUBLICS also groth16_verify*
+VERDICT_POINT, VERDICT_PAIRING = 12, 13                             # groth16_verify* only
 
 
 
@@ -503,6 +508,76 @@ def aggregate_verify_batch(statements, texts, flags=0, prover=None, threads=0):
     if rc != 0:
         _verify_error(prover, rc, "zp_aggregate_verify_batch")
     return list(out)
+
+
+# ---- the BN254 pairing and the Groth16 verifier (csrc/pairing.hip): host code, with or without a Prover
+PAIRING_STATUS_OK, PAIRING_STATUS_RANGE, PAIRING_STATUS_CURVE, PAIRING_STATUS_SUBGROUP = range(4)
+
+
+def _pairs(g1, g2):
+    a = np.ascontiguousarray(np.asarray(g1, dtype=np.uint32).reshape(-1, 16))
+    b = np.ascontiguousarray(np.asarray(g2, dtype=np.uint32).reshape(-1, 32))
+    if a.shape[0] != b.shape[0]:
+        raise ValueError("as many G1 as G2 points")
+    return a, b
+
+
+def pairing_bn254(g1, g2, prover=None, threads=0):
+    """zp_pairing_bn254: (gt u32[n][12][8], status u8[n]) of n pairs in the MSM point layouts (u32[n][16], u32[n][32]; all-zero = infinity).  gt[j] are
+    the flat-basis words of e(P_j, Q_j), all-zero unless status[j] is PAIRING_STATUS_OK"""
+    a, b = _pairs(g1, g2)
+    n = a.shape[0]
+    gt, st = np.zeros((n, 12, 8), dtype=np.uint32), np.zeros(n, dtype=np.uint8)
+    rc = load_library().zp_pairing_bn254(prover.ctx if prover is not None else None, a.ctypes.data, b.ctypes.data, n, threads, gt.ctypes.data, st.ctypes.data)
+    if rc != 0:
+        _verify_error(prover, rc, "zp_pairing_bn254")
+    return gt, st
+
+
+def pairing_check_bn254(g1, g2, prover=None, threads=0):
+    """zp_pairing_check_bn254: True iff every point is valid and the product of the e(P_j, Q_j) is 1 (EIP-197); no pairs: True"""
+    a, b = _pairs(g1, g2)
+    ok = C.c_int32(0)
+    rc = load_library().zp_pairing_check_bn254(prover.ctx if prover is not None else None, a.ctypes.data, b.ctypes.data, a.shape[0], threads, C.byref(ok))
+    if rc != 0:
+        _verify_error(prover, rc, "zp_pairing_check_bn254")
+    return bool(ok.value)
+
+
+def _groth16_args(vk_words, proofs, publics):
+    vk = np.ascontiguousarray(np.asarray(vk_words, dtype=np.uint32).reshape(-1))
+    if vk.size < 112 + 16 or (vk.size - 112) % 16:
+        raise ValueError("a key is alpha1[16] | beta2[32] | gamma2[32] | delta2[32] | ic[n_ic][16] words")
+    n_ic = (vk.size - 112) // 16
+    pr = np.ascontiguousarray(np.asarray(proofs, dtype=np.uint32).reshape(-1, 64))
+    flat = [int(v) for row in publics for v in row]
+    if len(flat) != pr.shape[0] * (n_ic - 1) or any(v < 0 or v >> 256 for v in flat):
+        raise ValueError("n_ic - 1 public inputs below 2^256 per proof")
+    pub = np.array([[(v >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)] for v in flat] or [[0] * 4], dtype=np.uint64)
+    return vk, n_ic, pr, pub
+
+
+def groth16_verify(vk_words, proof_words, publics, prover=None):
+    """zp_groth16_verify: the verdict (VERDICT_ACCEPT, _PUBLICS, _POINT or _PAIRING) of one proof (u32[64]: pi_a | pi_b | pi_c) with its public inputs
+    (integers) under the key words (alpha1 | beta2 | gamma2 | delta2 | ic ...).  ZpError: a bad key"""
+    vk, n_ic, pr, pub = _groth16_args(vk_words, proof_words, [publics])
+    verdict = C.c_int32(-1)
+    rc = load_library().zp_groth16_verify(prover.ctx if prover is not None else None, vk.ctypes.data, n_ic, pr.ctypes.data, pub.ctypes.data, C.byref(verdict))
+    if rc != 0:
+        _verify_error(prover, rc, "zp_groth16_verify")
+    return verdict.value
+
+
+def groth16_verify_batch(vk_words, proofs_words, publics_list, prover=None, threads=0):
+    """zp_groth16_verify_batch: the verdicts of n proofs (u32[n][64]) under one key, each what groth16_verify gives (host threads; a Prover only receives
+    the error text)"""
+    vk, n_ic, pr, pub = _groth16_args(vk_words, proofs_words, publics_list)
+    out = np.zeros(max(pr.shape[0], 1), dtype=np.int32)
+    rc = load_library().zp_groth16_verify_batch(prover.ctx if prover is not None else None, vk.ctypes.data, n_ic, pr.ctypes.data, pub.ctypes.data, pr.shape[0],
+                                                threads, out.ctypes.data)
+    if rc != 0:
+        _verify_error(prover, rc, "zp_groth16_verify_batch")
+    return [int(v) for v in out[:pr.shape[0]]]
 
 
 def wrap_aux(openings, program, pubs, logn, root32, addr):

@@ -75,8 +75,12 @@ class EngineConfig:
                  witness_threads=8, prover_streams=8, pow_bits=20,
                  final_air="chunk16", final_logn=10, final_logb=2, final_queries=50, native_prover=True,
                  agg_queries=50, agg_pow_bits=0, aggregate_all_chunks=False, groth16_seed=None, witness="device",
-                 speculate_recursion=False, verify_before_wrap=True, final_ranks=1, final_devices=None, wrap_ranks=1, wrap_devices=None):
+                 speculate_recursion=False, verify_before_wrap=True, final_ranks=1, final_devices=None, wrap_ranks=1, wrap_devices=None,
+                 verify_final=False):
         self.air, self.logn, self.logb = air, logn, logb
+        # GenFinalProof: run the native Groth16 verifier (zp_groth16_verify) on the proof about to be returned and raise unless it is accepted
+        # ("groth16/verify" in the stage clock).  Off by default: no response and no timing changes.
+        self.verify_final = verify_final
         # GenFinalProof: check natively, before the final STARK and the wrap are made, what no query of the aggregation STARK covers (its
         # constraint identity at the out-of-domain point, its final layer, its grinding: stark/verifier.py).  Off only for timing experiments.
         self.verify_before_wrap = verify_before_wrap
@@ -907,6 +911,12 @@ class Engine:
                                                    **{"final/" + k: v for k, v in tmf.items()}}
         if self._wrap_sharded():
             self.stage_timings["final/" + batch_id]["groth16/ranks"] = self.cfg.wrap_ranks
+        if self.cfg.verify_final:
+            t0 = time.perf_counter()
+            verdict = groth16.verify(key.vk, proof, pub, self.be)
+            self.stage_timings["final/" + batch_id]["groth16/verify"] = time.perf_counter() - t0
+            if verdict != native.VERDICT_ACCEPT:
+                raise RuntimeError("the final Groth16 proof does not verify under its own key (verdict %d)" % verdict)
         n_v = key.dev["v_wires"][1] if key.dev else int((key.v != 0).any(axis=1).sum())      # wires with a non-zero column in B
         self.wrap_info = {"constraints": wc.c.n_constraints, "qap_domain_log2": wc.c.logm(), "wires": wc.c.n_wires,
                           "msm_points": {"A (G1)": wc.c.n_wires + 2, "B (G1)": n_v + 2, "B (G2)": n_v + 2, "C: l (G1)": wc.c.n_wires,

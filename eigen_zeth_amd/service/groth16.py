@@ -194,6 +194,31 @@ def prove_sharded(key, set_idx, set_val, provers, rand):
     return {"pi_a": _g1_point(a), "pi_b": _g2_point(b), "pi_c": _g1_point(c)}, pub, ms
 
 
+def vk_words(vk):
+    """the key's points as zp_groth16_verify takes them: alpha1[16] | beta2[32] | gamma2[32] | delta2[32] | ic[n_ic][16]"""
+    return np.concatenate([_g1_words(vk["alpha1"]), _g2_words(vk["beta2"]), _g2_words(vk["gamma2"]), _g2_words(vk["delta2"])] +
+                          [_g1_words(p) for p in vk["ic"]])
+
+
+def proof_words(proof):
+    """pi_a[16] | pi_b[32] | pi_c[16]"""
+    return np.concatenate([_g1_words(proof["pi_a"]), _g2_words(proof["pi_b"]), _g1_words(proof["pi_c"])])
+
+
+def verify(vk, proof, publics, be=None):
+    """zp_groth16_verify over the dict forms Key.vk and prove use: native.VERDICT_ACCEPT, _PUBLICS, _POINT or _PAIRING.  be: a backend whose ctx
+    receives the error text (HipBackend) or None; the check itself is host code either way"""
+    return native.groth16_verify(vk_words(vk), proof_words(proof), [int(v) for v in publics], prover=getattr(be, "p", None))
+
+
+def verify_batch(vk, proofs, publics_list, be=None, threads=0):
+    """zp_groth16_verify_batch: one verdict per proof under one key, the proofs spread over host threads"""
+    if not proofs:
+        return []
+    return native.groth16_verify_batch(vk_words(vk), np.stack([proof_words(p) for p in proofs]), [[int(v) for v in pub] for pub in publics_list],
+                                       prover=getattr(be, "p", None), threads=threads)
+
+
 def circuit_text(wc, key):
     """the "circuit" member of a final proof: what was proven, under which key"""
     if getattr(wc, "statement", None) is None:

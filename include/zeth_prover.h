@@ -615,8 +615,10 @@ int32_t zp_fixed_base_mul_bn254_g2(zp_ctx *ctx, const uint32_t *h_base, const ui
  * kernels); the transcript, the identity and the arithmetic at the queries are host code on `threads` threads (<= 0: one per core, at most 16). */
 enum { ZP_VERDICT_ACCEPT = 0, ZP_VERDICT_MALFORMED = 1, ZP_VERDICT_PARAMS = 2, ZP_VERDICT_IDENTITY = 3, ZP_VERDICT_POW = 4,
        ZP_VERDICT_INDICES = 5, ZP_VERDICT_FINAL_DEGREE = 6, ZP_VERDICT_OPENING = 7, ZP_VERDICT_FRI = 8,
-       /* zp_aggregate_verify* only */
-       ZP_VERDICT_TRANSCRIPT = 9, ZP_VERDICT_PUBLICS = 10, ZP_VERDICT_TREE = 11 };
+       /* zp_aggregate_verify*; PUBLICS also zp_groth16_verify* (a public input >= r) */
+       ZP_VERDICT_TRANSCRIPT = 9, ZP_VERDICT_PUBLICS = 10, ZP_VERDICT_TREE = 11,
+       /* zp_groth16_verify* only */
+       ZP_VERDICT_POINT = 12, ZP_VERDICT_PAIRING = 13 };
 enum { ZP_VERIFY_HEADER_ONLY = 1, ZP_VERIFY_TRUST_OPENINGS = 2 };
 int32_t zp_stark_verify(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const char *proof_json, size_t proof_len,
                         int32_t logn, int32_t logb, int32_t fri_logf, int32_t fri_final_log, int32_t n_queries, int32_t pow_bits,
@@ -727,6 +729,34 @@ int32_t zp_aggregate_verify(zp_ctx *ctx, const zp_agg_statement *stmts, int32_t 
  * openings of all outer STARKs of one statement in one launch; verdicts[n_texts]                                                                */
 int32_t zp_aggregate_verify_batch(zp_ctx *ctx, const zp_agg_statement *stmts, int32_t n_stmts, const char *const *texts, const size_t *lens,
                                   int32_t n_texts, uint32_t flags, int32_t threads, int32_t *verdicts);
+
+/* ---- the BN254 pairing and the Groth16 verifier (csrc/pairing.hip) ------------------------------
+ * Does the final proof (what zp_groth16_prove wrote, what goes to verifyBatches) verify?  The optimal-ate pairing e: G1 x G2 -> GT on alt_bn128,
+ * the product check of EIP-197, and the Groth16 equation on top.  Host buffers in and out.  EVERY call allows ctx = NULL, and in this version every
+ * call runs on the host on `threads` threads (<= 0: one per core, at most 16) whether a ctx is given or not: a ctx only receives the error text
+ * (zp_last_error).  The work of a call is spread pair by pair and proof by proof.
+ * Layouts: h_g1 u32[n][16] and h_g2 u32[n][32] are the MSM point layouts (standard form, x then y, F_q2 as c0 then c1; all-zero = infinity).
+ * h_gt u32[n][12][8]: coefficient k (standard form, < q) of w^k in F_q[w]/(w^12 - 18 w^6 + 82), the textbook flat basis.
+ * zp_pairing_bn254: h_gt[j] = e(P_j, Q_j); h_status[j] = 0 computed, 1 a coordinate >= q, 2 a point not on its curve (G1: y^2 = x^3 + 3; G2:
+ *   the twist y^2 = x^3 + 3/(9 + u)), 3 the G2 point outside the order-r subgroup ([r]Q != O).  h_gt[j] is all-zero unless the status is 0; a
+ *   point at infinity gives 1.  A refused pair is a status, not an error.
+ * zp_pairing_check_bn254: *ok = 1 iff every point is valid and the product of the e(P_j, Q_j) is 1 (the precompile's semantics): n Miller loops,
+ *   ONE final exponentiation.  n = 0 gives 1; an invalid point gives 0, not an error code.
+ * zp_groth16_verify: h_vk = alpha1[16] | beta2[32] | gamma2[32] | delta2[32] | ic[n_ic][16]; h_proof = pi_a[16] | pi_b[32] | pi_c[16];
+ *   h_publics u64[n_ic - 1][4], standard form (zp_groth16_prove's out_pub).  A verdict is ZP_OK; *verdict = the FIRST failing check, in this order:
+ *   PUBLICS a public input >= r;  POINT a proof coordinate >= q, pi_a or pi_c off the curve, pi_b off the twist or outside the subgroup;
+ *   PAIRING e(A, B) != e(alpha, beta) e(IC_0 + sum_j pub_j IC_j, gamma) e(C, delta), evaluated as a product of Miller values and one final
+ *   exponentiation per proof;  otherwise ACCEPT.  A proof point at infinity is judged by the equation with e(O, .) = 1.
+ *   ZP_ERR_ARG, the caller's mistakes, checked once per call: a null pointer, n_ic < 1, a key point that is invalid (as above, the subgroup
+ *   included), or alpha / beta / gamma / delta at infinity.
+ * zp_groth16_verify_batch: h_proofs u32[n][64], h_publics u64[n][n_ic - 1][4] under ONE key; verdicts[i] is exactly what zp_groth16_verify gives
+ *   for proof i (no random linear combination: that is probabilistic and gives no per-proof verdict).  The IC sums, the PUBLICS checks, the 3 n
+ *   Miller loops with the coordinate, curve and subgroup checks, and the n finishes are spread over the threads.                              */
+int32_t zp_pairing_bn254(zp_ctx *ctx, const uint32_t *h_g1, const uint32_t *h_g2, size_t n, int32_t threads, uint32_t *h_gt, uint8_t *h_status);
+int32_t zp_pairing_check_bn254(zp_ctx *ctx, const uint32_t *h_g1, const uint32_t *h_g2, size_t n, int32_t threads, int32_t *ok);
+int32_t zp_groth16_verify(zp_ctx *ctx, const uint32_t *h_vk, int32_t n_ic, const uint32_t *h_proof, const uint64_t *h_publics, int32_t *verdict);
+int32_t zp_groth16_verify_batch(zp_ctx *ctx, const uint32_t *h_vk, int32_t n_ic, const uint32_t *h_proofs, const uint64_t *h_publics, size_t n,
+                                int32_t threads, int32_t *verdicts);
 
 #ifdef __cplusplus
 }
