@@ -487,6 +487,7 @@ int32_t zp_set_tuning(zp_ctx *ctx, const char *key, int32_t value) {
     else if (!strcmp(key, "p254_bulk_log")) ctx->tune_p254_bulk_log = value;
     else if (!strcmp(key, "verify_lane_min")) ctx->tune_verify_lane_min = value;
     else if (!strcmp(key, "verify16_lane_min")) ctx->tune_verify16_lane_min = value;
+    else if (!strcmp(key, "verify_chain_dev")) { ZP_ARG(ctx, value >= 0 && value <= 2, "verify_chain_dev is 0 (never), 1 (default) or 2 (always)"); ctx->tune_verify_chain_dev = value; }
     else if (!strcmp(key, "fixed_eval_dev_min")) ctx->tune_fixed_eval_dev_min = value < 0 ? 1 << 15 : value;
     else { ctx->err = "unknown tuning key"; return ZP_ERR_ARG; }
     return ZP_OK;

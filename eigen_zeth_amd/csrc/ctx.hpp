@@ -102,6 +102,8 @@ struct zp_ctx {
     int tune_msm_c = 0;           // 0 = window width chosen from n
     int tune_verify_lane_min = 0;   // 0 = 256: zp_merkle_verify_batch / zp_stark_verify* use the lane-per-opening kernel from this many openings per call on (fewer: the 12-lane walk kernel).  256 (four full waves) is A GUESS until tools/verify_measure.py has run on the device: unmeasured
     int tune_verify16_lane_min = 0; // 0 = 2^14 JOBS (one permutation chain each): zp_merkle16_verify_batch_bn254 / zp_stark_verify*_bn128 hash one job per lane (state in LDS) from this many jobs per call on (fewer: 17 lanes per job).  2^14 is where the lane form wins for commitments: for openings A GUESS until tools/verify_bn128_measure.py has run on the device: unmeasured
+    int tune_verify_chain_dev = 1;  // the Fiat-Shamir transcripts (and the commitments of long public-input vectors) of zp_stark_verify* / zp_aggregate_verify* calls with a ctx as ONE sponge-chain launch per call: 0 never, 2 always, 1 (default): where the device beat the parent library at EVERY measured batch size -- today in neither mode (profiles/verify_chains.json: BN128-hash mode wins at 1 and 4 texts, 15.6 -> 10.9 and 61.3 -> 23.9 ms per call, and loses at 16, 25.8 -> 31.4, where the host spreads the header phases over 16 threads and the plan is made on one; Goldilocks mode loses at every size)
+    uint64_t verify_counters[4] = {0, 0, 0, 0};   // zp_verify_counters: chain launches, chain steps run on the device, public-input commitments made on the device, texts that took the host sponge on the device path
     int tune_msm_chunk_log = 0;   // 0 = default (2^24 points per Pippenger run)
     int tune_fixed_eval_dev_min = 1 << 15;   // zp_program_fixed_eval_ext_batch with a ctx: calls of fewer (points x sparse entries) run on the host (0: always the device; < 0 restores this default).  2^15: from ~12.5 ns per entry on 16 host threads against ~0.5 ms per device call (profiles/r12_fixed_eval_batch.json: every size measured there is above it and the device wins, 10x at one point of 4.4 x 10^5 entries); not measured AT the crossover
     // zp_stark_prove: device buffers kept between proofs (chunk after chunk has the same shapes; hipMalloc / hipFree of ~20 buffers
@@ -198,6 +200,17 @@ int32_t zpi_lde_plan_json(zp_ctx *ctx, int logn, int want_coef, std::string *out
 int32_t zpi_get_coset(zp_ctx *ctx, int logn, u64 shift, u64 pre, CosetTable **out);
 int32_t zpi_poseidon_sync_tables(zp_ctx *ctx);
 int32_t zpi_poseidon_chains(zp_ctx *ctx, const u64 *d_blocks, const unsigned char *d_absorb, const unsigned int *d_first, int nchains, u64 *d_out);
+// the width-17 twin (csrc/poseidon_bn254.hip: sponge_chains254_kernel, three chains to a workgroup): d_blocks u64[nsteps][16][4] standard form < r, d_out u64[nsteps][16][4]
+// the rate after every step
+int32_t zpi_poseidon254_chains(zp_ctx *ctx, const u64 *d_blocks, const unsigned char *d_absorb, const unsigned int *d_first, int nchains, u64 *d_out);
+// either mode's chains from host buffers (the verifier's transcripts; zp_poseidon_bn254_chains): one upload, one launch, one download, one synchronisation.
+// h_blocks / h_rates: 8 words per step (Goldilocks), 64 (BN254); h_first[nchains] steps in all, > 0.  Counted in ctx->verify_counters
+int32_t zpi_poseidon_chains_host(zp_ctx *ctx, const u64 *h_blocks, const uint8_t *h_absorb, const uint32_t *h_first, int nchains, u64 *h_rates);
+int32_t zpi_poseidon254_chains_host(zp_ctx *ctx, const u64 *h_blocks, const uint8_t *h_absorb, const uint32_t *h_first, int nchains, u64 *h_rates);
+// the commitments long public-input vectors enter a transcript as, of every such text of a call: canonical values in, h_out4 u64[n][4]; the trees are
+// built by the prover's kernels (rows of 8, binary: zp_merkle_commit_rows's; rows of 48, 16-ary: zp_merkle16_commit_bn254's); one synchronisation
+int32_t zpi_publics_digests(zp_ctx *ctx, const std::vector<const std::vector<u64> *> &pubs, u64 *h_out4);
+int32_t zpi_publics_digests_bn254(zp_ctx *ctx, const std::vector<const std::vector<u64> *> &pubs, u64 *h_out4);
 int32_t zpi_poseidon_openings_walk(zp_ctx *ctx, const u64 *d_op, const u64 *d_vals, u64 mw, const u64 *d_index, const u64 *d_sib, const u64 *d_sib_off,
                                    size_t count, u64 *d_inputs, u64 *d_digests);
 // one Merkle opening a verifier checks: `width` leaf values, `depth` siblings of four words (bottom-up), the leaf's position, and which of the

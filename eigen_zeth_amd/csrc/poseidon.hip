@@ -771,6 +771,69 @@ int32_t zpi_poseidon_chains(zp_ctx *ctx, const u64 *d_blocks, const unsigned cha
     return ZP_OK;
 }
 
+// the same from host buffers, for a verifier's transcripts (csrc/verify.hip): h_blocks u64[nsteps][8], h_rates u64[nsteps][8] = the rate after every
+// step.  [blocks][out, 20 words per step][first][absorb] in one device buffer; one upload, one launch, one download, one synchronisation
+int32_t zpi_poseidon_chains_host(zp_ctx *ctx, const u64 *h_blocks, const uint8_t *h_absorb, const uint32_t *h_first, int nchains, u64 *h_rates) {
+    ZP_BIND(ctx);
+    ZP_ARG(ctx, nchains > 0 && h_blocks && h_absorb && h_first && h_rates && h_first[nchains] > 0, "bad chains");
+    ZP_TRY(zpi_poseidon_sync_tables(ctx));
+    const size_t nsteps = h_first[nchains], o_out = 8 * nsteps, o_first = o_out + 20 * nsteps, o_abs = o_first + ((size_t)nchains + 2) / 2, total = o_abs + (nsteps + 7) / 8;
+    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (an earlier small copy may still read the staging buffer)
+    void *stv = nullptr;
+    ZP_TRY(zpi_pinned(ctx, total * 8, &stv));
+    u64 *buf = (u64 *)stv, *dbuf = nullptr;
+    memcpy(buf, h_blocks, 64 * nsteps);
+    memcpy(buf + o_first, h_first, 4 * ((size_t)nchains + 1));
+    memcpy(buf + o_abs, h_absorb, nsteps);
+    ZP_TRY(zpi_scratch(ctx, 3, total, &dbuf));
+    ZP_HIP(ctx, hipMemcpyAsync(dbuf, buf, 64 * nsteps, hipMemcpyHostToDevice, ctx->stream));
+    ZP_HIP(ctx, hipMemcpyAsync(dbuf + o_first, buf + o_first, (total - o_first) * 8, hipMemcpyHostToDevice, ctx->stream));
+    ZP_TRY(zpi_poseidon_chains(ctx, dbuf, (const unsigned char *)(dbuf + o_abs), (const unsigned int *)(dbuf + o_first), nchains, dbuf + o_out));
+    ZP_HIP(ctx, hipMemcpyAsync(buf + o_out, dbuf + o_out, 160 * nsteps, hipMemcpyDeviceToHost, ctx->stream));
+    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t s = 0; s < nsteps; s++) memcpy(h_rates + 8 * s, buf + o_out + 20 * s + 12, 64);
+    ctx->verify_counters[0] += 1;
+    ctx->verify_counters[1] += nsteps;
+    return ZP_OK;
+}
+
+// The commitment of every long public-input vector of a call in Goldilocks mode (csrc/verify.hip: publics_digest_host is the host's statement of the
+// same): rows of 8 values, zero padded, 2^k >= 2 rows, the binary tree of zp_merkle_commit_rows, tree after tree on the stream; the roots come back in
+// one copy after one synchronisation.  One buffer: [rows of every vector][tree of every vector][roots]
+int32_t zpi_publics_digests(zp_ctx *ctx, const std::vector<const std::vector<u64> *> &pubs, u64 *h_out4) {
+    ZP_BIND(ctx);
+    const size_t n = pubs.size();
+    if (!n) return ZP_OK;
+    std::vector<size_t> rows(n), row_at(n), tree_at(n);
+    size_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        size_t M = 2;
+        while (M * 8 < pubs[i]->size()) M <<= 1;
+        rows[i] = M; row_at[i] = at; at += 8 * M;
+    }
+    const size_t n_rows = at;
+    for (size_t i = 0; i < n; i++) { tree_at[i] = at; at += 4 * (2 * rows[i] - 1); }
+    const size_t o_roots = at, total = at + 4 * n;
+    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    void *stv = nullptr;
+    ZP_TRY(zpi_pinned(ctx, (n_rows > 4 * n ? n_rows : 4 * n) * 8, &stv));
+    u64 *buf = (u64 *)stv, *dbuf = nullptr;
+    for (size_t i = 0; i < n; i++) {
+        memcpy(buf + row_at[i], pubs[i]->data(), 8 * pubs[i]->size());
+        memset(buf + row_at[i] + pubs[i]->size(), 0, 8 * (8 * rows[i] - pubs[i]->size()));
+    }
+    ZP_TRY(zpi_scratch(ctx, 3, total, &dbuf));
+    ZP_HIP(ctx, hipMemcpyAsync(dbuf, buf, n_rows * 8, hipMemcpyHostToDevice, ctx->stream));
+    for (size_t i = 0; i < n; i++) {
+        ZP_TRY(commit_tree<true>(ctx, dbuf + row_at[i], rows[i], 8, dbuf + tree_at[i]));
+        ZP_HIP(ctx, hipMemcpyAsync(dbuf + o_roots + 4 * i, dbuf + tree_at[i] + 4 * (2 * rows[i] - 2), 32, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    ZP_HIP(ctx, hipMemcpyAsync(buf, dbuf + o_roots, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
+    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(h_out4, buf, 32 * n);
+    return ZP_OK;
+}
+
 // the leaf hash and the path of `count` openings in one launch (openings_walk_kernel)
 int32_t zpi_poseidon_openings_walk(zp_ctx *ctx, const u64 *d_op, const u64 *d_vals, u64 mw, const u64 *d_index, const u64 *d_sib, const u64 *d_sib_off,
                                    size_t count, u64 *d_inputs, u64 *d_digests) {

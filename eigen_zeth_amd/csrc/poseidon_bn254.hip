@@ -586,6 +586,44 @@ __global__ void __launch_bounds__(64) poseidon254_sponge_kernel(u64 *buf, int nb
     }
 }
 
+// Whole BN128-mode Fiat-Shamir transcripts in ONE launch: the width-17 twin of csrc/poseidon.hip's sponge_chains_kernel on perm_coop.  A job is a
+// chain: 17 lanes, three chains to a 64-lane workgroup (verify16_coop_kernel's packing).  Chain c walks the steps [first[c], first[c + 1]) from the
+// zero state; a step overwrites elements 1..16 with its block (absorb[s] != 0; blocks u64[nsteps][16][4], standard form, < r: the host validated
+// them) and permutes; out u64[nsteps][16][4] = the rate after each step, standard form.
+// perm_coop holds barriers, so the three chains of a workgroup walk the LONGEST of the three together: the trip count is read once from first[] and is
+// the same for every lane; a chain that has ended keeps going through the permutation with `on` false -- no table load, no LDS store, no global
+// access, every barrier.  Nothing here waits on another workgroup.
+__global__ void __launch_bounds__(64) sponge_chains254_kernel(const u64 *__restrict__ blocks, const unsigned char *__restrict__ absorb,
+                                                              const unsigned int *__restrict__ first, int nchains, u64 *__restrict__ out, P254Dev d) {
+    constexpr int T = 17, PPW = 3;
+    __shared__ u32 sh[PPW][T][9];
+    const int q = threadIdx.x / T, e = threadIdx.x % T;
+    const int c0 = (int)blockIdx.x * PPW, c = c0 + q;
+    const bool on = q < PPW && c < nchains;
+    unsigned int trips = 0;
+    for (int k = 0; k < PPW; k++)
+        if (c0 + k < nchains) { const unsigned int n = first[c0 + k + 1] - first[c0 + k]; trips = n > trips ? n : trips; }
+    const unsigned int s0 = on ? first[c] : 0u, mine = on ? first[c + 1] - s0 : 0u;
+    fr s = fr_zero();
+    for (unsigned int i = 0; i < trips; i++) {
+        const bool act = on && i < mine;
+        const size_t st = (size_t)s0 + i;
+        if (act && e >= 1 && absorb[st]) {
+            u64 w[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) w[k] = blocks[(st * 16 + (e - 1)) * 4 + k];
+            s = fr_to_mont(fr_from_u64(w));
+        }
+        s = perm_coop<T>(s, q, e, act, sh, d);
+        if (act && e >= 1) {
+            u64 w[4];
+            fr_to_u64(fr_from_mont(s), w);
+#pragma unroll
+            for (int k = 0; k < 4; k++) out[(st * 16 + (e - 1)) * 4 + k] = w[k];
+        }
+    }
+}
+
 // 16-ary Merkle tree, t = 17: state = [capacity, 16 inputs]; digest = state[0] after the permutation.
 // leaves: row i of the Goldilocks matrix cols[W][M], three values per field element (a + b 2^64 + c 2^128), sponge over
 // blocks of 16 elements with the digest as the next capacity.  nodes: 16 child digests (missing children = 0).
@@ -1205,6 +1243,74 @@ int32_t zpi_merkle16_verify_openings_bn254(zp_ctx *ctx, const ZpOpening *ops, si
     ZP_HIP(ctx, hipMemcpyAsync(buf + o_ok, dbuf + o_ok, (total - o_ok) * 8, hipMemcpyDeviceToHost, ctx->stream));
     ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t o = 0; o < n; o++) ok[o] = flags[o] ? 1 : 0;
+    return ZP_OK;
+}
+
+// nchains sponge chains in one launch (sponge_chains254_kernel); d_*: device buffers the caller filled (every block element < r), d_out u64[nsteps][16][4]
+int32_t zpi_poseidon254_chains(zp_ctx *ctx, const u64 *d_blocks, const unsigned char *d_absorb, const unsigned int *d_first, int nchains, u64 *d_out) {
+    const P254Table *tb;
+    ZP_TRY(table_for(ctx, 17, &tb));
+    if (nchains <= 0) return ZP_OK;
+    hipLaunchKernelGGL(sponge_chains254_kernel, dim3((unsigned)((nchains + 2) / 3)), dim3(64), 0, ctx->stream, d_blocks, d_absorb, d_first, nchains, d_out, dev_of(ctx, tb));
+    ZP_HIP(ctx, hipGetLastError());
+    return ZP_OK;
+}
+
+// the same from host buffers: [blocks][rates][first][absorb] in one device buffer, one upload, one launch, one download, one synchronisation
+int32_t zpi_poseidon254_chains_host(zp_ctx *ctx, const u64 *h_blocks, const uint8_t *h_absorb, const uint32_t *h_first, int nchains, u64 *h_rates) {
+    ZP_BIND(ctx);
+    const P254Table *tb;
+    ZP_TRY(table_for(ctx, 17, &tb));
+    ZP_ARG(ctx, nchains > 0 && h_blocks && h_absorb && h_first && h_rates && h_first[nchains] > 0, "bad chains");
+    const size_t nsteps = h_first[nchains], o_out = 64 * nsteps, o_first = 2 * o_out, o_abs = o_first + ((size_t)nchains + 2) / 2, total = o_abs + (nsteps + 7) / 8;
+    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (an earlier small copy may still read the staging buffer)
+    void *stv = nullptr;
+    ZP_TRY(zpi_pinned(ctx, total * 8, &stv));
+    u64 *buf = (u64 *)stv, *dbuf = nullptr;
+    memcpy(buf, h_blocks, 512 * nsteps);
+    memcpy(buf + o_first, h_first, 4 * ((size_t)nchains + 1));
+    memcpy(buf + o_abs, h_absorb, nsteps);
+    ZP_TRY(zpi_scratch(ctx, 3, total, &dbuf));
+    ZP_HIP(ctx, hipMemcpyAsync(dbuf, buf, 512 * nsteps, hipMemcpyHostToDevice, ctx->stream));
+    ZP_HIP(ctx, hipMemcpyAsync(dbuf + o_first, buf + o_first, (total - o_first) * 8, hipMemcpyHostToDevice, ctx->stream));
+    ZP_TRY(zpi_poseidon254_chains(ctx, dbuf, (const unsigned char *)(dbuf + o_abs), (const unsigned int *)(dbuf + o_first), nchains, dbuf + o_out));
+    ZP_HIP(ctx, hipMemcpyAsync(buf + o_out, dbuf + o_out, 512 * nsteps, hipMemcpyDeviceToHost, ctx->stream));
+    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(h_rates, buf + o_out, 512 * nsteps);
+    ctx->verify_counters[0] += 1;
+    ctx->verify_counters[1] += nsteps;
+    return ZP_OK;
+}
+
+// The commitment of every long public-input vector of a call (csrc/verify.hip: publics_digest_host254 is the host's statement of the same): rows of 48
+// values, >= 1 row, as the columns of a 48-wide matrix through zp_merkle16_commit_bn254's kernels, tree after tree on the stream; the roots come back
+// in one copy after one synchronisation.  One buffer: [columns of every vector][tree of every vector][roots]
+int32_t zpi_publics_digests_bn254(zp_ctx *ctx, const std::vector<const std::vector<u64> *> &pubs, u64 *h_out4) {
+    ZP_BIND(ctx);
+    const size_t n = pubs.size();
+    if (!n) return ZP_OK;
+    std::vector<size_t> rows(n), col_at(n), tree_at(n);
+    size_t at = 0;
+    for (size_t i = 0; i < n; i++) { rows[i] = (pubs[i]->size() + 47) / 48; rows[i] = rows[i] ? rows[i] : 1; col_at[i] = at; at += 48 * rows[i]; }
+    const size_t n_cols = at;
+    for (size_t i = 0; i < n; i++) { tree_at[i] = at; at += 4 * zp_merkle16_nodes(rows[i]); }
+    const size_t o_roots = at, total = at + 4 * n;
+    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    void *stv = nullptr;
+    ZP_TRY(zpi_pinned(ctx, (n_cols > 4 * n ? n_cols : 4 * n) * 8, &stv));
+    u64 *buf = (u64 *)stv, *dbuf = nullptr;
+    for (size_t i = 0; i < n; i++)
+        for (size_t j = 0; j < 48; j++)
+            for (size_t r = 0; r < rows[i]; r++) buf[col_at[i] + j * rows[i] + r] = 48 * r + j < pubs[i]->size() ? (*pubs[i])[48 * r + j] : 0;
+    ZP_TRY(zpi_scratch(ctx, 3, total, &dbuf));
+    ZP_HIP(ctx, hipMemcpyAsync(dbuf, buf, n_cols * 8, hipMemcpyHostToDevice, ctx->stream));
+    for (size_t i = 0; i < n; i++) {
+        ZP_TRY(zp_merkle16_commit_bn254(ctx, (const uint64_t *)(dbuf + col_at[i]), rows[i], 48, (uint64_t *)(dbuf + tree_at[i])));
+        ZP_HIP(ctx, hipMemcpyAsync(dbuf + o_roots + 4 * i, dbuf + tree_at[i] + 4 * (zp_merkle16_nodes(rows[i]) - 1), 32, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    ZP_HIP(ctx, hipMemcpyAsync(buf, dbuf + o_roots, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
+    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(h_out4, buf, 32 * n);
     return ZP_OK;
 }
 

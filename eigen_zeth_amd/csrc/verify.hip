@@ -36,6 +36,14 @@ extern int32_t zpi_fixed_eval_device(zp_ctx *ctx, const uint64_t *h_program, siz
                                      int32_t n_pubchal, int32_t logn, uint64_t root32, const uint64_t *h_zeta, int32_t n_points, uint64_t *h_sparse, uint8_t *h_on_domain)
     __attribute__((weak));            // csrc/fixed_eval.hip (absent: zp_program_fixed_eval_ext_batch runs on the host whatever the ctx)
 extern int32_t zpi_p254_host_tables(zp_ctx *ctx, std::vector<u32> *rc, std::vector<u32> *mds, int *rp) __attribute__((weak));
+// the transcripts of a call on the device (absent: the host sponges whatever the knob says): sponge chains from host buffers, one launch and one
+// synchronisation each (csrc/poseidon.hip, csrc/poseidon_bn254.hip), and the commitments of long public-input vectors with the kernels that build
+// those trees for the prover
+extern int32_t zpi_poseidon_chains_host(zp_ctx *ctx, const u64 *h_blocks, const uint8_t *h_absorb, const uint32_t *h_first, int nchains, u64 *h_rates) __attribute__((weak));
+extern int32_t zpi_poseidon254_chains_host(zp_ctx *ctx, const u64 *h_blocks, const uint8_t *h_absorb, const uint32_t *h_first, int nchains, u64 *h_rates)
+    __attribute__((weak));
+extern int32_t zpi_publics_digests(zp_ctx *ctx, const std::vector<const std::vector<u64> *> &pubs, u64 *h_out4) __attribute__((weak));
+extern int32_t zpi_publics_digests_bn254(zp_ctx *ctx, const std::vector<const std::vector<u64> *> &pubs, u64 *h_out4) __attribute__((weak));
 
 namespace {
 
@@ -392,7 +400,7 @@ struct HostPoseidon {
     }
 };
 
-// stark/transcript.py: absorb queues; a squeeze first absorbs the queue in blocks of 8 that overwrite the rate (one permutation when nothing is
+// stark/transcript.py: absorb queues; a squeeze first absorbs the queue in blocks that overwrite the rate (one bare permutation when nothing is
 // queued), then hands out the rate
 struct Transcript {                            // what the header phase asks of either mode's sponge
     virtual void absorb(const u64 *v, size_t n) = 0;
@@ -402,27 +410,110 @@ struct Transcript {                            // what the header phase asks of 
     e3 challenge() { u64 c[3]; squeeze(3, c); return e3_make(c[0], c[1], c[2]); }
 };
 
-struct HostSponge : Transcript {
-    const HostPoseidon &H;
-    u64 st[12] = {0};
+// What a hash mode makes of the queue: BW words per block, NOUT values per rate.
+// Goldilocks mode: a value is a word, a root four of them, blocks of 8, the rate as it stands.
+struct GlMode {
+    static constexpr size_t BW = 8, NOUT = 8;
+    static void queue(std::vector<u64> &q, const u64 *v, size_t n) { for (size_t i = 0; i < n; i++) q.push_back(gl_canon(v[i])); }
+    static void queue_root(std::vector<u64> &q, const u64 *root4) { queue(q, root4, 4); }
+    static void read(const u64 *rate, u64 *avail) { memcpy(avail, rate, 8 * NOUT); }
+};
+// BN128 mode (oracle/stark_verify.py SpongeBN128; stark/transcript.py TranscriptBN128): an element is four words, standard form; Goldilocks values go
+// three to an element (each absorb padded separately), a root is one element; blocks of 16 elements; the rate is read as the three low 64-bit words of
+// each of its 16 elements mod p
+struct BnMode {
+    static constexpr size_t BW = 64, NOUT = 48;
+    static void queue(std::vector<u64> &q, const u64 *v, size_t n) {
+        for (size_t i = 0; i < n; i += 3) {
+            for (size_t c = 0; c < 3; c++) q.push_back(i + c < n ? gl_canon(v[i + c]) : 0);
+            q.push_back(0);
+        }
+    }
+    static void queue_root(std::vector<u64> &q, const u64 *root4) { q.insert(q.end(), root4, root4 + 4); }
+    static void read(const u64 *rate, u64 *avail) {
+        for (int e = 0; e < 16; e++)
+            for (int c = 0; c < 3; c++) avail[3 * e + c] = gl_canon(rate[4 * e + c]);
+    }
+};
+
+// THE block rule, once for both modes and for everything that walks a transcript: a squeeze that finds values queued (or the rate used up) turns the
+// queue into STEPS -- (absorb flag, block): one bare permutation when nothing is queued, else one absorbing step per block of BW words, the last
+// one zero padded -- and then reads the rate after the last step.  What a step does is the user's: hash (HostSponge, HostSponge254), record
+// (PlanSponge), or advance through recorded steps whose rates the device wrote (ReplaySponge).
+template <class M>
+struct BlockSponge : Transcript {
     std::vector<u64> q;
-    int pos = 8;
-    explicit HostSponge(const HostPoseidon &h) : H(h) {}
-    void absorb(const u64 *v, size_t n) override { for (size_t i = 0; i < n; i++) q.push_back(gl_canon(v[i])); pos = 8; }
-    void absorb_root(const u64 *root4) override { absorb(root4, 4); }
+    u64 avail[M::NOUT];
+    size_t pos = M::NOUT;
+    virtual void step(bool absorb, const u64 *block) = 0;      // block: BW words (absorb) or NULL
+    virtual void rate(u64 *out) = 0;                           // the rate after the last step, BW standard words
+    void absorb(const u64 *v, size_t n) override { M::queue(q, v, n); pos = M::NOUT; }
+    void absorb_root(const u64 *root4) override { M::queue_root(q, root4); pos = M::NOUT; }
     void squeeze(size_t n, u64 *out) override {
         for (size_t k = 0; k < n; k++) {
-            if (!q.empty() || pos == 8) {
-                if (q.empty()) H.perm(st);
-                for (size_t off = 0; off < q.size(); off += 8) {
-                    for (size_t j = 0; j < 8; j++) st[j] = off + j < q.size() ? q[off + j] : 0;
-                    H.perm(st);
+            if (!q.empty() || pos == M::NOUT) {
+                if (q.empty()) step(false, nullptr);
+                for (size_t off = 0; off < q.size(); off += M::BW) {
+                    u64 blk[M::BW];
+                    for (size_t j = 0; j < M::BW; j++) blk[j] = off + j < q.size() ? q[off + j] : 0;
+                    step(true, blk);
                 }
                 q.clear();
+                u64 r[M::BW];
+                rate(r);
+                M::read(r, avail);
                 pos = 0;
             }
-            out[k] = st[pos++];
+            out[k] = avail[pos++];
         }
+    }
+};
+
+struct HostSponge : BlockSponge<GlMode> {
+    const HostPoseidon &H;
+    u64 st[12] = {0};
+    explicit HostSponge(const HostPoseidon &h) : H(h) {}
+    void step(bool absorb, const u64 *block) override { if (absorb) memcpy(st, block, 64); H.perm(st); }
+    void rate(u64 *out) override { memcpy(out, st, 64); }
+};
+
+// The transcripts of a call as sponge chains (csrc/poseidon.hip: sponge_chains_kernel; csrc/poseidon_bn254.hip: sponge_chains254_kernel): nothing a
+// verifier absorbs depends on a challenge, so the steps of every text are known once it is parsed.  Chain c is the steps [first[c], first[c + 1]);
+// blocks: bw words per step (zero for a bare step); rates: bw words per step, written by the device.
+struct ChainPlan {
+    std::vector<u64> blocks, rates;
+    std::vector<uint8_t> absorb;
+    std::vector<uint32_t> first = {0};
+};
+// records the steps and returns nothing (every squeezed value reads 0: the schedule of a transcript does not depend on them)
+template <class M>
+struct PlanSponge : BlockSponge<M> {
+    ChainPlan &cp;
+    explicit PlanSponge(ChainPlan &c) : cp(c) {}
+    void step(bool absorb, const u64 *block) override {
+        cp.absorb.push_back(absorb ? 1 : 0);
+        if (absorb) cp.blocks.insert(cp.blocks.end(), block, block + M::BW);
+        else cp.blocks.resize(cp.blocks.size() + M::BW, 0);
+    }
+    void rate(u64 *out) override { memset(out, 0, 8 * M::BW); }
+    size_t next_word() const { return cp.blocks.size() + this->q.size(); }      // where, in cp.blocks, the next queued word will stand
+    void close() { cp.first.push_back((uint32_t)cp.absorb.size()); }
+};
+// holds a chain's recorded steps and the rates the device wrote: absorbing advances through the plan, squeezing hands out the recorded rate of the
+// step it has reached.  A replay that leaves its plan (another step than the recorded one, or one too many) is a bug of this file, never a verdict
+struct ReplayLeftPlan {};
+template <class M>
+struct ReplaySponge : BlockSponge<M> {
+    const ChainPlan &cp;
+    size_t at, begin, end;
+    ReplaySponge(const ChainPlan &c, size_t chain) : cp(c), at(c.first[chain]), begin(c.first[chain]), end(c.first[chain + 1]) {}
+    void step(bool absorb, const u64 *block) override {
+        if (at >= end || (cp.absorb[at] != 0) != absorb || (absorb && memcmp(&cp.blocks[at * M::BW], block, 8 * M::BW) != 0)) throw ReplayLeftPlan{};
+        at++;
+    }
+    void rate(u64 *out) override {
+        if (at == begin) throw ReplayLeftPlan{};
+        memcpy(out, &cp.rates[(at - 1) * M::BW], 8 * M::BW);
     }
 };
 
@@ -529,43 +620,16 @@ struct HostPoseidon254 {
     }
 };
 
-// oracle/stark_verify.py SpongeBN128 (stark/transcript.py TranscriptBN128): element 0 = capacity, 1..16 = rate.  Goldilocks values go three to an
-// element (each absorb padded separately), a root is one element; a squeeze absorbs the queue in blocks of 16 that overwrite the rate (one permutation
-// when nothing is queued) and hands out the three low 64-bit words of each rate element mod p
-struct HostSponge254 : Transcript {
+// the width-17 sponge of BN128 mode on the host: element 0 = capacity, 1..16 = rate (BnMode and the block rule above)
+struct HostSponge254 : BlockSponge<BnMode> {
     const HostPoseidon254 &H;
     fr st[17];
-    std::vector<u64> q;                        // four words per queued element
-    u64 avail[48];
-    int pos = 48;
     explicit HostSponge254(const HostPoseidon254 &h) : H(h) { for (fr &x : st) x = fr_zero(); }
-    void absorb(const u64 *v, size_t n) override {
-        for (size_t i = 0; i < n; i += 3) {
-            for (size_t c = 0; c < 3; c++) q.push_back(i + c < n ? gl_canon(v[i + c]) : 0);
-            q.push_back(0);
-        }
-        pos = 48;
+    void step(bool absorb, const u64 *block) override {
+        if (absorb) for (size_t j = 0; j < 16; j++) st[1 + j] = fr_to_mont(fr_from_u64(block + 4 * j));
+        H.perm(st);
     }
-    void absorb_root(const u64 *root4) override { q.insert(q.end(), root4, root4 + 4); pos = 48; }
-    void squeeze(size_t n, u64 *out) override {
-        for (size_t k = 0; k < n; k++) {
-            if (!q.empty() || pos == 48) {
-                if (q.empty()) H.perm(st);
-                for (size_t off = 0; off < q.size(); off += 64) {
-                    for (size_t j = 0; j < 16; j++) st[1 + j] = off + 4 * j < q.size() ? fr_to_mont(fr_from_u64(&q[off + 4 * j])) : fr_zero();
-                    H.perm(st);
-                }
-                q.clear();
-                for (int e = 0; e < 16; e++) {
-                    u64 w[4];
-                    fr_to_u64(fr_from_mont(st[1 + e]), w);
-                    for (int c = 0; c < 3; c++) avail[3 * e + c] = gl_canon(w[c]);
-                }
-                pos = 0;
-            }
-            out[k] = avail[pos++];
-        }
-    }
+    void rate(u64 *out) override { for (int e = 0; e < 16; e++) fr_to_u64(fr_from_mont(st[1 + e]), out + 4 * e); }
 };
 
 // the same commitment in BN128 mode (publics_rows: rows of 48 values, three to an element, >= 1 row; the 16-ary tree of zp_merkle16_commit_bn254)
@@ -810,11 +874,78 @@ int32_t identity_at_zeta(const ProgramInfo &pg, const VerifyParams &vp, const st
     return ZP_OK;
 }
 
-int32_t header_phase(const char *text, size_t len, const ProgramInfo &pg, const VerifyParams &vp, const HostPoseidon &H, Pending *pd, PublicSponge *ps = nullptr) {
-    auto verdict = [&](int v) { pd->verdict = v; return ZP_OK; };
-    ProofHeader h;
+void fri_schedule(const VerifyParams &vp, std::vector<std::pair<int, int>> *sched, int *final_log) {
+    int cur = vp.logn + vp.logb;
+    const int stop = vp.fri_final_log + vp.logb;
+    while (cur > stop) { const int f = vp.fri_logf < cur - stop ? vp.fri_logf : cur - stop; sched->push_back({cur, f}); cur -= f; }
+    *final_log = cur;
+}
+
+// what opens a transcript: the statement and the parameters, then the public inputs themselves when there are at most 64 (PUBLICS_INLINE) -- ONE
+// absorb (BN128 mode packs three values to an element per absorb); a longer vector follows as the root of its commitment
+std::vector<u64> transcript_head(const ProgramInfo &pg, const VerifyParams &vp, const std::vector<u64> &pubs) {
+    std::vector<u64> head = {(u64)vp.logn, (u64)vp.logb, (u64)pg.W, (u64)pg.W2, (u64)vp.fri_logf, (u64)vp.fri_final_log, (u64)vp.n_queries, (u64)vp.pow_bits, vp.root32, vp.shift,
+                             pg.digest_words[0], pg.digest_words[1], pg.digest_words[2], pg.digest_words[3], (u64)pubs.size()};
+    if (pubs.size() <= 64) head.insert(head.end(), pubs.begin(), pubs.end());
+    return head;
+}
+
+// The schedule of a text's transcript: only the absorb and squeeze calls of the header phase below, in its order, on a parsed header -- what a
+// PlanSponge records.  *digest_word: where in the plan's blocks the four words of the public inputs' commitment stand (more than 64 public inputs;
+// zeros are planned, the caller writes the digest in).  false: the header lacks a member the walk needs, or has one of another size than the statement
+// dictates, or (BN128 mode) a root >= r: no plan -- the header phase ends such a text MALFORMED / PARAMS / POW before much is hashed.
+template <class M>
+bool transcript_schedule(const ProofHeader &h, const ProgramInfo &pg, const VerifyParams &vp, PlanSponge<M> &tr, bool *long_pubs, size_t *digest_word) {
     const bool bn = vp.H254 != nullptr;
-    if (!parse_header(text, len, bn, &h)) return verdict(ZP_VERDICT_MALFORMED);
+    const size_t Wt = pg.W + pg.W2, nq = (size_t)vp.n_queries;
+    std::vector<std::pair<int, int>> sched;
+    int final_log = 0;
+    fri_schedule(vp, &sched, &final_log);
+    auto root_ok = [&](const u64 *r) { return !bn || fr_is_canonical_u64(r); };
+    if (!h.has_pubs || h.pubs.size() != pg.n_pub || !h.rows_ok || !h.has_root[0] || !h.has_root[2] || (pg.n_s2 && !h.has_root[1]) || !h.has_z || !h.has_zw ||
+        h.ev_z.size() != 3 * (Wt + 3 * pg.Q) || h.ev_zw.size() != 3 * Wt || !h.has_fri_roots || !h.has_final || h.fri_roots.size() != 4 * sched.size() || h.final_l.size() != 3 ||
+        (vp.pow_bits && !h.has_nonce))
+        return false;
+    if (!root_ok(h.root[0].data()) || !root_ok(h.root[2].data()) || (pg.n_s2 && !root_ok(h.root[1].data()))) return false;
+    for (size_t l = 0; l < sched.size(); l++)
+        if (!root_ok(&h.fri_roots[4 * l])) return false;
+    for (int c = 0; c < 3; c++)
+        if (h.final_l[c].size() != ((size_t)1 << final_log)) return false;
+    std::vector<u64> out(nq > 4 ? nq : 4);
+    const std::vector<u64> head = transcript_head(pg, vp, h.pubs);
+    tr.absorb(head.data(), head.size());
+    *long_pubs = h.pubs.size() > 64;
+    if (*long_pubs) {
+        const u64 zero[4] = {0, 0, 0, 0};
+        *digest_word = tr.next_word();
+        tr.absorb_root(zero);
+    }
+    tr.absorb_root(h.root[0].data());
+    if (pg.n_s2) { tr.squeeze(3, out.data()); tr.absorb_root(h.root[1].data()); }
+    tr.squeeze(3, out.data());                 // alpha
+    tr.absorb_root(h.root[2].data());
+    tr.squeeze(3, out.data());                 // zeta
+    tr.absorb(h.ev_z.data(), h.ev_z.size());
+    tr.absorb(h.ev_zw.data(), h.ev_zw.size());
+    tr.squeeze(3, out.data());                 // gamma
+    for (size_t l = 0; l < sched.size(); l++) { tr.absorb_root(&h.fri_roots[4 * l]); tr.squeeze(3, out.data()); }      // beta_l
+    for (int c = 0; c < 3; c++) tr.absorb(h.final_l[c].data(), h.final_l[c].size());
+    if (vp.pow_bits) { tr.squeeze(4, out.data()); const u64 nonce = h.nonce; tr.absorb(&nonce, 1); }
+    tr.squeeze(nq, out.data());
+    return true;
+}
+
+// what a caller that ran the transcripts of its texts elsewhere hands the header phase: the header it parsed, the sponge that replays the text's
+// chain (NULL: the text got no plan and takes the host sponge), and the commitment of a long public-input vector when the device made it
+struct HeaderAid { ProofHeader *parsed = nullptr; bool parsed_ok = false; Transcript *replay = nullptr; const u64 *pub_digest = nullptr; };
+
+int32_t header_phase(const char *text, size_t len, const ProgramInfo &pg, const VerifyParams &vp, const HostPoseidon &H, Pending *pd, PublicSponge *ps = nullptr,
+                     const HeaderAid *aid = nullptr) {
+    auto verdict = [&](int v) { pd->verdict = v; return ZP_OK; };
+    ProofHeader own;
+    ProofHeader &h = aid && aid->parsed ? *aid->parsed : own;
+    const bool bn = vp.H254 != nullptr;
+    if (!(aid && aid->parsed ? aid->parsed_ok : parse_header(text, len, bn, &own))) return verdict(ZP_VERDICT_MALFORMED);
     // 1. parameters, domain, statement, counts
     const u64 want[ProofHeader::NPARAM] = {(u64)vp.logn, (u64)vp.logb, (u64)vp.fri_logf, (u64)vp.fri_final_log, (u64)vp.n_queries, (u64)vp.pow_bits};
     if (!h.has_params) return verdict(ZP_VERDICT_MALFORMED);
@@ -835,16 +966,17 @@ int32_t header_phase(const char *text, size_t len, const ProgramInfo &pg, const 
     HostSponge tr_gl(H);
     static const HostPoseidon254 no_tables;
     HostSponge254 tr_bn(bn ? *vp.H254 : no_tables);
-    Transcript &tr = ps ? (Transcript &)*ps : bn ? (Transcript &)tr_bn : (Transcript &)tr_gl;      // ps: the transcript is READ (an inner header of an aggregated proof)
+    // ps: the transcript is READ (an inner header of an aggregated proof); aid->replay: its permutations ran on the device, in the call's one chain launch
+    Transcript &tr = ps ? (Transcript &)*ps : aid && aid->replay ? *aid->replay : bn ? (Transcript &)tr_bn : (Transcript &)tr_gl;
     auto root_ok = [&](const u64 *r) { return !bn || fr_is_canonical_u64(r); };      // "malformed BN128 root"
     {
-        std::vector<u64> head = {(u64)logn, (u64)logb, (u64)W, (u64)W2, (u64)vp.fri_logf, (u64)vp.fri_final_log, (u64)vp.n_queries, (u64)vp.pow_bits, vp.root32, vp.shift,
-                                 pg.digest_words[0], pg.digest_words[1], pg.digest_words[2], pg.digest_words[3], (u64)h.pubs.size()};
-        if (h.pubs.size() <= 64) head.insert(head.end(), h.pubs.begin(), h.pubs.end());      // PUBLICS_INLINE
+        const std::vector<u64> head = transcript_head(pg, vp, h.pubs);
         tr.absorb(head.data(), head.size());
         if (h.pubs.size() > 64) {
             u64 dg[4];
-            if (bn) publics_digest_host254(*vp.H254, h.pubs, dg); else publics_digest_host(H, h.pubs, dg);
+            if (aid && aid->pub_digest) memcpy(dg, aid->pub_digest, 32);
+            else if (bn) publics_digest_host254(*vp.H254, h.pubs, dg);
+            else publics_digest_host(H, h.pubs, dg);
             tr.absorb_root(dg);
         }
     }
@@ -1145,6 +1277,82 @@ int32_t queries_phase(zp_ctx *ctx, const VerifyParams &vp, const HostPoseidon &H
     return ZP_OK;
 }
 
+// ---- The transcripts of a call on the device ("verify_chain_dev"; ctx.hpp).  Every text of the call is parsed and its schedule recorded as one chain;
+// the commitments of the long public-input vectors are made with the prover's tree kernels and written into their blocks (first synchronisation); ALL
+// chains of the call run in ONE launch of the mode's chain kernel (second synchronisation); the header phases then replay them.  A text that gets no
+// plan takes the host sponge (counted: zp_verify_counters).  Verdicts, *where, indices and error codes are the host path's word for word: the device
+// path moves permutations and nothing else.
+bool chains_on_device(const zp_ctx *ctx, bool bn) {
+    if (!ctx || ctx->tune_verify_chain_dev == 0) return false;
+    (void)bn;
+    return ctx->tune_verify_chain_dev == 2;            // the default leaves both modes on the host: neither beat the parent at every measured batch size (ctx.hpp)
+}
+struct TextPlan {
+    ProofHeader h;
+    bool parsed_ok = false, planned = false, long_pubs = false;
+    size_t chain = 0, digest_word = 0;
+    u64 digest[4] = {0, 0, 0, 0};
+};
+struct PlanItem { const char *text; size_t len; const ProgramInfo *pg; const VerifyParams *vp; };
+struct DeviceTranscripts {
+    bool on = false, bn = false;
+    ChainPlan cp;
+    std::vector<TextPlan> tp;
+
+    template <class M>
+    int32_t run_mode(zp_ctx *ctx, const std::vector<PlanItem> &items) {
+        const auto chains = bn ? zpi_poseidon254_chains_host : zpi_poseidon_chains_host;
+        const auto digests = bn ? zpi_publics_digests_bn254 : zpi_publics_digests;
+        if (!chains || !digests) { ctx->err = "this build has no device side"; return ZP_ERR_UNSUPPORTED; }
+        tp = std::vector<TextPlan>(items.size());
+        std::vector<const std::vector<u64> *> longs;
+        std::vector<size_t> who;
+        for (size_t i = 0; i < items.size(); i++) {
+            TextPlan &t = tp[i];
+            t.parsed_ok = parse_header(items[i].text, items[i].len, bn, &t.h);
+            if (t.parsed_ok) {
+                PlanSponge<M> ps(cp);
+                t.planned = transcript_schedule(t.h, *items[i].pg, *items[i].vp, ps, &t.long_pubs, &t.digest_word);      // (false: nothing was recorded)
+                if (t.planned) { t.chain = cp.first.size() - 1; ps.close(); }
+            }
+            if (!t.planned) { ctx->verify_counters[3]++; continue; }
+            if (t.long_pubs) {
+                for (u64 &v : t.h.pubs) v = gl_canon(v);
+                longs.push_back(&t.h.pubs); who.push_back(i);
+            }
+        }
+        if (!longs.empty()) {
+            std::vector<u64> dg(4 * longs.size());
+            ZP_TRY(digests(ctx, longs, dg.data()));
+            for (size_t k = 0; k < who.size(); k++) {
+                memcpy(tp[who[k]].digest, &dg[4 * k], 32);
+                memcpy(&cp.blocks[tp[who[k]].digest_word], &dg[4 * k], 32);
+            }
+            ctx->verify_counters[2] += longs.size();
+        }
+        if (cp.absorb.empty()) return ZP_OK;
+        if (cp.absorb.size() >= ((size_t)1 << 31)) { ctx->err = "too many transcript steps in one call"; return ZP_ERR_ARG; }
+        cp.rates.resize(cp.blocks.size());
+        return chains(ctx, cp.blocks.data(), cp.absorb.data(), cp.first.data(), (int)(cp.first.size() - 1), cp.rates.data());
+    }
+    int32_t run(zp_ctx *ctx, bool bn_mode, const std::vector<PlanItem> &items) {
+        on = true; bn = bn_mode;
+        return bn ? run_mode<BnMode>(ctx, items) : run_mode<GlMode>(ctx, items);
+    }
+    // the header phase of text i on its chain
+    int32_t header(size_t i, const char *text, size_t len, const ProgramInfo &pg, const VerifyParams &vp, const HostPoseidon &H, Pending *pd) {
+        TextPlan &t = tp[i];
+        HeaderAid aid;
+        aid.parsed = &t.h; aid.parsed_ok = t.parsed_ok;
+        if (!t.planned) return header_phase(text, len, pg, vp, H, pd, nullptr, &aid);
+        if (t.long_pubs) aid.pub_digest = t.digest;
+        ReplaySponge<GlMode> gl(cp, t.chain);
+        ReplaySponge<BnMode> b254(cp, t.chain);
+        aid.replay = bn ? (Transcript *)&b254 : (Transcript *)&gl;
+        return header_phase(text, len, pg, vp, H, pd, nullptr, &aid);
+    }
+};
+
 int32_t verify_batch_impl(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const char *const *proofs, const size_t *lens, int32_t n_proofs, VerifyParams vp,
                           int32_t *verdicts, int32_t *where, uint64_t *h_indices) {
     if (!h_program || !proofs || !lens || !verdicts || n_proofs < 1 || n_proofs > (1 << 20)) return ZP_ERR_ARG;
@@ -1160,15 +1368,27 @@ int32_t verify_batch_impl(zp_ctx *ctx, const uint64_t *h_program, size_t program
 
     std::vector<Pending> pend((size_t)n_proofs);
     std::vector<int32_t> hrc((size_t)n_proofs, ZP_OK);
+    // the transcripts of all texts as one chain launch, where they go to the device
+    DeviceTranscripts dt;
+    if (chains_on_device(ctx, vp.H254 != nullptr)) {
+        std::vector<PlanItem> items((size_t)n_proofs);
+        for (int32_t i = 0; i < n_proofs; i++) items[i] = {proofs[i], lens[i], &pg, &vp};
+        ZP_TRY(dt.run(ctx, vp.H254 != nullptr, items));
+    }
     // headers: a transcript is a serial chain, proofs are independent
     spread((size_t)n_proofs, n_proofs > 1 ? vp.threads : 1, [&](size_t i) {
-        try { VerifyParams one = vp; if (n_proofs > 1) one.threads = 1; hrc[i] = header_phase(proofs[i], lens[i], pg, one, H, &pend[i]); }
+        try {
+            VerifyParams one = vp;
+            if (n_proofs > 1) one.threads = 1;
+            hrc[i] = dt.on ? dt.header(i, proofs[i], lens[i], pg, one, H, &pend[i]) : header_phase(proofs[i], lens[i], pg, one, H, &pend[i]);
+        }
         catch (const std::bad_alloc &) { hrc[i] = ZP_ERR_NOMEM; }
         catch (...) { hrc[i] = ZP_ERR_INTERNAL; }
     });
     for (int32_t r : hrc)
         if (r != ZP_OK) {
-            if (ctx) ctx->err = r == ZP_ERR_UNSUPPORTED ? "a proof in BN128-hash mode handed to the Goldilocks-mode call (or a build without the openings parser)" : "the program blob could not be evaluated at the proof's point";
+            if (ctx) ctx->err = r == ZP_ERR_UNSUPPORTED ? "a proof in BN128-hash mode handed to the Goldilocks-mode call (or a build without the openings parser)"
+                              : r == ZP_ERR_INTERNAL ? "internal error in a header phase (a transcript replay that left its plan)" : "the program blob could not be evaluated at the proof's point";
             return r;
         }
 
@@ -1344,13 +1564,6 @@ struct TextJob {
     TextJob &operator=(const TextJob &) = delete;
 };
 
-void fri_schedule(const VerifyParams &vp, std::vector<std::pair<int, int>> *sched, int *final_log) {
-    int cur = vp.logn + vp.logb;
-    const int stop = vp.fri_final_log + vp.logb;
-    while (cur > stop) { const int f = vp.fri_logf < cur - stop ? vp.fri_logf : cur - stop; sched->push_back({cur, f}); cur -= f; }
-    *final_log = cur;
-}
-
 // the structure of a node and of everything below it, pre-order; nothing is hashed or evaluated here
 void plan_node(TextJob *tj, const AggNode &nd, const std::vector<u64> *pubs, const std::vector<AggStmt> &st, bool top) {
     NodeJob *nj = new NodeJob;
@@ -1509,14 +1722,28 @@ int32_t aggregate_verify_impl(zp_ctx *ctx, const zp_agg_statement *stmts, int32_
         for (NodeJob *n : t.nodes)
             if (n->verdict == ZP_VERDICT_ACCEPT) units.push_back({&t, n});
     }
-    // 2. every header phase (a transcript is a serial chain; nodes and texts are independent)
+    // 2. every header phase (a transcript is a serial chain; nodes and texts are independent).  The transcripts of the outer STARKs of all texts are
+    // one chain launch where they go to the device; inner headers are READ off their vouching public inputs either way
+    DeviceTranscripts dt;
+    std::vector<size_t> outer_slot(units.size(), 0);
+    if (chains_on_device(ctx, false)) {
+        std::vector<PlanItem> items;
+        for (size_t u = 0; u < units.size(); u++)
+            if (!units[u].n) {
+                const TextJob &t = *units[u].t;
+                outer_slot[u] = items.size();
+                items.push_back({t.outer.text.p, t.outer.text.n, &st[t.top_stmt].pg, &st[t.top_stmt].vp});
+            }
+        ZP_TRY(dt.run(ctx, false, items));
+    }
     spread(units.size(), threads, [&](size_t u) {
         TextJob &t = *units[u].t;
         int32_t *rc = units[u].n ? &units[u].n->rc : &t.outer.rc;
         try {
             if (units[u].n) { run_node(units[u].n, st, H); return; }
             t.outer.pd.defer_identity = true;
-            *rc = header_phase(t.outer.text.p, t.outer.text.n, st[t.top_stmt].pg, st[t.top_stmt].vp, H, &t.outer.pd);
+            const AggStmt &S = st[t.top_stmt];
+            *rc = dt.on ? dt.header(outer_slot[u], t.outer.text.p, t.outer.text.n, S.pg, S.vp, H, &t.outer.pd) : header_phase(t.outer.text.p, t.outer.text.n, S.pg, S.vp, H, &t.outer.pd);
         } catch (const std::bad_alloc &) { *rc = ZP_ERR_NOMEM; }
         catch (...) { *rc = ZP_ERR_INTERNAL; }
     });
@@ -1632,6 +1859,51 @@ int32_t zp_stark_verify_batch_bn128(zp_ctx *ctx, const uint64_t *h_program, size
         const VerifyParams vp = {logn, logb, fri_logf, fri_final_log, n_queries, 0, flags, threads, 0, 0, &H254};
         return verify_batch_impl(ctx, h_program, program_words, proofs, lens, n_proofs, vp, verdicts, nullptr, nullptr);
     });
+}
+
+// The chain primitive of the BN128-mode transcripts on its own: chain c walks the steps [h_first[c], h_first[c + 1]) from the zero state; a step
+// overwrites elements 1..16 with its block when h_absorb says so, then permutes; h_rates receives the rate after every step.  With a ctx: the
+// installed tables, all chains in one launch (csrc/poseidon_bn254.hip: sponge_chains254_kernel); ctx = NULL: the caller's tables, HostPoseidon254
+int32_t zp_poseidon_bn254_chains(zp_ctx *ctx, const uint64_t *h_blocks, const uint8_t *h_absorb, const uint32_t *h_first, int32_t nchains, int32_t rp, const uint64_t *h_rc,
+                                 const uint64_t *h_mds, uint64_t *h_rates) {
+    return verify_guarded(ctx, [&]() -> int32_t {
+        auto bad = [&](const char *msg) { if (ctx) ctx->err = std::string("bad argument: ") + msg; return ZP_ERR_ARG; };
+        if (nchains < 0) return bad("nchains < 0");
+        if (nchains > 0 && !h_first) return bad("null h_first");
+        size_t nsteps = 0;
+        if (nchains > 0) {
+            if (h_first[0] != 0) return bad("h_first must start at 0");
+            for (int32_t c = 0; c < nchains; c++)
+                if (h_first[c + 1] < h_first[c]) return bad("h_first must be non-decreasing");
+            nsteps = h_first[nchains];
+        }
+        if (nsteps >= ((size_t)1 << 24)) return bad("too many steps");
+        if (nsteps && (!h_blocks || !h_absorb || !h_rates)) return bad("null pointer");
+        for (size_t i = 0; i < nsteps * 16; i++)
+            if (!fr_is_canonical_u64((const u64 *)h_blocks + 4 * i)) return bad("block element not reduced mod r");
+        HostPoseidon254 H254;
+        ZP_TRY(tables254(ctx, rp, h_rc, h_mds, &H254));
+        if (!nsteps) return ZP_OK;
+        if (ctx) {
+            if (!zpi_poseidon254_chains_host) { ctx->err = "this build has no device side"; return ZP_ERR_UNSUPPORTED; }
+            return zpi_poseidon254_chains_host(ctx, (const u64 *)h_blocks, h_absorb, h_first, nchains, (u64 *)h_rates);
+        }
+        for (int32_t c = 0; c < nchains; c++) {
+            HostSponge254 sp(H254);
+            for (size_t s = h_first[c]; s < h_first[c + 1]; s++) {
+                sp.step(h_absorb[s] != 0, (const u64 *)h_blocks + 64 * s);
+                sp.rate((u64 *)h_rates + 64 * s);
+            }
+        }
+        return ZP_OK;
+    });
+}
+
+// since zp_create: chain launches; chain steps run on the device; public-input commitments made on the device; texts that fell back to the host sponge
+int32_t zp_verify_counters(zp_ctx *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return ZP_ERR_ARG;
+    for (int i = 0; i < 4; i++) out[i] = ctx->verify_counters[i];
+    return ZP_OK;
 }
 
 int32_t zp_aggregate_verify(zp_ctx *ctx, const zp_agg_statement *stmts, int32_t n_stmts, const char *text, size_t len, uint32_t flags, int32_t threads, int32_t *verdict,

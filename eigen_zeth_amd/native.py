@@ -103,6 +103,8 @@ SIGNATURES = {
     "zp_poly_eval_ext": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, _u64p, _u64p]),
     "zp_program_eval_ext": (C.c_int32, [_u64p, C.c_size_t, _u64p, C.c_int32, C.c_int32, C.c_uint64, _u64p, _u64p, _u64p, C.c_int32, _u64p, C.c_int32, C.c_int32]),
     "zp_program_fixed_eval_ext": (C.c_int32, [_u64p, C.c_size_t, _u64p, C.c_int32, C.c_int32, C.c_uint64, _u64p, _u64p, C.c_int32, C.c_int32]),
+    "zp_poseidon_bn254_chains": (C.c_int32, [_vp, _u64p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.c_int32, C.c_int32, _u64p, _u64p, _u64p]),
+    "zp_verify_counters": (C.c_int32, [_vp, _u64p]),
     "zp_aggregate_verify": (C.c_int32, [_vp, C.POINTER(AggStatement), C.c_int32, C.c_char_p, C.c_size_t, C.c_uint32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "zp_aggregate_verify_batch": (C.c_int32, [_vp, C.POINTER(AggStatement), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int32, C.c_uint32, C.c_int32,
                                               C.POINTER(C.c_int32)]),
@@ -465,6 +467,35 @@ def stark_verify_batch_bn128(program, texts, params, flags=0, prover=None, threa
     if rc != 0:
         _verify_error(prover, rc, "zp_stark_verify_batch_bn128")
     return list(out)
+
+
+def poseidon_bn254_chains(blocks, absorb, first, prover=None, bn_tables=None):
+    """zp_poseidon_bn254_chains: sponge chains of the width-17 transcript.  blocks u64[nsteps][16][4] (standard form, < r), absorb u8[nsteps],
+    first u32[nchains + 1] -> rates u64[nsteps][16][4], the rate after every step.  Chain c starts from the zero state and walks the steps
+    [first[c], first[c + 1]); a step overwrites the rate with its block when absorb says so, then permutes.  prover = None: on the host with
+    bn_tables = (rc, mds, rp); otherwise one launch on that ctx with the tables installed on it"""
+    fi = np.ascontiguousarray(first, dtype=np.uint32).reshape(-1)
+    ab = np.ascontiguousarray(absorb, dtype=np.uint8).reshape(-1)
+    bl = np.ascontiguousarray(blocks, dtype=np.uint64).reshape(-1)
+    rates = np.zeros(max(bl.size, 1), dtype=np.uint64)
+    tb, keep = _verify_params_bn128({"logn": 0, "logb": 0, "fri_logf": 0, "fri_final_log": 0, "n_queries": 0}, prover, bn_tables)
+    rc = load_library().zp_poseidon_bn254_chains(prover.ctx if prover is not None else None, bl.ctypes.data_as(_u64p) if bl.size else None,
+                                                 ab.ctypes.data_as(C.POINTER(C.c_uint8)) if ab.size else None, fi.ctypes.data_as(C.POINTER(C.c_uint32)) if fi.size else None,
+                                                 fi.size - 1, *tb[5:], rates.ctypes.data_as(_u64p))
+    del keep
+    if rc != 0:
+        if prover is not None:
+            prover._chk(rc)
+        raise ZpError(rc, "zp_poseidon_bn254_chains: bad arguments")
+    return rates[:bl.size].reshape(-1, 16, 4)
+
+
+def verify_counters(prover):
+    """zp_verify_counters: what the verifier calls of this ctx ran where since it was made -- {"launches": chain launches, "steps": chain steps run on
+    the device, "digests": public-input commitments made on the device, "fallbacks": texts that took the host sponge on the device path}"""
+    out = np.zeros(4, dtype=np.uint64)
+    prover._chk(load_library().zp_verify_counters(prover.ctx, out.ctypes.data_as(_u64p)))
+    return dict(zip(("launches", "steps", "digests", "fallbacks"), (int(v) for v in out)))
 
 
 def agg_statements(entries):

@@ -660,6 +660,24 @@ int32_t zp_stark_verify_batch_bn128(zp_ctx *ctx, const uint64_t *h_program, size
 int32_t zp_merkle16_verify_batch_bn254(zp_ctx *ctx, const uint64_t *h_values, size_t width, const uint64_t *h_index, const uint64_t *h_paths,
                                        size_t M, const uint64_t *h_root4, size_t n, uint8_t *h_ok);
 
+/* ---- the transcripts of the verifier calls above as sponge chains.  Nothing a verifier absorbs depends on a challenge, so the whole schedule of
+ * every text of a call is known once it is parsed.  With a ctx and "verify_chain_dev" (zp_set_tuning: 0 never, 2 always, 1 the default: where it
+ * measured faster than the host at every batch size -- today in neither hash mode) zp_stark_verify*, zp_stark_verify*_bn128 and the outer STARKs of zp_aggregate_verify* run ALL transcripts of a call
+ * as ONE launch of the mode's chain kernel, and make the commitments of public-input vectors longer than 64 on the device before it (at most two
+ * synchronisations per call for transcripts).  Verdicts, *where, h_indices and error codes are the host path's; a text whose header lacks what a
+ * transcript needs takes the host sponge (and ends MALFORMED / PARAMS / POW there).  The grinding permutation stays on the host.  ctx = NULL: unchanged.
+ * zp_poseidon_bn254_chains: the BN128-mode chain primitive on host buffers.  Chain c starts from the zero state and walks the steps
+ *   [h_first[c], h_first[c + 1]); a step overwrites elements 1..16 with its block when h_absorb[s] != 0, then permutes (width 17).
+ *   h_blocks u64[nsteps][16][4] standard form; h_absorb u8[nsteps]; h_first u32[nchains + 1]; h_rates u64[nsteps][16][4]: the rate after each step.
+ *   With a ctx: the installed t = 17 tables (rp = 0, h_rc = h_mds = NULL, as zp_stark_verify_bn128) and one kernel launch; ctx = NULL: the caller's
+ *   tables, on the host.  ZP_ERR_ARG: a block element >= r (of any step), h_first not non-decreasing from 0, nchains < 0, a null pointer with a
+ *   non-empty call.  A chain of zero steps is legal and writes nothing.
+ * zp_verify_counters: since zp_create -- out[0] chain launches, out[1] chain steps run on the device, out[2] public-input commitments made on the
+ *   device, out[3] texts that took the host sponge although the call's transcripts went to the device.                                          */
+int32_t zp_poseidon_bn254_chains(zp_ctx *ctx, const uint64_t *h_blocks, const uint8_t *h_absorb, const uint32_t *h_first, int32_t nchains,
+                                 int32_t rp, const uint64_t *h_rc, const uint64_t *h_mds, uint64_t *h_rates);
+int32_t zp_verify_counters(zp_ctx *ctx, uint64_t out[4]);
+
 /* ---- host-buffer conveniences (H2D + compute + D2H + sync), the form a non-GPU-aware host uses */
 int32_t zp_ntt_host(zp_ctx *ctx, uint64_t *h_cols, int32_t logn, int32_t W, int32_t inverse);
 int32_t zp_lde_host(zp_ctx *ctx, const uint64_t *h_in, uint64_t *h_out, int32_t logn, int32_t logb,
@@ -686,6 +704,7 @@ int32_t zp_hbm_copy_probe(zp_ctx *ctx, const void *d_src, void *d_dst, size_t by
  * 512-thread workgroups per CU (2: 128-KiB tiles); "p254_block" 2: the lane-per-permutation Poseidon-BN254 kernel walks its partial rounds one by
  * one instead of in blocks of four; "verify_lane_min" openings per call from which the verifier hashes one opening per lane (0 = 256: a guess, unmeasured);
  * "verify16_lane_min" hash jobs per call from which the BN128-mode verifier hashes one job per lane (0 = 2^14: a guess, unmeasured); 0 = default;
+ * "verify_chain_dev" the verifier's transcripts as one sponge-chain launch per call: 0 never, 1 default (today: never), 2 always (other values: ZP_ERR_ARG);
  * "fixed_eval_dev_min" (points x sparse entries) from which zp_program_fixed_eval_ext_batch uses the device -- the VALUE is the bound: 0 always the
  * device, < 0 restores the default 2^15 (derived from profiles/r12_fixed_eval_batch.json, not measured at that size)); not for production hosts */
 int32_t zp_set_tuning(zp_ctx *ctx, const char *key, int32_t value);

@@ -5,7 +5,11 @@ what the host transcript costs per proof; (b) zp_stark_verify_batch over 1, 4, 1
 milliseconds per proof, openings on the lane-per-opening kernel and on the 12-lane walk kernel ("verify_lane_min"); (c) zp_merkle_verify_batch
 alone (leaves of 24 values, depth 16: a FRI layer's openings) at 16 .. 8192 openings on both kernels, and the count from which the lane kernel is
 the faster one -- the default of "verify_lane_min".  Medians of five runs after one warm-up; every verdict is checked to be ACCEPT.
-python tools/verify_measure.py [out.json]"""
+python tools/verify_measure.py [out.json]
+--chains: the transcripts as device sponge chains ("verify_chain_dev") for batches of 1 / 4 / 16 / 64 chunk proofs with the knob at 0 and at 2, the
+counters of zp_verify_counters, and with --parent-lib PATH the parent commit's library alternating with the new one (tools/verify_bn128_measure.py
+has the driver).  Merged into profiles/verify_chains.json under "goldilocks".
+python tools/verify_measure.py --chains [--parent-lib PATH] [--rounds 3] [--logn 20] [--out profiles/verify_chains.json]"""
 import json
 import os
 import sys
@@ -104,5 +108,47 @@ def main():
     p.close()
 
 
+def chains_child(role, logn):
+    """one library, one process: ms per call of every batch size (a parent library has neither the knob nor the counters)"""
+    if role == "parent":
+        for name in ("zp_poseidon_bn254_chains", "zp_verify_counters"):
+            native.SIGNATURES.pop(name)
+    shape = (logn,) + SHAPE[1:]
+    p = native.Prover(0)
+    air = AIR.get_air("chunk64")
+    params = PR.StarkParams(*shape[:5], pow_bits=shape[5])
+    prog = np.ascontiguousarray(air.program(), dtype=np.uint64)
+    texts = []
+    for seed in (5, 6, 7, 8):
+        tr, pub = native.synth_trace(air.trace_kind, logn, air.width, seed)
+        d = p.upload(tr)
+        texts.append(p.stark_prove(air.name, prog, d, [int(v) for v in pub], *shape))
+        d.free()
+
+    def batch(n):
+        v = native.stark_verify_batch(prog, [texts[i % len(texts)] for i in range(n)], params, prover=p)
+        assert v == [native.VERDICT_ACCEPT] * n, v
+
+    out = {"role": role, "ms_per_call": {}}
+    for knob in ((None,) if role == "parent" else (0, 2)):
+        if knob is not None:
+            p.set_tuning("verify_chain_dev", knob)
+        before = native.verify_counters(p) if knob is not None else None
+        row = {str(n): median_ms(lambda: batch(n)) for n in (1, 4, 16, 64)}
+        if knob is not None:
+            after = native.verify_counters(p)
+            row["counters"] = {k: after[k] - before[k] for k in after}
+        out["ms_per_call"]["parent" if knob is None else "knob%d" % knob] = row
+    p.close()
+    print("CHAINS " + json.dumps(out), flush=True)
+
+
 if __name__ == "__main__":
-    main()
+    if "--chains-child" in sys.argv:
+        chains_child(sys.argv[sys.argv.index("--chains-child") + 1], int(sys.argv[sys.argv.index("--chains-child") + 2]))
+    elif "--chains" in sys.argv:
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        from verify_bn128_measure import chains_main
+        chains_main(sys.argv, "goldilocks", [sys.argv[sys.argv.index("--logn") + 1] if "--logn" in sys.argv else str(SHAPE[0])], script=__file__)
+    else:
+        main()
