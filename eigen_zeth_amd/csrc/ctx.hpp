@@ -240,6 +240,21 @@ bool zpi_program_fixed_table(const uint64_t *h_program, size_t program_words, st
 // zp_fixed_columns; only_pub: refresh just the columns that hold public inputs inside a buffer whose other columns are already built
 int32_t zpi_fixed_columns_build(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const uint64_t *h_pub, int32_t n_pub, int32_t logn, int32_t logb,
                                 uint64_t shift, uint64_t *d_out, size_t out_words, bool only_pub);
+// its first half: one period of every (selected) sparse column in scratch 4, behind two selector columns of sel_rows rows each (0: none) unless only_pub
+int32_t zpi_fixed_periods_build(zp_ctx *ctx, const uint64_t *h_program, const std::vector<ZpFixedCol> &fxc, const uint64_t *h_pub, size_t sel_rows, bool only_pub,
+                                u64 **d_in, size_t *in_words);
+// Everything a reader of a constraint program blob must refuse before it interprets one (csrc/verify.hip, host code): magic, lengths, the sparse columns'
+// table, header counts in range, at most 32 slots, the stage-2 table against the widths, canonical constants, every opcode, operand and destination,
+// the OUT count.  On success `out` holds the header fields and pointers into the blob; on failure *why (may be NULL) names the first refusal.
+struct ZpProgram {
+    size_t W, W2, n_fixed, n_pub, n_chal, n_const, n_instr, K, n_slots, n_s2, Q;
+    const uint64_t *consts, *ins, *stage2;
+    std::vector<ZpFixedCol> fxc;
+};
+bool zpi_program_validate(const uint64_t *h_program, size_t program_words, ZpProgram *out, const char **why);
+// zp_stark_check_witness on a ctx (csrc/witness_check.hip): arguments validated by the caller (csrc/witness_host.hip), pubchal = publics then the challenge
+int32_t zpi_witness_check_device(zp_ctx *ctx, const ZpProgram &pg, const std::vector<u64> &pubchal, const u64 *d_trace, int logn, uint64_t *h_report,
+                                 uint64_t *h_counts, uint64_t *h_first_row);
 // device buffers from / back to the per-ctx pool of zp_stark_prove (csrc/prove.hip): everything runs on the ctx stream, so reuse is ordered
 int32_t zpi_pool_alloc(zp_ctx *ctx, size_t bytes, void **out);
 void zpi_pool_release(zp_ctx *ctx, void *p, size_t bytes);

@@ -908,30 +908,24 @@ extern "C" size_t zp_fixed_columns_words(const uint64_t *h_program, size_t progr
     return w;
 }
 
-// only_pub: (re)build just the columns that hold public inputs, into a buffer whose other columns are already there -- the provers keep a
-// statement's fixed columns per ctx and refresh the public ones per proof (a verifier AIR at the service's size: 52 + 15 of its 104 sparse
-// columns and both selectors never change; round 5)
-int32_t zpi_fixed_columns_build(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const uint64_t *h_pub, int32_t n_pub, int32_t logn, int32_t logb,
-                                uint64_t shift, uint64_t *d_out, size_t out_words, bool only_pub) {
-    ZP_ARG(ctx, h_program && d_out && logn >= 1 && logb >= 0 && logn + logb <= 32, "bad arguments");
-    std::vector<ZpFixedCol> fxc;
-    ZP_ARG(ctx, zpi_program_fixed_table(h_program, program_words, &fxc), "constraint program length does not match its header");
-    ZP_ARG(ctx, (u64)n_pub >= h_program[4] && (h_program[4] == 0 || h_pub), "public inputs missing");
-    const size_t need = zp_fixed_columns_words(h_program, program_words, logn, logb);
-    ZP_ARG(ctx, need != 0 && out_words >= need, "output buffer smaller than zp_fixed_columns_words()");
-    if (shift == 0) shift = ctx->coset_shift;
-    ZP_ARG(ctx, shift < GL_P, "shift not canonical");
-    const size_t N = (size_t)1 << logn, M = N << logb;
+// One period of every (selected) sparse column, on the device: [selector L_first: sel_rows][L_last: sel_rows][column 2: 2^lp_2][column 3: ...] in scratch 4
+// (sel_rows = 0: no selector columns; only_pub: just the columns that hold public inputs, and no selectors).  The columns are sparse (a
+// non-periodic public-input column of a verifier AIR has N rows and ~10^3 entries): the periods are built ON THE DEVICE -- zero fill, then one
+// scatter of (index, value) pairs -- instead of N-word host vectors and their upload.  What the extension of zpi_fixed_columns_build starts from,
+// and what the witness check (csrc/witness_check.hip) reads as it is: on the trace domain a period IS the column.  *in_words = 0: nothing selected.
+int32_t zpi_fixed_periods_build(zp_ctx *ctx, const uint64_t *h_program, const std::vector<ZpFixedCol> &fxc, const uint64_t *h_pub, size_t sel_rows, bool only_pub,
+                                u64 **d_in, size_t *in_words_out) {
+    const size_t N = sel_rows;
     auto wanted = [&](const ZpFixedCol &fc) { return !only_pub || fc.has_pub; };
     // input staging holds the selected columns only, one after the other
     size_t in_words = only_pub ? 0 : 2 * N;
     for (const ZpFixedCol &fc : fxc)
         if (wanted(fc)) in_words += (size_t)1 << fc.lp;
+    *d_in = nullptr;
+    *in_words_out = in_words;
     if (in_words == 0) return ZP_OK;
-    // the columns are sparse (a non-periodic public-input column of a verifier AIR has N rows and ~10^3 entries): the periods are
-    // built ON THE DEVICE -- zero fill, then one scatter of (index, value) pairs -- instead of N-word host vectors and their upload
     std::vector<u64> pairs;
-    if (!only_pub) {
+    if (!only_pub && N) {
         pairs.push_back(0); pairs.push_back(1);                      // L_first[0] = 1
         pairs.push_back(N + N - 1); pairs.push_back(1);              // L_last[N - 1] = 1
     }
@@ -962,6 +956,29 @@ int32_t zpi_fixed_columns_build(zp_ctx *ctx, const uint64_t *h_program, size_t p
         hipLaunchKernelGGL(scatter_pairs_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, din, (const u64 *)dpairs, np);
         if (hipGetLastError() != hipSuccess) rc = ZP_ERR_HIP;
     }
+    *d_in = din;
+    return rc;
+}
+
+// only_pub: (re)build just the columns that hold public inputs, into a buffer whose other columns are already there -- the provers keep a
+// statement's fixed columns per ctx and refresh the public ones per proof (a verifier AIR at the service's size: 52 + 15 of its 104 sparse
+// columns and both selectors never change; round 5)
+int32_t zpi_fixed_columns_build(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const uint64_t *h_pub, int32_t n_pub, int32_t logn, int32_t logb,
+                                uint64_t shift, uint64_t *d_out, size_t out_words, bool only_pub) {
+    ZP_ARG(ctx, h_program && d_out && logn >= 1 && logb >= 0 && logn + logb <= 32, "bad arguments");
+    std::vector<ZpFixedCol> fxc;
+    ZP_ARG(ctx, zpi_program_fixed_table(h_program, program_words, &fxc), "constraint program length does not match its header");
+    ZP_ARG(ctx, (u64)n_pub >= h_program[4] && (h_program[4] == 0 || h_pub), "public inputs missing");
+    const size_t need = zp_fixed_columns_words(h_program, program_words, logn, logb);
+    ZP_ARG(ctx, need != 0 && out_words >= need, "output buffer smaller than zp_fixed_columns_words()");
+    if (shift == 0) shift = ctx->coset_shift;
+    ZP_ARG(ctx, shift < GL_P, "shift not canonical");
+    const size_t N = (size_t)1 << logn, M = N << logb;
+    auto wanted = [&](const ZpFixedCol &fc) { return !only_pub || fc.has_pub; };
+    u64 *din = nullptr;
+    size_t in_words = 0;
+    int32_t rc = zpi_fixed_periods_build(ctx, h_program, fxc, h_pub, N, only_pub, &din, &in_words);
+    if (in_words == 0) return rc;
     if (rc == ZP_OK && !only_pub) rc = zpi_lde(ctx, (const u64 *)din, (u64 *)d_out, nullptr, logn, logb, 2, shift);
     size_t in_at = only_pub ? 0 : 2 * N, out_at = 2 * M;
     for (size_t k = 0; rc == ZP_OK && k < fxc.size();) {      // consecutive SELECTED columns of one period go through one LDE call

@@ -142,6 +142,67 @@ bool zpi_program_fixed_table(const uint64_t *h_program, size_t program_words, st
     return at == program_words;
 }
 
+// The whole of a blob, as a reader that INTERPRETS it must have it (the row interpreters: csrc/stark.hip zp_eval_quotient_rows makes these checks inline,
+// csrc/prove.hip make_shape the stage-2 ones; the witness check takes them from here, host and device alike).
+bool zpi_program_validate(const uint64_t *h_program, size_t program_words, ZpProgram *out, const char **why) {
+    const char *dummy;
+    const char *&w = why ? *why : dummy;
+    static const unsigned char magic[8] = {'Z', 'P', 'A', 'I', 'R', '1', 0, 0};
+    w = "constraint program shorter than its header";
+    if (!h_program || program_words < 12) return false;
+    w = "not a ZPAIR1 constraint program";
+    if (memcmp(h_program, magic, 8) != 0) return false;
+    ZpProgram &pg = *out;
+    pg.W = h_program[1]; pg.W2 = h_program[2]; pg.n_fixed = h_program[3]; pg.n_pub = h_program[4]; pg.n_chal = h_program[5]; pg.n_const = h_program[6];
+    pg.n_instr = h_program[7]; pg.K = h_program[8]; pg.n_slots = h_program[9]; pg.n_s2 = h_program[10]; pg.Q = h_program[11];
+    w = "constraint program length does not match its header";
+    if (pg.n_const >= (1u << 16) || pg.n_instr >= (1u << 24) || pg.n_s2 >= (1u << 16) || pg.n_fixed < 2 || pg.n_fixed >= 4096 ||
+        !zpi_program_fixed_table(h_program, program_words, &pg.fxc))
+        return false;
+    w = "constraint program needs more slots than the interpreter has (32)";
+    if (pg.n_slots < 1 || pg.n_slots > 32) return false;
+    w = "program dimensions out of range";
+    if (pg.W < 1 || pg.W >= 4096 || pg.W2 >= 4096 || pg.K < 1 || pg.Q < 1 || pg.Q > 16) return false;
+    w = "stage-2 table and widths disagree";
+    if ((pg.n_s2 == 0) != (pg.W2 == 0) || pg.n_chal != (pg.n_s2 ? 3u : 0u)) return false;
+    pg.consts = h_program + 12; pg.ins = pg.consts + pg.n_const; pg.stage2 = pg.ins + pg.n_instr;
+    size_t w2sum = 0;
+    for (size_t k = 0; k < pg.n_s2; k++) {
+        const uint64_t *st = pg.stage2 + 4 * k;
+        w = "unknown stage-2 argument";
+        if (st[0] != 1 && st[0] != 2) return false;
+        w = "stage-2 column out of range";
+        if (st[1] >= pg.W || st[2] >= pg.W || st[3] >= pg.W) return false;
+        w2sum += st[0] == 1 ? 3 : 9;
+    }
+    w = "stage-2 width does not match its table";
+    if (w2sum != pg.W2) return false;
+    w = "constant not canonical";
+    for (size_t i = 0; i < pg.n_const; i++)
+        if (pg.consts[i] >= GL_P) return false;
+    size_t outs = 0;
+    for (size_t i = 0; i < pg.n_instr; i++) {
+        const u64 x = pg.ins[i];
+        const unsigned op = (unsigned)(x & 0xFF), dst = (unsigned)((x >> 8) & 0xFFFF);
+        w = "unknown opcode in constraint program";
+        if (op < 1 || op > 4) return false;
+        w = "operand out of range in constraint program";
+        for (int o = 0; o < (op == 4 ? 1 : 2); o++) {
+            const unsigned kind = (unsigned)((x >> (24 + 20 * o)) & 0xF), idx = (unsigned)((x >> (28 + 20 * o)) & 0xFFFF);
+            const size_t lim = kind == 0 ? pg.n_slots : (kind == 1 || kind == 2) ? pg.W + pg.W2 : kind == 3 ? pg.n_fixed : kind == 4 ? pg.n_pub + pg.n_chal
+                               : kind == 5 ? pg.n_const : kind == 6 ? 1 : 0;
+            if (idx >= lim) return false;
+        }
+        w = "destination slot out of range in constraint program";
+        if (op != 4 && dst >= pg.n_slots) return false;
+        outs += op == 4;
+    }
+    w = "OUT count does not match the header";
+    if (outs != pg.K) return false;
+    w = "";
+    return true;
+}
+
 extern "C" {
 
 // Values of the K constraints of a program at the out-of-domain point of a proof over a trace of 2^logn rows.

@@ -1,0 +1,228 @@
+// zp_stark_check_witness on a ctx: the trace stays in HBM and is only read.  Entry point, refusals and the host path: csrc/witness_host.hip.
+//   (1) witness_canonical_kernel: one streaming pass over all W * N words (the interpreter loads only the columns an instruction names), 16-byte
+//       loads; a wave that saw a word >= p issues one atomicAdd on the count and one atomicMin on the first word index.
+//   (2) the stage-2 columns by the prover's own primitives (zp_grand_product / zp_logup_columns) and one period of every sparse fixed column
+//       (zpi_fixed_periods_build: the first half of the prover's fixed-column build, no transform -- on the trace domain a period IS the column).
+//   (3) witness_program_kernel: quotient_program_kernel's shape (csrc/stark.hip: lane = row, slot file in LDS as [slot][lane], the instruction
+//       word wave-uniform through readfirstlane, every operand kind a uniform branch) on the TRACE domain: next row = r + 1 mod N, the selectors
+//       computed from r, x = w^r from the plan's two-level table; at an OUT no accumulation but a ballot of the lanes whose value is not 0 --
+//       only when it is not empty one lane adds its popcount to the constraint's count and lowers the constraint's first row and the call's
+//       first (row, constraint) key.  An honest trace issues no atomic at all.
+// (2) and (3) run only when (1) found nothing: the field code takes canonical words.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <vector>
+
+#include "ctx.hpp"
+
+namespace {
+
+typedef unsigned long long ull;
+
+__device__ __forceinline__ ull wave_min_u64(ull v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const ull t = __shfl_xor(v, o); v = t < v ? t : v; }
+    return v;
+}
+__device__ __forceinline__ ull wave_add_u64(ull v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// words [head, head + 2 npairs) as 16-byte pairs (p + head is 16-byte aligned), grid-stride; the word in front of them (head = 1) and the one
+// behind them (an odd rest) are lane 0's.  res[0] += words >= p, res[1] = min(res[1], index of such a word)
+__global__ void __launch_bounds__(256) witness_canonical_kernel(const u64 *__restrict__ p, u64 total, u64 head, u64 npairs, ull *res) {
+    const u64 tid = (u64)blockIdx.x * 256 + threadIdx.x, stride = (u64)gridDim.x * 256;
+    const ulonglong2 *q = (const ulonglong2 *)(p + head);
+    ull cnt = 0, mn = ~0ULL;
+#pragma unroll 4
+    for (u64 i = tid; i < npairs; i += stride) {
+        const ulonglong2 v = q[i];
+        const u64 at = head + 2 * i;
+        if (v.y >= GL_P) { cnt++; mn = at + 1 < mn ? at + 1 : mn; }
+        if (v.x >= GL_P) { cnt++; mn = at < mn ? at : mn; }
+    }
+    if (tid == 0) {
+        const u64 tail = head + 2 * npairs;
+        if (tail < total && p[tail] >= GL_P) { cnt++; mn = tail < mn ? tail : mn; }
+        if (head && p[0] >= GL_P) { cnt++; mn = 0; }
+    }
+    if (__ballot(cnt != 0) == 0) return;                 // wave-uniform
+    const ull c = wave_add_u64(cnt), m = wave_min_u64(mn);
+    if ((threadIdx.x & 63) == 0) {
+        atomicAdd(&res[0], c);
+        atomicMin(&res[1], m);
+    }
+}
+
+struct WProgArgs {
+    const u64 *prog;            // device copy of header | constants | instructions
+    const u64 *trace, *s2;      // columns idx < W: the caller's trace (read only); the rest: the stage-2 scratch
+    const u64 *pub;             // publics, then the challenge
+    const u64 *xs_lo, *xs_hi;   // w_N^e = lo[e & (2^lb - 1)] * hi[e >> lb]
+    const u64 *fixedx, *fx_tab; // one period per sparse column; (offset, index mask) per column
+    ull *counts, *first_row, *first_key;
+    u64 N, wlast;
+    int W, lb, n_const, n_instr;
+};
+
+__global__ void __launch_bounds__(256) witness_program_kernel(WProgArgs a) {
+    extern __shared__ __attribute__((aligned(16))) u64 slots[];   // [n_slots][256]
+    const int tid = threadIdx.x;
+    const u64 r = (u64)blockIdx.x * 256 + tid;
+    const bool live = r < a.N;
+    const u64 rr = live ? r : 0;                                  // a dead lane (N < 256) walks row 0: in bounds, masked out of every ballot
+    const u64 rn = (rr + 1) & (a.N - 1);
+    const u64 x = gl_mul(a.xs_lo[rr & ((1ULL << a.lb) - 1)], a.xs_hi[rr >> a.lb]);
+    const u64 xml = gl_sub(x, a.wlast);
+    const u64 *consts = a.prog + 12, *ins = consts + a.n_const;
+    int k_out = 0;
+    for (int i = 0; i < a.n_instr; i++) {
+        const u64 w = ins[i];                                     // uniform address: scalar load
+        const u32 wl = __builtin_amdgcn_readfirstlane((u32)w), wh = __builtin_amdgcn_readfirstlane((u32)(w >> 32));
+        const u64 wu = ((u64)wh << 32) | wl;
+        const int op = (int)(wu & 0xFF), dst = (int)((wu >> 8) & 0xFFFF);
+        u64 v[2];
+#pragma unroll
+        for (int o = 0; o < 2; o++) {
+            const int kind = (int)((wu >> (24 + 20 * o)) & 0xF), idx = (int)((wu >> (28 + 20 * o)) & 0xFFFF);
+            u64 val;
+            switch (kind) {
+                case 0: val = slots[idx * 256 + tid]; break;
+                case 1: val = idx < a.W ? a.trace[(u64)idx * a.N + rr] : a.s2[(u64)(idx - a.W) * a.N + rr]; break;
+                case 2: val = idx < a.W ? a.trace[(u64)idx * a.N + rn] : a.s2[(u64)(idx - a.W) * a.N + rn]; break;
+                case 3:
+                    if (idx == 0) val = rr == 0;
+                    else if (idx == 1) val = rr == a.N - 1;
+                    else val = a.fixedx[a.fx_tab[2 * (idx - 2)] + (rr & a.fx_tab[2 * (idx - 2) + 1])];
+                    break;
+                case 4: val = a.pub[idx]; break;
+                case 5: val = consts[idx]; break;
+                default: val = xml; break;
+            }
+            v[o] = val;
+            if (op == 4) break;
+        }
+        if (op == 1) slots[dst * 256 + tid] = gl_add(v[0], v[1]);
+        else if (op == 2) slots[dst * 256 + tid] = gl_sub(v[0], v[1]);
+        else if (op == 3) slots[dst * 256 + tid] = gl_mul(v[0], v[1]);
+        else {
+            const ull m = __ballot(live && v[0] != 0);            // wave-uniform
+            if (m != 0 && (tid & 63) == __ffsll((long long)m) - 1) {      // the lowest violating lane of the wave: its row is the wave's smallest
+                atomicAdd(&a.counts[k_out], (ull)__popcll(m));
+                atomicMin(&a.first_row[k_out], (ull)r);
+                atomicMin(a.first_key, ((ull)r << 24) | (ull)k_out);
+            }
+            k_out++;
+        }
+    }
+}
+
+}  // namespace
+
+int32_t zpi_witness_check_device(zp_ctx *ctx, const ZpProgram &pg, const std::vector<u64> &pubchal, const u64 *d_trace, int logn, uint64_t *h_report,
+                                 uint64_t *h_counts, uint64_t *h_first_row) {
+    ZP_BIND(ctx);
+    ZP_ARG(ctx, logn <= 30, "logn out of range");
+    const size_t N = (size_t)1 << logn, K = pg.K, total = pg.W * N;
+    ZP_ARG(ctx, (uintptr_t)d_trace % 8 == 0, "trace pointer not aligned");
+    NttPlan *pl;
+    ZP_TRY(zpi_get_plan(ctx, logn, false, &pl));
+    // results, one buffer: [bad words][first bad word][first key][first_row: K][counts: K]; the stage-2 columns behind it
+    const size_t res_words = 3 + 2 * K, s2_words = pg.W2 * N, pool_bytes = (res_words + s2_words) * 8;
+    void *poolv = nullptr;
+    ZP_TRY(zpi_pool_alloc(ctx, pool_bytes, &poolv));
+    struct Release { zp_ctx *c; void *p; size_t b; ~Release() { zpi_pool_release(c, p, b); } } release_{ctx, poolv, pool_bytes};
+    ull *res = (ull *)poolv;
+    u64 *s2 = (u64 *)poolv + res_words;
+    u64 rep[8] = {ZP_WITNESS_SATISFIED, ~0ULL, ~0ULL, 0, 0, 0, ~0ULL, ~0ULL};
+    std::vector<u64> out(res_words);
+    {
+        ZpStage stage_(ctx, "witness_canonical");
+        ZP_HIP(ctx, hipMemsetAsync(res, 0, 8, ctx->stream));
+        ZP_HIP(ctx, hipMemsetAsync(res + 1, 0xFF, (2 + K) * 8, ctx->stream));
+        ZP_HIP(ctx, hipMemsetAsync(res + 3 + K, 0, K * 8, ctx->stream));
+        const u64 head = ((uintptr_t)d_trace % 16) ? 1 : 0, npairs = (total - head) / 2;
+        u64 blocks = (npairs + 255) / 256, cap = (u64)ctx->num_cu * 8;
+        blocks = blocks < 1 ? 1 : blocks > cap ? cap : blocks;
+        hipLaunchKernelGGL(witness_canonical_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_trace, (u64)total, head, npairs, res);
+        ZP_HIP(ctx, hipGetLastError());
+        ZP_TRY(zpi_d2h_small(ctx, out.data(), res, 16));
+    }
+    if (out[0] != 0) {
+        rep[0] = ZP_WITNESS_NONCANONICAL;
+        rep[5] = out[0]; rep[6] = out[1] / N; rep[7] = out[1] % N;
+        memcpy(h_report, rep, sizeof rep);
+        if (h_counts) memset(h_counts, 0, K * 8);
+        if (h_first_row) memset(h_first_row, 0xFF, K * 8);
+        return ZP_OK;
+    }
+    {
+        ZpStage stage_(ctx, "witness_stage2");
+        const uint64_t *g = (const uint64_t *)pubchal.data() + pg.n_pub;
+        size_t at = 0;
+        for (size_t k = 0; k < pg.n_s2; k++) {
+            const uint64_t *st = pg.stage2 + 4 * k;
+            const uint64_t *tr = (const uint64_t *)d_trace;
+            if (st[0] == 1) {
+                ZP_TRY(zp_grand_product(ctx, tr + st[1] * N, tr + st[2] * N, N, g, (uint64_t *)(s2 + at * N)));
+                at += 3;
+            } else {
+                ZP_TRY(zp_logup_columns(ctx, tr + st[1] * N, tr + st[2] * N, tr + st[3] * N, N, g, (uint64_t *)(s2 + at * N)));
+                at += 9;
+            }
+        }
+    }
+    ZpStage stage_(ctx, "witness_program");
+    u64 *d_periods = nullptr;
+    size_t period_words = 0;
+    ZP_TRY(zpi_fixed_periods_build(ctx, pg.consts - 12, pg.fxc, (const uint64_t *)pubchal.data(), 0, false, &d_periods, &period_words));
+    // one upload (after the stage-2 primitives: they use the same scratch slot): header, constants, instructions | publics and challenge |
+    // (offset, mask) of the sparse columns -- not the columns' entry tables, which the kernel never reads
+    const size_t pw = 12 + pg.n_const + pg.n_instr, total_up = pw + pubchal.size() + 2 * pg.fxc.size() + 1;
+    std::vector<u64> h(total_up, 0);
+    memcpy(h.data(), pg.consts - 12, pw * 8);
+    memcpy(h.data() + pw, pubchal.data(), pubchal.size() * 8);
+    {
+        u64 *t = h.data() + pw + pubchal.size(), off = 0;
+        for (size_t k = 0; k < pg.fxc.size(); k++) {
+            const u64 len = 1ULL << pg.fxc[k].lp;
+            t[2 * k] = off;
+            t[2 * k + 1] = len - 1;
+            off += len;
+        }
+    }
+    u64 *d = nullptr;
+    ZP_TRY(zpi_scratch(ctx, 3, total_up, &d));
+    if (total_up * 8 <= ZP_SMALL_COPY) ZP_TRY(zpi_h2d_small(ctx, d, h.data(), total_up * 8));
+    else {
+        ZP_HIP(ctx, hipMemcpyAsync(d, h.data(), total_up * 8, hipMemcpyHostToDevice, ctx->stream));
+        ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    WProgArgs a;
+    a.prog = d; a.trace = d_trace; a.s2 = s2; a.pub = d + pw; a.fx_tab = a.pub + pubchal.size(); a.fixedx = d_periods;
+    a.xs_lo = pl->d_twl; a.xs_hi = pl->d_twh; a.lb = pl->lb;
+    a.first_key = res + 2; a.first_row = res + 3; a.counts = res + 3 + K;
+    a.N = N; a.wlast = gl_inv(gl_root(ctx->root32, logn));
+    a.W = (int)pg.W; a.n_const = (int)pg.n_const; a.n_instr = (int)pg.n_instr;
+    hipLaunchKernelGGL(witness_program_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), pg.n_slots * 256 * 8, ctx->stream, a);
+    ZP_HIP(ctx, hipGetLastError());
+    if (res_words * 8 <= ZP_SMALL_COPY) ZP_TRY(zpi_d2h_small(ctx, out.data(), res, res_words * 8));
+    else {
+        ZP_HIP(ctx, hipMemcpyAsync(out.data(), res, res_words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    const u64 *first = out.data() + 3, *counts = first + K;
+    for (size_t k = 0; k < K; k++) { rep[3] += counts[k]; rep[4] += counts[k] != 0; }
+    if (rep[3]) {
+        rep[0] = ZP_WITNESS_VIOLATED;
+        rep[1] = out[2] >> 24;
+        rep[2] = out[2] & 0xFFFFFF;
+    }
+    memcpy(h_report, rep, sizeof rep);
+    if (h_counts) memcpy(h_counts, counts, K * 8);
+    if (h_first_row) memcpy(h_first_row, first, K * 8);
+    return ZP_OK;
+}

@@ -195,6 +195,7 @@ SIGNATURES = {
     "zp_pairing_check_bn254": (C.c_int32, [_vp, _vp, _vp, C.c_size_t, C.c_int32, C.POINTER(C.c_int32)]),
     "zp_groth16_verify": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.POINTER(C.c_int32)]),
     "zp_groth16_verify_batch": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, C.c_int32, _vp]),
+    "zp_stark_check_witness": (C.c_int32, [_vp, _u64p, C.c_size_t, _vp, C.c_size_t, _u64p, C.c_int32, C.c_int32, _u64p, _u64p, _u64p, _u64p, C.c_int32, C.c_int32]),
 }
 
 
@@ -370,6 +371,71 @@ def program_eval_ext(program, pubchal, logn, root32, zeta, ev_z, ev_zw, threads=
     if rc != 0:
         raise ValueError("zp_program_eval_ext: malformed program or evaluations (%d)" % rc)
     return out
+
+
+WITNESS_SATISFIED, WITNESS_VIOLATED, WITNESS_NONCANONICAL = range(3)
+_NONE64 = (1 << 64) - 1
+
+
+class WitnessReport:
+    """what zp_stark_check_witness says of a trace: ok / verdict (WITNESS_*); first_row and first_constraint (the smallest violated row, the smallest
+    violated constraint on it; None when nothing is violated); violations (violated (row, constraint) pairs); violated_constraints (distinct ones);
+    counts[k] (rows at which constraint k is violated) and first_rows[k] (the smallest such row or None); noncanonical (trace words >= p) and
+    first_noncanonical ((column, row) of the first in memory order, or None)"""
+
+    def __init__(self, report, counts, first_rows):
+        opt = lambda v: None if int(v) == _NONE64 else int(v)
+        self.verdict = int(report[0])
+        self.ok = self.verdict == WITNESS_SATISFIED
+        self.first_row, self.first_constraint = opt(report[1]), opt(report[2])
+        self.violations, self.violated_constraints, self.noncanonical = int(report[3]), int(report[4]), int(report[5])
+        self.first_noncanonical = None if int(report[6]) == _NONE64 else (int(report[6]), int(report[7]))
+        self.counts = [int(v) for v in counts]
+        self.first_rows = [opt(v) for v in first_rows]
+
+    def __str__(self):
+        if self.verdict == WITNESS_NONCANONICAL:
+            return "witness not canonical: %d trace word(s) >= p, the first in column %d at row %d" % ((self.noncanonical,) + self.first_noncanonical)
+        if self.ok:
+            return "witness satisfies all %d constraints" % len(self.counts)
+        return "witness violates constraint %d at row %d (that constraint at %d row(s); %d constraint(s) violated, %d violations in all)" % (
+            self.first_constraint, self.first_row, self.counts[self.first_constraint], self.violated_constraints, self.violations)
+
+
+class WitnessError(ValueError):
+    """a trace that does not satisfy its constraint program was handed to a prover that checks first; .report: the WitnessReport"""
+
+    def __init__(self, report):
+        super().__init__(str(report))
+        self.report = report
+
+
+def _check_witness(ctx, program, trace_ptr, trace_words, pubs, logn, chal, threads):
+    prog = np.ascontiguousarray(np.asarray(program, dtype=np.uint64))
+    if prog.ndim != 1 or prog.size < 12:
+        return -1, None
+    K = int(prog[8])
+    if K > (1 << 24):
+        return -1, None
+    pb = np.ascontiguousarray(np.asarray([int(v) for v in pubs] + [0], dtype=np.uint64))
+    ch = None if chal is None else np.ascontiguousarray(np.asarray([int(v) for v in chal], dtype=np.uint64))
+    if ch is not None and ch.size != 3:
+        return -1, None
+    rep, counts, first = np.zeros(8, dtype=np.uint64), np.zeros(max(K, 1), dtype=np.uint64), np.zeros(max(K, 1), dtype=np.uint64)
+    p = lambda a: a.ctypes.data_as(_u64p)
+    rc = load_library().zp_stark_check_witness(ctx, p(prog), prog.size, trace_ptr, trace_words, p(pb), len(pb) - 1, logn, None if ch is None else p(ch), p(rep),
+                                               p(counts), p(first), K, threads)
+    return rc, (WitnessReport(rep, counts[:K], first[:K]) if rc == 0 else None)
+
+
+def check_witness_host(program, trace, pubs, logn, chal=None, threads=0):
+    """zp_stark_check_witness without a ctx: host trace uint64 [W][2^logn] (or flat) against the program, on `threads` host threads -> WitnessReport.
+    chal: the stage-2 challenge (3 canonical words), None = derived from the program.  ZpError: a malformed blob or argument"""
+    tr = np.ascontiguousarray(np.asarray(trace, dtype=np.uint64))
+    rc, rep = _check_witness(None, program, tr.ctypes.data, tr.size, pubs, logn, chal, threads)
+    if rc != 0:
+        raise ZpError(rc, "zp_stark_check_witness: malformed program, or a trace / public inputs / challenge that are not the program's")
+    return rep
 
 
 # zp_stark_verify: the verdict classes and the flags (include/zeth_prover.h)
@@ -1238,6 +1304,15 @@ class Prover:
             return C.string_at(out.value, n.value).decode()
         finally:
             self.lib.zp_free_buffer(out)
+
+    def check_witness(self, program, d_trace, pubs, logn, chal=None):
+        """zp_stark_check_witness on this ctx: the device trace u64[W][2^logn] (only read) against the program -> WitnessReport"""
+        prog = np.asarray(program, dtype=np.uint64)
+        rc, rep = _check_witness(self.ctx, prog, _ptr(d_trace), self._words(d_trace, prog, logn), pubs, logn, chal, 0)
+        if rc != 0 and prog.size < 12:
+            raise ZpError(rc, "zp_stark_check_witness: malformed program")
+        self._chk(rc)
+        return rep
 
     def stark_prove_bn128(self, air_name, program, d_trace, pubs, logn, logb, fri_logf, fri_final_log, n_queries):
         """zp_stark_prove_bn128: the one-call prover in BN128-hash mode (install_poseidon_bn254(17) first)"""

@@ -35,6 +35,8 @@ from . import wrap_circuit as WC
 from . import wrap_arith as WA
 from ..stark import verifier as SV
 
+WitnessError = native.WitnessError      # what a proving request raises under EngineConfig(check_witness=True) for a trace that violates its AIR
+
 
 @contextlib.contextmanager
 def _no_cyclic_gc():
@@ -76,8 +78,13 @@ class EngineConfig:
                  final_air="chunk16", final_logn=10, final_logb=2, final_queries=50, native_prover=True,
                  agg_queries=50, agg_pow_bits=0, aggregate_all_chunks=False, groth16_seed=None, witness="device",
                  speculate_recursion=False, verify_before_wrap=True, final_ranks=1, final_devices=None, wrap_ranks=1, wrap_devices=None,
-                 verify_final=False):
+                 verify_final=False, check_witness=False):
         self.air, self.logn, self.logb = air, logn, logb
+        # Every STARK this engine proves (chunk proofs, the aggregation STARK, the final STARK) first has its trace checked against its constraint
+        # program (zp_stark_check_witness: on the proving backend's GPU where it can, on the host otherwise; "witness_check" in the stage timings).
+        # A trace that violates its AIR raises WitnessError with the first failing constraint and row, and no proof is made of it -- instead of a
+        # well-formed text that no verifier accepts.  Off by default: no extra call, launch, byte or timing.  What it costs: DESIGN.md par.5.
+        self.check_witness = check_witness
         # GenFinalProof: run the native Groth16 verifier (zp_groth16_verify) on the proof about to be returned and raise unless it is accepted
         # ("groth16/verify" in the stage clock).  Off by default: no response and no timing changes.
         self.verify_final = verify_final
@@ -265,6 +272,19 @@ class Engine:
                                    self._state_root(chain_id, int(blocks[0]) - 1)),
                 "post_state_root": fetched[-1]["state_root"] if fetched else self._state_root(chain_id, int(blocks[-1]))}
 
+    def _check_witness(self, be, air, trace, pubs, timings):
+        """cfg.check_witness: the trace against the AIR's program before anything is proven of it; raises WitnessError (and frees a device trace)"""
+        t0 = time.perf_counter()
+        if hasattr(be, "check_witness"):
+            report = be.check_witness(air, trace, pubs)
+        else:
+            report = native.check_witness_host(air.program(), trace, [int(v) for v in pubs], int(trace.shape[-1]).bit_length() - 1)
+        timings["witness_check"] = time.perf_counter() - t0
+        if not report.ok:
+            if isinstance(trace, native.DeviceBuffer):
+                trace.free()
+            raise WitnessError(report)
+
     @staticmethod
     def _chunk_witness(air, ch, out=None):
         """the witness of one chunk: the synthetic generator (stand-in for the zkVM executor) started from the statement limbs"""
@@ -390,6 +410,8 @@ class Engine:
             try:
                 tm = {"witness(%s)" % where: tw}
                 params = self.stark_params(ch["logn"])
+                if self.cfg.check_witness:
+                    self._check_witness(be, air, trace, pubs, tm)
                 if self.cfg.native_prover and hasattr(be, "prove_native"):
                     # one C-ABI call per chunk (zp_stark_prove): the orchestration runs in the library, Python only frames the result
                     t0 = time.perf_counter()
@@ -547,6 +569,8 @@ class Engine:
         timings["verifier-witness"] = time.perf_counter() - t0
         self._last_verifier_pubs = pubs                 # the public inputs of the STARK made next (GenFinalProof's wrap needs the final STARK's)
         params = params_of(shape)
+        if self.cfg.check_witness:
+            self._check_witness(be, vair, trace, pubs, timings)
         t0 = time.perf_counter()
         self._sharded_openings = None
         if self.cfg.native_prover and self.cfg.final_ranks > 1 and params.hash == "bn128" and hasattr(be, "prove_native_sharded"):

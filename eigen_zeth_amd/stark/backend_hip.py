@@ -212,6 +212,17 @@ class HipBackend:
         finally:
             d_tr.free()
 
+    def check_witness(self, air, trace, pubs):
+        """zp_stark_check_witness on this backend's GPU: does the trace (host array, uploaded for the check, or a device buffer from prefetch_trace,
+        only read) satisfy the AIR's program -> native.WitnessReport.  The stage-2 challenge is derived from the program: it finds mistakes"""
+        logn = int(trace.shape[-1]).bit_length() - 1
+        d_tr = trace if isinstance(trace, native.DeviceBuffer) else self.p.upload(trace)
+        try:
+            return self.p.check_witness(air.program(), d_tr, [int(v) for v in pubs], logn)
+        finally:
+            if d_tr is not trace:
+                d_tr.free()
+
     def prove_native_sharded(self, air, trace, pubs, params, ranks, devices=None):
         """ONE proof over `ranks` thread-ranks of this process (zp_stark_prove_sharded / zp_stark_prove_sharded_bn128 on an in-process
         communicator, csrc/comm.hip: zp_comm_create_local): rank r drives devices[r] with a ctx of its own (default: every rank on this

@@ -8,6 +8,10 @@
 //   with rank / world / id-file: ONE proof over `world` GPUs, one process per GPU (zp_stark_prove_sharded on an RCCL communicator; rank 0
 //   publishes the 128-byte RCCL id in <id-file>, the others wait for the record that carries this run's nonce: host/rendezvous.hpp).  Rank r reads only ITS columns of trace.bin (ceil(W / world) per rank, the tail ranks fewer) and drives GPU r;
 //   every rank obtains the same proof text (rank 0 writes <out.json>), byte for byte the single-GPU text.
+//   --check (anywhere on the line): before proving, zp_stark_check_witness judges the trace against the program -- on the GPU, in HBM, for one
+//   process; on the host for a sharded run, where no rank holds all columns -- and prints the report as ONE JSON line
+//   {"witness_check":{"verdict":..,"first_row":..,"first_constraint":..,"violations":..,"violated_constraints":..,"noncanonical":..,
+//   "first_noncanonical":[column,row]}} (null where the report says none); a trace that is not satisfied ends the run with exit status 3, unproven.
 //   program.bin : the constraint program blob (u64 words, layout in the header)
 //   trace.bin   : u64[W][2^logn] column-major, canonical values
 //   publics.bin : u64[n_pub]
@@ -42,7 +46,28 @@ static std::vector<uint64_t> read_words(const char *path) {
         if (rc_ != 0) { fprintf(stderr, "%s -> %d: %s\n", #call, rc_, ctx ? zp_last_error(ctx) : "no context"); return 1; } \
     } while (0)
 
+// the report of zp_stark_check_witness as one JSON line; true: satisfied
+static bool print_report(const uint64_t *r) {
+    auto opt = [](uint64_t v) { return v == ~0ULL ? std::string("null") : std::to_string((unsigned long long)v); };
+    static const char *names[3] = {"satisfied", "violated", "noncanonical"};
+    printf("{\"witness_check\":{\"verdict\":\"%s\",\"first_row\":%s,\"first_constraint\":%s,\"violations\":%llu,\"violated_constraints\":%llu,"
+           "\"noncanonical\":%llu,\"first_noncanonical\":%s}}\n",
+           r[0] < 3 ? names[r[0]] : "?", opt(r[1]).c_str(), opt(r[2]).c_str(), (unsigned long long)r[3], (unsigned long long)r[4], (unsigned long long)r[5],
+           r[6] == ~0ULL ? "null" : ("[" + opt(r[6]) + "," + opt(r[7]) + "]").c_str());
+    fflush(stdout);
+    return r[0] == ZP_WITNESS_SATISFIED;
+}
+
 int main(int argc, char **argv) {
+    bool check = false;
+    {
+        int n = 1;
+        for (int i = 1; i < argc; i++) {
+            if (strcmp(argv[i], "--check") == 0) check = true;
+            else argv[n++] = argv[i];
+        }
+        argc = n;
+    }
     if (argc < 11) { fprintf(stderr, "usage: see the header of host/prove_chunk.cpp\n"); return 2; }
     const std::vector<uint64_t> program = read_words(argv[1]), trace = read_words(argv[2]), pubs = read_words(argv[3]);
     const int logn = atoi(argv[4]), logb = atoi(argv[5]), fri_logf = atoi(argv[6]), fri_final_log = atoi(argv[7]), n_queries = atoi(argv[8]),
@@ -60,9 +85,15 @@ int main(int argc, char **argv) {
     }
     if (pubs.size() != program[4]) { fprintf(stderr, "%s: %zu public inputs, the program declares %llu\n", argv[3], pubs.size(), (unsigned long long)program[4]); return 2; }
     for (uint64_t v : trace)
-        if (v >= 0xFFFFFFFF00000001ULL) { fprintf(stderr, "%s: non-canonical trace value (precondition of zp_stark_prove)\n", argv[2]); return 2; }
+        if (!check && v >= 0xFFFFFFFF00000001ULL) { fprintf(stderr, "%s: non-canonical trace value (precondition of zp_stark_prove)\n", argv[2]); return 2; }
     if (world < 1 || rank < 0 || rank >= world) { fprintf(stderr, "bad rank / world\n"); return 2; }
     zp_ctx *ctx = nullptr;
+    uint64_t report[8];
+    if (check && sharded) {                            // every rank reads the whole file: each judges it on the host and they agree
+        CHECK(zp_stark_check_witness(nullptr, program.data(), program.size(), trace.data(), trace.size(), pubs.data(), (int32_t)pubs.size(), logn, nullptr, report,
+                                     nullptr, nullptr, 0, 0));
+        if (rank == 0 ? !print_report(report) : report[0] != ZP_WITNESS_SATISFIED) return 3;
+    }
     CHECK(zp_create(&ctx, rank));                      // one process per GPU: rank r drives device r
     // rank r owns columns [r wl, min((r + 1) wl, W)), wl = ceil(W / world): the tail ranks hold fewer columns, or none (include/zeth_prover.h)
     const size_t Wc = (size_t)program[1], wl = (Wc + (size_t)world - 1) / (size_t)world, c0 = (size_t)rank * wl < Wc ? (size_t)rank * wl : Wc,
@@ -71,6 +102,15 @@ int main(int argc, char **argv) {
     void *d_trace = nullptr;
     CHECK(zp_dev_alloc(ctx, (words ? words : 1) * 8, &d_trace));
     if (words) CHECK(zp_h2d(ctx, d_trace, mine, words * 8));
+    if (check && !sharded) {
+        CHECK(zp_stark_check_witness(ctx, program.data(), program.size(), (const uint64_t *)d_trace, trace.size(), pubs.data(), (int32_t)pubs.size(), logn, nullptr,
+                                     report, nullptr, nullptr, 0, 0));
+        if (!print_report(report)) {
+            zp_dev_free(ctx, d_trace);
+            zp_destroy(ctx);
+            return 3;
+        }
+    }
     char *json = nullptr;
     size_t len = 0;
     zp_comm *comm = nullptr;

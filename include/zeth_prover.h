@@ -211,6 +211,34 @@ int32_t zp_stark_set_air_kernel_rows(zp_ctx *ctx, const uint64_t *h_program, siz
  * witness builder needs for the inner proofs' statement (zp_recursion_witness: the head of the transcript stream). */
 int32_t zp_program_digest(const uint64_t *h_program, size_t program_words, uint8_t *out32, uint64_t *out_words4);
 
+/* ---- the check BEFORE the proof: does this trace satisfy this constraint program, and if not, which constraint at which row ----------------
+ * zp_stark_prove proves whatever it is handed; a trace that violates its AIR gives a well-formed proof text that no verifier accepts.  This call
+ * evaluates the program on the TRACE domain (row r of N = 2^logn; no extension, no blow-up), exactly as a row evaluator of the blob layout above:
+ * constraint k (in OUT order) is violated at row r when its OUT value is non-zero with kind 2 operands reading row (r + 1) mod N, fixed column 0 =
+ * [r = 0], fixed column 1 = [r = N - 1], fixed column j >= 2 = its period at r mod 2^lp_j (public-input entries resolved) and kind 6 =
+ * w^r - w^(N-1), w the root of order N (of the ctx; the library's default without one).
+ * trace u64[W][2^logn] column-major, W from the program header; trace_words must equal W * 2^logn.  With a ctx, trace is a DEVICE pointer and the check
+ * runs on the GPU (csrc/witness_check.hip); it only reads the trace and returns synchronised.  ctx = NULL: trace is a HOST pointer, everything runs on
+ * `threads` host threads (<= 0: one per core, at most 16) with the library's default domain constants, as for zp_stark_verify.
+ * Programs with stage-2 arguments (n_stage2 > 0): the checker makes the stage-2 columns itself from the trace, with the prover's own primitives
+ * (zp_grand_product / zp_logup_columns; on the host their definitions above, one inversion per row), then evaluates ALL constraints, column indices
+ * >= W reading those columns.  h_chal3 = the challenge (canonical); NULL derives one from the program: words 0..2 of zp_program_digest's out_words4,
+ * word 1 set to 1 if words 1 and 2 are both 0 (outside the base field, so a base-field value plus it is never zero).  A derived challenge finds
+ * MISTAKES, not adversaries: whoever knows it can build a wrong permutation or lookup that passes; only the prover's Fiat-Shamir challenge binds.
+ * A broken permutation or lookup shows at the cyclic row N - 1 of the wrap-around constraints.
+ * Returns ZP_OK whenever a verdict was reached (a violated witness is a verdict, not an error); ZP_ERR_ARG for the caller's mistakes -- a malformed
+ * blob (everything zp_eval_quotient_rows and zp_stark_prove refuse: more than 32 slots included), trace_words != W * 2^logn, n_pubs not the program's,
+ * a public input or challenge word >= p, logn < 1, a sparse column with lp > logn, h_counts or h_first_row given with n_constraints != K.  On an
+ * error the output arrays are left as they were; no exception crosses the ABI.
+ * h_report[8]: [0] verdict  [1] smallest violated row or ~0  [2] smallest violated constraint on that row or ~0  [3] violated (row, constraint) pairs
+ *   [4] distinct violated constraints  [5] trace words >= p  [6] column and [7] row of the first such word in memory order (smallest c N + r), or ~0.
+ * h_counts[k] (or NULL) = rows at which constraint k is violated; h_first_row[k] (or NULL) = the smallest such row or ~0.
+ * Any trace word >= p: verdict NONCANONICAL and the constraints are not evaluated ([1], [2] = ~0, [3], [4] = 0, counts 0, first rows ~0).        */
+enum { ZP_WITNESS_SATISFIED = 0, ZP_WITNESS_VIOLATED = 1, ZP_WITNESS_NONCANONICAL = 2 };
+int32_t zp_stark_check_witness(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const uint64_t *trace, size_t trace_words,
+                               const uint64_t *h_pubs, int32_t n_pubs, int32_t logn, const uint64_t *h_chal3, uint64_t *h_report /* [8] */,
+                               uint64_t *h_counts /* [K] or NULL */, uint64_t *h_first_row /* [K] or NULL */, int32_t n_constraints, int32_t threads);
+
 /* ---- N5: FRI fold ------------------------------------------------------------------------------
  * d_in u64[3][2^logn] = f on shift*<w_n> (natural order);  d_out u64[3][2^(logn-logf)] =
  * sum_j beta^j g_j on shift^(2^logf)*<w_(n>>logf)>,  f(x) = sum_j x^j g_j(x^(2^logf)), logf in 1..4 */
