@@ -2,12 +2,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/zeth_prover.h"
+#include "air_program.hpp"
 #include "gl.hpp"
 
 #define ZP_ROOT32_DEFAULT 1753635133440165772ULL /* 7^((p-1)/2^32), SURVEY.md 8a-N1 */
@@ -179,12 +181,32 @@ void zpi_split_over_threads(size_t n, int T, Work work) {
     for (auto &th : pool) th.join();
 }
 
+// how many host threads an entry point with a `threads` argument uses: threads <= 0 is one per core; at most 16
+inline unsigned zpi_host_threads(int threads) {
+    const unsigned nt = threads > 0 ? (unsigned)threads : std::thread::hardware_concurrency();
+    return nt < 1 ? 1 : nt > 16 ? 16 : nt;
+}
+// work(t) for every t < T: T - 1 threads are started, share 0 runs here, and so does the share of every thread that could not be started; returns
+// once all have ended
+template <class Work>
+void zpi_over_threads(unsigned T, Work work) {
+    std::vector<std::thread> pool;
+    unsigned started = 0;
+    try { for (unsigned t = 1; t < T; t++) { pool.emplace_back(work, t); started = t; } } catch (...) {}
+    work(0u);
+    for (unsigned t = started + 1; t < T; t++) work(t);
+    for (auto &th : pool) th.join();
+}
+
 // internal helpers implemented across the .hip files
 int32_t zpi_scratch(zp_ctx *ctx, int which, size_t elems, u64 **out);
 int32_t zpi_pinned(zp_ctx *ctx, size_t bytes, void **out);
 // small copies through the pinned staging buffer (synchronous on the ctx stream)
 int32_t zpi_d2h_small(zp_ctx *ctx, void *h_dst, const void *d_src, size_t bytes);
 int32_t zpi_h2d_small(zp_ctx *ctx, void *d_dst, const void *h_src, size_t bytes);
+// a copy of any size, done when the call returns: through the pinned buffer when small, else an async copy and a synchronisation of the ctx stream
+int32_t zpi_d2h(zp_ctx *ctx, void *h_dst, const void *d_src, size_t bytes);
+int32_t zpi_h2d(zp_ctx *ctx, void *d_dst, const void *h_src, size_t bytes);
 int32_t zpi_upload(zp_ctx *ctx, const std::vector<u64> &h, u64 **d);   // a new device buffer holding h (synchronous)
 #define ZP_SMALL_COPY (4u << 20)
 int32_t zpi_get_plan(zp_ctx *ctx, int logn, bool inverse, NttPlan **out);
@@ -232,26 +254,19 @@ struct NttRunOpts {
     int in_valid_log = -1;                   // >=0: input columns have 2^in_valid_log elements, rest is zero
     bool seam_last = false;                  // the passes before the last only: the last one runs inside lde_seam_kernel
 };
-// the sparse periodic fixed columns (2..n_fixed-1) of a constraint program: table behind the stage-2 table,
-// per column [lp | n_entries << 8] then n_entries x (pos | is_pub << 63, value or public index)
-struct ZpFixedCol { int lp; size_t first_entry_word, n_entries; bool has_pub; };
-// validates the whole-blob length and the table; fills `cols` (empty for n_fixed == 2).  false: malformed
-bool zpi_program_fixed_table(const uint64_t *h_program, size_t program_words, std::vector<ZpFixedCol> *cols);
 // zp_fixed_columns; only_pub: refresh just the columns that hold public inputs inside a buffer whose other columns are already built
 int32_t zpi_fixed_columns_build(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const uint64_t *h_pub, int32_t n_pub, int32_t logn, int32_t logb,
                                 uint64_t shift, uint64_t *d_out, size_t out_words, bool only_pub);
 // its first half: one period of every (selected) sparse column in scratch 4, behind two selector columns of sel_rows rows each (0: none) unless only_pub
 int32_t zpi_fixed_periods_build(zp_ctx *ctx, const uint64_t *h_program, const std::vector<ZpFixedCol> &fxc, const uint64_t *h_pub, size_t sel_rows, bool only_pub,
                                 u64 **d_in, size_t *in_words);
-// Everything a reader of a constraint program blob must refuse before it interprets one (csrc/verify.hip, host code): magic, lengths, the sparse columns'
-// table, header counts in range, at most 32 slots, the stage-2 table against the widths, canonical constants, every opcode, operand and destination,
-// the OUT count.  On success `out` holds the header fields and pointers into the blob; on failure *why (may be NULL) names the first refusal.
-struct ZpProgram {
-    size_t W, W2, n_fixed, n_pub, n_chal, n_const, n_instr, K, n_slots, n_s2, Q;
-    const uint64_t *consts, *ins, *stage2;
-    std::vector<ZpFixedCol> fxc;
-};
-bool zpi_program_validate(const uint64_t *h_program, size_t program_words, ZpProgram *out, const char **why);
+// The device copy of a parsed program that both row interpreters read (csrc/stark.hip), in scratch 3: header, constants and instructions -- NOT the
+// sparse columns' entry tables behind them, which no kernel reads (for a verifier AIR they are 7 MB of the blob: this upload was 16 ms of a 63 ms
+// aggregation STARK) | publics and challenges, one zero word behind them | the caller's extra vectors, one after the other | (offset, index mask) of
+// every sparse column's period of 2^(lp + logb) words.  One upload, done when the call returns.
+struct ZpSpan { const u64 *p; size_t n; };
+struct ZpProgramDev { const u64 *consts, *ins, *pubchal, *extra, *fx_tab; };
+int32_t zpi_program_upload(zp_ctx *ctx, const ZpProgram &pg, ZpSpan pubchal, std::initializer_list<ZpSpan> extra, int logb, ZpProgramDev *out);
 // zp_stark_check_witness on a ctx (csrc/witness_check.hip): arguments validated by the caller (csrc/witness_host.hip), pubchal = publics then the challenge
 int32_t zpi_witness_check_device(zp_ctx *ctx, const ZpProgram &pg, const std::vector<u64> &pubchal, const u64 *d_trace, int logn, uint64_t *h_report,
                                  uint64_t *h_counts, uint64_t *h_first_row);

@@ -80,6 +80,20 @@ int32_t zpi_h2d_small(zp_ctx *ctx, void *d_dst, const void *h_src, size_t bytes)
     return ZP_OK;
 }
 
+int32_t zpi_d2h(zp_ctx *ctx, void *h_dst, const void *d_src, size_t bytes) {
+    if (bytes <= ZP_SMALL_COPY) return zpi_d2h_small(ctx, h_dst, d_src, bytes);
+    ZP_HIP(ctx, hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ZP_OK;
+}
+
+int32_t zpi_h2d(zp_ctx *ctx, void *d_dst, const void *h_src, size_t bytes) {
+    if (bytes <= ZP_SMALL_COPY) return zpi_h2d_small(ctx, d_dst, h_src, bytes);
+    ZP_HIP(ctx, hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ZP_OK;
+}
+
 int32_t zpi_upload(zp_ctx *ctx, const std::vector<u64> &h, u64 **d) {
     ZP_HIP(ctx, hipMalloc((void **)d, h.size() * sizeof(u64)));
     ZP_HIP(ctx, hipMemcpy(*d, h.data(), h.size() * sizeof(u64), hipMemcpyHostToDevice));

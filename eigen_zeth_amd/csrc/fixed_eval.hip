@@ -140,10 +140,10 @@ int32_t entry_build(zp_ctx *ctx, const uint64_t *prog, size_t program_words, con
         for (size_t i = 1; i < hi.size(); i++) hi[i] = gl_mul(hi[i - 1], wl);
         const size_t first = w.size();
         for (size_t e = 0; e < fc.n_entries; e++) {
-            const u64 a = prog[fc.first_entry_word + 2 * e], v = prog[fc.first_entry_word + 2 * e + 1];
-            const bool is_pub = (a >> 63) != 0;
+            const ZpFixedEntry en = zpi_fixed_entry(prog, fc, e);
+            const bool is_pub = en.is_pub;
+            const u64 v = en.value, pos = en.pos;
             if (!is_pub && v == 0) continue;
-            const u64 pos = a & ~(1ULL << 63);
             const u64 wj = gl_mul(lo[pos & (((u64)1 << lb) - 1)], hi[pos >> lb]);
             w.push_back(wj);
             c.push_back(is_pub ? gl_mul(wj, pinv) : gl_mul(gl_mul(v, wj), pinv));

@@ -362,10 +362,9 @@ struct StageClock {
 
 // ... validated, with what the provers read from the program header and derive from the parameters
 struct Shape : ProveArgs {
+    ZpProgram pg;                      // the parsed program: W, W2, K, Q, n_s2, stage2 (n_s2 x (kind, three trace columns)), fxc
     bool bn;
-    size_t W, W2, Wt, K, Q, n_s2;
-    const u64 *stage2;                 // the stage-2 table of the program: n_s2 x (kind, three trace columns)
-    std::vector<ZpFixedCol> fxc;
+    size_t Wt;                         // pg.W + pg.W2
     int logm;
     size_t N, M;
     u64 shift, root32, wN;
@@ -395,39 +394,21 @@ int32_t make_shape(zp_ctx *ctx, bool bn, const ProveArgs &a, Shape *sh) {
         }
         ZP_ARG(ctx, ok, "air_name must be 1..64 characters of [A-Za-z0-9_.-]");
     }
-    const uint64_t *h_program = a.h_program;
-    ZP_ARG(ctx, a.program_words >= 12, "constraint program shorter than its header");
-    static const unsigned char magic[8] = {'Z', 'P', 'A', 'I', 'R', '1', 0, 0};
-    ZP_ARG(ctx, memcmp(h_program, magic, 8) == 0, "not a ZPAIR1 constraint program");
-    const size_t W = h_program[1], W2 = h_program[2], n_pub_prog = h_program[4], n_chal = h_program[5], n_const = h_program[6],
-                 n_instr = h_program[7], K = h_program[8], n_s2 = h_program[10], Q = h_program[11];
-    ZP_ARG(ctx, n_const < (1u << 16) && n_instr < (1u << 24) && n_s2 < (1u << 16) && zpi_program_fixed_table(h_program, a.program_words, &sh->fxc),
-           "constraint program length does not match its header");
-    ZP_ARG(ctx, (size_t)a.n_pubs == n_pub_prog, "number of public inputs does not match the program");
-    ZP_ARG(ctx, W >= 1 && W < 4096 && W2 < 4096 && K >= 1 && Q >= 1 && Q <= 16, "program dimensions out of range");
+    const char *why;
+    ZP_ARG(ctx, zpi_program_read(a.h_program, a.program_words, ZPG_PROVE, &sh->pg, &why), why);
+    ZP_ARG(ctx, (size_t)a.n_pubs == sh->pg.n_pub, "number of public inputs does not match the program");
     ZP_ARG(ctx, a.logn >= 1 && a.logb >= 1 && a.logn + a.logb <= 30 && a.fri_logf >= 1 && a.fri_logf <= 4 && a.fri_final_log >= 0 &&
                     a.fri_final_log < a.logn && a.n_queries >= 1 && a.n_queries <= 4096 && a.pow_bits >= 0 && a.pow_bits <= 40,
            "STARK parameters out of range");
-    ZP_ARG(ctx, Q <= ((size_t)1 << a.logb), "the blow-up must cover the quotient degree");
-    ZP_ARG(ctx, (n_s2 == 0) == (W2 == 0) && (n_s2 == 0 || n_chal == 3), "stage-2 table and widths disagree");
+    ZP_ARG(ctx, sh->pg.Q <= ((size_t)1 << a.logb), "the blow-up must cover the quotient degree");
     for (int i = 0; i < a.n_pubs; i++) ZP_ARG(ctx, a.h_pubs[i] < GL_P, "public input not canonical");
-    const u64 *stage2 = (const u64 *)h_program + 12 + n_const + n_instr;
-    size_t w2sum = 0;
-    for (size_t k = 0; k < n_s2; k++) {
-        const u64 kind = stage2[4 * k];
-        ZP_ARG(ctx, kind == 1 || kind == 2, "unknown stage-2 argument");
-        ZP_ARG(ctx, stage2[4 * k + 1] < W && stage2[4 * k + 2] < W && stage2[4 * k + 3] < W, "stage-2 column out of range");
-        w2sum += kind == 1 ? 3 : 9;
-    }
-    ZP_ARG(ctx, w2sum == W2, "stage-2 width does not match its table");
 
     static_cast<ProveArgs &>(*sh) = a;
     sh->bn = bn;
-    sh->W = W; sh->W2 = W2; sh->Wt = W + W2; sh->K = K; sh->Q = Q; sh->n_s2 = n_s2;
-    sh->stage2 = stage2;
+    sh->Wt = sh->pg.W + sh->pg.W2;
     sh->logm = a.logn + a.logb; sh->N = (size_t)1 << a.logn; sh->M = (size_t)1 << sh->logm;
     sh->shift = ctx->coset_shift; sh->root32 = ctx->root32; sh->wN = gl_root(sh->root32, a.logn);
-    program_digest(ctx, h_program, a.program_words, sh->dg);
+    program_digest(ctx, a.h_program, a.program_words, sh->dg);
     for (int i = 0; i < 8; i++) snprintf(sh->dg_hex + 2 * i, 3, "%02x", sh->dg[i]);
     sh->mark = StageClock{ctx, a.air_name, a.logn, std::chrono::steady_clock::now()};
     return ZP_OK;
@@ -435,7 +416,7 @@ int32_t make_shape(zp_ctx *ctx, bool bn, const ProveArgs &a, Shape *sh) {
 
 // the first block of the transcript: parameters, domain, AIR digest, public inputs
 int32_t transcript_head(zp_ctx *ctx, const Shape &sh, Transcript &tr, const Trees &T, DevBufs &dev) {
-    std::vector<u64> first = {(u64)sh.logn, (u64)sh.logb, (u64)sh.W, (u64)sh.W2, (u64)sh.fri_logf, (u64)sh.fri_final_log, (u64)sh.n_queries, (u64)sh.pow_bits,
+    std::vector<u64> first = {(u64)sh.logn, (u64)sh.logb, (u64)sh.pg.W, (u64)sh.pg.W2, (u64)sh.fri_logf, (u64)sh.fri_final_log, (u64)sh.n_queries, (u64)sh.pow_bits,
                               sh.root32, sh.shift};
     for (int i = 0; i < 4; i++) {
         u64 wd = 0;
@@ -487,11 +468,11 @@ int32_t transcript_head(zp_ctx *ctx, const Shape &sh, Transcript &tr, const Tree
 // to the ctx.  (Both provers: the sharded one cuts its row windows out of it.)
 int32_t fixed_columns_cached(zp_ctx *ctx, const Shape &sh, u64 **out) {
     bool has_pub = false;
-    for (const ZpFixedCol &fc : sh.fxc) has_pub |= fc.has_pub;
+    for (const ZpFixedCol &fc : sh.pg.fxc) has_pub |= fc.has_pub;
     const size_t fwords = zp_fixed_columns_words(sh.h_program, sh.program_words, sh.logn, sh.logb);
     ZP_ARG(ctx, fwords != 0, "fixed column longer than the trace");
     char key[128];
-    snprintf(key, sizeof key, "%d/%d/%llx/%llx/%s", sh.logn, sh.logb, (unsigned long long)sh.shift, (unsigned long long)sh.root32, sh.fxc.empty() ? "" : sh.dg_hex);
+    snprintf(key, sizeof key, "%d/%d/%llx/%llx/%s", sh.logn, sh.logb, (unsigned long long)sh.shift, (unsigned long long)sh.root32, sh.pg.fxc.empty() ? "" : sh.dg_hex);
     auto it = ctx->prove_fixed.find(key);
     if (it != ctx->prove_fixed.end()) {
         *out = it->second;
@@ -557,9 +538,9 @@ struct QuotientOps {
     int32_t xlb = 0;
 };
 int32_t quotient_operands(zp_ctx *ctx, const Shape &sh, const char *form, const e3 &alpha, const std::vector<u64> &pubchal, DevBufs &dev, QuotientOps *q) {
-    q->apow.resize(3 * sh.K);
+    q->apow.resize(3 * sh.pg.K);
     e3 cur = e3_make(1, 0, 0);
-    for (size_t k = 0; k < sh.K; k++) { memcpy(&q->apow[3 * k], cur.c, 24); cur = e3_mul(cur, alpha); }
+    for (size_t k = 0; k < sh.pg.K; k++) { memcpy(&q->apow[3 * k], cur.c, 24); cur = e3_mul(cur, alpha); }
     q->zhinv.resize((size_t)1 << sh.logb);
     const u64 sN = gl_pow(sh.shift, (u64)sh.N), wb = gl_root(sh.root32, sh.logb);
     u64 p = 1;
@@ -586,7 +567,7 @@ int32_t quotient_operands(zp_ctx *ctx, const Shape &sh, const char *form, const 
 // (*pext: u64[3 Q][M]) get committed.  (Q == 1: the quotient is committed as it stands and never leaves the evaluation form.)  Ends with
 // the forward transform ENQUEUED: the caller synchronises before it releases *dqcoef and *pad, its own way
 int32_t split_quotient(zp_ctx *ctx, const Shape &sh, DevBufs &dev, const u64 *dq, u64 **dqcoef, u64 **pad, u64 **pext) {
-    const size_t Q = sh.Q, N = sh.N, M = sh.M;
+    const size_t Q = sh.pg.Q, N = sh.N, M = sh.M;
     PV_TRY(dev.alloc(3 * M, dqcoef));
     PV_TRY(zp_intt(ctx, (const uint64_t *)dq, (uint64_t *)*dqcoef, sh.logm, 3));
     PV_TRY(dev.alloc(3 * Q * M, pad));
@@ -686,12 +667,12 @@ int32_t write_proof(zp_ctx *ctx, const Shape &sh, const Transcript &tr, const Pr
     const size_t nl = p.fri.layers.size();
     if (bn) {       // the same openings in binary, for the Groth16 wrap's witness (zp_stark_openings -> zp_wrap_assign): no text round trip
         std::vector<TreeOut> trees = {{p.root1, &p.trace}, {p.rootq, &p.quotient}};
-        if (sh.n_s2) trees.push_back({p.root2, &p.stage2});
+        if (sh.pg.n_s2) trees.push_back({p.root2, &p.stage2});
         for (size_t li = 0; li < nl; li++) trees.push_back({p.fri.layers[li].root, &p.fo[li]});
         openings_record(ctx, tr, p.qidx, sh.logm, trees);
     }
     std::string s;
-    s.reserve(p.qidx.size() * (sh.Wt + 3 * sh.Q + 64) * 24 + (1 << 16));
+    s.reserve(p.qidx.size() * (sh.Wt + 3 * sh.pg.Q + 64) * 24 + (1 << 16));
     s += "{\"air\":\"";
     s += sh.air_name;
     s += "\",\"air_digest\":\"";
@@ -706,7 +687,7 @@ int32_t write_proof(zp_ctx *ctx, const Shape &sh, const Transcript &tr, const Pr
     s += ",\"publics\":"; j_list(s, (const u64 *)sh.h_pubs, (size_t)sh.n_pubs);
     s += ",\"roots\":{\"trace\":"; j_root(s, p.root1, bn);
     s += ",\"quotient\":"; j_root(s, p.rootq, bn);
-    if (sh.n_s2) { s += ",\"stage2\":"; j_root(s, p.root2, bn); }
+    if (sh.pg.n_s2) { s += ",\"stage2\":"; j_root(s, p.root2, bn); }
     s += "},\"evals\":{\"z\":"; j_e3list(s, p.ev_all);
     s += ",\"zw\":"; j_e3list(s, p.ev_next);
     s += "},\"fri\":{\"roots\":[";
@@ -725,7 +706,7 @@ int32_t write_proof(zp_ctx *ctx, const Shape &sh, const Transcript &tr, const Pr
         };
         s += ",\"trace\":"; opening(p.trace);
         s += ",\"quotient\":"; opening(p.quotient);
-        if (sh.n_s2) { s += ",\"stage2\":"; opening(p.stage2); }
+        if (sh.pg.n_s2) { s += ",\"stage2\":"; opening(p.stage2); }
         s += ",\"fri\":[";
         for (size_t li = 0; li < nl; li++) { if (li) s += ','; opening(p.fo[li]); }
         s += "]}";
@@ -765,7 +746,7 @@ int32_t prove_impl(zp_ctx *ctx, bool bn, const ProveArgs &a) {
     ZP_ARG(ctx, a.d_trace, "null pointer");
     Shape sh;
     PV_TRY(make_shape(ctx, bn, a, &sh));
-    const size_t W = sh.W, W2 = sh.W2, Wt = sh.Wt, n_s2 = sh.n_s2, Q = sh.Q, N = sh.N, M = sh.M;
+    const size_t W = sh.pg.W, W2 = sh.pg.W2, Wt = sh.Wt, n_s2 = sh.pg.n_s2, Q = sh.pg.Q, N = sh.N, M = sh.M;
     const int logn = sh.logn, logb = sh.logb, logm = sh.logm;
     const u64 shift = sh.shift, wN = sh.wN;
     const uint64_t *d_trace = a.d_trace;
@@ -797,7 +778,7 @@ int32_t prove_impl(zp_ctx *ctx, bool bn, const ProveArgs &a) {
         PV_TRY(dev.alloc(W2 * N, &s2));
         size_t at = 0;
         for (size_t k = 0; k < n_s2; k++) {
-            const u64 *st = sh.stage2 + 4 * k;
+            const u64 *st = sh.pg.stage2 + 4 * k;
             if (st[0] == 1) {
                 PV_TRY(zp_grand_product(ctx, d_trace + st[1] * N, d_trace + st[2] * N, N, (const uint64_t *)chal.c, (uint64_t *)(s2 + at * N)));
                 at += 3;
@@ -997,7 +978,7 @@ int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, bool bn, const ProveArgs 
     const int G = zp_comm_world(comm), rank = zp_comm_rank(comm);
     Shape sh;
     PV_TRY(make_shape(ctx, bn, a, &sh));
-    const size_t W = sh.W, W2 = sh.W2, Wt = sh.Wt, n_s2 = sh.n_s2, Q = sh.Q, N = sh.N, M = sh.M, b = (size_t)1 << sh.logb;
+    const size_t W = sh.pg.W, W2 = sh.pg.W2, Wt = sh.Wt, n_s2 = sh.pg.n_s2, Q = sh.pg.Q, N = sh.N, M = sh.M, b = (size_t)1 << sh.logb;
     const int logn = sh.logn, logb = sh.logb, logm = sh.logm;
     const u64 shift = sh.shift, wN = sh.wN;
     const uint64_t *d_trace = a.d_trace;
@@ -1065,7 +1046,7 @@ int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, bool bn, const ProveArgs 
         };
         size_t at = 0;
         for (size_t k = 0; k < n_s2; k++) {
-            const u64 *st = sh.stage2 + 4 * k;
+            const u64 *st = sh.pg.stage2 + 4 * k;
             PV_TRY(column(st[1], colb));
             PV_TRY(column(st[2], colb + N));
             if (st[0] == 1) {

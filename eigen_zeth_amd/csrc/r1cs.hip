@@ -1301,13 +1301,14 @@ int32_t zp_wrap_assign(const uint64_t *script, size_t script_words, const uint64
 int32_t zp_wrap_aux(const uint64_t *openings, size_t open_words, const uint64_t *h_program, size_t program_words, const uint64_t *h_pub, int32_t n_pub, int32_t logn,
                     uint64_t root32, const uint64_t *addr4, uint64_t *out_aux, size_t cap, size_t *n_aux, uint64_t *zeta3_out) {
     Openings o;
-    if (!h_program || program_words < 12 || !addr4 || !out_aux || !n_aux || !parse_openings(openings, open_words, &o) || o.n_chal < 2 || !std_canonical(addr4))
-        return ZP_ERR_ARG;
-    const uint64_t n_fixed = h_program[3];
-    if (n_fixed < 2 || n_fixed > 4096 || cap < n_fixed - 1) return ZP_ERR_ARG;
+    if (!addr4 || !out_aux || !n_aux || !parse_openings(openings, open_words, &o) || o.n_chal < 2 || !std_canonical(addr4)) return ZP_ERR_ARG;
     uint64_t zeta[3];
     for (int k = 0; k < 3; k++) zeta[k] = o.chal[4 + k] % GLP;
     try {
+        // the one header word that sizes this call's arrays, by name; zp_program_fixed_eval_ext parses the blob (once) and refuses what it refuses
+        if (!h_program || program_words < ZPH_WORDS) return ZP_ERR_ARG;
+        const uint64_t n_fixed = h_program[ZPH_N_FIXED];
+        if (n_fixed < 2 || n_fixed > 4096 || cap < n_fixed - 1) return ZP_ERR_ARG;
         std::vector<uint64_t> fixed(3 * n_fixed);
         const int32_t rc = zp_program_fixed_eval_ext(h_program, program_words, h_pub, n_pub, logn, root32, zeta, fixed.data(), (int32_t)n_fixed, 0);
         if (rc != ZP_OK) return rc;

@@ -807,28 +807,59 @@ extern "C" int32_t zp_grand_product(zp_ctx *ctx, const uint64_t *d_a, const uint
 
 // ---- N4 through the C-ABI: interpreter of a constraint program (include/zeth_prover.h "constraint program") ----------
 // A host that cannot generate and compile a kernel per AIR (the Rust host of src/prover/provider.rs:358-377 has no hipcc at
-// run time) hands the AIR over as data.  lane = LDE row; the instruction stream is wave-uniform, so decoding is scalar
+// run time) hands the AIR over as data.  The walk is air_program.hpp's (zpi_program_walk); this file supplies its environment on the LDE
+// domain.  lane = LDE row; the instruction stream is wave-uniform, so decoding is scalar
 // work (s_load + SALU) and every operand kind is a uniform branch; the slot file lives in LDS as [slot][lane] (no bank
 // conflicts: consecutive lanes, consecutive 8-byte words).  Constraint k is folded into three unreduced 160-bit
 // accumulators (alpha^k planes) at its OUT instruction; one reduction and the 1/Z_H multiplication at the end.
 namespace {
 
-constexpr int QP_MAX_SLOTS = 32;   // 32 * 256 lanes * 8 B = 64 KiB of LDS per workgroup
-
 struct QProgArgs {
-    const u64 *prog;      // device copy of the blob
+    ZpProgramDev pg;      // device copy of the program (zpi_program_upload); its extra vectors: apow, then zhinv
     const u64 *cols, *fixedc;
-    const u64 *pub, *apow, *zhinv;
+    const u64 *apow, *zhinv;
     const u64 *xs_lo, *xs_hi;
     u64 *out;
     u64 M, b, shift, wlast;
     u64 nrows, sc, sf, so;   // rows of this launch (a window of the M-row domain), column strides of cols / fixed / out
     int wrap;                // 1: the window is the whole domain, the next row wraps mod M; 0: rows r + b are in the buffer (halo)
-    int lb, n_const, n_instr, n_slots;
+    int lb, n_instr;
     // fixed columns 2..: periodic, kept as ONE extended period each (2^(lp + logb) values) behind the two selector columns;
-    // fx_tab holds (offset, index mask) per column, row0 = the domain row of local row 0
-    const u64 *fixedx, *fx_tab;
+    // pg.fx_tab holds (offset, index mask) per column, row0 = the domain row of local row 0
+    const u64 *fixedx;
     u64 row0;
+};
+
+// the environment of zpi_program_walk for one LDE row per lane
+struct QuotientEnv {
+    typedef u64 value;
+    static __device__ __forceinline__ u64 add(u64 a, u64 b) { return gl_add(a, b); }
+    static __device__ __forceinline__ u64 sub(u64 a, u64 b) { return gl_sub(a, b); }
+    static __device__ __forceinline__ u64 mul(u64 a, u64 b) { return gl_mul(a, b); }
+    const QProgArgs &a;
+    u64 *slots;               // LDS, [n_slots][256]
+    int tid;
+    u64 rr, rn, xml;
+    gl_acc &s0, &s1, &s2;     // the kernel's own: members by value cost 8 VGPRs (copies of the planes around the OUT branch)
+    __device__ __forceinline__ u64 &slot(int i) { return slots[i * 256 + tid]; }
+    __device__ __forceinline__ u64 load(int kind, int idx) const {
+        switch (kind) {
+            case ZPK_SLOT: return slots[idx * 256 + tid];
+            case ZPK_COL: return a.cols[(u64)idx * a.sc + rr];
+            case ZPK_NEXT: return a.cols[(u64)idx * a.sc + rn];
+            case ZPK_FIXED:
+                if (idx < 2) return a.fixedc[(u64)idx * a.sf + rr];
+                return a.fixedx[a.pg.fx_tab[2 * (idx - 2)] + ((a.row0 + rr) & a.pg.fx_tab[2 * (idx - 2) + 1])];
+            case ZPK_PUB: return a.pg.pubchal[idx];
+            case ZPK_CONST: return a.pg.consts[idx];
+            default: return xml;
+        }
+    }
+    __device__ __forceinline__ void out(int k, u64 v) {
+        gl_acc_mac(s0, v, a.apow[3 * k]);
+        gl_acc_mac(s1, v, a.apow[3 * k + 1]);
+        gl_acc_mac(s2, v, a.apow[3 * k + 2]);
+    }
 };
 
 __global__ void __launch_bounds__(256) quotient_program_kernel(QProgArgs a) {
@@ -839,45 +870,9 @@ __global__ void __launch_bounds__(256) quotient_program_kernel(QProgArgs a) {
     const u64 rr = live ? r : 0;
     const u64 rn = a.wrap ? ((rr + a.b) & (a.M - 1)) : rr + a.b;
     const u64 x = gl_mul(a.shift, gl_mul(a.xs_lo[rr & ((1ULL << a.lb) - 1)], a.xs_hi[rr >> a.lb]));
-    const u64 xml = gl_sub(x, a.wlast);
-    const u64 *consts = a.prog + 12, *ins = consts + a.n_const;
     gl_acc s0 = gl_acc_zero(), s1 = gl_acc_zero(), s2 = gl_acc_zero();
-    int k_out = 0;
-    for (int i = 0; i < a.n_instr; i++) {
-        const u64 w = ins[i];                                   // uniform address: scalar load
-        const u32 wl = __builtin_amdgcn_readfirstlane((u32)w), wh = __builtin_amdgcn_readfirstlane((u32)(w >> 32));
-        const u64 wu = ((u64)wh << 32) | wl;
-        const int op = (int)(wu & 0xFF), dst = (int)((wu >> 8) & 0xFFFF);
-        u64 v[2];
-#pragma unroll
-        for (int o = 0; o < 2; o++) {
-            const int kind = (int)((wu >> (24 + 20 * o)) & 0xF), idx = (int)((wu >> (28 + 20 * o)) & 0xFFFF);
-            u64 val;
-            switch (kind) {
-                case 0: val = slots[idx * 256 + tid]; break;
-                case 1: val = a.cols[(u64)idx * a.sc + rr]; break;
-                case 2: val = a.cols[(u64)idx * a.sc + rn]; break;
-                case 3:
-                    if (idx < 2) val = a.fixedc[(u64)idx * a.sf + rr];
-                    else val = a.fixedx[a.fx_tab[2 * (idx - 2)] + ((a.row0 + rr) & a.fx_tab[2 * (idx - 2) + 1])];
-                    break;
-                case 4: val = a.pub[idx]; break;
-                case 5: val = consts[idx]; break;
-                default: val = xml; break;
-            }
-            v[o] = val;
-            if (op == 4) break;
-        }
-        if (op == 1) slots[dst * 256 + tid] = gl_add(v[0], v[1]);
-        else if (op == 2) slots[dst * 256 + tid] = gl_sub(v[0], v[1]);
-        else if (op == 3) slots[dst * 256 + tid] = gl_mul(v[0], v[1]);
-        else {
-            gl_acc_mac(s0, v[0], a.apow[3 * k_out]);
-            gl_acc_mac(s1, v[0], a.apow[3 * k_out + 1]);
-            gl_acc_mac(s2, v[0], a.apow[3 * k_out + 2]);
-            k_out++;
-        }
-    }
+    QuotientEnv env{a, slots, tid, rr, rn, gl_sub(x, a.wlast), s0, s1, s2};
+    zpi_program_walk(a.pg.ins, a.n_instr, env);
     if (!live) return;
     const u64 zi = a.zhinv[r & (a.b - 1)];
     a.out[r] = gl_mul(gl_acc_reduce(s0), zi);
@@ -898,10 +893,10 @@ __global__ void __launch_bounds__(256) scatter_pairs_kernel(u64 *__restrict__ ds
 // shift^(N/p) * <w_(p b)>: ONE extended period (an LDE of p values with the coset shift shift^(N/p)) holds every value, row r
 // reads entry r mod p b.  Nothing of size M is built for them.
 extern "C" size_t zp_fixed_columns_words(const uint64_t *h_program, size_t program_words, int32_t logn, int32_t logb) {
-    std::vector<ZpFixedCol> fxc;
-    if (!h_program || logn < 0 || logb < 0 || logn + logb > 32 || !zpi_program_fixed_table(h_program, program_words, &fxc)) return 0;
+    ZpProgram pg;
+    if (logn < 0 || logb < 0 || logn + logb > 32 || !zpi_program_read(h_program, program_words, ZPG_FIXED_COLUMNS, &pg, nullptr)) return 0;
     size_t w = (size_t)2 << (logn + logb);
-    for (const ZpFixedCol &fc : fxc) {
+    for (const ZpFixedCol &fc : pg.fxc) {
         if (fc.lp > logn) return 0;
         w += (size_t)1 << (fc.lp + logb);
     }
@@ -934,13 +929,10 @@ int32_t zpi_fixed_periods_build(zp_ctx *ctx, const uint64_t *h_program, const st
         for (const ZpFixedCol &fc : fxc) {
             if (!wanted(fc)) continue;
             for (size_t e = 0; e < fc.n_entries; e++) {
-                const u64 a = h_program[fc.first_entry_word + 2 * e], v = h_program[fc.first_entry_word + 2 * e + 1];
-                u64 val = v;
-                if (a >> 63) {
-                    val = h_pub[v];
-                    ZP_ARG(ctx, val < GL_P, "public input not canonical");
-                }
-                pairs.push_back(at + (a & ~(1ULL << 63)));
+                const ZpFixedEntry en = zpi_fixed_entry(h_program, fc, e);
+                const u64 val = en.is_pub ? h_pub[en.value] : en.value;
+                ZP_ARG(ctx, val < GL_P, "public input not canonical");
+                pairs.push_back(at + en.pos);
                 pairs.push_back(val);
             }
             at += (size_t)1 << fc.lp;
@@ -966,9 +958,11 @@ int32_t zpi_fixed_periods_build(zp_ctx *ctx, const uint64_t *h_program, const st
 int32_t zpi_fixed_columns_build(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const uint64_t *h_pub, int32_t n_pub, int32_t logn, int32_t logb,
                                 uint64_t shift, uint64_t *d_out, size_t out_words, bool only_pub) {
     ZP_ARG(ctx, h_program && d_out && logn >= 1 && logb >= 0 && logn + logb <= 32, "bad arguments");
-    std::vector<ZpFixedCol> fxc;
-    ZP_ARG(ctx, zpi_program_fixed_table(h_program, program_words, &fxc), "constraint program length does not match its header");
-    ZP_ARG(ctx, (u64)n_pub >= h_program[4] && (h_program[4] == 0 || h_pub), "public inputs missing");
+    ZpProgram pg;
+    const char *why;
+    ZP_ARG(ctx, zpi_program_read(h_program, program_words, ZPG_FIXED_COLUMNS, &pg, &why), why);
+    const std::vector<ZpFixedCol> &fxc = pg.fxc;
+    ZP_ARG(ctx, (u64)n_pub >= pg.n_pub && (pg.n_pub == 0 || h_pub), "public inputs missing");
     const size_t need = zp_fixed_columns_words(h_program, program_words, logn, logb);
     ZP_ARG(ctx, need != 0 && out_words >= need, "output buffer smaller than zp_fixed_columns_words()");
     if (shift == 0) shift = ctx->coset_shift;
@@ -994,6 +988,35 @@ int32_t zpi_fixed_columns_build(zp_ctx *ctx, const uint64_t *h_program, size_t p
         k = j;
     }
     return rc;
+}
+
+int32_t zpi_program_upload(zp_ctx *ctx, const ZpProgram &pg, ZpSpan pubchal, std::initializer_list<ZpSpan> extra, int logb, ZpProgramDev *out) {
+    const size_t pw = ZPH_WORDS + pg.n_const + pg.n_instr;
+    size_t n_extra = 0;
+    for (const ZpSpan &x : extra) n_extra += x.n;
+    std::vector<u64> h(pw + pubchal.n + 1 + n_extra + 2 * pg.fxc.size() + 1, 0);
+    u64 *at = h.data();
+    auto put = [&](const u64 *p, size_t n) { if (n) memcpy(at, p, n * 8); at += n; };
+    put((const u64 *)pg.words, pw);
+    put(pubchal.p, pubchal.n);
+    at++;                                        // the zero word: the section is never empty
+    for (const ZpSpan &x : extra) put(x.p, x.n);
+    u64 off = 0;
+    for (const ZpFixedCol &fc : pg.fxc) {
+        const u64 len = 1ULL << (fc.lp + logb);
+        *at++ = off;
+        *at++ = len - 1;
+        off += len;
+    }
+    u64 *d;
+    ZP_TRY(zpi_scratch(ctx, 3, h.size(), &d));
+    ZP_TRY(zpi_h2d(ctx, d, h.data(), h.size() * 8));
+    out->consts = d + ZPH_WORDS;
+    out->ins = out->consts + pg.n_const;
+    out->pubchal = d + pw;
+    out->extra = out->pubchal + pubchal.n + 1;
+    out->fx_tab = out->extra + n_extra;
+    return ZP_OK;
 }
 
 extern "C" int32_t zp_fixed_columns(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const uint64_t *h_pub, int32_t n_pub,
@@ -1029,35 +1052,12 @@ extern "C" int32_t zp_eval_quotient_rows(zp_ctx *ctx, const uint64_t *h_program,
     ZpStage stage_(ctx, "eval_quotient");
     ZP_ARG(ctx, h_program && d_cols && d_fixed && h_alpha_pows && h_zhinv && d_out, "null pointer");
     ZP_ARG(ctx, logm >= 0 && logm <= 32 && logb >= 0 && logb <= logm, "logm/logb out of range");
-    ZP_ARG(ctx, program_words >= 12, "constraint program shorter than its header");
-    static const unsigned char magic[8] = {'Z', 'P', 'A', 'I', 'R', '1', 0, 0};
-    ZP_ARG(ctx, memcmp(h_program, magic, 8) == 0, "not a ZPAIR1 constraint program");
-    const u64 width = h_program[1], width2 = h_program[2], n_fixed = h_program[3], np = h_program[4], nchal = h_program[5];
-    const u64 n_const = h_program[6], n_instr = h_program[7], n_cons = h_program[8], n_slots = h_program[9], n_s2 = h_program[10];
-    std::vector<ZpFixedCol> fxc;
-    ZP_ARG(ctx, n_const < (1u << 16) && n_instr < (1u << 24) && n_s2 < (1u << 16) && n_fixed >= 2 && n_fixed < 4096 &&
-                    zpi_program_fixed_table(h_program, program_words, &fxc), "constraint program length does not match its header");
-    ZP_ARG(ctx, n_slots >= 1 && n_slots <= (u64)QP_MAX_SLOTS, "constraint program needs more slots than the interpreter has (32)");
-    ZP_ARG(ctx, (u64)n_pub == np + nchal && (np + nchal == 0 || h_pub), "n_pub must equal publics + challenges of the program");
-    for (const ZpFixedCol &fc : fxc) ZP_ARG(ctx, fc.lp <= logm - logb, "fixed column longer than the trace");
+    ZpProgram pg;
+    const char *why;
+    ZP_ARG(ctx, zpi_program_read(h_program, program_words, ZPG_QUOTIENT_ROWS, &pg, &why), why);
+    ZP_ARG(ctx, (u64)n_pub == pg.n_pub + pg.n_chal && (n_pub == 0 || h_pub), "n_pub must equal publics + challenges of the program");
+    for (const ZpFixedCol &fc : pg.fxc) ZP_ARG(ctx, fc.lp <= logm - logb, "fixed column longer than the trace");
     ZP_ARG(ctx, shift < GL_P && w_last < GL_P, "shift / w_last not canonical");
-    const uint64_t *consts = h_program + 12, *ins = consts + n_const;
-    u64 outs = 0;
-    for (u64 i = 0; i < n_const; i++) ZP_ARG(ctx, consts[i] < GL_P, "constant not canonical");
-    for (u64 i = 0; i < n_instr; i++) {
-        const u64 w = ins[i];
-        const unsigned op = (unsigned)(w & 0xFF), dst = (unsigned)((w >> 8) & 0xFFFF);
-        ZP_ARG(ctx, op >= 1 && op <= 4, "unknown opcode in constraint program");
-        for (int o = 0; o < (op == 4 ? 1 : 2); o++) {
-            const unsigned kind = (unsigned)((w >> (24 + 20 * o)) & 0xF), idx = (unsigned)((w >> (28 + 20 * o)) & 0xFFFF);
-            const u64 lim = kind == 0 ? n_slots : (kind == 1 || kind == 2) ? width + width2 : kind == 3 ? n_fixed
-                            : kind == 4 ? np + nchal : kind == 5 ? n_const : kind == 6 ? 1 : 0;
-            ZP_ARG(ctx, idx < lim, "operand out of range in constraint program");
-        }
-        if (op != 4) ZP_ARG(ctx, dst < n_slots, "destination slot out of range in constraint program");
-        outs += op == 4;
-    }
-    ZP_ARG(ctx, outs == n_cons, "OUT count does not match the header");
     for (int i = 0; i < n_pub; i++) ZP_ARG(ctx, h_pub[i] < GL_P, "public input not canonical");
     const u64 M = 1ULL << logm, b = 1ULL << logb;
     const bool whole = row0 == 0 && nrows == M;
@@ -1067,41 +1067,12 @@ extern "C" int32_t zp_eval_quotient_rows(zp_ctx *ctx, const uint64_t *h_program,
     if (nrows == 0) return ZP_OK;
     NttPlan *pl;
     ZP_TRY(zpi_get_plan(ctx, logm, false, &pl));
-    // one upload: program (header, constants, instructions -- NOT the sparse columns' entry tables behind them: the kernel never reads those,
-    // and for a verifier AIR they are 7 MB of the blob; round 5: this upload was 16 ms of a 63 ms aggregation STARK) | pub | apow | zhinv |
-    // (offset, mask) of the periodic fixed columns
-    const size_t pw = 12 + (size_t)n_const + (size_t)n_instr;
-    const size_t np_all = (size_t)n_pub + 1, total = pw + np_all + 3 * (size_t)n_cons + (size_t)b + 2 * fxc.size() + 1;
-    std::vector<u64> h(total);
-    memcpy(h.data(), h_program, pw * 8);
-    for (int i = 0; i < n_pub; i++) h[pw + i] = h_pub[i];
-    h[pw + n_pub] = 0;
-    memcpy(h.data() + pw + np_all, h_alpha_pows, 3 * (size_t)n_cons * 8);
-    memcpy(h.data() + pw + np_all + 3 * (size_t)n_cons, h_zhinv, (size_t)b * 8);
-    {
-        u64 *t = h.data() + pw + np_all + 3 * (size_t)n_cons + (size_t)b, off = 0;
-        for (size_t k = 0; k < fxc.size(); k++) {
-            const u64 len = 1ULL << (fxc[k].lp + logb);
-            t[2 * k] = off;
-            t[2 * k + 1] = len - 1;
-            off += len;
-        }
-    }
-    u64 *d;
-    ZP_TRY(zpi_scratch(ctx, 3, total, &d));
-    if (total * 8 <= ZP_SMALL_COPY) ZP_TRY(zpi_h2d_small(ctx, d, h.data(), total * 8));
-    else {
-        ZP_HIP(ctx, hipMemcpyAsync(d, h.data(), total * 8, hipMemcpyHostToDevice, ctx->stream));
-        ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
     QProgArgs a;
-    a.prog = d;
+    ZP_TRY(zpi_program_upload(ctx, pg, ZpSpan{(const u64 *)h_pub, (size_t)n_pub}, {ZpSpan{(const u64 *)h_alpha_pows, 3 * pg.K}, ZpSpan{(const u64 *)h_zhinv, (size_t)b}}, logb, &a.pg));
     a.cols = (const u64 *)d_cols;
     a.fixedc = (const u64 *)d_fixed;
-    a.pub = d + pw;
-    a.apow = a.pub + np_all;
-    a.zhinv = a.apow + 3 * (size_t)n_cons;
-    a.fx_tab = a.zhinv + (size_t)b;
+    a.apow = a.pg.extra;
+    a.zhinv = a.apow + 3 * pg.K;
     a.fixedx = (const u64 *)d_fixed + 2 * stride_fixed;
     a.row0 = row0;
     a.xs_lo = pl->d_twl;
@@ -1110,8 +1081,8 @@ extern "C" int32_t zp_eval_quotient_rows(zp_ctx *ctx, const uint64_t *h_program,
     a.M = M; a.b = b; a.wlast = w_last;
     a.shift = gl_mul(shift, gl_pow(gl_root(ctx->root32, logm), (u64)row0));   // x of local row j = (shift * w_M^row0) * w_M^j
     a.nrows = nrows; a.sc = stride_cols; a.sf = stride_fixed; a.so = stride_out; a.wrap = whole ? 1 : 0;
-    a.lb = pl->lb; a.n_const = (int)n_const; a.n_instr = (int)n_instr; a.n_slots = (int)n_slots;
-    hipLaunchKernelGGL(quotient_program_kernel, dim3((unsigned)((nrows + 255) / 256)), dim3(256), (size_t)n_slots * 256 * 8, ctx->stream, a);
+    a.lb = pl->lb; a.n_instr = (int)pg.n_instr;
+    hipLaunchKernelGGL(quotient_program_kernel, dim3((unsigned)((nrows + 255) / 256)), dim3(256), pg.n_slots * 256 * 8, ctx->stream, a);
     ZP_HIP(ctx, hipGetLastError());
     return ZP_OK;
 }

@@ -69,10 +69,9 @@ int fixed_col_at(const uint64_t *prog, const ZpFixedCol &fc, const uint64_t *pub
     std::vector<u64> coef;
     den.reserve(fc.n_entries); coef.reserve(fc.n_entries);
     for (size_t e = 0; e < fc.n_entries; e++) {
-        const u64 a = prog[fc.first_entry_word + 2 * e], v = prog[fc.first_entry_word + 2 * e + 1];
-        const u64 val = (a >> 63) ? pubs[v] % GL_P : v;
+        const ZpFixedEntry en = zpi_fixed_entry(prog, fc, e);
+        const u64 val = en.is_pub ? pubs[en.value] % GL_P : en.value, pos = en.pos;
         if (!val) continue;
-        const u64 pos = a & ~(1ULL << 63);
         const u64 wj = gl_mul(lo[pos & (((u64)1 << lb) - 1)], hi[pos >> lb]);
         coef.push_back(gl_mul(gl_mul(val, wj), pinv));
         den.push_back(e3_make(gl_sub(y.c[0], wj), y.c[1], y.c[2]));
@@ -105,103 +104,34 @@ bool selectors_at(const e3 &zeta, const e3 &zh, u64 wlast, u64 ninv, e3 *first, 
     return true;
 }
 
+// zp_program_eval_ext's interpreter: the environment of zpi_program_walk over F_{p^3} at the point zeta
+struct ExtEnv {
+    typedef e3 value;
+    static e3 add(const e3 &a, const e3 &b) { return e3_add(a, b); }
+    static e3 sub(const e3 &a, const e3 &b) { return e3_sub(a, b); }
+    static e3 mul(const e3 &a, const e3 &b) { return e3_mul(a, b); }
+    std::vector<e3> file;
+    const uint64_t *ev_z, *ev_zw, *pubchal;
+    const u64 *consts;
+    const e3 *fixed;
+    e3 xml;                                      // zeta - w^(N-1)
+    uint64_t *h_out;
+    e3 &slot(int i) { return file[i]; }
+    e3 load(int kind, int idx) const {
+        switch (kind) {
+            case ZPK_SLOT: return file[idx];
+            case ZPK_COL: return e3_make(ev_z[3 * idx], ev_z[3 * idx + 1], ev_z[3 * idx + 2]);
+            case ZPK_NEXT: return e3_make(ev_zw[3 * idx], ev_zw[3 * idx + 1], ev_zw[3 * idx + 2]);
+            case ZPK_FIXED: return fixed[idx];
+            case ZPK_PUB: return e3_base(pubchal[idx]);
+            case ZPK_CONST: return e3_base(consts[idx] % GL_P);      // this reader does not ask for canonical constants
+            default: return xml;
+        }
+    }
+    void out(int k, const e3 &v) { memcpy(h_out + 3 * k, v.c, 24); }
+};
+
 }  // namespace
-
-// The table of sparse periodic fixed columns behind a program's stage-2 table (layout: stark/air.py compile_program): validates the whole-blob
-// length and every entry; fills `cols`.  Lives in this host-only translation unit so that everything that PARSES a program blob builds
-// under the host sanitizers (tests/test_verify_fuzz.py).
-bool zpi_program_fixed_table(const uint64_t *h_program, size_t program_words, std::vector<ZpFixedCol> *cols) {
-    if (program_words < 12) return false;
-    const u64 n_fixed = h_program[3], n_pub = h_program[4], n_const = h_program[6], n_instr = h_program[7], n_s2 = h_program[10];
-    // EVERY count of the header is bounded before it enters a sum or sizes anything: n_pub + n_chal wraps for a blob that says n_pub = 2^64 - 3,
-    // and a public-input entry index is checked against n_pub alone (round-5 advisor item; this file is the sanitizer / fuzz surface for blobs)
-    if (n_fixed < 2 || n_fixed > 4096 || n_const > (1u << 16) || n_instr > (1u << 24) || n_s2 > (1u << 16) || n_pub > (1u << 24) ||
-        h_program[5] > (1u << 24) || h_program[8] > (1u << 24))
-        return false;
-    size_t at = 12 + (size_t)n_const + (size_t)n_instr + 4 * (size_t)n_s2;
-    if (cols) cols->clear();
-    for (u64 k = 2; k < n_fixed; k++) {
-        if (at >= program_words) return false;
-        const u64 hd = h_program[at];
-        ZpFixedCol fc;
-        fc.lp = (int)(hd & 0xFF);
-        fc.n_entries = (size_t)(hd >> 8);
-        fc.first_entry_word = at + 1;
-        fc.has_pub = false;
-        if (fc.lp > 32 || fc.n_entries > ((size_t)1 << fc.lp) || at + 1 + 2 * fc.n_entries > program_words) return false;
-        for (size_t e = 0; e < fc.n_entries; e++) {
-            const u64 a = h_program[at + 1 + 2 * e], v = h_program[at + 2 + 2 * e];
-            const bool is_pub = (a >> 63) != 0;
-            if ((a & ~(1ULL << 63)) >= (1ULL << fc.lp)) return false;
-            if (is_pub ? v >= n_pub : v >= GL_P) return false;
-            fc.has_pub |= is_pub;
-        }
-        at += 1 + 2 * fc.n_entries;
-        if (cols) cols->push_back(fc);
-    }
-    return at == program_words;
-}
-
-// The whole of a blob, as a reader that INTERPRETS it must have it (the row interpreters: csrc/stark.hip zp_eval_quotient_rows makes these checks inline,
-// csrc/prove.hip make_shape the stage-2 ones; the witness check takes them from here, host and device alike).
-bool zpi_program_validate(const uint64_t *h_program, size_t program_words, ZpProgram *out, const char **why) {
-    const char *dummy;
-    const char *&w = why ? *why : dummy;
-    static const unsigned char magic[8] = {'Z', 'P', 'A', 'I', 'R', '1', 0, 0};
-    w = "constraint program shorter than its header";
-    if (!h_program || program_words < 12) return false;
-    w = "not a ZPAIR1 constraint program";
-    if (memcmp(h_program, magic, 8) != 0) return false;
-    ZpProgram &pg = *out;
-    pg.W = h_program[1]; pg.W2 = h_program[2]; pg.n_fixed = h_program[3]; pg.n_pub = h_program[4]; pg.n_chal = h_program[5]; pg.n_const = h_program[6];
-    pg.n_instr = h_program[7]; pg.K = h_program[8]; pg.n_slots = h_program[9]; pg.n_s2 = h_program[10]; pg.Q = h_program[11];
-    w = "constraint program length does not match its header";
-    if (pg.n_const >= (1u << 16) || pg.n_instr >= (1u << 24) || pg.n_s2 >= (1u << 16) || pg.n_fixed < 2 || pg.n_fixed >= 4096 ||
-        !zpi_program_fixed_table(h_program, program_words, &pg.fxc))
-        return false;
-    w = "constraint program needs more slots than the interpreter has (32)";
-    if (pg.n_slots < 1 || pg.n_slots > 32) return false;
-    w = "program dimensions out of range";
-    if (pg.W < 1 || pg.W >= 4096 || pg.W2 >= 4096 || pg.K < 1 || pg.Q < 1 || pg.Q > 16) return false;
-    w = "stage-2 table and widths disagree";
-    if ((pg.n_s2 == 0) != (pg.W2 == 0) || pg.n_chal != (pg.n_s2 ? 3u : 0u)) return false;
-    pg.consts = h_program + 12; pg.ins = pg.consts + pg.n_const; pg.stage2 = pg.ins + pg.n_instr;
-    size_t w2sum = 0;
-    for (size_t k = 0; k < pg.n_s2; k++) {
-        const uint64_t *st = pg.stage2 + 4 * k;
-        w = "unknown stage-2 argument";
-        if (st[0] != 1 && st[0] != 2) return false;
-        w = "stage-2 column out of range";
-        if (st[1] >= pg.W || st[2] >= pg.W || st[3] >= pg.W) return false;
-        w2sum += st[0] == 1 ? 3 : 9;
-    }
-    w = "stage-2 width does not match its table";
-    if (w2sum != pg.W2) return false;
-    w = "constant not canonical";
-    for (size_t i = 0; i < pg.n_const; i++)
-        if (pg.consts[i] >= GL_P) return false;
-    size_t outs = 0;
-    for (size_t i = 0; i < pg.n_instr; i++) {
-        const u64 x = pg.ins[i];
-        const unsigned op = (unsigned)(x & 0xFF), dst = (unsigned)((x >> 8) & 0xFFFF);
-        w = "unknown opcode in constraint program";
-        if (op < 1 || op > 4) return false;
-        w = "operand out of range in constraint program";
-        for (int o = 0; o < (op == 4 ? 1 : 2); o++) {
-            const unsigned kind = (unsigned)((x >> (24 + 20 * o)) & 0xF), idx = (unsigned)((x >> (28 + 20 * o)) & 0xFFFF);
-            const size_t lim = kind == 0 ? pg.n_slots : (kind == 1 || kind == 2) ? pg.W + pg.W2 : kind == 3 ? pg.n_fixed : kind == 4 ? pg.n_pub + pg.n_chal
-                               : kind == 5 ? pg.n_const : kind == 6 ? 1 : 0;
-            if (idx >= lim) return false;
-        }
-        w = "destination slot out of range in constraint program";
-        if (op != 4 && dst >= pg.n_slots) return false;
-        outs += op == 4;
-    }
-    w = "OUT count does not match the header";
-    if (outs != pg.K) return false;
-    w = "";
-    return true;
-}
 
 extern "C" {
 
@@ -218,16 +148,13 @@ static int32_t program_eval_ext_impl(const uint64_t *h_program, size_t program_w
     if (zeta_on_domain) *zeta_on_domain = false;
     const bool only_fixed = h_fixed_out != nullptr;
     try {
-        if (!h_program || !zeta3 || program_words < 12 || logn < 1 || logn > 32 || n_pubchal < 0 || (n_pubchal && !h_pubchal)) return ZP_ERR_ARG;
+        if (!zeta3 || logn < 1 || logn > 32 || n_pubchal < 0 || (n_pubchal && !h_pubchal)) return ZP_ERR_ARG;
         if (!only_fixed && (!h_ev_z || !h_ev_zw || !h_out)) return ZP_ERR_ARG;
-        static const unsigned char magic[8] = {'Z', 'P', 'A', 'I', 'R', '1', 0, 0};
-        if (memcmp(h_program, magic, 8) != 0) return ZP_ERR_ARG;
-        const size_t W = h_program[1], W2 = h_program[2], n_fixed = h_program[3], n_pub = h_program[4], n_chal = h_program[5], n_const = h_program[6],
-                     n_instr = h_program[7], K = h_program[8], n_slots = h_program[9];
-        std::vector<ZpFixedCol> fxc;
-        if (!zpi_program_fixed_table(h_program, program_words, &fxc) || W < 1 || W >= 4096 || W2 >= 4096 || n_slots > (1u << 16) || K < 1 ||
-            (size_t)n_pubchal != n_pub + n_chal || root32 == 0 || root32 >= GL_P)
-            return ZP_ERR_ARG;
+        ZpProgram pg;
+        if (!zpi_program_read(h_program, program_words, ZPG_FIXED_EVAL, &pg, nullptr)) return ZP_ERR_ARG;
+        const size_t W = pg.W, W2 = pg.W2, n_fixed = pg.n_fixed, K = pg.K;
+        const std::vector<ZpFixedCol> &fxc = pg.fxc;
+        if ((size_t)n_pubchal != pg.n_pub + pg.n_chal || root32 == 0 || root32 >= GL_P) return ZP_ERR_ARG;
         // the caller's arrays are sized by ITS idea of the statement: they must be the program's (a blob with another width or constraint count
         // would be read / written past them)
         if (!only_fixed && (n_cols < 0 || (size_t)n_cols != W + W2 || n_out < 0 || (size_t)n_out != K)) return ZP_ERR_ARG;
@@ -248,24 +175,14 @@ static int32_t program_eval_ext_impl(const uint64_t *h_program, size_t program_w
         } else {
             if (!selectors_at(zeta, zh, wlast, ninv, &fixed[0], &fixed[1])) { if (zeta_on_domain) *zeta_on_domain = true; return ZP_ERR_ARG; }
             // the sparse columns over threads (columns differ a lot in length: hand them out one at a time)
-            unsigned nt = threads > 0 ? (unsigned)threads : std::thread::hardware_concurrency();
-            nt = nt < 1 ? 1 : nt > 16 ? 16 : nt;
-            if (fxc.size() < 8) nt = 1;
+            const unsigned nt = fxc.size() < 8 ? 1 : zpi_host_threads(threads);
             std::vector<int> bad(nt, 0);
-            auto work = [&](unsigned t) noexcept {
+            zpi_over_threads(nt, [&](unsigned t) noexcept {
                 try {
                     for (size_t k = t; k < fxc.size(); k += nt)
                         if (const int r = fixed_col_at(h_program, fxc[k], h_pubchal, logn, root32, zeta, zh, &fixed[2 + k])) { bad[t] = r; return; }
                 } catch (...) { bad[t] = FIXED_NOMEM; }
-            };
-            {
-                std::vector<std::thread> th;
-                unsigned started = 0;
-                try { for (unsigned t = 1; t < nt; t++) { th.emplace_back(work, t); started = t; } } catch (...) {}
-                work(0);
-                for (unsigned t = started + 1; t < nt; t++) work(t);      // threads that could not be started: their share runs here
-                for (auto &x : th) x.join();
-            }
+            });
             for (int b : bad)
                 if (b == FIXED_NOMEM) return ZP_ERR_NOMEM;
             for (int b : bad)
@@ -277,40 +194,15 @@ static int32_t program_eval_ext_impl(const uint64_t *h_program, size_t program_w
             for (size_t k = 0; k < n_fixed; k++) memcpy(h_fixed_out + 3 * k, fixed[k].c, 24);
             return ZP_OK;
         }
-        const e3 xml = e3_make(gl_sub(zeta.c[0], wlast), zeta.c[1], zeta.c[2]);
-        // the three-address code in F_{p^3} (layout: stark/air.py compile_program; the prover's interpreter: csrc/stark.hip quotient_program_kernel)
-        const uint64_t *consts = h_program + 12, *ins = consts + n_const;
-        std::vector<e3> slot(n_slots ? n_slots : 1, e3_base(0));
-        size_t k_out = 0;
-        bool ok = true;
-        auto operand = [&](u64 kind, u64 idx) -> e3 {
-            switch (kind) {
-                case 0: if (idx >= slot.size()) { ok = false; return e3_base(0); } return slot[idx];
-                case 1: if (idx >= Wt) { ok = false; return e3_base(0); } return e3_make(h_ev_z[3 * idx], h_ev_z[3 * idx + 1], h_ev_z[3 * idx + 2]);
-                case 2: if (idx >= Wt) { ok = false; return e3_base(0); } return e3_make(h_ev_zw[3 * idx], h_ev_zw[3 * idx + 1], h_ev_zw[3 * idx + 2]);
-                case 3: if (idx >= n_fixed) { ok = false; return e3_base(0); } return fixed[idx];
-                case 4: if (idx >= (size_t)n_pubchal) { ok = false; return e3_base(0); } return e3_base(h_pubchal[idx]);
-                case 5: if (idx >= n_const) { ok = false; return e3_base(0); } return e3_base(consts[idx] % GL_P);
-                case 6: if (idx != 0) { ok = false; return e3_base(0); } return xml;     // one such factor: index 0, as the prover's interpreter checks it
-                default: ok = false; return e3_base(0);
-            }
-        };
-        for (size_t i = 0; i < n_instr && ok; i++) {
-            const u64 w = ins[i], op = w & 0xFF, d = (w >> 8) & 0xFFFF, ka = (w >> 24) & 0xF, ia = (w >> 28) & 0xFFFF, kb = (w >> 44) & 0xF, ib = (w >> 48) & 0xFFFF;
-            const e3 a = operand(ka, ia);
-            if (op == 4) {                     // OUT: constraint k_out is this value
-                if (k_out >= K) return ZP_ERR_ARG;
-                memcpy(h_out + 3 * k_out++, a.c, 24);
-                continue;
-            }
-            const e3 b = operand(kb, ib);
-            if (d >= slot.size()) return ZP_ERR_ARG;
-            if (op == 1) slot[d] = e3_add(a, b);
-            else if (op == 2) slot[d] = e3_sub(a, b);
-            else if (op == 3) slot[d] = e3_mul(a, b);
-            else return ZP_ERR_ARG;
-        }
-        return ok && k_out == K ? ZP_OK : ZP_ERR_ARG;
+        // the three-address code in F_{p^3}: the code group first (here, behind the fixed columns: a point on the trace domain is reported as that
+        // whatever the code holds), so the walk checks nothing
+        if (!zpi_program_check(&pg, ZPG_CODE, nullptr)) return ZP_ERR_ARG;
+        ExtEnv env;
+        env.file.assign(pg.slot_file(), e3_base(0));
+        env.ev_z = h_ev_z; env.ev_zw = h_ev_zw; env.pubchal = h_pubchal; env.consts = pg.consts; env.fixed = fixed.data(); env.h_out = h_out;
+        env.xml = e3_make(gl_sub(zeta.c[0], wlast), zeta.c[1], zeta.c[2]);
+        zpi_program_walk(pg.ins, (int)pg.n_instr, env);
+        return ZP_OK;
     } catch (...) {
         return ZP_ERR_NOMEM;
     }
@@ -340,17 +232,13 @@ int32_t zp_program_fixed_eval_ext(const uint64_t *h_program, size_t program_word
 int32_t zp_program_fixed_eval_ext_batch(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const uint64_t *h_pubchal, int32_t n_pubchal, int32_t logn,
                                         uint64_t root32, const uint64_t *h_zeta, int32_t n_points, uint64_t *h_fixed, int32_t n_fixed, uint8_t *h_on_domain, int32_t threads) {
     try {
-        if (!h_program || n_points < 0 || (n_points && (!h_zeta || !h_fixed || !h_on_domain)) || program_words < 12 || logn < 1 || logn > 32 || n_pubchal < 0 ||
-            (n_pubchal && n_points && !h_pubchal))
+        if (n_points < 0 || (n_points && (!h_zeta || !h_fixed || !h_on_domain)) || logn < 1 || logn > 32 || n_pubchal < 0 || (n_pubchal && n_points && !h_pubchal))
             return ZP_ERR_ARG;
         // the refusals of program_eval_ext_impl that do not depend on the point, once (n_points = 0 is refused like any other count)
-        static const unsigned char magic[8] = {'Z', 'P', 'A', 'I', 'R', '1', 0, 0};
-        if (memcmp(h_program, magic, 8) != 0) return ZP_ERR_ARG;
-        const size_t W = h_program[1], W2 = h_program[2], n_pub = h_program[4], n_chal = h_program[5], K = h_program[8], n_slots = h_program[9];
-        std::vector<ZpFixedCol> fxc;
-        if (!zpi_program_fixed_table(h_program, program_words, &fxc) || W < 1 || W >= 4096 || W2 >= 4096 || n_slots > (1u << 16) || K < 1 ||
-            (size_t)n_pubchal != n_pub + n_chal || root32 == 0 || root32 >= GL_P || n_fixed < 0 || (size_t)n_fixed != h_program[3])
-            return ZP_ERR_ARG;
+        ZpProgram pg;
+        if (!zpi_program_read(h_program, program_words, ZPG_FIXED_EVAL, &pg, nullptr)) return ZP_ERR_ARG;
+        const std::vector<ZpFixedCol> &fxc = pg.fxc;
+        if ((size_t)n_pubchal != pg.n_pub + pg.n_chal || root32 == 0 || root32 >= GL_P || n_fixed < 0 || (size_t)n_fixed != pg.n_fixed) return ZP_ERR_ARG;
         size_t entries = 0;
         for (const ZpFixedCol &fc : fxc) {
             if (fc.lp > logn) return ZP_ERR_ARG;
@@ -880,7 +768,7 @@ void intt_unscaled(std::vector<u64> &a, int lg, u64 root32) {
 }
 
 struct VerifyParams { int logn, logb, fri_logf, fri_final_log, n_queries, pow_bits; uint32_t flags; int threads; u64 root32, shift; const HostPoseidon254 *H254; };      // H254: BN128-hash mode
-struct ProgramInfo { const uint64_t *words; size_t n_words; size_t W, W2, n_pub, n_chal, K, Q, n_s2; char digest_hex[17]; u64 digest_words[4]; };
+struct ProgramInfo : ZpProgram { char digest_hex[17]; u64 digest_words[4]; };      // a statement as the verifiers hold it: the parsed blob and its digest
 
 // one proof between the header checks and the verdict: what the query phase needs
 struct Pending {
@@ -1223,16 +1111,8 @@ void query_arith(const Pending &pd, const VerifyParams &vp, const std::vector<e3
 
 template <class F>
 void spread(size_t n, int threads, F f) {              // f(i) for i < n over `threads` host threads (as zp_program_eval_ext spreads its columns)
-    unsigned nt = threads > 0 ? (unsigned)threads : std::thread::hardware_concurrency();
-    nt = nt < 1 ? 1 : nt > 16 ? 16 : nt;
-    if (n < 8) nt = 1;
-    auto work = [&](unsigned t) noexcept { for (size_t i = t; i < n; i += nt) f(i); };
-    std::vector<std::thread> th;
-    unsigned started = 0;
-    try { for (unsigned t = 1; t < nt; t++) { th.emplace_back(work, t); started = t; } } catch (...) {}
-    work(0);
-    for (unsigned t = started + 1; t < nt; t++) work(t);
-    for (auto &x : th) x.join();
+    const unsigned nt = n < 8 ? 1 : zpi_host_threads(threads);
+    zpi_over_threads(nt, [&](unsigned t) noexcept { for (size_t i = t; i < n; i += nt) f(i); });
 }
 
 // the first failing check in the protocol's order: per query the trace, quotient and stage-2 openings, then per layer its opening and its
@@ -1256,12 +1136,8 @@ bool params_in_range(const VerifyParams &vp) {
              vp.n_queries > 4096 || vp.pow_bits < 0 || vp.pow_bits > 40 || (vp.flags & ~(uint32_t)(ZP_VERIFY_HEADER_ONLY | ZP_VERIFY_TRUST_OPENINGS)));
 }
 bool program_info(const uint64_t *h_program, size_t program_words, ProgramInfo *out) {
-    static const unsigned char magic[8] = {'Z', 'P', 'A', 'I', 'R', '1', 0, 0};
-    if (program_words < 12 || memcmp(h_program, magic, 8) != 0 || !zpi_program_fixed_table(h_program, program_words, nullptr)) return false;
     ProgramInfo &pg = *out;
-    pg.words = h_program; pg.n_words = program_words;
-    pg.W = h_program[1]; pg.W2 = h_program[2]; pg.n_pub = h_program[4]; pg.n_chal = h_program[5]; pg.K = h_program[8]; pg.n_s2 = h_program[10]; pg.Q = h_program[11];
-    if (pg.W < 1 || pg.W >= 4096 || pg.W2 >= 4096 || pg.K < 1 || pg.Q < 1 || pg.Q > 16 || (pg.n_s2 == 0) != (pg.W2 == 0) || pg.n_chal != (pg.n_s2 ? 3u : 0u)) return false;
+    if (!zpi_program_read(h_program, program_words, ZPG_VERIFY, &pg, nullptr)) return false;
     uint8_t dg[32];
     Sha256::digest((const uint8_t *)h_program, program_words * 8, dg);
     for (int i = 0; i < 8; i++) snprintf(pg.digest_hex + 2 * i, 3, "%02x", dg[i]);
@@ -1826,7 +1702,7 @@ int32_t aggregate_verify_impl(zp_ctx *ctx, const zp_agg_statement *stmts, int32_
         std::vector<HeaderJob *> &jobs = by_stmt[k];
         if (jobs.empty()) continue;
         const AggStmt &S = st[k];
-        const size_t n = jobs.size(), npc = S.pg.n_pub + S.pg.n_chal, n_fixed = (size_t)S.pg.words[3];
+        const size_t n = jobs.size(), npc = S.pg.n_pub + S.pg.n_chal, n_fixed = S.pg.n_fixed;
         std::vector<u64> pc(n * npc + 1), zeta(n * 3), fixed(n * n_fixed * 3);
         std::vector<uint8_t> on_domain(n);
         for (size_t i = 0; i < n; i++) {

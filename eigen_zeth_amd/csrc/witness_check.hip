@@ -4,7 +4,9 @@
 //   (2) the stage-2 columns by the prover's own primitives (zp_grand_product / zp_logup_columns) and one period of every sparse fixed column
 //       (zpi_fixed_periods_build: the first half of the prover's fixed-column build, no transform -- on the trace domain a period IS the column).
 //   (3) witness_program_kernel: quotient_program_kernel's shape (csrc/stark.hip: lane = row, slot file in LDS as [slot][lane], the instruction
-//       word wave-uniform through readfirstlane, every operand kind a uniform branch) on the TRACE domain: next row = r + 1 mod N, the selectors
+//       word wave-uniform, every operand kind a uniform branch) on the TRACE domain.  The loop is written out here over air_program.hpp's field
+//       accessors and constants, NOT as an environment of zpi_program_walk: as one it measured 1 % slower on the MI355X with the same vector
+//       and LDS instructions (profiles/program_walk_static_and_ab.txt).  Next row = r + 1 mod N, the selectors
 //       computed from r, x = w^r from the plan's two-level table; at an OUT no accumulation but a ballot of the lanes whose value is not 0 --
 //       only when it is not empty one lane adds its popcount to the constraint's count and lowers the constraint's first row and the call's
 //       first (row, constraint) key.  An honest trace issues no atomic at all.
@@ -77,37 +79,35 @@ __global__ void __launch_bounds__(256) witness_program_kernel(WProgArgs a) {
     const u64 rn = (rr + 1) & (a.N - 1);
     const u64 x = gl_mul(a.xs_lo[rr & ((1ULL << a.lb) - 1)], a.xs_hi[rr >> a.lb]);
     const u64 xml = gl_sub(x, a.wlast);
-    const u64 *consts = a.prog + 12, *ins = consts + a.n_const;
+    const u64 *consts = a.prog + ZPH_WORDS, *ins = consts + a.n_const;
     int k_out = 0;
     for (int i = 0; i < a.n_instr; i++) {
-        const u64 w = ins[i];                                     // uniform address: scalar load
-        const u32 wl = __builtin_amdgcn_readfirstlane((u32)w), wh = __builtin_amdgcn_readfirstlane((u32)(w >> 32));
-        const u64 wu = ((u64)wh << 32) | wl;
-        const int op = (int)(wu & 0xFF), dst = (int)((wu >> 8) & 0xFFFF);
+        const u64 wu = zpi_wave_uniform(ins[i]);                  // uniform address: scalar load
+        const int op = zpi_op(wu), dst = zpi_dst(wu);
         u64 v[2];
 #pragma unroll
         for (int o = 0; o < 2; o++) {
-            const int kind = (int)((wu >> (24 + 20 * o)) & 0xF), idx = (int)((wu >> (28 + 20 * o)) & 0xFFFF);
+            const int kind = zpi_kind(wu, o), idx = zpi_idx(wu, o);
             u64 val;
             switch (kind) {
-                case 0: val = slots[idx * 256 + tid]; break;
-                case 1: val = idx < a.W ? a.trace[(u64)idx * a.N + rr] : a.s2[(u64)(idx - a.W) * a.N + rr]; break;
-                case 2: val = idx < a.W ? a.trace[(u64)idx * a.N + rn] : a.s2[(u64)(idx - a.W) * a.N + rn]; break;
-                case 3:
+                case ZPK_SLOT: val = slots[idx * 256 + tid]; break;
+                case ZPK_COL: val = idx < a.W ? a.trace[(u64)idx * a.N + rr] : a.s2[(u64)(idx - a.W) * a.N + rr]; break;
+                case ZPK_NEXT: val = idx < a.W ? a.trace[(u64)idx * a.N + rn] : a.s2[(u64)(idx - a.W) * a.N + rn]; break;
+                case ZPK_FIXED:
                     if (idx == 0) val = rr == 0;
                     else if (idx == 1) val = rr == a.N - 1;
                     else val = a.fixedx[a.fx_tab[2 * (idx - 2)] + (rr & a.fx_tab[2 * (idx - 2) + 1])];
                     break;
-                case 4: val = a.pub[idx]; break;
-                case 5: val = consts[idx]; break;
+                case ZPK_PUB: val = a.pub[idx]; break;
+                case ZPK_CONST: val = consts[idx]; break;
                 default: val = xml; break;
             }
             v[o] = val;
-            if (op == 4) break;
+            if (op == ZPI_OUT) break;
         }
-        if (op == 1) slots[dst * 256 + tid] = gl_add(v[0], v[1]);
-        else if (op == 2) slots[dst * 256 + tid] = gl_sub(v[0], v[1]);
-        else if (op == 3) slots[dst * 256 + tid] = gl_mul(v[0], v[1]);
+        if (op == ZPI_ADD) slots[dst * 256 + tid] = gl_add(v[0], v[1]);
+        else if (op == ZPI_SUB) slots[dst * 256 + tid] = gl_sub(v[0], v[1]);
+        else if (op == ZPI_MUL) slots[dst * 256 + tid] = gl_mul(v[0], v[1]);
         else {
             const ull m = __ballot(live && v[0] != 0);            // wave-uniform
             if (m != 0 && (tid & 63) == __ffsll((long long)m) - 1) {      // the lowest violating lane of the wave: its row is the wave's smallest
@@ -164,7 +164,7 @@ int32_t zpi_witness_check_device(zp_ctx *ctx, const ZpProgram &pg, const std::ve
         const uint64_t *g = (const uint64_t *)pubchal.data() + pg.n_pub;
         size_t at = 0;
         for (size_t k = 0; k < pg.n_s2; k++) {
-            const uint64_t *st = pg.stage2 + 4 * k;
+            const u64 *st = pg.stage2 + 4 * k;
             const uint64_t *tr = (const uint64_t *)d_trace;
             if (st[0] == 1) {
                 ZP_TRY(zp_grand_product(ctx, tr + st[1] * N, tr + st[2] * N, N, g, (uint64_t *)(s2 + at * N)));
@@ -178,42 +178,19 @@ int32_t zpi_witness_check_device(zp_ctx *ctx, const ZpProgram &pg, const std::ve
     ZpStage stage_(ctx, "witness_program");
     u64 *d_periods = nullptr;
     size_t period_words = 0;
-    ZP_TRY(zpi_fixed_periods_build(ctx, pg.consts - 12, pg.fxc, (const uint64_t *)pubchal.data(), 0, false, &d_periods, &period_words));
-    // one upload (after the stage-2 primitives: they use the same scratch slot): header, constants, instructions | publics and challenge |
-    // (offset, mask) of the sparse columns -- not the columns' entry tables, which the kernel never reads
-    const size_t pw = 12 + pg.n_const + pg.n_instr, total_up = pw + pubchal.size() + 2 * pg.fxc.size() + 1;
-    std::vector<u64> h(total_up, 0);
-    memcpy(h.data(), pg.consts - 12, pw * 8);
-    memcpy(h.data() + pw, pubchal.data(), pubchal.size() * 8);
-    {
-        u64 *t = h.data() + pw + pubchal.size(), off = 0;
-        for (size_t k = 0; k < pg.fxc.size(); k++) {
-            const u64 len = 1ULL << pg.fxc[k].lp;
-            t[2 * k] = off;
-            t[2 * k + 1] = len - 1;
-            off += len;
-        }
-    }
-    u64 *d = nullptr;
-    ZP_TRY(zpi_scratch(ctx, 3, total_up, &d));
-    if (total_up * 8 <= ZP_SMALL_COPY) ZP_TRY(zpi_h2d_small(ctx, d, h.data(), total_up * 8));
-    else {
-        ZP_HIP(ctx, hipMemcpyAsync(d, h.data(), total_up * 8, hipMemcpyHostToDevice, ctx->stream));
-        ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    ZP_TRY(zpi_fixed_periods_build(ctx, pg.words, pg.fxc, (const uint64_t *)pubchal.data(), 0, false, &d_periods, &period_words));
+    // the upload comes after the stage-2 primitives: they use the same scratch slot
+    ZpProgramDev dv;
+    ZP_TRY(zpi_program_upload(ctx, pg, ZpSpan{pubchal.data(), pubchal.size()}, {}, 0, &dv));
     WProgArgs a;
-    a.prog = d; a.trace = d_trace; a.s2 = s2; a.pub = d + pw; a.fx_tab = a.pub + pubchal.size(); a.fixedx = d_periods;
+    a.prog = dv.consts - ZPH_WORDS; a.trace = d_trace; a.s2 = s2; a.pub = dv.pubchal; a.fx_tab = dv.fx_tab; a.fixedx = d_periods;
     a.xs_lo = pl->d_twl; a.xs_hi = pl->d_twh; a.lb = pl->lb;
     a.first_key = res + 2; a.first_row = res + 3; a.counts = res + 3 + K;
     a.N = N; a.wlast = gl_inv(gl_root(ctx->root32, logn));
     a.W = (int)pg.W; a.n_const = (int)pg.n_const; a.n_instr = (int)pg.n_instr;
     hipLaunchKernelGGL(witness_program_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), pg.n_slots * 256 * 8, ctx->stream, a);
     ZP_HIP(ctx, hipGetLastError());
-    if (res_words * 8 <= ZP_SMALL_COPY) ZP_TRY(zpi_d2h_small(ctx, out.data(), res, res_words * 8));
-    else {
-        ZP_HIP(ctx, hipMemcpyAsync(out.data(), res, res_words * 8, hipMemcpyDeviceToHost, ctx->stream));
-        ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    ZP_TRY(zpi_d2h(ctx, out.data(), res, res_words * 8));
     const u64 *first = out.data() + 3, *counts = first + K;
     for (size_t k = 0; k < K; k++) { rep[3] += counts[k]; rep[4] += counts[k] != 0; }
     if (rep[3]) {

@@ -5,7 +5,7 @@
 // This file is HOST code only and builds on its own as plain C++ (tests/test_witness_check_fuzz.py links it with csrc/verify.hip under the host
 // sanitizers): the entry point, every refusal, the derived challenge, and the whole check for ctx = NULL.  With a ctx the validated arguments go
 // to csrc/witness_check.hip (a weak reference: absent in the sanitizer build, where only ctx = NULL is served).
-// The blob is validated by csrc/verify.hip (zpi_program_validate), the field code is gl.hpp's: no decoder of its own.
+// The blob is read and walked by air_program.hpp (zpi_program_read with ZPG_WITNESS, zpi_program_walk), the field code is gl.hpp's: no decoder of its own.
 #include <cstring>
 #include <exception>
 #include <thread>
@@ -26,7 +26,7 @@ constexpr u64 NONE = ~0ULL;
 void stage2_columns(const ZpProgram &pg, const u64 *trace, size_t N, const e3 &g, u64 *s2) {
     size_t at = 0;
     for (size_t k = 0; k < pg.n_s2; k++) {
-        const uint64_t *st = pg.stage2 + 4 * k;
+        const u64 *st = pg.stage2 + 4 * k;
         const u64 *a = trace + st[1] * N, *b = trace + st[2] * N, *m = trace + st[3] * N;
         u64 *o = s2 + at * N;
         if (st[0] == 1) {
@@ -54,80 +54,68 @@ void stage2_columns(const ZpProgram &pg, const u64 *trace, size_t N, const e3 &g
     }
 }
 
-struct HostCheck {
+// the environment of zpi_program_walk for one trace row over the base field
+struct HostEnv {
+    typedef u64 value;
+    static u64 add(u64 a, u64 b) { return gl_add(a, b); }
+    static u64 sub(u64 a, u64 b) { return gl_sub(a, b); }
+    static u64 mul(u64 a, u64 b) { return gl_mul(a, b); }
     const ZpProgram *pg;
     const u64 *trace, *s2, *pubchal;
     const std::vector<std::vector<u64>> *periods;
-    size_t N;
-    u64 wN, wlast;
+    size_t N, r, rn;
+    u64 xml;
+    u64 *counts, *first;       // of the rows walked so far: counts[k] = violated rows of constraint k, first[k] = the smallest of them
+    u64 file[32];
+    u64 &slot(int i) { return file[i]; }
+    u64 column(size_t idx, size_t row) const { return idx < pg->W ? trace[idx * N + row] : s2[(idx - pg->W) * N + row]; }
+    u64 load(int kind, int idx) const {
+        switch (kind) {
+            case ZPK_SLOT: return file[idx];
+            case ZPK_COL: return column(idx, r);
+            case ZPK_NEXT: return column(idx, rn);
+            case ZPK_FIXED: {
+                if (idx < 2) return idx == 0 ? r == 0 : r == N - 1;
+                const std::vector<u64> &p = (*periods)[idx - 2];
+                return p[r & (p.size() - 1)];
+            }
+            case ZPK_PUB: return pubchal[idx];
+            case ZPK_CONST: return pg->consts[idx];
+            default: return xml;
+        }
+    }
+    void out(int k, u64 v) {
+        if (v == 0) return;
+        counts[k]++;
+        if (first[k] == NONE) first[k] = r;
+    }
 };
 
-// rows [r0, r1): counts[k] += violated rows of constraint k, first[k] = the smallest of them
-void check_rows(const HostCheck &h, size_t r0, size_t r1, u64 *counts, u64 *first) {
-    const ZpProgram &pg = *h.pg;
-    u64 slot[32] = {0};
-    u64 x = gl_pow(h.wN, (u64)r0);
-    for (size_t r = r0; r < r1; r++, x = gl_mul(x, h.wN)) {
-        const size_t rn = (r + 1) & (h.N - 1);
-        const u64 xml = gl_sub(x, h.wlast);
-        size_t k_out = 0;
-        for (size_t i = 0; i < pg.n_instr; i++) {
-            const u64 w = pg.ins[i];
-            const unsigned op = (unsigned)(w & 0xFF), dst = (unsigned)((w >> 8) & 0xFFFF);
-            u64 v[2] = {0, 0};
-            for (int o = 0; o < (op == 4 ? 1 : 2); o++) {
-                const unsigned kind = (unsigned)((w >> (24 + 20 * o)) & 0xF), idx = (unsigned)((w >> (28 + 20 * o)) & 0xFFFF);
-                switch (kind) {
-                    case 0: v[o] = slot[idx]; break;
-                    case 1: v[o] = idx < pg.W ? h.trace[idx * h.N + r] : h.s2[(idx - pg.W) * h.N + r]; break;
-                    case 2: v[o] = idx < pg.W ? h.trace[idx * h.N + rn] : h.s2[(idx - pg.W) * h.N + rn]; break;
-                    case 3:
-                        if (idx == 0) v[o] = r == 0;
-                        else if (idx == 1) v[o] = r == h.N - 1;
-                        else { const std::vector<u64> &p = (*h.periods)[idx - 2]; v[o] = p[r & (p.size() - 1)]; }
-                        break;
-                    case 4: v[o] = h.pubchal[idx]; break;
-                    case 5: v[o] = pg.consts[idx]; break;
-                    default: v[o] = xml; break;
-                }
-            }
-            if (op == 1) slot[dst] = gl_add(v[0], v[1]);
-            else if (op == 2) slot[dst] = gl_sub(v[0], v[1]);
-            else if (op == 3) slot[dst] = gl_mul(v[0], v[1]);
-            else {
-                if (v[0] != 0) {
-                    counts[k_out]++;
-                    if (first[k_out] == NONE) first[k_out] = r;
-                }
-                k_out++;
-            }
-        }
+// rows [r0, r1) in ascending order
+void check_rows(HostEnv h, u64 wN, u64 wlast, size_t r0, size_t r1, u64 *counts, u64 *first) {
+    h.counts = counts; h.first = first;
+    memset(h.file, 0, sizeof h.file);
+    u64 x = gl_pow(wN, (u64)r0);
+    for (size_t r = r0; r < r1; r++, x = gl_mul(x, wN)) {
+        h.r = r; h.rn = (r + 1) & (h.N - 1); h.xml = gl_sub(x, wlast);
+        zpi_program_walk(h.pg->ins, (int)h.pg->n_instr, h);
     }
 }
 
-// work(t, first, end) on the t-th of T near-equal ranges of n items; a thread that cannot be started has its range run here
-template <class Work>
-void over_threads(size_t n, unsigned T, Work work) {
-    std::vector<std::thread> pool;
-    unsigned started = 0;
-    try {
-        for (unsigned t = 1; t < T; t++) { pool.emplace_back(work, t, n * t / T, n * (t + 1) / T); started = t; }
-    } catch (...) {}
-    work(0u, (size_t)0, n / T);
-    for (unsigned t = started + 1; t < T; t++) work(t, n * t / T, n * (t + 1) / T);
-    for (auto &th : pool) th.join();
-}
+// the t-th of T near-equal ranges of n items
+inline void share(size_t n, unsigned T, unsigned t, size_t *a, size_t *b) { *a = n * t / T; *b = n * (t + 1) / T; }
 
 int32_t check_host(const ZpProgram &pg, const std::vector<u64> &pubchal, const u64 *trace, int logn, int threads, uint64_t *h_report, uint64_t *h_counts,
                    uint64_t *h_first_row) {
     const size_t N = (size_t)1 << logn, K = pg.K, words = pg.W * N;
-    unsigned T = threads > 0 ? (unsigned)threads : std::thread::hardware_concurrency();
-    T = T < 1 ? 1 : T > 16 ? 16 : T;
+    const unsigned T = zpi_host_threads(threads);
     // (1) every word of the trace, read or not by an instruction, against p
     std::vector<u64> bad_n(T, 0), bad_at(T, NONE);
     {
         const unsigned Tc = words < 4096 ? 1 : T;
-        over_threads(words, Tc, [&](unsigned t, size_t a, size_t b) noexcept {
+        zpi_over_threads(Tc, [&](unsigned t) noexcept {
+            size_t a, b;
+            share(words, Tc, t, &a, &b);
             for (size_t i = a; i < b; i++)
                 if (trace[i] >= GL_P) { bad_n[t]++; if (bad_at[t] == NONE) bad_at[t] = i; }
         });
@@ -148,17 +136,22 @@ int32_t check_host(const ZpProgram &pg, const std::vector<u64> &pubchal, const u
         for (size_t k = 0; k < pg.fxc.size(); k++) {
             const ZpFixedCol &fc = pg.fxc[k];
             periods[k].assign((size_t)1 << fc.lp, 0);
-            const uint64_t *ent = pg.consts - 12 + fc.first_entry_word;       // consts = blob + 12
-            for (size_t e = 0; e < fc.n_entries; e++) periods[k][ent[2 * e] & ~(1ULL << 63)] = (ent[2 * e] >> 63) ? pubchal[ent[2 * e + 1]] : ent[2 * e + 1];
+            for (size_t e = 0; e < fc.n_entries; e++) {
+                const ZpFixedEntry en = zpi_fixed_entry(pg.words, fc, e);
+                periods[k][en.pos] = en.is_pub ? pubchal[en.value] : en.value;
+            }
         }
         // (3) rows over threads, per-thread counts merged at the end
         const unsigned Tr = N < 64 ? 1 : (N / 16 < T ? (unsigned)(N / 16) : T);
         std::vector<u64> tc((size_t)Tr * K, 0), tf((size_t)Tr * K, NONE);
-        HostCheck h;
+        HostEnv h{};
         h.pg = &pg; h.trace = trace; h.s2 = s2.data(); h.pubchal = pubchal.data(); h.periods = &periods; h.N = N;
-        h.wN = gl_root(ZP_ROOT32_DEFAULT, logn);
-        h.wlast = gl_inv(h.wN);
-        over_threads(N, Tr, [&](unsigned t, size_t a, size_t b) noexcept { check_rows(h, a, b, &tc[(size_t)t * K], &tf[(size_t)t * K]); });
+        const u64 wN = gl_root(ZP_ROOT32_DEFAULT, logn), wlast = gl_inv(wN);
+        zpi_over_threads(Tr, [&](unsigned t) noexcept {
+            size_t a, b;
+            share(N, Tr, t, &a, &b);
+            check_rows(h, wN, wlast, a, b, &tc[(size_t)t * K], &tf[(size_t)t * K]);
+        });
         for (unsigned t = 0; t < Tr; t++)
             for (size_t k = 0; k < K; k++) {
                 counts[k] += tc[(size_t)t * K + k];
@@ -191,7 +184,7 @@ extern "C" int32_t zp_stark_check_witness(zp_ctx *ctx, const uint64_t *h_program
     };
     try {
         ZpProgram pg;
-        if (!zpi_program_validate(h_program, program_words, &pg, &why)) return refuse(why);
+        if (!zpi_program_read(h_program, program_words, ZPG_WITNESS, &pg, &why)) return refuse(why);
         if (!trace || !h_report) return refuse("null pointer");
         if (logn < 1 || logn > 32) return refuse("logn out of range");
         if (trace_words != pg.W << logn) return refuse("trace_words must be W * 2^logn");

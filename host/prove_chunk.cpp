@@ -78,12 +78,13 @@ int main(int argc, char **argv) {
     // the shapes must agree BEFORE anything reaches the GPU: W comes from the program header (word 1), the number of public
     // inputs from word 4; the library checks trace_words again (ZP_ERR_ARG otherwise)
     if (program.size() < 12) { fprintf(stderr, "%s: shorter than a constraint-program header\n", argv[1]); return 2; }
-    if (program[1] < 1 || program[1] >= 4096) { fprintf(stderr, "%s: width %llu out of range\n", argv[1], (unsigned long long)program[1]); return 2; }   // before it is shifted
-    if (logn < 1 || logn > 30 || trace.size() != (size_t)(program[1] << logn)) {
-        fprintf(stderr, "%s: %zu words, the program needs W * 2^logn = %llu * 2^%d\n", argv[2], trace.size(), (unsigned long long)program[1], logn);
+    const uint64_t prog_w = program[1], prog_n_pub = program[4];       // the only two header words a host needs (include/zeth_prover.h "constraint program")
+    if (prog_w < 1 || prog_w >= 4096) { fprintf(stderr, "%s: width %llu out of range\n", argv[1], (unsigned long long)prog_w); return 2; }   // before it is shifted
+    if (logn < 1 || logn > 30 || trace.size() != (size_t)(prog_w << logn)) {
+        fprintf(stderr, "%s: %zu words, the program needs W * 2^logn = %llu * 2^%d\n", argv[2], trace.size(), (unsigned long long)prog_w, logn);
         return 2;
     }
-    if (pubs.size() != program[4]) { fprintf(stderr, "%s: %zu public inputs, the program declares %llu\n", argv[3], pubs.size(), (unsigned long long)program[4]); return 2; }
+    if (pubs.size() != prog_n_pub) { fprintf(stderr, "%s: %zu public inputs, the program declares %llu\n", argv[3], pubs.size(), (unsigned long long)prog_n_pub); return 2; }
     for (uint64_t v : trace)
         if (!check && v >= 0xFFFFFFFF00000001ULL) { fprintf(stderr, "%s: non-canonical trace value (precondition of zp_stark_prove)\n", argv[2]); return 2; }
     if (world < 1 || rank < 0 || rank >= world) { fprintf(stderr, "bad rank / world\n"); return 2; }
@@ -96,7 +97,7 @@ int main(int argc, char **argv) {
     }
     CHECK(zp_create(&ctx, rank));                      // one process per GPU: rank r drives device r
     // rank r owns columns [r wl, min((r + 1) wl, W)), wl = ceil(W / world): the tail ranks hold fewer columns, or none (include/zeth_prover.h)
-    const size_t Wc = (size_t)program[1], wl = (Wc + (size_t)world - 1) / (size_t)world, c0 = (size_t)rank * wl < Wc ? (size_t)rank * wl : Wc,
+    const size_t Wc = (size_t)prog_w, wl = (Wc + (size_t)world - 1) / (size_t)world, c0 = (size_t)rank * wl < Wc ? (size_t)rank * wl : Wc,
                  cols = Wc - c0 < wl ? Wc - c0 : wl, words = cols << logn;
     const uint64_t *mine = trace.data() + (c0 << logn);                // this rank's columns (a real host would read only these)
     void *d_trace = nullptr;

@@ -348,7 +348,10 @@ int32_t zp_domain_tables(zp_ctx *ctx, int32_t logm, const uint64_t **d_lo, const
  * zp_eval_quotient evaluates the program on every row of the LDE domain (M = 2^logm rows, x = shift*w_M^r), combines
  * constraint k with alpha^k in F_{p^3} (h_alpha_pows [K][3]), multiplies by h_zhinv[r mod 2^logb] and writes the three
  * planes d_out u64[3][M].  d_cols u64[W+W2][M], d_fixed u64[2][M]; h_pub = publics then challenges (n_pub values).
- * A malformed program (bad magic, lengths, operand or slot out of range, more than 32 slots) is ZP_ERR_ARG.        */
+ * A malformed program (bad magic, lengths, operand or slot out of range, more than 32 slots) is ZP_ERR_ARG.
+ * Every entry point that takes a program parses it with the same code (csrc/air_program.hpp: counts bounded, the sparse columns' table,
+ * the whole-blob length) and then asks for the groups of checks it needs -- widths, Q, the stage-2 table, the code, the slot file,
+ * canonical constants; which reader asks for which is a table there and in DESIGN.md ("Readers of a constraint program").           */
 int32_t zp_eval_quotient(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const uint64_t *d_cols,
                          const uint64_t *d_fixed, int32_t logm, int32_t logb, const uint64_t *h_pub, int32_t n_pub,
                          const uint64_t *h_alpha_pows, const uint64_t *h_zhinv, uint64_t shift, uint64_t w_last,

@@ -192,3 +192,81 @@ def test_malformed_programs_are_refused_before_anything_is_launched(prover):
         assert e.value.code == -1, cls
     d_out.free()
     assert (gpu_quotient(prover, blob, d, logm, logb) == want).all()
+
+
+# ---- the acceptance table of csrc/air_program.hpp on the GPU readers: the variants of tests/test_program_readers.py.  Every variant is refused in
+# front of the launch or runs a valid program: what zp_eval_quotient accepts of them differs from the good blob only in header words no kernel reads
+# (Q, W with every operand in range, n_chal with a public-input vector to match, the stage-2 table), so its planes are the good blob's.
+QUOTIENT_ACCEPTS = {("good", "plain"), ("good", "perm"), ("Q_0", "plain"), ("Q_17", "plain"), ("W_4096", "plain"), ("n_chal_1_no_stage2", "plain"),
+                    ("Q_0", "perm"), ("Q_17", "perm"), ("W_4096", "perm"), ("stage2_kind_3", "perm"), ("stage2_column_W", "perm")}
+
+
+def reader_variants(logn):
+    """(name, base, blob) of tests/test_program_readers.py with the stage-2 program on 2^logn rows; bases: name -> (blob, trace, publics)"""
+    import test_program_readers as TR
+    import witness_cases as WC
+    _, vs = TR.variants()
+    _, perm, ptrace, ppubs = WC.honest_case("perm", logn)
+    perm4 = WC.honest_case("perm", 4)[1]
+    assert (perm == perm4).all()                          # the program does not depend on the trace length: the variants cut at 2^4 rows are its variants
+    blob, shape, _ = refusal_base()
+    trace, pubs = WC.random_inputs(shape, 5, 4100)
+    return {"plain": (blob, trace, pubs), "perm": (perm, ptrace, ppubs)}, [v for v in vs if v[1] != "one_slot"]
+
+
+def test_reader_variants_through_the_quotient_interpreter(prover):
+    """zp_eval_quotient at (logm, logb) = (6, 1), one partial workgroup: accept or refuse per variant, and the accepted ones give the good blob's planes"""
+    logm, logb = 6, 1
+    bases, vs = reader_variants(5)
+    good, seen = {}, set()
+    for name, base, blob in vs:
+        g = bases[base][0]
+        shape = {"width": int(g[1]) + int(g[2]), "K": int(g[8]), "n_pub": int(g[4]) + int(g[5]), "lp": [l for l, _ in decode(g)[1]]}
+        d = inputs(shape, logm, logb, 8900)
+        d["pubs"] = d["pubs"] + [7] * (int(blob[4]) + int(blob[5]) - len(d["pubs"]))      # as many as the variant's header announces
+        try:
+            got = gpu_quotient(prover, blob, d, logm, logb)
+        except native.ZpError as e:
+            assert e.code == -1, (name, base)
+            continue
+        seen.add((name, base))
+        if name == "good":
+            good[base] = got
+        assert (got == good[base]).all(), (name, base)
+    assert seen == QUOTIENT_ACCEPTS
+    blob, shape, d = refusal_base()
+    assert (good["plain"] == checker_quotient(blob, inputs(shape, logm, logb, 8900), logm, logb)).all()
+
+
+def test_reader_variants_through_the_device_witness_check(prover):
+    """zp_stark_check_witness with a ctx on 2^5 rows: the witness check asks for every group, so only the good blobs are taken"""
+    import witness_cases as WC
+    bases, vs = reader_variants(5)
+    for name, base, blob in vs:
+        _, trace, pubs = bases[base]
+        d_trace = prover.upload(np.ascontiguousarray(trace))
+        chal = WC.EXPLICIT_CHALLENGE if int(blob[10]) else None
+        if name == "good":
+            rep = prover.check_witness(blob, d_trace, pubs, 5, chal)
+            assert rep.ok == (base == "perm")             # perm's own witness; a random trace for the other
+        else:
+            with pytest.raises(native.ZpError) as e:
+                prover.check_witness(blob, d_trace, pubs, 5, chal)
+            assert e.value.code == -1, (name, base)
+        d_trace.free()
+
+
+def test_stage2_variants_through_the_prover(prover):
+    """zp_stark_prove on 2^5 rows, blow-up 2: a stage-2 table with an unknown kind or a column outside the trace is refused by make_shape"""
+    import witness_cases as WC
+    bases, vs = reader_variants(5)
+    blob, trace, pubs = bases["perm"]
+    assert int(blob[11]) <= 2
+    d_trace = prover.upload(np.ascontiguousarray(trace))
+    assert prover.stark_prove("perm", blob, d_trace, pubs, 5, 1, 2, 3, 3, 0).startswith("{")
+    for name, base, bad in vs:
+        if name.startswith("stage2"):
+            with pytest.raises(native.ZpError) as e:
+                prover.stark_prove("perm", bad, d_trace, pubs, 5, 1, 2, 3, 3, 0)
+            assert e.value.code == -1, name
+    d_trace.free()
