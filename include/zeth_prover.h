@@ -172,7 +172,9 @@ int32_t zp_merkle16_open_batch_bn254(zp_ctx *ctx, const uint64_t *d_tree, size_t
  *   inverse = 1: x_i = g^-i / N * sum_k y_k w^(-ik)  (the inverse of the above)
  * zp_qap_quotient_bn254: d_a, d_b, d_c hold the evaluations of A(x), B(x), C(x) on <w> (2^logm points each);
  *   on return d_a holds the 2^logm coefficients of H = (A B - C) / (x^m - 1) (the top one is 0 for a satisfied
- *   system); d_b, d_c are overwritten (evaluations on the coset g <w>).  g must not be an m-th root of unity.      */
+ *   system); d_b, d_c are overwritten (evaluations on the coset g <w>).  g must not be an m-th root of unity.
+ *   An unsatisfied system is not detected: with A B - C = H (x^m - 1) - D, deg D < m, d_a receives H - D / (g^m - 1),
+ *   which depends on g and in general has a non-zero top coefficient.                                                */
 int32_t zp_ntt_bn254(zp_ctx *ctx, uint64_t *d_data, int32_t logn, int32_t inverse, const uint64_t *h_coset);
 int32_t zp_qap_quotient_bn254(zp_ctx *ctx, uint64_t *d_a, uint64_t *d_b, uint64_t *d_c, int32_t logm, const uint64_t *h_coset);
 
