@@ -108,6 +108,8 @@ struct zp_ctx {
     uint64_t verify_counters[4] = {0, 0, 0, 0};   // zp_verify_counters: chain launches, chain steps run on the device, public-input commitments made on the device, texts that took the host sponge on the device path
     int tune_msm_chunk_log = 0;   // 0 = default (2^24 points per Pippenger run)
     int tune_fixed_eval_dev_min = 1 << 15;   // zp_program_fixed_eval_ext_batch with a ctx: calls of fewer (points x sparse entries) run on the host (0: always the device; < 0 restores this default).  2^15: from ~12.5 ns per entry on 16 host threads against ~0.5 ms per device call (profiles/r12_fixed_eval_batch.json: every size measured there is above it and the device wins, 10x at one point of 4.4 x 10^5 entries); not measured AT the crossover
+    int tune_witness_kernel = 1;  // the constraint check (zp_stark_check_witness on a ctx, the provers under "prove_check") runs the program's GENERATED witness kernel when one is registered (zp_stark_set_air_kernel_witness); 0: always the interpreter.  Same reports either way (figures: profiles/witness_check_inproof.json)
+    int tune_prove_check = 0;     // 1: zp_stark_prove / zp_stark_prove_bn128 check the trace inside the proof (canonical words first, the constraints at the transcript's own stage-2 challenge) and refuse a false witness with ZP_ERR_WITNESS; 0: they prove whatever they are handed
     // zp_stark_prove: device buffers kept between proofs (chunk after chunk has the same shapes; hipMalloc / hipFree of ~20 buffers
     // cost milliseconds per proof) and the LDE of the two boundary selectors per (logn, logb, shift, root)
     std::multimap<size_t, void *> prove_pool;
@@ -117,6 +119,7 @@ struct zp_ctx {
     std::map<std::string, void *> air_kernels;   // 64-hex-digit program digest -> generated constraint kernel (AIR plug-in ABI): zp_stark_set_air_kernel
     struct DigestEntry { std::vector<uint64_t> words; uint8_t dg[32]; };
     std::vector<DigestEntry> digest_cache;   // SHA-256 of the large constraint programs seen last (csrc/prove.hip: program_digest)
+    struct WitnessVerdict { bool valid = false; u64 rep[8], chal[3]; std::vector<u64> counts, first_row; } last_witness;   // the last proof checked under "prove_check" (zp_stark_prove_witness_report)
     std::vector<u64> last_openings;          // BN128-hash mode: roots, query indices, opened values and paths of the last proof, binary (zp_stark_openings)
     // per-launch event profiling (zp_set_profiling)
     bool profiling = false;
@@ -270,6 +273,16 @@ int32_t zpi_program_upload(zp_ctx *ctx, const ZpProgram &pg, ZpSpan pubchal, std
 // zp_stark_check_witness on a ctx (csrc/witness_check.hip): arguments validated by the caller (csrc/witness_host.hip), pubchal = publics then the challenge
 int32_t zpi_witness_check_device(zp_ctx *ctx, const ZpProgram &pg, const std::vector<u64> &pubchal, const u64 *d_trace, int logn, uint64_t *h_report,
                                  uint64_t *h_counts, uint64_t *h_first_row);
+// its three pieces (csrc/witness_check.hip), shared with the one-call provers under "prove_check" (csrc/prove.hip): the canonical pass; the report of a
+// non-canonical trace; the constraints over (trace, GIVEN stage-2 columns, publics then challenge) -- through the program's generated witness kernel when
+// dg32 names one and "witness_kernel" allows it, else the interpreter
+int32_t zpi_witness_canonical(zp_ctx *ctx, const u64 *d_trace, size_t total, u64 *bad_n, u64 *bad_at);
+void zpi_witness_noncanonical_report(size_t K, size_t N, u64 bad_n, u64 bad_at, uint64_t *h_report, uint64_t *h_counts, uint64_t *h_first_row);
+int32_t zpi_witness_constraints(zp_ctx *ctx, const ZpProgram &pg, const uint8_t *dg32, const std::vector<u64> &pubchal, const u64 *d_trace, const u64 *d_s2,
+                                int logn, uint64_t *h_report, uint64_t *h_counts, uint64_t *h_first_row);
+// csrc/prove.hip: the SHA-256 of a program through the ctx's cache of large blobs; the key a generated kernel of that digest is kept under
+void zpi_program_digest_cached(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, uint8_t dg[32]);
+std::string zpi_air_kernel_key(const char *form, const uint8_t dg[32]);
 // device buffers from / back to the per-ctx pool of zp_stark_prove (csrc/prove.hip): everything runs on the ctx stream, so reuse is ordered
 int32_t zpi_pool_alloc(zp_ctx *ctx, size_t bytes, void **out);
 void zpi_pool_release(zp_ctx *ctx, void *p, size_t bytes);

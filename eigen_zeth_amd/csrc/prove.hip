@@ -24,7 +24,9 @@ namespace {
 
 // The program of a verifier AIR is megabytes (one table entry per scheduled row of every sparse column) and the same blob comes back proof
 // after proof: its digest is kept per ctx next to a copy of the blob (compared word for word: a cache hit is a memcmp, not a trust decision).
-void program_digest(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, uint8_t dg[32]) {
+void program_digest(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, uint8_t dg[32]) { zpi_program_digest_cached(ctx, h_program, program_words, dg); }
+}  // namespace
+void zpi_program_digest_cached(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, uint8_t dg[32]) {
     if (program_words < (1u << 14)) {                     // small statements: hashing is cheaper than remembering
         Sha256::digest((const uint8_t *)h_program, program_words * 8, dg);
         return;
@@ -40,6 +42,7 @@ void program_digest(zp_ctx *ctx, const uint64_t *h_program, size_t program_words
     ctx->digest_cache.back().words.assign(h_program, h_program + program_words);
     memcpy(ctx->digest_cache.back().dg, dg, 32);
 }
+namespace {
 
 // ---- the Fiat-Shamir sponges of stark/transcript.py.  Goldilocks mode: Poseidon-12, rate 8 / capacity 4, on zp_poseidon_sponge.
 // BN128 mode: Poseidon-BN254 of width 17 (element 0 = capacity, 1..16 = rate) on zp_poseidon_bn254_sponge; Goldilocks values are
@@ -501,16 +504,20 @@ int32_t fixed_columns_cached(zp_ctx *ctx, const Shape &sh, u64 **out) {
 }
 
 // Generated constraint kernels (AIR plug-in ABI: stark/air.py writes them) are kept per ctx under the 64 hex digits of the program's
-// digest: form "" = the whole-domain kernel (`zpair_<air>_quotient`), form "rows:" = its row-window form (`zpair_<air>_quotient_rows`)
+// digest: form "" = the whole-domain kernel (`zpair_<air>_quotient`), form "rows:" = its row-window form (`zpair_<air>_quotient_rows`), form
+// "witness:" = the constraint check on the trace domain (`zpair_<air>_quotient_witness`, run by csrc/witness_check.hip)
 typedef int (*zp_air_quotient_fn)(void *stream, const u64 *cols, const u64 *fixedc, u64 M, u64 b, const u64 *pub, const u64 *apow, const u64 *zhinv,
                                   const u64 *xs_lo, const u64 *xs_hi, int lb, u64 shift, u64 wlast, u64 *out);
 typedef int (*zp_air_quotient_rows_fn)(void *stream, const u64 *cols, u64 sc, const u64 *fixedc, u64 sf, u64 M, u64 b, u64 row0, u64 nrows, const u64 *pub,
                                        const u64 *apow, const u64 *zhinv, const u64 *xs_lo, const u64 *xs_hi, int lb, u64 shift, u64 wlast, u64 *out, u64 so);
-std::string air_kernel_key(const char *form, const uint8_t dg[32]) {
+std::string air_kernel_key(const char *form, const uint8_t dg[32]) { return zpi_air_kernel_key(form, dg); }
+}  // namespace
+std::string zpi_air_kernel_key(const char *form, const uint8_t dg[32]) {
     char hex[65];
     for (int i = 0; i < 32; i++) snprintf(hex + 2 * i, 3, "%02x", dg[i]);
     return std::string(form) + std::string(hex, 64);
 }
+namespace {
 int32_t set_air_kernel(zp_ctx *ctx, const char *form, const uint64_t *h_program, size_t program_words, void *fn) {
     if (!ctx) return ZP_ERR_ARG;
     ZP_ARG(ctx, h_program && program_words >= 8 && program_words < ((size_t)1 << 28), "null / implausible program");
@@ -740,6 +747,57 @@ int32_t guarded(zp_ctx *ctx, Body body) {
     }
 }
 
+// ---- "prove_check" (zp_set_tuning): the check INSIDE the one-call provers.  The verdict of the proof's trace stays on the ctx
+// (zp_stark_prove_witness_report); anything but SATISFIED ends the call with ZP_ERR_WITNESS and a line naming the first constraint and row, or the
+// first non-canonical column and row.  The pieces are csrc/witness_check.hip's, the ones zp_stark_check_witness runs.
+int32_t witness_refusal(zp_ctx *ctx) {
+    const zp_ctx::WitnessVerdict &v = ctx->last_witness;
+    char line[256];
+    if (v.rep[0] == ZP_WITNESS_NONCANONICAL)
+        snprintf(line, sizeof line, "witness not canonical: %llu trace word(s) >= p, the first in column %llu at row %llu", (unsigned long long)v.rep[5],
+                 (unsigned long long)v.rep[6], (unsigned long long)v.rep[7]);
+    else
+        snprintf(line, sizeof line, "witness violates constraint %llu at row %llu (that constraint at %llu row(s); %llu constraint(s) violated, %llu violations in all)",
+                 (unsigned long long)v.rep[2], (unsigned long long)v.rep[1], (unsigned long long)v.counts[v.rep[2]], (unsigned long long)v.rep[4],
+                 (unsigned long long)v.rep[3]);
+    ctx->err = line;
+    return ZP_ERR_WITNESS;
+}
+// before anything else touches the caller's trace: every word against p
+int32_t prove_check_canonical(zp_ctx *ctx, const Shape &sh) {
+    zp_ctx::WitnessVerdict &v = ctx->last_witness;
+    v.valid = false;
+    // the interpreter's requirements (at most 32 slots, canonical constants, checked code) on top of the prover's: a generated kernel needs none of
+    // them, but one statement must not be checkable or not by what happens to be registered
+    const char *why;
+    ZP_ARG(ctx, zpi_program_check(&sh.pg, ZPG_WITNESS, &why), why);
+    u64 bad_n, bad_at;
+    PV_TRY(zpi_witness_canonical(ctx, (const u64 *)sh.d_trace, sh.pg.W * sh.N, &bad_n, &bad_at));
+    if (bad_n == 0) return ZP_OK;
+    v.counts.assign(sh.pg.K, 0);
+    v.first_row.assign(sh.pg.K, ~0ULL);
+    zpi_witness_noncanonical_report(sh.pg.K, sh.N, bad_n, bad_at, (uint64_t *)v.rep, nullptr, nullptr);
+    memset(v.chal, 0, sizeof v.chal);
+    v.valid = true;
+    sh.mark("witness refused");
+    return witness_refusal(ctx);
+}
+// as soon as the operands exist: the constraints over (trace, s2, publics | the transcript's stage-2 challenge)
+int32_t prove_check_constraints(zp_ctx *ctx, const Shape &sh, const std::vector<u64> &pubs, const u64 *s2, const e3 *chal) {
+    zp_ctx::WitnessVerdict &v = ctx->last_witness;
+    std::vector<u64> pubchal(pubs);
+    if (chal) pubchal.insert(pubchal.end(), chal->c, chal->c + 3);
+    pubchal.push_back(0);                 // never empty
+    v.counts.assign(sh.pg.K, 0);
+    v.first_row.assign(sh.pg.K, ~0ULL);
+    PV_TRY(zpi_witness_constraints(ctx, sh.pg, sh.dg, pubchal, (const u64 *)sh.d_trace, s2, sh.logn, (uint64_t *)v.rep, (uint64_t *)v.counts.data(),
+                                   (uint64_t *)v.first_row.data()));
+    for (int c = 0; c < 3; c++) v.chal[c] = chal ? chal->c[c] : 0;
+    v.valid = true;
+    sh.mark("witness checked");
+    return v.rep[0] == ZP_WITNESS_SATISFIED ? ZP_OK : witness_refusal(ctx);
+}
+
 // zp_stark_prove / zp_stark_prove_bn128: the whole trace on one device
 int32_t prove_impl(zp_ctx *ctx, bool bn, const ProveArgs &a) {
     ZpStage stage_(ctx, bn ? "stark_prove_bn128" : "stark_prove");
@@ -755,6 +813,12 @@ int32_t prove_impl(zp_ctx *ctx, bool bn, const ProveArgs &a) {
     Transcript tr(ctx, bn);
     const Trees T{ctx, bn};
     PV_TRY(transcript_head(ctx, sh, tr, T, dev));
+    std::vector<u64> pubchal(a.h_pubs, a.h_pubs + a.n_pubs);
+    const bool check = ctx->tune_prove_check != 0;
+    if (check) {          // the trace is resident and untouched: its words, and without stage-2 arguments its constraints, before the first extension
+        PV_TRY(prove_check_canonical(ctx, sh));
+        if (!n_s2) PV_TRY(prove_check_constraints(ctx, sh, pubchal, nullptr, nullptr));
+    }
 
     // 1. commit the trace (ext has room for the stage-2 columns behind the trace columns).  No coefficient buffer since round 5: the
     //    out-of-domain evaluations come from the resident extension (zp_ood_eval), so the extensions run without their coefficient
@@ -769,7 +833,6 @@ int32_t prove_impl(zp_ctx *ctx, bool bn, const ProveArgs &a) {
     u64 root1[4], root2[4] = {0, 0, 0, 0}, rootq[4];
     PV_TRY(T.root(tree1, Mt, root1));
     tr.absorb_root(root1);
-    std::vector<u64> pubchal(a.h_pubs, a.h_pubs + a.n_pubs);
     u64 *tree2 = nullptr, *s2_kept = nullptr;
     if (n_s2) {
         const e3 chal = tr.challenge();
@@ -787,6 +850,8 @@ int32_t prove_impl(zp_ctx *ctx, bool bn, const ProveArgs &a) {
                 at += 9;
             }
         }
+        // the stage-2 columns exist on the trace domain, made with the challenge that binds; nothing has been extended from them yet
+        if (check) PV_TRY(prove_check_constraints(ctx, sh, pubchal, s2, &chal));
         PV_TRY(zp_lde(ctx, (const uint64_t *)s2, (uint64_t *)(ext + W * M), nullptr, logn, logb, (int32_t)W2, shift));
         PV_TRY(dev.alloc(T.tree_words(M2), &tree2));
         PV_TRY(T.commit(ext + W * M, M2, (int)W2g, tree2));
@@ -1360,6 +1425,28 @@ int32_t zp_stark_set_air_kernel(zp_ctx *ctx, const uint64_t *h_program, size_t p
 // values, proofs byte-identical either way.  fn = NULL forgets it.
 int32_t zp_stark_set_air_kernel_rows(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, void *quotient_rows_fn) {
     return set_air_kernel(ctx, "rows:", h_program, program_words, quotient_rows_fn);
+}
+
+// The WITNESS form of a generated constraint kernel (`zpair_<air>_quotient_witness` of the same library): the constraint check on the trace domain --
+// zp_stark_check_witness on this ctx and the one-call provers under "prove_check" -- runs it instead of the interpreter while "witness_kernel" is 1.
+// Same reports, word for word.  fn = NULL forgets it.
+int32_t zp_stark_set_air_kernel_witness(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, void *witness_fn) {
+    return set_air_kernel(ctx, "witness:", h_program, program_words, witness_fn);
+}
+
+// The verdict of the LAST proof zp_stark_prove / zp_stark_prove_bn128 checked on this ctx ("prove_check" = 1), accepted or refused: zp_stark_check_witness's
+// report layout, and the stage-2 challenge it was judged at (the transcript's; zeros without stage-2 arguments or when the trace was not canonical).
+int32_t zp_stark_prove_witness_report(zp_ctx *ctx, uint64_t *h_report, uint64_t *h_chal3, uint64_t *h_counts, uint64_t *h_first_row, int32_t n_constraints) {
+    if (!ctx) return ZP_ERR_ARG;
+    const zp_ctx::WitnessVerdict &v = ctx->last_witness;
+    ZP_ARG(ctx, v.valid, "no checked proof has run on this ctx");
+    ZP_ARG(ctx, h_report != nullptr, "null pointer");
+    ZP_ARG(ctx, n_constraints >= 0 && (size_t)n_constraints == v.counts.size(), "n_constraints is not the program's");
+    memcpy(h_report, v.rep, sizeof v.rep);
+    if (h_chal3) memcpy(h_chal3, v.chal, sizeof v.chal);
+    if (h_counts) memcpy(h_counts, v.counts.data(), v.counts.size() * 8);
+    if (h_first_row) memcpy(h_first_row, v.first_row.data(), v.first_row.size() * 8);
+    return ZP_OK;
 }
 
 // SHA-256 of a constraint program blob: the AIR digest.  out32 = the 32 digest bytes (a proof text names the first 8 as 16 hex digits);

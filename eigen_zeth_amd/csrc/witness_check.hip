@@ -122,43 +122,128 @@ __global__ void __launch_bounds__(256) witness_program_kernel(WProgArgs a) {
 
 }  // namespace
 
+// (1) the canonical pass over W * 2^logn words: *bad_n = words >= p, *bad_at = the index of the first in memory order (~0: none).  Synchronised.
+int32_t zpi_witness_canonical(zp_ctx *ctx, const u64 *d_trace, size_t total, u64 *bad_n, u64 *bad_at) {
+    ZP_ARG(ctx, (uintptr_t)d_trace % 8 == 0, "trace pointer not aligned");
+    void *poolv = nullptr;
+    ZP_TRY(zpi_pool_alloc(ctx, 16, &poolv));
+    struct Release { zp_ctx *c; void *p; ~Release() { zpi_pool_release(c, p, 16); } } release_{ctx, poolv};
+    ull *res = (ull *)poolv;
+    ZpStage stage_(ctx, "witness_canonical");
+    ZP_HIP(ctx, hipMemsetAsync(res, 0, 8, ctx->stream));
+    ZP_HIP(ctx, hipMemsetAsync(res + 1, 0xFF, 8, ctx->stream));
+    const u64 head = ((uintptr_t)d_trace % 16) ? 1 : 0, npairs = (total - head) / 2;
+    u64 blocks = (npairs + 255) / 256, cap = (u64)ctx->num_cu * 8;
+    blocks = blocks < 1 ? 1 : blocks > cap ? cap : blocks;
+    hipLaunchKernelGGL(witness_canonical_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_trace, (u64)total, head, npairs, res);
+    ZP_HIP(ctx, hipGetLastError());
+    u64 out[2];
+    ZP_TRY(zpi_d2h_small(ctx, out, res, 16));
+    *bad_n = out[0]; *bad_at = out[1];
+    return ZP_OK;
+}
+
+// the report of a trace with words >= p: the constraints are not evaluated
+void zpi_witness_noncanonical_report(size_t K, size_t N, u64 bad_n, u64 bad_at, uint64_t *h_report, uint64_t *h_counts, uint64_t *h_first_row) {
+    const u64 rep[8] = {ZP_WITNESS_NONCANONICAL, ~0ULL, ~0ULL, 0, 0, bad_n, bad_at / N, bad_at % N};
+    memcpy(h_report, rep, sizeof rep);
+    if (h_counts) memset(h_counts, 0, K * 8);
+    if (h_first_row) memset(h_first_row, 0xFF, K * 8);
+}
+
+// (3) the constraints over (trace, GIVEN stage-2 columns on the trace domain, publics then the challenge): one period of every sparse fixed column,
+// then either the generated kernel of this program (AIR plug-in ABI: `<symbol>_witness`, registered under the digest dg32 by
+// zp_stark_set_air_kernel_witness; knob "witness_kernel" = 1; stage "witness_program_gen") with [publics | challenge | 0] as its only upload, or
+// the interpreter over the uploaded program (stage "witness_program").  One result buffer [first key][first_row: K][counts: K], one download.
+// Both callers -- zp_stark_check_witness on a ctx and the one-call provers under "prove_check" -- come through here.  pubchal: publics, then the
+// challenge when the program has stage-2 arguments (a trailing pad word is ignored); dg32 = NULL: no kernel is looked up.
+int32_t zpi_witness_constraints(zp_ctx *ctx, const ZpProgram &pg, const uint8_t *dg32, const std::vector<u64> &pubchal, const u64 *d_trace, const u64 *d_s2,
+                                int logn, uint64_t *h_report, uint64_t *h_counts, uint64_t *h_first_row) {
+    ZP_BIND(ctx);
+    ZP_ARG(ctx, logn >= 1 && logn <= 30, "logn out of range");
+    for (const ZpFixedCol &fc : pg.fxc) ZP_ARG(ctx, fc.lp <= logn, "fixed column longer than the trace");
+    const size_t N = (size_t)1 << logn, K = pg.K, n_pc = pg.n_pub + pg.n_chal;
+    ZP_ARG(ctx, pubchal.size() >= n_pc, "publics and challenge shorter than the program's");
+    NttPlan *pl;
+    ZP_TRY(zpi_get_plan(ctx, logn, false, &pl));
+    void *plug = nullptr;
+    if (dg32 && ctx->tune_witness_kernel) {
+        auto it = ctx->air_kernels.find(zpi_air_kernel_key("witness:", dg32));
+        if (it != ctx->air_kernels.end()) plug = it->second;
+    }
+    const size_t res_words = 1 + 2 * K;
+    void *poolv = nullptr;
+    ZP_TRY(zpi_pool_alloc(ctx, res_words * 8, &poolv));
+    struct Release { zp_ctx *c; void *p; size_t b; ~Release() { zpi_pool_release(c, p, b); } } release_{ctx, poolv, res_words * 8};
+    ull *res = (ull *)poolv;
+    std::vector<u64> out(res_words);
+    {
+        ZpStage stage_(ctx, plug ? "witness_program_gen" : "witness_program");
+        ZP_HIP(ctx, hipMemsetAsync(res, 0xFF, (1 + K) * 8, ctx->stream));
+        ZP_HIP(ctx, hipMemsetAsync(res + 1 + K, 0, K * 8, ctx->stream));
+        u64 *d_periods = nullptr;
+        size_t period_words = 0;
+        ZP_TRY(zpi_fixed_periods_build(ctx, pg.words, pg.fxc, (const uint64_t *)pubchal.data(), 0, false, &d_periods, &period_words));
+        const u64 wlast = gl_inv(gl_root(ctx->root32, logn));
+        if (plug) {
+            std::vector<u64> ops(pubchal.begin(), pubchal.begin() + n_pc);
+            ops.push_back(0);                         // never empty
+            u64 *d_ops;
+            ZP_TRY(zpi_scratch(ctx, 3, ops.size(), &d_ops));
+            ZP_TRY(zpi_h2d(ctx, d_ops, ops.data(), ops.size() * 8));
+            const int hrc = ((zp_air_witness_fn)plug)((void *)ctx->stream, (const uint64_t *)d_trace, (const uint64_t *)(d_s2 ? d_s2 : d_trace),
+                                                      (const uint64_t *)(d_periods ? d_periods : d_ops), (const uint64_t *)d_ops, (const uint64_t *)pl->d_twl,
+                                                      (const uint64_t *)pl->d_twh, pl->lb, (uint64_t)N, wlast, (uint64_t *)res);
+            if (hrc != 0) {
+                ctx->err = "generated witness kernel: launch failed (hip error " + std::to_string(hrc) + ")";
+                return ZP_ERR_HIP;
+            }
+        } else {
+            // the upload comes after whatever made the stage-2 columns: those primitives use the same scratch slot
+            ZpProgramDev dv;
+            ZP_TRY(zpi_program_upload(ctx, pg, ZpSpan{pubchal.data(), n_pc}, {}, 0, &dv));
+            WProgArgs a;
+            a.prog = dv.consts - ZPH_WORDS; a.trace = d_trace; a.s2 = d_s2 ? d_s2 : d_trace; a.pub = dv.pubchal; a.fx_tab = dv.fx_tab; a.fixedx = d_periods;
+            a.xs_lo = pl->d_twl; a.xs_hi = pl->d_twh; a.lb = pl->lb;
+            a.first_key = res; a.first_row = res + 1; a.counts = res + 1 + K;
+            a.N = N; a.wlast = wlast;
+            a.W = (int)pg.W; a.n_const = (int)pg.n_const; a.n_instr = (int)pg.n_instr;
+            hipLaunchKernelGGL(witness_program_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), pg.slot_file() * 256 * 8, ctx->stream, a);
+            ZP_HIP(ctx, hipGetLastError());
+        }
+        ZP_TRY(zpi_d2h(ctx, out.data(), res, res_words * 8));
+    }
+    u64 rep[8] = {ZP_WITNESS_SATISFIED, ~0ULL, ~0ULL, 0, 0, 0, ~0ULL, ~0ULL};
+    const u64 *first = out.data() + 1, *counts = first + K;
+    for (size_t k = 0; k < K; k++) { rep[3] += counts[k]; rep[4] += counts[k] != 0; }
+    if (rep[3]) {
+        rep[0] = ZP_WITNESS_VIOLATED;
+        rep[1] = out[0] >> 24;
+        rep[2] = out[0] & 0xFFFFFF;
+    }
+    memcpy(h_report, rep, sizeof rep);
+    if (h_counts) memcpy(h_counts, counts, K * 8);
+    if (h_first_row) memcpy(h_first_row, first, K * 8);
+    return ZP_OK;
+}
+
+// zp_stark_check_witness on a ctx: (1), then (2) the stage-2 columns made HERE from the trace at the caller's challenge, then (3)
 int32_t zpi_witness_check_device(zp_ctx *ctx, const ZpProgram &pg, const std::vector<u64> &pubchal, const u64 *d_trace, int logn, uint64_t *h_report,
                                  uint64_t *h_counts, uint64_t *h_first_row) {
     ZP_BIND(ctx);
     ZP_ARG(ctx, logn <= 30, "logn out of range");
-    const size_t N = (size_t)1 << logn, K = pg.K, total = pg.W * N;
-    ZP_ARG(ctx, (uintptr_t)d_trace % 8 == 0, "trace pointer not aligned");
-    NttPlan *pl;
-    ZP_TRY(zpi_get_plan(ctx, logn, false, &pl));
-    // results, one buffer: [bad words][first bad word][first key][first_row: K][counts: K]; the stage-2 columns behind it
-    const size_t res_words = 3 + 2 * K, s2_words = pg.W2 * N, pool_bytes = (res_words + s2_words) * 8;
-    void *poolv = nullptr;
-    ZP_TRY(zpi_pool_alloc(ctx, pool_bytes, &poolv));
-    struct Release { zp_ctx *c; void *p; size_t b; ~Release() { zpi_pool_release(c, p, b); } } release_{ctx, poolv, pool_bytes};
-    ull *res = (ull *)poolv;
-    u64 *s2 = (u64 *)poolv + res_words;
-    u64 rep[8] = {ZP_WITNESS_SATISFIED, ~0ULL, ~0ULL, 0, 0, 0, ~0ULL, ~0ULL};
-    std::vector<u64> out(res_words);
-    {
-        ZpStage stage_(ctx, "witness_canonical");
-        ZP_HIP(ctx, hipMemsetAsync(res, 0, 8, ctx->stream));
-        ZP_HIP(ctx, hipMemsetAsync(res + 1, 0xFF, (2 + K) * 8, ctx->stream));
-        ZP_HIP(ctx, hipMemsetAsync(res + 3 + K, 0, K * 8, ctx->stream));
-        const u64 head = ((uintptr_t)d_trace % 16) ? 1 : 0, npairs = (total - head) / 2;
-        u64 blocks = (npairs + 255) / 256, cap = (u64)ctx->num_cu * 8;
-        blocks = blocks < 1 ? 1 : blocks > cap ? cap : blocks;
-        hipLaunchKernelGGL(witness_canonical_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, d_trace, (u64)total, head, npairs, res);
-        ZP_HIP(ctx, hipGetLastError());
-        ZP_TRY(zpi_d2h_small(ctx, out.data(), res, 16));
-    }
-    if (out[0] != 0) {
-        rep[0] = ZP_WITNESS_NONCANONICAL;
-        rep[5] = out[0]; rep[6] = out[1] / N; rep[7] = out[1] % N;
-        memcpy(h_report, rep, sizeof rep);
-        if (h_counts) memset(h_counts, 0, K * 8);
-        if (h_first_row) memset(h_first_row, 0xFF, K * 8);
+    const size_t N = (size_t)1 << logn;
+    u64 bad_n, bad_at;
+    ZP_TRY(zpi_witness_canonical(ctx, d_trace, pg.W * N, &bad_n, &bad_at));
+    if (bad_n != 0) {
+        zpi_witness_noncanonical_report(pg.K, N, bad_n, bad_at, h_report, h_counts, h_first_row);
         return ZP_OK;
     }
+    const size_t s2_bytes = (pg.W2 * N ? pg.W2 * N : 1) * 8;
+    void *s2v = nullptr;
+    ZP_TRY(zpi_pool_alloc(ctx, s2_bytes, &s2v));
+    struct Release { zp_ctx *c; void *p; size_t b; ~Release() { zpi_pool_release(c, p, b); } } release_{ctx, s2v, s2_bytes};
+    u64 *s2 = (u64 *)s2v;
     {
         ZpStage stage_(ctx, "witness_stage2");
         const uint64_t *g = (const uint64_t *)pubchal.data() + pg.n_pub;
@@ -175,31 +260,10 @@ int32_t zpi_witness_check_device(zp_ctx *ctx, const ZpProgram &pg, const std::ve
             }
         }
     }
-    ZpStage stage_(ctx, "witness_program");
-    u64 *d_periods = nullptr;
-    size_t period_words = 0;
-    ZP_TRY(zpi_fixed_periods_build(ctx, pg.words, pg.fxc, (const uint64_t *)pubchal.data(), 0, false, &d_periods, &period_words));
-    // the upload comes after the stage-2 primitives: they use the same scratch slot
-    ZpProgramDev dv;
-    ZP_TRY(zpi_program_upload(ctx, pg, ZpSpan{pubchal.data(), pubchal.size()}, {}, 0, &dv));
-    WProgArgs a;
-    a.prog = dv.consts - ZPH_WORDS; a.trace = d_trace; a.s2 = s2; a.pub = dv.pubchal; a.fx_tab = dv.fx_tab; a.fixedx = d_periods;
-    a.xs_lo = pl->d_twl; a.xs_hi = pl->d_twh; a.lb = pl->lb;
-    a.first_key = res + 2; a.first_row = res + 3; a.counts = res + 3 + K;
-    a.N = N; a.wlast = gl_inv(gl_root(ctx->root32, logn));
-    a.W = (int)pg.W; a.n_const = (int)pg.n_const; a.n_instr = (int)pg.n_instr;
-    hipLaunchKernelGGL(witness_program_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), pg.n_slots * 256 * 8, ctx->stream, a);
-    ZP_HIP(ctx, hipGetLastError());
-    ZP_TRY(zpi_d2h(ctx, out.data(), res, res_words * 8));
-    const u64 *first = out.data() + 3, *counts = first + K;
-    for (size_t k = 0; k < K; k++) { rep[3] += counts[k]; rep[4] += counts[k] != 0; }
-    if (rep[3]) {
-        rep[0] = ZP_WITNESS_VIOLATED;
-        rep[1] = out[2] >> 24;
-        rep[2] = out[2] & 0xFFFFFF;
-    }
-    memcpy(h_report, rep, sizeof rep);
-    if (h_counts) memcpy(h_counts, counts, K * 8);
-    if (h_first_row) memcpy(h_first_row, first, K * 8);
-    return ZP_OK;
+    // the digest names the kernel: one SHA-256 of the blob per call (a program of >= 2^14 words: one memcmp against the ctx's digest cache) -- paid only
+    // by a ctx that has a generated kernel registered and the knob on; the provers pass the digest their transcript needs anyway
+    uint8_t dg[32];
+    const bool lookup = ctx->tune_witness_kernel && !ctx->air_kernels.empty();
+    if (lookup) zpi_program_digest_cached(ctx, pg.words, pg.n_words, dg);
+    return zpi_witness_constraints(ctx, pg, lookup ? dg : nullptr, pubchal, d_trace, s2, logn, h_report, h_counts, h_first_row);
 }

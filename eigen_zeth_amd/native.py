@@ -74,6 +74,8 @@ SIGNATURES = {
     "zp_free_buffer": (C.c_int32, [_vp]),
     "zp_stark_set_air_kernel": (C.c_int32, [C.c_void_p, _u64p, C.c_size_t, C.c_void_p]),
     "zp_stark_set_air_kernel_rows": (C.c_int32, [C.c_void_p, _u64p, C.c_size_t, C.c_void_p]),
+    "zp_stark_set_air_kernel_witness": (C.c_int32, [C.c_void_p, _u64p, C.c_size_t, C.c_void_p]),
+    "zp_stark_prove_witness_report": (C.c_int32, [_vp, _u64p, _u64p, _u64p, _u64p, C.c_int32]),
     "zp_poseidon_sponge": (C.c_int32, [_vp, _u64p, _u64p, C.c_size_t, C.c_size_t, _u64p]),
     "zp_poseidon_sponge_caps": (C.c_int32, [_vp, _u64p, _u64p, C.c_size_t, C.c_size_t, _u64p, _u64p]),
     "zp_deep_quotient_rows": (C.c_int32, [_vp, _vp, C.c_int32, C.c_size_t, _vp, C.c_int32, C.c_size_t, C.c_int32, C.c_size_t, C.c_size_t, C.c_int32,
@@ -374,6 +376,7 @@ def program_eval_ext(program, pubchal, logn, root32, zeta, ev_z, ev_zw, threads=
 
 
 WITNESS_SATISFIED, WITNESS_VIOLATED, WITNESS_NONCANONICAL = range(3)
+ZP_ERR_WITNESS = -7     # zp_stark_prove / zp_stark_prove_bn128 under set_tuning("prove_check", 1): a false witness, no proof (include/zeth_prover.h)
 _NONE64 = (1 << 64) - 1
 
 
@@ -403,7 +406,8 @@ class WitnessReport:
 
 
 class WitnessError(ValueError):
-    """a trace that does not satisfy its constraint program was handed to a prover that checks first; .report: the WitnessReport"""
+    """a trace that does not satisfy its constraint program was handed to a prover that checks first; .report: the WitnessReport (.report.chal: the
+    stage-2 challenge it was judged at, when the check ran inside a proof)"""
 
     def __init__(self, report):
         super().__init__(str(report))
@@ -1297,13 +1301,31 @@ class Prover:
         prog = np.ascontiguousarray(np.asarray(program, dtype=np.uint64))
         pb = np.ascontiguousarray(np.asarray(list(pubs) + [0], dtype=np.uint64))
         out, n = C.c_void_p(), C.c_size_t(0)
-        self._chk(self.lib.zp_stark_prove(self.ctx, air_name.encode(), prog.ctypes.data, prog.size, _ptr(d_trace), self._words(d_trace, prog, logn),
-                                          pb.ctypes.data, len(pubs),
-                                          logn, logb, fri_logf, fri_final_log, n_queries, pow_bits, C.byref(out), C.byref(n)))
+        self._chk_proof(self.lib.zp_stark_prove(self.ctx, air_name.encode(), prog.ctypes.data, prog.size, _ptr(d_trace), self._words(d_trace, prog, logn),
+                                                pb.ctypes.data, len(pubs),
+                                                logn, logb, fri_logf, fri_final_log, n_queries, pow_bits, C.byref(out), C.byref(n)), prog)
         try:
             return C.string_at(out.value, n.value).decode()
         finally:
             self.lib.zp_free_buffer(out)
+
+    def _chk_proof(self, rc, prog):
+        """a one-call prover's return code: ZP_ERR_WITNESS ("prove_check") becomes WitnessError with the report attached"""
+        if rc == ZP_ERR_WITNESS:
+            raise WitnessError(self.prove_witness_report(int(prog[8])))      # its line is zp_last_error's (compared in tests/test_gpu_witness_inproof.py)
+        self._chk(rc)
+
+    def prove_witness_report(self, n_constraints):
+        """zp_stark_prove_witness_report: the WitnessReport of the last proof this ctx checked under set_tuning("prove_check", 1), accepted or refused;
+        .chal = the stage-2 challenge it was judged at (the proof's own; zeros without stage 2)"""
+        K = int(n_constraints)
+        rep, chal = np.zeros(8, dtype=np.uint64), np.zeros(3, dtype=np.uint64)
+        counts, first = np.zeros(max(K, 1), dtype=np.uint64), np.zeros(max(K, 1), dtype=np.uint64)
+        p = lambda a: a.ctypes.data_as(_u64p)
+        self._chk(self.lib.zp_stark_prove_witness_report(self.ctx, p(rep), p(chal), p(counts), p(first), K))
+        out = WitnessReport(rep, counts[:K], first[:K])
+        out.chal = [int(v) for v in chal]
+        return out
 
     def check_witness(self, program, d_trace, pubs, logn, chal=None):
         """zp_stark_check_witness on this ctx: the device trace u64[W][2^logn] (only read) against the program -> WitnessReport"""
@@ -1319,9 +1341,9 @@ class Prover:
         prog = np.ascontiguousarray(np.asarray(program, dtype=np.uint64))
         pb = np.ascontiguousarray(np.asarray(list(pubs) + [0], dtype=np.uint64))
         out, n = C.c_void_p(), C.c_size_t(0)
-        self._chk(self.lib.zp_stark_prove_bn128(self.ctx, air_name.encode(), prog.ctypes.data, prog.size, _ptr(d_trace),
-                                                self._words(d_trace, prog, logn), pb.ctypes.data, len(pubs),
-                                                logn, logb, fri_logf, fri_final_log, n_queries, C.byref(out), C.byref(n)))
+        self._chk_proof(self.lib.zp_stark_prove_bn128(self.ctx, air_name.encode(), prog.ctypes.data, prog.size, _ptr(d_trace),
+                                                      self._words(d_trace, prog, logn), pb.ctypes.data, len(pubs),
+                                                      logn, logb, fri_logf, fri_final_log, n_queries, C.byref(out), C.byref(n)), prog)
         try:
             return C.string_at(out.value, n.value).decode()
         finally:
@@ -1486,6 +1508,13 @@ class Prover:
         blob = np.ascontiguousarray(program, dtype=np.uint64)
         addr = C.cast(fn, C.c_void_p).value if fn is not None else None
         self._chk(self.lib.zp_stark_set_air_kernel_rows(self.ctx, blob.ctypes.data_as(_u64p), blob.size, addr))
+
+    def set_air_kernel_witness(self, program, fn):
+        """zp_stark_set_air_kernel_witness: the witness form of the generated constraint kernel (`<symbol>_witness`), for check_witness on this ctx and
+        for the one-call provers under set_tuning("prove_check", 1); set_tuning("witness_kernel", 0) keeps the interpreter"""
+        blob = np.ascontiguousarray(program, dtype=np.uint64)
+        addr = C.cast(fn, C.c_void_p).value if fn is not None else None
+        self._chk(self.lib.zp_stark_set_air_kernel_witness(self.ctx, blob.ctypes.data_as(_u64p), blob.size, addr))
 
     def stark_openings(self):
         """zp_stark_openings: the binary openings of the last BN128-mode proof of this ctx (a copy)"""

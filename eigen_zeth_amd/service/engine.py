@@ -84,6 +84,10 @@ class EngineConfig:
         # program (zp_stark_check_witness: on the proving backend's GPU where it can, on the host otherwise; "witness_check" in the stage timings).
         # A trace that violates its AIR raises WitnessError with the first failing constraint and row, and no proof is made of it -- instead of a
         # well-formed text that no verifier accepts.  Off by default: no extra call, launch, byte or timing.  What it costs: DESIGN.md par.5.
+        # check_witness="prove": the check runs INSIDE the one-call provers instead (zp_set_tuning "prove_check" on the backends' contexts: canonical
+        # words, then the constraints at the proof's own stage-2 challenge, on the stage-2 columns the proof makes anyway); a refusal (ZP_ERR_WITNESS)
+        # is the same WitnessError.  A proof that does not go through a one-call prover of a single ctx (the Python orchestration, the sharded final
+        # STARK) is checked by the separate call as under True.
         self.check_witness = check_witness
         # GenFinalProof: run the native Groth16 verifier (zp_groth16_verify) on the proof about to be returned and raise unless it is accepted
         # ("groth16/verify" in the stage clock).  Off by default: no response and no timing changes.
@@ -285,6 +289,13 @@ class Engine:
                 trace.free()
             raise WitnessError(report)
 
+    def _check_in_proof(self, be, sharded=False):
+        """cfg.check_witness == "prove": True when the proof about to be made on `be` checks its own trace (the knob is set on its ctx)"""
+        if self.cfg.check_witness != "prove" or sharded or not (self.cfg.native_prover and hasattr(be, "prove_native") and hasattr(be, "p")):
+            return False
+        be.p.set_tuning("prove_check", 1)
+        return True
+
     @staticmethod
     def _chunk_witness(air, ch, out=None):
         """the witness of one chunk: the synthetic generator (stand-in for the zkVM executor) started from the statement limbs"""
@@ -410,7 +421,7 @@ class Engine:
             try:
                 tm = {"witness(%s)" % where: tw}
                 params = self.stark_params(ch["logn"])
-                if self.cfg.check_witness:
+                if self.cfg.check_witness and not self._check_in_proof(be):
                     self._check_witness(be, air, trace, pubs, tm)
                 if self.cfg.native_prover and hasattr(be, "prove_native"):
                     # one C-ABI call per chunk (zp_stark_prove): the orchestration runs in the library, Python only frames the result
@@ -569,11 +580,12 @@ class Engine:
         timings["verifier-witness"] = time.perf_counter() - t0
         self._last_verifier_pubs = pubs                 # the public inputs of the STARK made next (GenFinalProof's wrap needs the final STARK's)
         params = params_of(shape)
-        if self.cfg.check_witness:
+        sharded = self.cfg.native_prover and self.cfg.final_ranks > 1 and params.hash == "bn128" and hasattr(be, "prove_native_sharded")
+        if self.cfg.check_witness and not self._check_in_proof(be, sharded):
             self._check_witness(be, vair, trace, pubs, timings)
         t0 = time.perf_counter()
         self._sharded_openings = None
-        if self.cfg.native_prover and self.cfg.final_ranks > 1 and params.hash == "bn128" and hasattr(be, "prove_native_sharded"):
+        if sharded:
             text, self._sharded_openings = be.prove_native_sharded(vair, trace, pubs, params, self.cfg.final_ranks, self.cfg.final_devices)
         elif self.cfg.native_prover and hasattr(be, "prove_native"):
             text = be.prove_native(vair, trace, pubs, params)

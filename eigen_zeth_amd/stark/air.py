@@ -504,3 +504,77 @@ def emit_quotient_source(air, target="hip"):
             + 'extern "C" int %s_rows(void *stream, const u64 *cols, u64 sc, const u64 *fixedc, u64 sf, u64 M, u64 b, u64 row0, u64 nrows, %s, u64 so) {\n'
             % (air.symbol, tail.replace("__restrict__ ", ""))
             + launch % (air.symbol, "nrows", "sc", "sf", "row0", "nrows", "so"))
+
+
+class _WitnessEmitter(_Emitter):
+    """the same straight-line code on the TRACE domain: a column or a fixed column is loaded where it is first named (a constraint's operands
+    are live from there on, not from the top of the kernel), a sparse fixed column from its one period"""
+
+    def __init__(self, air):
+        super().__init__(air.n_pub)
+        self.width = air.width
+        self.periods, acc = {}, 0          # zpi_fixed_periods_build without selectors: one period behind the other
+        for k, fc in enumerate(air.fixed_cols):
+            self.periods[2 + k] = (acc, (1 << fc.lp) - 1)
+            acc += 1 << fc.lp
+
+    def emit(self, e):
+        if isinstance(e, (Col, Fixed)) and e.key() not in self.memo:
+            if isinstance(e, Col):
+                base, i = ("trace", e.i) if e.i < self.width else ("s2", e.i - self.width)
+                self.lines.append("    const u64 c%d%s = %s[(u64)%d * N + %s];" % (e.i, "n" if e.nxt else "", base, i, "rn" if e.nxt else "rr"))
+            elif isinstance(e, Fixed):
+                if e.i < 2:
+                    self.lines.append("    const u64 f%d = rr == %s;" % (e.i, "0" if e.i == 0 else "N - 1"))
+                else:
+                    self.lines.append("    const u64 f%d = fixedx[%dULL + (rr & %dULL)];" % ((e.i,) + self.periods[e.i]))
+        return super().emit(e)
+
+
+def emit_witness_source(air):
+    """device kernel + host launcher exported as air.symbol + "_witness": the constraints on the TRACE domain (lane = row r < N, next row
+    (r + 1) & (N - 1), columns >= W from the stage-2 base, selectors from r, sparse fixed columns from one period each, x - w^(N-1) from the
+    two-level table), reported as csrc/witness_check.hip's interpreter reports them -- res = [first (row << 24 | k) key][first_row: K][counts: K],
+    one lane per violated (wave, constraint) adds the ballot's popcount and lowers the two minima; an honest trace issues no atomic.  The body is
+    one template: the plain instance ORs the constraint values into a word, the reporting instance (a function of its own, not inlined) is entered
+    by WHOLE waves on the ballot of that word (its per-constraint ballots need every live lane of the wave).  Appended to emit_quotient_source's text in generated/<air>.hip."""
+    em = _WitnessEmitter(air)
+    K = len(air.constraints)
+    for k, c in enumerate(air.constraints):
+        o = em.emit(c)
+        em.lines.append("    if (REPORT) zpw_report(res, %d, %d, %s, live, r); else any |= %s;" % (K, k, o, o))
+    sym = air.symbol + "_witness"
+    ops = ("const u64 *__restrict__ trace, const u64 *__restrict__ s2, const u64 *__restrict__ fixedx, const u64 *__restrict__ pub, u64 N, "
+           "u64 r, u64 rr, u64 rn, u64 xml, bool live, unsigned long long *res")
+    kargs = ("const u64 *__restrict__ trace, const u64 *__restrict__ s2, const u64 *__restrict__ fixedx, const u64 *__restrict__ pub, "
+             "const u64 *__restrict__ xs_lo, const u64 *__restrict__ xs_hi, int lb, u64 N, u64 wlast, unsigned long long *res")
+    return ("// generated by eigen_zeth_amd/stark/air.py for AIR '%s' (digest %s) -- do not edit\n"
+            "// row-parallel constraint CHECK on the trace domain: lane = trace row, %d constraints, result [first key][first_row: K][counts: K].\n"
+            % (air.name, air.digest(), K)
+            + "#ifndef ZPW_REPORT\n#define ZPW_REPORT\n"
+            "__device__ __forceinline__ void zpw_report(unsigned long long *res, int K, int k, u64 v, bool live, u64 r) {\n"
+            "    const unsigned long long m = __ballot(live && v != 0);      // wave-uniform\n"
+            "    if (m != 0 && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) {     // the lowest violating lane: its row is the wave's smallest\n"
+            "        atomicAdd(&res[1 + K + k], (unsigned long long)__popcll(m));\n"
+            "        atomicMin(&res[1 + k], (unsigned long long)r);\n"
+            "        atomicMin(&res[0], ((unsigned long long)r << 24) | (unsigned long long)k);\n"
+            "    }\n}\n#endif\n"
+            + "template <bool REPORT>\n__device__ __forceinline__ u64 %s_body(%s) {\n    u64 any = 0;\n%s\n    return any;\n}\n"
+            % (sym, ops, "\n".join(em.lines))
+            # the reporting instance stays OUT of line: inlined next to the plain one the compiler keeps every constraint value of the first walk
+            # alive for the second (chunk64: 256 VGPRs + 87 AGPRs, one wave per SIMD; out of line 134 VGPRs, three)
+            + "__device__ __noinline__ void %s_report(%s) {\n    (void)%s_body<true>(trace, s2, fixedx, pub, N, r, rr, rn, xml, live, res);\n}\n"
+            % (sym, ops, sym)
+            + "__global__ void __launch_bounds__(256) %s_kernel(%s) {\n" % (sym, kargs)
+            + "    const u64 r = (u64)blockIdx.x * 256 + threadIdx.x;\n"
+            "    const bool live = r < N;\n"
+            "    const u64 rr = live ? r : 0;          // a dead lane (N < 256) walks row 0: in bounds, masked out of every ballot\n"
+            "    const u64 rn = (rr + 1) & (N - 1);\n"
+            "    const u64 xml = gl_sub(gl_mul(xs_lo[rr & ((1ULL << lb) - 1)], xs_hi[rr >> lb]), wlast);\n"
+            + "    const u64 any = %s_body<false>(trace, s2, fixedx, pub, N, r, rr, rn, xml, live, res);\n" % sym
+            + "    if (__ballot(live && any != 0) == 0) return;          // whole waves: an honest trace ends here, no atomic issued\n"
+            + "    %s_report(trace, s2, fixedx, pub, N, r, rr, rn, xml, live, res);\n}\n" % sym
+            + 'extern "C" int %s(void *stream, %s) {\n' % (sym, kargs.replace("__restrict__ ", ""))
+            + "    hipLaunchKernelGGL(%s_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,\n" % sym
+            + "                       trace, s2, fixedx, pub, xs_lo, xs_hi, lb, N, wlast, res);\n"
+            "    return (int)hipGetLastError();\n}\n")

@@ -187,10 +187,8 @@ class HipBackend:
         """the binary openings of the last BN128-mode proof prove_native made on this backend (zp_stark_openings)"""
         return self.p.stark_openings()
 
-    def prove_native(self, air, trace, pubs, params):
-        """the whole chunk STARK through zp_stark_prove (one C-ABI call, orchestration in the library's host C++): proof TEXT,
-        byte-identical to proof_to_json(prove(...)) over this backend.  trace: host array or a device buffer from prefetch_trace."""
-        assert self.hash_mode == params.hash
+    def _register_kernels(self, air):
+        """hand the ctx the AIR's generated kernels -- the quotient for the one-call prover, the witness form for the check -- once per AIR"""
         kkey = (air.name, air.digest())
         if self.quotient_mode == "kernel" and kkey not in self._native_kernels and (not air.fixed_cols or os.path.exists(build_airs.lib_path(air))):
             # the one-call prover evaluates this AIR's constraints through its generated kernel too (zp_stark_set_air_kernel); a host without the
@@ -199,9 +197,16 @@ class HipBackend:
             # (compile_air_kernel: the service's prewarm does, for the two recursion programs it will prove)
             try:
                 self.p.set_air_kernel(air.program(), self._airlib(air))
+                self.p.set_air_kernel_witness(air.program(), self._airlib_witness(air))
             except (OSError, RuntimeError, AttributeError, subprocess.CalledProcessError):
                 pass
             self._native_kernels.add(kkey)
+
+    def prove_native(self, air, trace, pubs, params):
+        """the whole chunk STARK through zp_stark_prove (one C-ABI call, orchestration in the library's host C++): proof TEXT,
+        byte-identical to proof_to_json(prove(...)) over this backend.  trace: host array or a device buffer from prefetch_trace."""
+        assert self.hash_mode == params.hash
+        self._register_kernels(air)
         d_tr = trace if isinstance(trace, native.DeviceBuffer) else self.p.upload(trace)
         try:
             if self.hash_mode == "bn128":       # zp_stark_prove_bn128: 16-ary Poseidon-BN254 trees, transcript over F_r, no grinding
@@ -214,8 +219,11 @@ class HipBackend:
 
     def check_witness(self, air, trace, pubs):
         """zp_stark_check_witness on this backend's GPU: does the trace (host array, uploaded for the check, or a device buffer from prefetch_trace,
-        only read) satisfy the AIR's program -> native.WitnessReport.  The stage-2 challenge is derived from the program: it finds mistakes"""
+        only read) satisfy the AIR's program -> native.WitnessReport.  The stage-2 challenge is derived from the program: it finds mistakes.
+        Registers the AIR's generated kernels on the ctx first (_register_kernels: the witness form this check runs, and with it the quotient
+        kernel the proof that follows would have registered anyway)"""
         logn = int(trace.shape[-1]).bit_length() - 1
+        self._register_kernels(air)
         d_tr = trace if isinstance(trace, native.DeviceBuffer) else self.p.upload(trace)
         try:
             return self.p.check_witness(air.program(), d_tr, [int(v) for v in pubs], logn)
@@ -452,21 +460,29 @@ class HipBackend:
             self._airlibs[k] = fn
         return self._airlibs[k]
 
-    def _airlib_rows(self, air):
-        """the row-window entry point of the AIR's generated library (one kernel, two launchers: stark/air.py emit_quotient_source)"""
-        k = (air.name, air.digest(), "rows")
+    def _airlib_form(self, air, form):
+        """another entry point of the AIR's generated library: "rows" = the quotient's row window, "witness" = the constraint check on the trace
+        domain (one library, three symbols: stark/air.py emit_quotient_source + emit_witness_source)"""
+        k = (air.name, air.digest(), form)
         if k not in self._airlibs:
             lib = C.CDLL(build_airs.build_air(air))
-            fn = getattr(lib, air.symbol + "_rows")
+            fn = getattr(lib, air.symbol + "_" + form)
             fn.restype = C.c_int
             self._airlibs[k] = fn
         return self._airlibs[k]
+
+    def _airlib_rows(self, air):
+        return self._airlib_form(air, "rows")
+
+    def _airlib_witness(self, air):
+        return self._airlib_form(air, "witness")
 
     def compile_air_kernel(self, air):
         """generate, compile (hipcc: seconds to a minute for a verifier AIR) and load the constraint kernel of `air` and hand it to the one-call
         prover of this ctx; returns False on a host without a compiler (the interpreter then serves: same proofs)"""
         try:
             self.p.set_air_kernel(air.program(), self._airlib(air))
+            self.p.set_air_kernel_witness(air.program(), self._airlib_witness(air))
             self._native_kernels.add((air.name, air.digest()))
             return True
         except (OSError, RuntimeError, AttributeError, subprocess.CalledProcessError):

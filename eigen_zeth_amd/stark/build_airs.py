@@ -19,10 +19,10 @@ def lib_path(air):
 
 
 def build_air(air, force=False):
-    from .air import emit_quotient_source
+    from .air import emit_quotient_source, emit_witness_source
     os.makedirs(GEN, exist_ok=True)
     src = os.path.join(GEN, _stem(air) + ".hip")
-    code = emit_quotient_source(air, "hip")
+    code = emit_quotient_source(air, "hip") + emit_witness_source(air)      # one library, three symbols: <symbol>, <symbol>_rows, <symbol>_witness
     if force or not os.path.exists(src) or open(src).read() != code:
         with open(src, "w") as f:
             f.write(code)

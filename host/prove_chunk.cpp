@@ -12,6 +12,9 @@
 //   process; on the host for a sharded run, where no rank holds all columns -- and prints the report as ONE JSON line
 //   {"witness_check":{"verdict":..,"first_row":..,"first_constraint":..,"violations":..,"violated_constraints":..,"noncanonical":..,
 //   "first_noncanonical":[column,row]}} (null where the report says none); a trace that is not satisfied ends the run with exit status 3, unproven.
+//   --check-prove (one process only): the check runs INSIDE the proof instead (zp_set_tuning "prove_check": canonical words, then the constraints at
+//   the proof's own stage-2 challenge); the same JSON line (zp_stark_prove_witness_report) in front of the result, and a refusal (ZP_ERR_WITNESS)
+//   ends the run with exit status 3, unproven.
 //   program.bin : the constraint program blob (u64 words, layout in the header)
 //   trace.bin   : u64[W][2^logn] column-major, canonical values
 //   publics.bin : u64[n_pub]
@@ -59,11 +62,12 @@ static bool print_report(const uint64_t *r) {
 }
 
 int main(int argc, char **argv) {
-    bool check = false;
+    bool check = false, check_prove = false;
     {
         int n = 1;
         for (int i = 1; i < argc; i++) {
             if (strcmp(argv[i], "--check") == 0) check = true;
+            else if (strcmp(argv[i], "--check-prove") == 0) check_prove = true;
             else argv[n++] = argv[i];
         }
         argc = n;
@@ -86,8 +90,9 @@ int main(int argc, char **argv) {
     }
     if (pubs.size() != prog_n_pub) { fprintf(stderr, "%s: %zu public inputs, the program declares %llu\n", argv[3], pubs.size(), (unsigned long long)prog_n_pub); return 2; }
     for (uint64_t v : trace)
-        if (!check && v >= 0xFFFFFFFF00000001ULL) { fprintf(stderr, "%s: non-canonical trace value (precondition of zp_stark_prove)\n", argv[2]); return 2; }
+        if (!check && !check_prove && v >= 0xFFFFFFFF00000001ULL) { fprintf(stderr, "%s: non-canonical trace value (precondition of zp_stark_prove)\n", argv[2]); return 2; }
     if (world < 1 || rank < 0 || rank >= world) { fprintf(stderr, "bad rank / world\n"); return 2; }
+    if (check_prove && sharded) { fprintf(stderr, "--check-prove: the sharded provers do not check their trace; use --check\n"); return 2; }
     zp_ctx *ctx = nullptr;
     uint64_t report[8];
     if (check && sharded) {                            // every rank reads the whole file: each judges it on the host and they agree
@@ -129,6 +134,17 @@ int main(int argc, char **argv) {
         if (rank == 0) zp_rendezvous::retire(argv[14]);
         CHECK(zp_stark_prove_sharded(comm, air_name, program.data(), program.size(), (const uint64_t *)d_trace, words, pubs.data(), (int32_t)pubs.size(), logn,
                                      logb, fri_logf, fri_final_log, n_queries, pow_bits, &json, &len));
+    } else if (check_prove) {
+        CHECK(zp_set_tuning(ctx, "prove_check", 1));
+        const int32_t rc = zp_stark_prove(ctx, air_name, program.data(), program.size(), (const uint64_t *)d_trace, trace.size(), pubs.data(), (int32_t)pubs.size(),
+                                          logn, logb, fri_logf, fri_final_log, n_queries, pow_bits, &json, &len);
+        if (rc != 0 && rc != ZP_ERR_WITNESS) { fprintf(stderr, "zp_stark_prove -> %d: %s\n", rc, zp_last_error(ctx)); return 1; }
+        CHECK(zp_stark_prove_witness_report(ctx, report, nullptr, nullptr, nullptr, (int32_t)program[8]));
+        if (!print_report(report) || rc != 0) {
+            zp_dev_free(ctx, d_trace);
+            zp_destroy(ctx);
+            return 3;
+        }
     } else {
         CHECK(zp_stark_prove(ctx, air_name, program.data(), program.size(), (const uint64_t *)d_trace, trace.size(), pubs.data(), (int32_t)pubs.size(), logn, logb,
                              fri_logf, fri_final_log, n_queries, pow_bits, &json, &len));

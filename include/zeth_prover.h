@@ -42,7 +42,8 @@ enum {
     ZP_ERR_NOMEM = -3,   /* device allocation failed */
     ZP_ERR_UNSUPPORTED = -4,
     ZP_ERR_INTERNAL = -5, /* an internal failure that is not the caller's (never an exception: nothing unwinds across this ABI) */
-    ZP_ERR_COMM = -6      /* the communicator is dead: a peer rank failed, aborted or did not reach a collective within the timeout */
+    ZP_ERR_COMM = -6,     /* the communicator is dead: a peer rank failed, aborted or did not reach a collective within the timeout */
+    ZP_ERR_WITNESS = -7   /* zp_stark_prove / zp_stark_prove_bn128 under "prove_check": the trace violates its program or holds a word >= p; no proof was made */
 };
 
 /* kinds for zp_set_constants */
@@ -187,8 +188,18 @@ int32_t zp_qap_quotient_bn254(zp_ctx *ctx, uint64_t *d_a, uint64_t *d_b, uint64_
  * byte-identical to what the Python orchestration (eigen_zeth_amd/stark/prover.py) writes for the same inputs and is what
  * oracle/stark_verify.py checks.  Conjectured security = n_queries * logb + pow_bits bits.  air_name only labels the proof.
  * trace_words = the number of u64 words behind d_trace; it must equal W * 2^logn with W from the program header (a short
- * buffer or a wrong logn is ZP_ERR_ARG instead of a read past the allocation).  PRECONDITION: trace values are canonical
- * (< p); they are not checked (a full pass over the witness) and non-canonical words give an unspecified, rejected proof.
+ * buffer or a wrong logn is ZP_ERR_ARG instead of a read past the allocation).  PRECONDITION, with "prove_check" = 0 (zp_set_tuning;
+ * the default): trace values are canonical (< p) and satisfy the program; neither is checked, non-canonical words give an
+ * unspecified, rejected proof and a violated constraint a well-formed text no verifier accepts.  With "prove_check" = 1 both are
+ * checked INSIDE the proof and the precondition is gone: one streaming pass over the caller's trace before anything else touches it,
+ * then the constraints on the trace domain (zp_stark_check_witness's semantics and report) as soon as their operands exist -- without
+ * stage-2 arguments before the first extension, with them on the stage-2 columns the proof itself made at the transcript's
+ * challenge (the one that binds), before their extension and commitment.  A satisfied trace yields exactly the text of
+ * "prove_check" = 0.  A violated or non-canonical one ends the call with ZP_ERR_WITNESS: no text, nothing launched after the point of
+ * refusal, zp_last_error names the first constraint and row (or the first non-canonical column and row), the ctx stays usable and
+ * zp_stark_prove_witness_report hands out the whole report.  The program must then also meet the interpreter's limits (at most 32
+ * slots, canonical constants: ZP_ERR_ARG otherwise).  The sharded provers do NOT read the knob: their trace is column-sharded and a row
+ * check would need one more exchange.
  * On any error *out_json = NULL, *out_len = 0; no C++ exception leaves the call (ZP_ERR_NOMEM / ZP_ERR_INTERNAL).          */
 int32_t zp_stark_prove(zp_ctx *ctx, const char *air_name, const uint64_t *h_program, size_t program_words, const uint64_t *d_trace,
                        size_t trace_words, const uint64_t *h_pubs, int32_t n_pubs, int32_t logn, int32_t logb, int32_t fri_logf,
@@ -208,6 +219,16 @@ int32_t zp_stark_set_air_kernel(zp_ctx *ctx, const uint64_t *h_program, size_t p
  * first row, b halo rows behind every column unless the window is the whole domain): int fn(stream, cols, stride_cols, fixed, stride_fixed, M, b,
  * row0, nrows, pub, apow, zhinv, xs_lo, xs_hi, lb, shift, wlast, out, stride_out).  Proof bytes are the same with the kernel or the interpreter. */
 int32_t zp_stark_set_air_kernel_rows(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, void *quotient_rows_fn);
+/* the same for the constraint CHECK on the trace domain (zp_stark_check_witness on this ctx, the one-call provers under "prove_check"):
+ * `zpair_<air>_quotient_witness` of the same library (zp_air_witness_fn below) runs instead of the interpreter while "witness_kernel" is 1 (zp_set_tuning;
+ * 0: always the interpreter).  Reports are the same word for word; the stage clock names the two forms "witness_program_gen" / "witness_program". */
+int32_t zp_stark_set_air_kernel_witness(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, void *witness_fn);
+/* The report of the LAST proof zp_stark_prove / zp_stark_prove_bn128 checked on this ctx ("prove_check" = 1), accepted or refused, in
+ * zp_stark_check_witness's layout: h_report[8], h_counts[K] / h_first_row[K] (or NULL); h_chal3 (or NULL) = the stage-2 challenge it was judged at --
+ * the proof's own Fiat-Shamir challenge; zeros for a program without stage-2 arguments or a non-canonical trace.  ZP_ERR_ARG when no checked proof has
+ * run on the ctx or n_constraints != K. */
+int32_t zp_stark_prove_witness_report(zp_ctx *ctx, uint64_t *h_report /* [8] */, uint64_t *h_chal3 /* [3] or NULL */, uint64_t *h_counts /* [K] or NULL */,
+                                      uint64_t *h_first_row /* [K] or NULL */, int32_t n_constraints);
 /* the AIR digest of a constraint program blob (host code, no ctx): SHA-256, out32 = the digest bytes (a proof's "air_digest" is the hex of the
  * first 8), out_words4 (or NULL) = the four 64-bit words (little-endian, mod p) a prover absorbs into its transcript and a verifier-AIR
  * witness builder needs for the inner proofs' statement (zp_recursion_witness: the head of the transcript stream). */
@@ -334,7 +355,14 @@ int32_t zp_merkle_open_batch(zp_ctx *ctx, const uint64_t *d_tree, size_t M, cons
  *        u64 row0, u64 nrows, const u64 *d_pub, const u64 *d_alpha_pows, const u64 *d_zhinv, const u64 *d_xs_lo, const u64 *d_xs_hi, int lb,
  *        u64 shift, u64 w_last, u64 *d_out, u64 stride_out);
  *   rows [row0, row0 + nrows) of the M-row domain; unless nrows == M every column carries the window's blowup halo rows behind it.
+ *   and the constraint CHECK on the trace domain (no extension): int zpair_<air>_quotient_witness(void *hip_stream, const u64 *d_trace,
+ *        const u64 *d_stage2, const u64 *d_fixed_periods, const u64 *d_pub, const u64 *d_xs_lo, const u64 *d_xs_hi, int lb, u64 N, u64 w_last, u64 *d_res);
+ *   lane = row r < N; d_trace [W][N], d_stage2 [W2][N] (columns >= W), d_fixed_periods = one period of every sparse fixed column, one behind the
+ *   other; d_pub = publics then the challenge; w_N^r = lo[r & mask] * hi[r >> lb]; d_res [1 + 2K] = [first (row << 24 | k)][first_row: K][counts: K],
+ *   pre-set by the caller to ~0 / ~0 / 0 and written only for violated constraints.
  * zp_domain_tables hands such kernels the ctx-owned two-level table of w_M^e (x = shift*lo[e&mask]*hi[e>>lb]). */
+typedef int (*zp_air_witness_fn)(void *hip_stream, const uint64_t *d_trace, const uint64_t *d_stage2, const uint64_t *d_fixed_periods, const uint64_t *d_pub,
+                                 const uint64_t *d_xs_lo, const uint64_t *d_xs_hi, int lb, uint64_t N, uint64_t w_last, uint64_t *d_res);
 int32_t zp_domain_tables(zp_ctx *ctx, int32_t logm, const uint64_t **d_lo, const uint64_t **d_hi, int32_t *lb);
 /* ---- N4 as data: the constraint program ----------------------------------------------------------------
  * An AIR handed over as a u64 blob instead of a generated kernel (a host without hipcc at run time can still
@@ -739,7 +767,10 @@ int32_t zp_hbm_copy_probe(zp_ctx *ctx, const void *d_src, void *d_dst, size_t by
  * "verify16_lane_min" hash jobs per call from which the BN128-mode verifier hashes one job per lane (0 = 2^14: a guess, unmeasured); 0 = default;
  * "verify_chain_dev" the verifier's transcripts as one sponge-chain launch per call: 0 never, 1 default (today: never), 2 always (other values: ZP_ERR_ARG);
  * "fixed_eval_dev_min" (points x sparse entries) from which zp_program_fixed_eval_ext_batch uses the device -- the VALUE is the bound: 0 always the
- * device, < 0 restores the default 2^15 (derived from profiles/r12_fixed_eval_batch.json, not measured at that size)); not for production hosts */
+ * device, < 0 restores the default 2^15 (derived from profiles/r12_fixed_eval_batch.json, not measured at that size));
+ * "witness_kernel" 1 (default): the constraint check runs a registered generated witness kernel, 0: always the interpreter; "prove_check" 1: the one-call
+ * provers check their trace inside the proof and refuse a false witness with ZP_ERR_WITNESS (0, the default: they prove whatever they are handed);
+ * not for production hosts */
 int32_t zp_set_tuning(zp_ctx *ctx, const char *key, int32_t value);
 
 /* ---- introspection ------------------------------------------------------------------------- */
