@@ -22,6 +22,7 @@
 #include "wave_xchg.hpp"
 #include "gl_asm.hpp"
 #include "gl_limb.hpp"
+#include "ntt_geo.hpp"
 
 // the data of a pass is touched exactly once: non-temporal loads/stores (measured +1 % on the 2^24 bench, same results)
 #define ZP_LDG(p) __builtin_nontemporal_load(p)
@@ -32,6 +33,15 @@ namespace {
 typedef __attribute__((ext_vector_type(4))) int zp_i32x4;
 typedef __attribute__((address_space(1))) u64 zp_gu64;     // global memory, said so: an address that went through sgpr_opaque has lost what the compiler inferred
 typedef __attribute__((address_space(1))) char zp_gchar;
+typedef __attribute__((address_space(3))) u64 zp_lu64;
+
+// A word of the tile by its LDS byte address.  ntt_pass2_kernel and lde_seam_kernel declare no static LDS, so their dynamic segment -- `lds`, the
+// tile first -- starts at LDS address 0 (group_segment_fixed_size 0; the compiler itself adds that 0 to every `lds[i]`, after the point where it
+// could fold it).  The factored slot addresses of ntt_geo.hpp are XORs of bit fields: they ARE the LDS address only with the base in no term,
+// so these two take the address whole, and a write costs the one instruction that makes it.  (A static __shared__ in either kernel would
+// move the segment: every NTT test fails at once.)
+__device__ __forceinline__ void tile_store_at(int byte_pos, u64 x) { *(zp_lu64 *)(__UINTPTR_TYPE__)(u32)byte_pos = x; }
+__device__ __forceinline__ u64 tile_load_at(int byte_pos) { return *(const zp_lu64 *)(__UINTPTR_TYPE__)(u32)byte_pos; }
 
 // A wave-uniform value the compiler may not look through: what is computed from it is computed where it is used (in scalar registers), not
 // ahead of the loop and kept.  No instruction.
@@ -68,55 +78,6 @@ struct PassArgs {
     int logPin;  // itab: k = u0 >> logPin, the Pprev of the pass before this one
     int flags;  // 1: inter-pass twiddle  2: multiply by `scale`  4: coset post-scale  8: a middle pass (MODE 1 whether it multiplies or not)
     int ncols;  // MODE 3: the grid is one-dimensional, columns of one launch
-};
-
-__device__ __forceinline__ constexpr int brev(int x, int bits) {
-    int r = 0;
-    for (int i = 0; i < bits; i++) r |= ((x >> i) & 1) << (bits - 1 - i);
-    return r;
-}
-__device__ __forceinline__ constexpr int slot_of(int o, int j, int pos, int A) {
-    return ((o >> pos) << (pos + A)) | (j << pos) | (o & ((1 << pos) - 1));
-}
-
-template <int A1, int A2, int A3, int LOGT>
-struct Geo {
-    static constexpr int L = A1 + A2 + A3;
-    static constexpr int R = 1 << L;
-    static constexpr int T = 1 << LOGT;
-    static constexpr int LT = LOGT;
-    static constexpr int NT = (R * T) / 16;
-    static constexpr int J = 1 + (A2 > 0 ? 1 : 0) + (A3 > 0 ? 1 : 0);
-    static constexpr int POS1 = L - A1;
-    static constexpr int POS2 = L - A1 - A2;
-    static constexpr int AJ = (J == 1) ? A1 : (J == 2 ? A2 : A3);
-    // output index k held by slot sigma once all rounds are done
-    __device__ static __forceinline__ int kof(int sigma) {
-        int k = (sigma >> POS1) & ((1 << A1) - 1);
-        if (A2 > 0) k |= ((sigma >> POS2) & ((1 << A2) - 1)) << A1;
-        if (A3 > 0) k |= (sigma & ((1 << A3) - 1)) << (A1 + A2);
-        return k;
-    }
-    __device__ static __forceinline__ int sigma_of_k(int k) {
-        int s = (k & ((1 << A1) - 1)) << POS1;
-        if (A2 > 0) s |= ((k >> A1) & ((1 << A2) - 1)) << POS2;
-        if (A3 > 0) s |= (k >> (A1 + A2)) & ((1 << A3) - 1);
-        return s;
-    }
-    // LDS position of (slot sigma, column t).  t is XORed with the low bits of the output index (conflict-free row accesses
-    // and transposing copy-out at T >= 16).  With T < 16 one slot is only T*8 < 128 bytes, so the 32 lanes of a half-wave
-    // span 32/T slots and those must fall into different 32/T-ths of a 256-byte bank row: the low bits of sigma (inside
-    // the last-round field) are XORed with the low bits of the middle field (last-round reads and writes: consecutive lanes
-    // = consecutive middle-field values) and, one bit up, with the top-field bits the t-swizzle does not use (transposing
-    // copy-out: consecutive lanes = consecutive top-field values, then the middle field steps by one).
-    __device__ static __forceinline__ int lpos(int sigma, int t) {
-        int s2 = sigma;
-        if constexpr (LOGT < 4 && A3 > 0) {
-            constexpr int GB = 5 - LOGT;
-            s2 ^= ((sigma >> POS2) & ((1 << GB) - 1)) ^ (((sigma >> (POS1 + LOGT)) & ((1 << (A1 - LOGT)) - 1)) << 1);
-        }
-        return (s2 << LOGT) + (t ^ (kof(sigma) & (T - 1)));
-    }
 };
 
 __device__ __forceinline__ u64 tw_lookup(const u64 *lo, const u64 *hi, int lb, u64 e) {
@@ -181,7 +142,7 @@ __device__ __forceinline__ void exchange_read(u64 *v, const u64 *lds, int tid) {
 
 // twr: LDS copy of w_(2^(POS+A))^e (TWSH = 0) or, for the radix-2^11 / 2^12 passes whose LDS is all tile, the global
 // table of w_4096^e (TWSH = 12 - (POS + A)); 32 KiB, read by every workgroup, L2 / L1 resident
-template <typename G, int A, int POS, int ANEXT, int POSNEXT, int TWSH>
+template <typename G, int A, int POS, int ANEXT, int POSNEXT, int TWSH, bool FACT = true>
 __device__ __forceinline__ void exchange2(u64 *v, u64 *lds, const u64 *twr, int j0inv, int tid) {
     constexpr int GR = 16 >> A;
 #pragma unroll
@@ -199,10 +160,24 @@ __device__ __forceinline__ void exchange2(u64 *v, u64 *lds, const u64 *twr, int 
             const int kja = (j0inv * brev(p, A)) & ((1 << A) - 1), kjb = (j0inv * brev(p + 1, A)) & ((1 << A) - 1);
             gl_mul2(v[g * (1 << A) + p], twr[(kja * rho) << TWSH], v[g * (1 << A) + p + 1], twr[(kjb * rho) << TWSH]);
         }
+        // The slot of register p takes the runtime k_j twice: as the round's field and, where that field reaches k's low bits, in the column
+        // swizzle.  Factored (ntt_geo.hpp): the lane's part once per round, the two uniform parts of k_j in scalar registers, one XOR per
+        // write.  Written out as lpos(slot_of(o, kj, ..), t) the compiler rebuilt the whole position for every register: five VALU a write.
+        // The tiles of 8 columns and fewer with three rounds (slot swizzle: radix 2^11, 2^12) keep lpos, and so does a first pass on the
+        // per-lane twiddle chain (FACT false): it spills already, and the lane part held across a round's writes costs it more scratch.
+        if constexpr (G::FACTORED && FACT) {
+            const int lane = G::wr_lane(o, t, POS, A);
 #pragma unroll
-        for (int p = 0; p < (1 << A); p++) {
-            const int kj = (j0inv * brev(p, A)) & ((1 << A) - 1);  // wave-uniform
-            lds[G::lpos(slot_of(o, kj, POS, A), t)] = v[g * (1 << A) + p];
+            for (int p = 0; p < (1 << A); p++) {
+                const int kj = (j0inv * brev(p, A)) & ((1 << A) - 1);  // wave-uniform
+                tile_store_at(lane ^ G::wr_uni(kj, POS, A), v[g * (1 << A) + p]);
+            }
+        } else {
+#pragma unroll
+            for (int p = 0; p < (1 << A); p++) {
+                const int kj = (j0inv * brev(p, A)) & ((1 << A) - 1);  // wave-uniform
+                lds[G::lpos(slot_of(o, kj, POS, A), t)] = v[g * (1 << A) + p];
+            }
         }
     }
     lds_barrier();
@@ -288,20 +263,36 @@ __device__ __forceinline__ void exchange2_l4(const gl_l4 *x, u64 *v, u64 *lds, c
 
 // ---- the step of a tile that ntt_pass2_kernel and lde_seam_kernel share
 // Table copy-out of a first pass: the tile sits in LDS, so v is dead and its registers take the 16 factors (twb: the plan's table at this tile) of the elements this lane copies out to blk
-template <typename G>
-__device__ __forceinline__ void table_copy_out(u64 *v, const u64 *lds, const u64 *twb, u64 *blk, int tid) {
-    constexpr int L = G::L, NT = G::NT;
+// Element i NT + tid of the tile in output order, i < 16: table entry, LDS word and destination.  Table and destination are the uniform base
+// of row i, walked by scalar adds (WALK: through sgpr_opaque, as fetch_tile does), beside the lane's 32-bit byte offset 8 tid -- the table
+// form is never BIG, and this offset is below 16 KiB whatever the transform.  The LDS word is the lane's rd_lane XOR a constant (ntt_geo.hpp):
+// idx mod R does not depend on i, which the compiler cannot see through the opaque lane id.
+template <typename G, bool WALK>
+__device__ __forceinline__ void table_copy_out(u64 *v, const u64 *twb, u64 *blk, int tid) {
+    constexpr int NT = G::NT;
+    static_assert(G::FACTORED && NT >= G::R, "table first passes: two rounds, tiles of 16 columns or more");
+    const u32 lane_bytes = (u32)tid << 3;
+    u64 tw_at = sgpr_opaque<WALK>((u64)twb);
 #pragma unroll
-    for (int i = 0; i < 16; i++) v[i] = twb[i * NT + tid];       // cacheable: the other columns of this tile hit in L2
+    for (int i = 0; i < 16; i++) {
+        const zp_gu64 *rowp = (const zp_gu64 *)tw_at;
+        tw_at = sgpr_opaque<WALK>(tw_at + 8ULL * NT);
+        v[i] = *(const zp_gu64 *)((const zp_gchar *)rowp + lane_bytes);       // cacheable: the other columns of this tile hit in L2
+    }
     lds_barrier();
+    const int rd = G::rd_lane(tid);
+    u64 st_at = sgpr_opaque<WALK>((u64)blk);
 #pragma unroll
     for (int i = 0; i < 16; i += 2) {
-        const int ia = i * NT + tid, ib = (i + 1) * NT + tid;
-        u64 xa = lds[G::lpos(G::sigma_of_k(ia & ((1 << L) - 1)), ia >> L)];
-        u64 xb = lds[G::lpos(G::sigma_of_k(ib & ((1 << L) - 1)), ib >> L)];
+        u64 xa = tile_load_at(rd ^ G::rd_xor(i));
+        u64 xb = tile_load_at(rd ^ G::rd_xor(i + 1));
         gl_mul2(xa, v[i], xb, v[i + 1]);
-        ZP_STG(&blk[ia], xa);
-        ZP_STG(&blk[ib], xb);
+        zp_gu64 *const ra = (zp_gu64 *)st_at;
+        st_at = sgpr_opaque<WALK>(st_at + 8ULL * NT);
+        zp_gu64 *const rb = (zp_gu64 *)st_at;
+        st_at = sgpr_opaque<WALK>(st_at + 8ULL * NT);
+        ZP_STG((zp_gu64 *)((zp_gchar *)ra + lane_bytes), xa);
+        ZP_STG((zp_gu64 *)((zp_gchar *)rb + lane_bytes), xb);
     }
 }
 
@@ -576,11 +567,11 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
         } else {
 #pragma unroll
         for (int g = 0; g < (16 >> A1); g++) dif_shift<A1>(v + g * (1 << A1));
-        exchange2<G, A1, G::POS1, A2, G::POS2, TWR_LDS ? 0 : 12 - L>(v, lds, TWR_LDS ? twr1 : a.tws, j0inv, tid);
+        exchange2<G, A1, G::POS1, A2, G::POS2, TWR_LDS ? 0 : 12 - L, LEAN>(v, lds, TWR_LDS ? twr1 : a.tws, j0inv, tid);
 #pragma unroll
         for (int g = 0; g < (16 >> A2); g++) dif_shift<A2>(v + g * (1 << A2));
         if constexpr (G::J >= 3) {
-            exchange2<G, A2, G::POS2, A3, 0, TWR_LDS ? 0 : 12 - (A2 + A3)>(v, lds, TWR_LDS ? twr2 : a.tws, j0inv, tid);
+            exchange2<G, A2, G::POS2, A3, 0, TWR_LDS ? 0 : 12 - (A2 + A3), LEAN>(v, lds, TWR_LDS ? twr2 : a.tws, j0inv, tid);
 #pragma unroll
             for (int g = 0; g < (16 >> A3); g++) dif_shift<A3>(v + g * (1 << A3));
         }
@@ -592,11 +583,13 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
             const int klow = G::kof(o << AJ);
             if constexpr (TW1) {
                 const int jr = j0inv & ((1 << AJ) - 1);
+                // (the field at bit 0: the swizzle takes k_j only on the tiles of 32 columns; the limb form keeps lpos -- its registers are counted)
+                const int lane = G::wr_lane(o, t, 0, AJ);
 #pragma unroll
                 for (int i = 0; i < (1 << AJ); i++) {
                     const int kj = (jr * i) & ((1 << AJ) - 1);
                     if constexpr (LIMB) lds[G::lpos(slot_of(o, kj, 0, AJ), t)] = gl_l4_canon(x[g * (1 << AJ) + brev(i, AJ)]);
-                    else lds[G::lpos(slot_of(o, kj, 0, AJ), t)] = v[g * (1 << AJ) + brev(i, AJ)];
+                    else tile_store_at(lane ^ G::wr_uni(kj, 0, AJ), v[g * (1 << AJ) + brev(i, AJ)]);
                 }
             } else if constexpr (TRANSPOSE) {
                 const int jr = j0inv & ((1 << AJ) - 1);  // odd, < 2^AJ: floor(jr*i/2^AJ) steps by 0 or 1
@@ -661,7 +654,7 @@ ntt_pass2_kernel(PassArgs a, int tiles_per_wg) {
             }
         }
         if constexpr (TW1) {
-            table_copy_out<G>(v, lds, a.tw1 + (u0 << L), dst + (u0 << L), tid);
+            table_copy_out<G, LEAN>(v, a.tw1 + (u0 << L), dst + (u0 << L), tid);
         } else if constexpr (TRANSPOSE) {
             lds_barrier();
             u64 *blk = dst + (u0 << L);
@@ -824,14 +817,15 @@ __global__ void __launch_bounds__(256, 4) lde_seam_kernel(SeamArgs a, int tiles_
             dif_shift<4>(v);
             {
                 const int jr = a.j0inv_f & 15;
+                const int lane = G::wr_lane(o, t, 0, 4);
 #pragma unroll
                 for (int i = 0; i < 16; i++) {
                     const int kj = (jr * i) & 15;
-                    lds[G::lpos(slot_of(o, kj, 0, 4), t)] = v[brev(i, 4)];
+                    tile_store_at(lane ^ G::wr_uni(kj, 0, 4), v[brev(i, 4)]);
                 }
             }
             const u64 u0f = ((u64)par << logNR) + u0;
-            table_copy_out<G>(v, lds, a.tw1 + (u0f << L), dst + (u0f << L), tid);
+            table_copy_out<G, true>(v, a.tw1 + (u0f << L), dst + (u0f << L), tid);
             lds_barrier();      // the tile is reused by the second forward tile / the next inverse tile
         }
     }
