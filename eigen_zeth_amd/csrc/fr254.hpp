@@ -245,12 +245,29 @@ GL_HD void fr_to_u64(const fr &a, u64 *w) {
         if (off > 64 - FR_B && k + 1 < 4) w[k + 1] |= (u64)a.l[i] >> (64 - off);
     }
 }
+// r as four little-endian 64-bit words, written HERE and nowhere else (an initialiser: r - 2, (r - 1) >> k, ... derive from it)
+#define FR_MODULUS_U64 {0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL}
 GL_HD bool fr_is_canonical_u64(const u64 *w) {   // value < r
-    const u64 R4[4] = {0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL};
+    const u64 R4[4] = FR_MODULUS_U64;
     for (int k = 3; k >= 0; k--) {
         if (w[k] != R4[k]) return w[k] < R4[k];
     }
     return false;
+}
+// host setup: base^e and a^-1 = a^(r - 2), Montgomery in and out; e: `words` little-endian 64-bit words
+inline fr fr_pow(fr base_m, const u64 *e, int words) {
+    fr r = fr_one();
+    for (int k = words - 1; k >= 0; k--)
+        for (int b = 63; b >= 0; b--) {
+            r = fr_mul(r, r);
+            if ((e[k] >> b) & 1) r = fr_mul(r, base_m);
+        }
+    return r;
+}
+inline fr fr_inv(fr a_m) {
+    u64 e[4] = FR_MODULUS_U64;
+    e[0] -= 2;
+    return fr_pow(a_m, e, 4);
 }
 // One sponge block of a 16-ary tree's leaf absorbs up to 56 Goldilocks values in its 16 rate elements: element k holds values base + 3k .. 3k+2 in
 // bits 0..191 and, in bits 192..223, 32-bit half number k of values base + 48 .. base + 55 (half 2i = low word of value 48 + i, half

@@ -147,27 +147,13 @@ __global__ void __launch_bounds__(256) fr_qap_pointwise_kernel(u64 *a, const u64
 
 // ---- host-side field helpers (fr254.hpp is host/device) ----
 fr h_from_words(const u64 *w) { return fr_to_mont(fr_from_u64(w)); }               // -> Montgomery
-fr h_pow(fr base_m, const u64 *ex, int nwords) {                                    // Montgomery in, Montgomery out
-    fr r = fr_one();
-    for (int k = nwords - 1; k >= 0; k--)
-        for (int b = 63; b >= 0; b--) {
-            r = fr_mul(r, r);
-            if ((ex[k] >> b) & 1) r = fr_mul(r, base_m);
-        }
-    return r;
-}
-fr h_inv(fr a_m) {                                                                  // a^(r-2)
-    const u64 e[4] = {0x43e1f593f0000001ULL - 2, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL};
-    return h_pow(a_m, e, 4);
-}
-fr h_pow_u64(fr base_m, u64 e) { return h_pow(base_m, &e, 1); }
+fr h_pow_u64(fr base_m, u64 e) { return fr_pow(base_m, &e, 1); }
 fr h_root(int logn) {                                                               // 5^((r-1)/2^logn), Montgomery
-    // (r - 1) >> 28
-    const u64 r1[4] = {0x43e1f593f0000000ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL};
-    u64 e[4];
+    u64 r1[4] = FR_MODULUS_U64, e[4];                                                // (r - 1) >> 28
+    r1[0] -= 1;
     for (int k = 0; k < 4; k++) e[k] = (r1[k] >> 28) | (k + 1 < 4 ? r1[k + 1] << 36 : 0);
     const u64 five[4] = {5, 0, 0, 0};
-    fr w = h_pow(h_from_words(five), e, 4);                                          // primitive 2^28-th root
+    fr w = fr_pow(h_from_words(five), e, 4);                                          // primitive 2^28-th root
     for (int i = logn; i < 28; i++) w = fr_mul(w, w);
     return w;
 }
@@ -221,7 +207,7 @@ int32_t get_plan(zp_ctx *ctx, int logn, bool inverse, FrPlan **out) {
     pl.npass = (logn + 7) / 8;
     for (int i = 0; i < pl.npass; i++) pl.L[i] = logn / pl.npass + (i < logn % pl.npass ? 1 : 0);
     fr w = h_root(logn);
-    if (inverse) w = h_inv(w);
+    if (inverse) w = fr_inv(w);
     ZP_TRY(build_two_level(ctx, w, fr_one(), logn, &pl.tw));
     for (int i = 0; i < pl.npass; i++) {
         const int R = 1 << pl.L[i];
@@ -234,7 +220,7 @@ int32_t get_plan(zp_ctx *ctx, int logn, bool inverse, FrPlan **out) {
         ZP_HIP(ctx, hipMemcpy(pl.d_wr[i], t.data(), t.size() * 4, hipMemcpyHostToDevice));
     }
     u64 nn[4] = {(u64)1 << logn, 0, 0, 0};
-    pl.ninv = h_inv(h_from_words(nn));
+    pl.ninv = fr_inv(h_from_words(nn));
     *out = &(g_plans[key] = pl);
     return ZP_OK;
 }
@@ -245,7 +231,7 @@ int32_t get_coset(zp_ctx *ctx, int logn, bool inverse, const u64 *cw, const fr &
     if (it != g_cosets.end()) { *out = &it->second; return ZP_OK; }
     fr g = h_from_words(cw);
     FrTables t;
-    if (inverse) ZP_TRY(build_two_level(ctx, h_inv(g), ninv, logn, &t));   // g^-k / N
+    if (inverse) ZP_TRY(build_two_level(ctx, fr_inv(g), ninv, logn, &t));   // g^-k / N
     else ZP_TRY(build_two_level(ctx, g, fr_one(), logn, &t));              // g^i
     *out = &(g_cosets[key] = t);
     return ZP_OK;
@@ -325,7 +311,7 @@ int32_t zp_qap_quotient_bn254(zp_ctx *ctx, uint64_t *d_a_, uint64_t *d_b_, uint6
     u64 zw[4];
     fr_to_u64(fr_from_mont(z), zw);
     ZP_ARG(ctx, (zw[0] | zw[1] | zw[2] | zw[3]) != 0, "coset shift lies in the evaluation domain");
-    const fr zinv_m = h_inv(z);                         // s 2^261
+    const fr zinv_m = fr_inv(z);                         // s 2^261
     const fr s2 = zinv_m;                               // plain value s 2^261: exactly the limbs of the Montgomery form
     const fr s1 = fr_mul(zinv_m, fr_r2());              // s 2^522 = mont(s 2^261, 2^522)
     for (u64 *d : {d_a, d_b, d_c}) {

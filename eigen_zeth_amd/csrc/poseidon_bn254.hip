@@ -809,16 +809,6 @@ P254Dev dev_of(const zp_ctx *ctx, const P254Table *tb) {       // (zp_set_tuning
 // unchanged and are carried through S (carry_0' = v^ . rest, carry_k' = rest_k) into the next round's constants; the last
 // carry lands in the constants of the first full round after the partial rounds.
 typedef std::vector<fr> FrVec;
-fr h_inv_fr(fr a) {
-    const u64 e[4] = {0x43e1f593f0000001ULL - 2, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL};
-    fr r = fr_one();
-    for (int k = 3; k >= 0; k--)
-        for (int b = 63; b >= 0; b--) {
-            r = fr_mul(r, r);
-            if ((e[k] >> b) & 1) r = fr_mul(r, a);
-        }
-    return r;
-}
 bool fr_is_zero(const fr &a) {
     u32 o = 0;
     for (int i = 0; i < 9; i++) o |= a.l[i];
@@ -836,7 +826,7 @@ bool mat_inv(const FrVec &a_in, int n, FrVec &out) {
         if (piv < 0) return false;
         if (piv != c)
             for (int k = 0; k < n; k++) { std::swap(a[(size_t)piv * n + k], a[(size_t)c * n + k]); std::swap(out[(size_t)piv * n + k], out[(size_t)c * n + k]); }
-        const fr pi = h_inv_fr(a[(size_t)c * n + c]);
+        const fr pi = fr_inv(a[(size_t)c * n + c]);
         for (int k = 0; k < n; k++) { a[(size_t)c * n + k] = fr_mul(a[(size_t)c * n + k], pi); out[(size_t)c * n + k] = fr_mul(out[(size_t)c * n + k], pi); }
         for (int r = 0; r < n; r++) {
             if (r == c || fr_is_zero(a[(size_t)r * n + c])) continue;
@@ -913,7 +903,7 @@ bool scaled_sparse_form(const FrVec &a, const FrVec &sp, int t, int rp, FrVec &s
         const fr *S = &sp[(size_t)j * (2 * t - 1)];
         if (fr_is_zero(S[0])) return false;
         const fr l2 = fr_mul(lam, lam), l5 = fr_mul(fr_mul(l2, l2), lam);
-        const fr next = fr_mul(l5, h_inv_fr(S[0])), l5inv = h_inv_fr(l5);
+        const fr next = fr_mul(l5, fr_inv(S[0])), l5inv = fr_inv(l5);
         fr *O = &sps[(size_t)j * (2 * t - 1)];
         O[0] = j + 1 < rp ? fr_mul(next, a[j + 1]) : fr_zero();
         for (int k = 1; k < t; k++) {
@@ -922,7 +912,7 @@ bool scaled_sparse_form(const FrVec &a, const FrVec &sp, int t, int rp, FrVec &s
         }
         lam = next;
     }
-    spt.assign(1, h_inv_fr(lam));
+    spt.assign(1, fr_inv(lam));
     return true;
 }
 int32_t upload_fr(zp_ctx *ctx, const FrVec &v, u32 **d) {

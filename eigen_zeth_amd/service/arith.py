@@ -16,7 +16,7 @@ a mod p or that plus p; q < 2^k with k from a's bound) and states the identity a
 and means the integer identity only while nothing wraps.
 
 The witness is not solved for: every internal wire is DEFINED by an op of the template's witness program (product, quotient and remainder by
-p, bits, inverse in F_p^3), run in order by the library (csrc/r1cs.hip: arith_witness) or by `Template.run` below (Python integers: the
+p, bits, inverse in F_p^3), run in order by the library (csrc/r1cs_host.hip: arith_witness) or by `Template.run` below (Python integers: the
 reference the tests compare the library with).  An op that cannot be carried out -- a value that does not fit its bits, a zero with no
 inverse -- means there is no witness: the statement is false.
 

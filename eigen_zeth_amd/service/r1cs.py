@@ -1,6 +1,6 @@
 """R1CS over the BN254 scalar field for the Groth16 wrap of GenFinalProof (proto/prover/v1/prover.proto:130-148): circuits made of many copies
-of ONE gadget -- a width-t Poseidon-BN254 permutation -- plus explicit glue constraints, in the form the library works on (csrc/r1cs.hip:
-zp_r1cs_eval completes and checks a witness and gives A w, B w, C w; zp_r1cs_key_scalars gives the key's scalars).
+of ONE gadget -- a width-t Poseidon-BN254 permutation -- plus explicit glue constraints, in the form the library works on (csrc/r1cs_circuit.hpp reads the
+blob; csrc/r1cs_host.hip: zp_r1cs_eval completes and checks a witness and gives A w, B w, C w; zp_r1cs_key_scalars gives the key's scalars).
 
 The gadget (`poseidon_template`): local wire 0 is the constant 1, wires 1..t the input state, then three wires per S-box (x^2, x^4, x^5 of
 the S-box input, which is a linear combination of earlier wires plus the round constant: linear layers cost no constraint) and one wire for

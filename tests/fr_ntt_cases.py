@@ -212,7 +212,7 @@ def qap_case(logm, seed=0):
 
 
 def qap_cosets(logm, rnd):
-    """7 (the product's, csrc/r1cs.hip), the primitive 2m-th root (g^m = -1) and a random shift just below r"""
+    """7 (the product's, csrc/groth16.hip), the primitive 2m-th root (g^m = -1) and a random shift just below r"""
     m = 1 << logm
     while True:
         near = FR - 1 - rnd.randrange(1, 1 << 64)

@@ -1,5 +1,5 @@
-// Host sanitizer driver for the host half of eigen_zeth_amd/csrc/r1cs.hip (built by tests/test_r1cs_fuzz.py with -DZP_R1CS_HOST_ONLY
-// -fsanitize=address,undefined): the circuit-blob parser ("PZR1CS02": Poseidon template + explicit constraints + ARITHMETIC TEMPLATES with their
+// Host sanitizer driver for the host code of the R1CS, eigen_zeth_amd/csrc/r1cs_circuit.hpp, r1cs_host.hip and wrap_assign.hip (built by
+// tests/test_r1cs_fuzz.py with -fsanitize=address,undefined): the circuit-blob parser ("PZR1CS02": Poseidon template + explicit constraints + ARITHMETIC TEMPLATES with their
 // witness programs, round 6), the host evaluator that runs those programs and checks every row, and the assignment script / openings record reader
 // (zp_wrap_assign).  These blobs are the service's own, but whatever reaches a C ABI must not be trusted to be well formed.  The case file holds
 //   [blob words][blob][n_set][wire ids][values x 4][expected public input x 4] [script words][script][openings words][openings][n_aux][aux x 4]

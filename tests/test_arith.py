@@ -1,4 +1,4 @@
-"""Goldilocks arithmetic inside F_r (service/arith.py) and arithmetic templates in the circuit blob (service/r1cs.py "PZR1CS02", csrc/r1cs.hip) -- the
+"""Goldilocks arithmetic inside F_r (service/arith.py) and arithmetic templates in the circuit blob (service/r1cs.py "PZR1CS02", csrc/r1cs_circuit.hpp, csrc/r1cs_host.hip) -- the
 machinery of wrap stage B-2, on the CPU: the gadgets compute what integer arithmetic mod p computes; a tampered wire violates a row; an impossible
 op (the inverse of zero, a value that does not fit its bits) is "no witness"; the library's host evaluator (witness programs + rows) and its key
 scalars equal the Python reference / the definition."""

@@ -1,7 +1,8 @@
 """The seeded small circuits of tests/r1cs_cases.py, on the CPU: for every shape the library's host evaluator (zp_r1cs_eval) equals
 Circuit.complete word for word, the checker's own reader of the blob (oracle/r1cs_blob.py) finds no violated row, and the blob has the wave
 bounds and the domain the shape is meant to have -- so that the device tests (tests/test_gpu_r1cs_device.py) stand on circuits that are what
-they claim to be.  Also the refusals the device tests compare: the host's code and *bad for each fault."""
+they claim to be.  Also the refusals the device tests compare: the host's code and *bad for each fault; and the key generator's scalars on the
+two shapes in which gadget rows, explicit rows and arithmetic rows meet in one key."""
 import numpy as np
 import pytest
 
@@ -69,3 +70,43 @@ def test_host_refusals_name_the_row_or_wire_at_fault():
             "violated: e3_inv of zero in the second arithmetic instance": (-20, first_arith + t["arith_rows"])}
     got = {k: RC.host_refusal(cs, v) for k, v in RC.faults(cs).items()}
     assert got == want
+
+
+@pytest.mark.parametrize("name", ["S2", "S4"])
+def test_key_scalars_match_the_definition_where_the_three_row_kinds_meet(name):
+    """zp_r1cs_key_scalars against u_j = sum_i A[i][j] L_i(tau) (v, w alike) in Python integers over Circuit.rows(): gadget instances, explicit
+    rows and arithmetic instances add into the same wires' scalars (S4: an arithmetic instance's internal wire read by a gadget and by a row)"""
+    cs = RC.case(name)
+    c, R = cs.circuit, RC.R
+    tau, al, be, ga, de = 123456789, 5, 7, 11, 13
+    u, v, l, h = native.r1cs_key_scalars(cs.blob, tau, al, be, ga, de)
+    m, om = 1 << cs.logm, pow(5, (R - 1) >> cs.logm, R)
+    zt = (pow(tau, m, R) - 1) % R
+    rows = list(c.rows())
+    assert len(rows) == cs.n_cons
+    wp = [1]
+    for _ in range(len(rows) - 1):
+        wp.append(wp[-1] * om % R)
+    scale = zt * pow(m, -1, R) % R
+    den, pre, run = [(tau - x) % R for x in wp], [], 1                # 1 / (tau - w^i): one inversion for all of them
+    for d in den:
+        pre.append(run)
+        run = run * d % R
+    inv, L = pow(run, -1, R), [0] * len(rows)
+    for i in range(len(rows) - 1, -1, -1):
+        L[i] = scale * wp[i] % R * (inv * pre[i] % R) % R
+        inv = inv * den[i] % R
+    acc = [[0] * cs.n_wires for _ in range(3)]
+    for Li, row in zip(L, rows):
+        for a, M in zip(acc, row):
+            for k, cf in M.items():
+                a[k] = (a[k] + cf * Li) % R
+    assert native.fr_ints(u) == acc[0] and native.fr_ints(v) == acc[1]
+    dinv, ginv = pow(de, -1, R), pow(ga, -1, R)
+    assert native.fr_ints(l) == [(be * acc[0][j] + al * acc[1][j] + acc[2][j]) * (ginv if j <= cs.n_pub else dinv) % R for j in range(cs.n_wires)]
+    hi = native.fr_ints(h)
+    assert len(hi) == m - 1 and hi[0] == zt * dinv % R and hi[m - 2] == pow(tau, m - 2, R) * zt * dinv % R
+    e0 = 12 * RC.TC
+    e1 = e0 + int(cs.blob[8])
+    gadget, explicit, arith = (set(k for row in rows[a:b] for M in row for k in M) - {0} for a, b in ((0, e0), (e0, e1), (e1, cs.n_cons)))
+    assert gadget & explicit and arith and (name != "S4" or (gadget & arith and explicit & arith))      # one wire's scalar takes terms of two row kinds

@@ -1,4 +1,4 @@
-"""The host half of eigen_zeth_amd/csrc/r1cs.hip under AddressSanitizer + UBSan (built with -DZP_R1CS_HOST_ONLY by g++): the circuit-blob parser
+"""The host code of the R1CS (eigen_zeth_amd/csrc/r1cs_circuit.hpp, r1cs_host.hip, wrap_assign.hip) under AddressSanitizer + UBSan (built by g++): the circuit-blob parser
 with its ARITHMETIC TEMPLATES (round 6: rows over local wires, linear-combination pools, witness programs, instance tables), the host evaluator that
 runs the witness programs and checks every row, and zp_wrap_assign over the assignment script and the openings record -- a valid stage B-2 case must
 give the reference's public input, and seeded mutations of the blob, the script and the record must be evaluated or refused without a single
@@ -44,9 +44,9 @@ def test_circuit_blob_and_assignment_under_sanitizers(tmp_path, tables):
     san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1", "-std=c++17"]
     csrc = os.path.join(ROOT, "eigen_zeth_amd", "csrc")
     objs = []
-    for src, extra in (("r1cs.hip", ["-DZP_R1CS_HOST_ONLY"]), ("verify.hip", [])):
+    for src in ("r1cs_host.hip", "wrap_assign.hip", "verify.hip"):
         obj = str(tmp_path / (src + ".o"))
-        subprocess.check_call(["g++", *san, "-x", "c++", "-D__HIP_PLATFORM_AMD__", *extra, "-I/opt/rocm/include", "-c", os.path.join(csrc, src), "-o", obj])
+        subprocess.check_call(["g++", *san, "-x", "c++", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-c", os.path.join(csrc, src), "-o", obj])
         objs.append(obj)
     exe = str(tmp_path / "r1cs_fuzz")
     subprocess.check_call(["g++", *san, os.path.join(ROOT, "tests", "native", "r1cs_fuzz.cpp"), *objs, "-o", exe, "-lpthread"])

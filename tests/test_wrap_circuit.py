@@ -1,6 +1,6 @@
 """The Groth16 wrap's circuit and the R1CS machinery under it (CPU tests: everything here is host code of the library or Python).
 
-* service/r1cs.py + csrc/r1cs.hip: the Poseidon-BN254 (t = 17) gadget template computes the permutation the oracle computes; zp_r1cs_eval
+* service/r1cs.py + csrc/r1cs_host.hip: the Poseidon-BN254 (t = 17) gadget template computes the permutation the oracle computes; zp_r1cs_eval
   completes a witness exactly as the Python reference does and gives A w, B w, C w per constraint; zp_r1cs_key_scalars matches the
   definition of a Groth16 key's scalars.
 * service/wrap_circuit.py over a real final-STARK-shaped proof (BN128-hash mode, from the CPU checker's backend): the witness completes, the
@@ -114,6 +114,32 @@ def test_key_scalars_match_the_definition(small):
     assert len(hi) == m - 1 and hi[0] == zt * pow(de, -1, R) % R and hi[7] == pow(tau, 7, R) * zt * pow(de, -1, R) % R
     with pytest.raises(native.ZpError):                           # tau on the domain is not a usable point
         native.r1cs_key_scalars(blob, 1, al, be, ga, de)
+
+
+@pytest.mark.parametrize("widths", [(1, 47), (48, 49), (55, 56), (57, 113)])
+def test_wrap_assign_packs_every_leaf_block_as_the_oracle_does(widths):
+    """zp_wrap_assign op 5 (the 16 elements of block c of the leaf of query a in tree b: leaf_block_element of csrc/fr254.hpp) on a hand-built
+    script and openings record -- two trees, one query -- at the leaf widths around the 48 packed values, the 56 of a block and a third block,
+    every block of every leaf, against oracle/naive.py pack_leaf_block.  (The proofs of this module reach the line at their AIR's widths only.)"""
+    import random
+    rnd = random.Random(sum(widths))
+    magic = lambda name: int.from_bytes(name, "little")
+    leaves = [[rnd.choice((0, 1, (1 << 64) - 1, 0xFFFFFFFF00000000, rnd.getrandbits(64))) for _ in range(w)] for w in widths]
+    trees = [(w, 16, 1) for w in widths]                          # (width, leaves, levels): one level of 16 digests behind every leaf
+    rec = [magic(b"PZOPEN03"), 1, 2, 4] + [x for t in trees for x in t] + [0] * 8          # header, trees, the two roots
+    rec += [5] + [x for vals in leaves for x in vals + [0] * 64]  # the query: its index, then per tree the leaf and the path
+    rec += [1, 1] + [0] * (64 + 64 + 4) + [0]                     # one absorbed block, one rate block, one capacity, no challenge
+    ops = [(5, 100 * (1 + 3 * b + c), 16, 0, b, c) for b, w in enumerate(widths) for c in range(-(-w // 56))]
+    script = [magic(b"PZWRAPS3"), len(ops), 16 * len(ops), 1, 2, 4] + [x for t in trees for x in t] + [1, 1] + [x for o in ops for x in o]
+    idx, val = native.wrap_assign(np.array(script, dtype=np.uint64), np.array(rec, dtype=np.uint64), [0])
+    want_idx = [o[1] + i for o in ops for i in range(16)]
+    want = [e for b, w in enumerate(widths) for c in range(-(-w // 56)) for e in NV.pack_leaf_block(leaves[b][56 * c:56 * c + 56])]
+    assert len(ops) == sum(-(-w // 56) for w in widths) and idx.tolist() == want_idx
+    assert native.fr_ints(val) == want
+    bad = list(script)
+    bad[-1] = -(-widths[1] // 56)                                 # a block behind the last one of the leaf
+    with pytest.raises(ValueError):
+        native.wrap_assign(np.array(bad, dtype=np.uint64), np.array(rec, dtype=np.uint64), [0])
 
 
 @pytest.fixture(scope="module")
