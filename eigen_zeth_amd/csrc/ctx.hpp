@@ -280,6 +280,11 @@ int32_t zpi_witness_canonical(zp_ctx *ctx, const u64 *d_trace, size_t total, u64
 void zpi_witness_noncanonical_report(size_t K, size_t N, u64 bad_n, u64 bad_at, uint64_t *h_report, uint64_t *h_counts, uint64_t *h_first_row);
 int32_t zpi_witness_constraints(zp_ctx *ctx, const ZpProgram &pg, const uint8_t *dg32, const std::vector<u64> &pubchal, const u64 *d_trace, const u64 *d_s2,
                                 int logn, uint64_t *h_report, uint64_t *h_counts, uint64_t *h_first_row);
+// the launch behind it, the result [first key][first_row: K][counts: K] left on the device in d_res.  win != NULL: rows [row0, row0 + nrows) only, d_trace
+// u64[W][stride] with one halo row at index nrows unless nrows == N; d_s2 whole (`<symbol>_witness_rows` or witness_program_kernel<true>)
+struct ZpWitnessWindow { size_t stride, row0, nrows; };
+int32_t zpi_witness_launch(zp_ctx *ctx, const ZpProgram &pg, const uint8_t *dg32, const std::vector<u64> &pubchal, const u64 *d_trace, const u64 *d_s2, int logn,
+                           const ZpWitnessWindow *win, u64 *d_res);
 // csrc/prove.hip: the SHA-256 of a program through the ctx's cache of large blobs; the key a generated kernel of that digest is kept under
 void zpi_program_digest_cached(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, uint8_t dg[32]);
 std::string zpi_air_kernel_key(const char *form, const uint8_t dg[32]);
@@ -299,6 +304,17 @@ int32_t zpi_merkle16_levels_bn254(zp_ctx *ctx, u64 *d_tree, size_t n);   // the 
 struct zp_comm;
 zp_ctx *zpi_comm_ctx(const zp_comm *comm);      // the ctx a communicator was created on (csrc/comm.hip)
 int32_t zpi_comm_fail(zp_comm *comm, int32_t rc);   // rc != ZP_OK: kill the communicator (no peer waits for this rank); returns rc
+// the witness check over the ranks (csrc/witness_sharded.hip): every rank passes its columns and receives the same answer.  Collectives inside: a
+// caller hands a failure to zpi_comm_fail.  canonical: words >= p over all ranks and the GLOBAL index c N + r of the first; constraints: given the
+// stage-2 columns whole (or NULL), the report of zpi_witness_constraints for the whole trace; the stage-2 columns themselves, as the sharded prover makes them
+int32_t zpi_witness_sharded_canonical(zp_comm *comm, size_t W, int logn, const u64 *d_trace_local, u64 *bad_n, u64 *bad_at);
+int32_t zpi_witness_sharded_constraints(zp_comm *comm, const ZpProgram &pg, const uint8_t *dg32, const std::vector<u64> &pubchal, const u64 *d_trace_local,
+                                        const u64 *d_s2, int logn, uint64_t *h_report, uint64_t *h_counts, uint64_t *h_first_row);
+int32_t zpi_stage2_columns_sharded(zp_comm *comm, const ZpProgram &pg, const u64 *d_trace_local, int logn, const u64 g[3], u64 *d_colb, u64 *d_s2);
+// csrc/witness_host.hip: the argument checks of zp_stark_check_witness and its sharded twin, the parsed program and [publics | challenge | 0]; NULL or the refusal
+const char *zpi_witness_args(const uint64_t *h_program, size_t program_words, const uint64_t *trace, size_t trace_words, int world, int rank,
+                             const uint64_t *h_pubs, int32_t n_pubs, int32_t logn, const uint64_t *h_chal3, const uint64_t *h_report, const uint64_t *h_counts,
+                             const uint64_t *h_first_row, int32_t n_constraints, ZpProgram *pg, std::vector<u64> *pubchal);
 // the slice rule of the sharded entry points: with k = ceil(n / world), rank r owns [r k, min((r + 1) k, n)) -- the tail ranks fewer, or none
 inline void zpi_shard_range(size_t n, int world, int rank, size_t *first, size_t *count) {
     const size_t k = (n + (size_t)world - 1) / (size_t)world, lo = (size_t)rank * k;

@@ -763,8 +763,9 @@ int32_t witness_refusal(zp_ctx *ctx) {
     ctx->err = line;
     return ZP_ERR_WITNESS;
 }
-// before anything else touches the caller's trace: every word against p
-int32_t prove_check_canonical(zp_ctx *ctx, const Shape &sh) {
+// before anything else touches the caller's trace: every word against p.  comm != NULL (the sharded provers): sh.d_trace holds this rank's columns,
+// the verdict is the one of the whole trace and every rank reaches it (csrc/witness_sharded.hip)
+int32_t prove_check_canonical(zp_ctx *ctx, const Shape &sh, zp_comm *comm = nullptr) {
     zp_ctx::WitnessVerdict &v = ctx->last_witness;
     v.valid = false;
     // the interpreter's requirements (at most 32 slots, canonical constants, checked code) on top of the prover's: a generated kernel needs none of
@@ -772,7 +773,8 @@ int32_t prove_check_canonical(zp_ctx *ctx, const Shape &sh) {
     const char *why;
     ZP_ARG(ctx, zpi_program_check(&sh.pg, ZPG_WITNESS, &why), why);
     u64 bad_n, bad_at;
-    PV_TRY(zpi_witness_canonical(ctx, (const u64 *)sh.d_trace, sh.pg.W * sh.N, &bad_n, &bad_at));
+    if (comm) PV_TRY(zpi_witness_sharded_canonical(comm, sh.pg.W, sh.logn, (const u64 *)sh.d_trace, &bad_n, &bad_at));
+    else PV_TRY(zpi_witness_canonical(ctx, (const u64 *)sh.d_trace, sh.pg.W * sh.N, &bad_n, &bad_at));
     if (bad_n == 0) return ZP_OK;
     v.counts.assign(sh.pg.K, 0);
     v.first_row.assign(sh.pg.K, ~0ULL);
@@ -783,15 +785,19 @@ int32_t prove_check_canonical(zp_ctx *ctx, const Shape &sh) {
     return witness_refusal(ctx);
 }
 // as soon as the operands exist: the constraints over (trace, s2, publics | the transcript's stage-2 challenge)
-int32_t prove_check_constraints(zp_ctx *ctx, const Shape &sh, const std::vector<u64> &pubs, const u64 *s2, const e3 *chal) {
+int32_t prove_check_constraints(zp_ctx *ctx, const Shape &sh, const std::vector<u64> &pubs, const u64 *s2, const e3 *chal, zp_comm *comm = nullptr) {
     zp_ctx::WitnessVerdict &v = ctx->last_witness;
     std::vector<u64> pubchal(pubs);
     if (chal) pubchal.insert(pubchal.end(), chal->c, chal->c + 3);
     pubchal.push_back(0);                 // never empty
     v.counts.assign(sh.pg.K, 0);
     v.first_row.assign(sh.pg.K, ~0ULL);
-    PV_TRY(zpi_witness_constraints(ctx, sh.pg, sh.dg, pubchal, (const u64 *)sh.d_trace, s2, sh.logn, (uint64_t *)v.rep, (uint64_t *)v.counts.data(),
-                                   (uint64_t *)v.first_row.data()));
+    if (comm)
+        PV_TRY(zpi_witness_sharded_constraints(comm, sh.pg, sh.dg, pubchal, (const u64 *)sh.d_trace, s2, sh.logn, (uint64_t *)v.rep, (uint64_t *)v.counts.data(),
+                                               (uint64_t *)v.first_row.data()));
+    else
+        PV_TRY(zpi_witness_constraints(ctx, sh.pg, sh.dg, pubchal, (const u64 *)sh.d_trace, s2, sh.logn, (uint64_t *)v.rep, (uint64_t *)v.counts.data(),
+                                       (uint64_t *)v.first_row.data()));
     for (int c = 0; c < 3; c++) v.chal[c] = chal ? chal->c[c] : 0;
     v.valid = true;
     sh.mark("witness checked");
@@ -1062,10 +1068,18 @@ int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, bool bn, const ProveArgs 
     // every rank anyway (stage 2 is replicated, the quotient is gathered for its out-of-domain evaluation), and 2^g rows per leaf make
     // them M / 2^g permutations against the trace tree's M: they are committed and opened replicated, exactly as prove_impl does
     ZP_ARG(ctx, !bn || sh.rows_per_leaf_log(W) == 0, "BN128 mode shards the trace tree by rows: it needs one row per leaf (more than 28 trace columns)");
+    // "prove_check" (set alike on every rank): zp_stark_prove's check over the ranks -- one more exchange, of the RAW trace, and one verdict
+    const bool check = ctx->tune_prove_check != 0;
+    ZP_ARG(ctx, !check || N / (size_t)G >= 2, "the witness check over the ranks needs at least two trace rows per rank");
     DevBufs dev(ctx);
     Transcript tr(ctx, bn);
     const Trees T{ctx, bn};
     PV_TRY(transcript_head(ctx, sh, tr, T, dev));
+    std::vector<u64> pubchal(a.h_pubs, a.h_pubs + a.n_pubs);
+    if (check) {          // my columns are resident and untouched: the words, and without stage-2 arguments the constraints, before the first extension
+        PV_TRY(prove_check_canonical(ctx, sh, comm));
+        if (!n_s2) PV_TRY(prove_check_constraints(ctx, sh, pubchal, nullptr, nullptr, comm));
+    }
 
     // 1. trace: LDE of my columns, ONE exchange columns -> rows, local subtree, sub-roots
     u64 *ext, *tree1 = nullptr;
@@ -1093,7 +1107,6 @@ int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, bool bn, const ProveArgs 
         memcpy(root1, top1.root, 32);
     }
     tr.absorb_root(root1);
-    std::vector<u64> pubchal(a.h_pubs, a.h_pubs + a.n_pubs);
     const int g2 = sh.rows_per_leaf_log(W2);
     const size_t M2 = M >> g2, W2g = W2 << g2;
     u64 *ext2_kept = nullptr;                     // BN128 mode: the stage-2 extension, whole (its tree's leaves mix rows of all shards)
@@ -1104,26 +1117,9 @@ int32_t prove_sharded_impl(zp_comm *comm, zp_ctx *ctx, bool bn, const ProveArgs 
         u64 *colb, *ext2;
         PV_TRY(dev.alloc(W2 * N, &s2));
         PV_TRY(dev.alloc(3 * N, &colb));           // the (at most three) witness columns an argument reads, on every rank
-        auto column = [&](u64 idx, u64 *dst) -> int32_t {       // broadcast from the rank that owns it
-            const int owner = (int)(idx / wl);
-            if (owner == rank) PV_TRY(zp_d2d(ctx, dst, d_trace + (idx % wl) * N, N * 8));
-            return zp_comm_broadcast(comm, (uint64_t *)dst, N, owner);
-        };
-        size_t at = 0;
-        for (size_t k = 0; k < n_s2; k++) {
-            const u64 *st = sh.pg.stage2 + 4 * k;
-            PV_TRY(column(st[1], colb));
-            PV_TRY(column(st[2], colb + N));
-            if (st[0] == 1) {
-                PV_TRY(zp_grand_product(ctx, (const uint64_t *)colb, (const uint64_t *)(colb + N), N, (const uint64_t *)chal.c, (uint64_t *)(s2 + at * N)));
-                at += 3;
-            } else {
-                PV_TRY(column(st[3], colb + 2 * N));
-                PV_TRY(zp_logup_columns(ctx, (const uint64_t *)colb, (const uint64_t *)(colb + N), (const uint64_t *)(colb + 2 * N), N, (const uint64_t *)chal.c,
-                                        (uint64_t *)(s2 + at * N)));
-                at += 9;
-            }
-        }
+        PV_TRY(zpi_stage2_columns_sharded(comm, sh.pg, (const u64 *)d_trace, logn, chal.c, colb, s2));
+        // the stage-2 columns exist on the trace domain, made with the challenge that binds; nothing has been extended from them yet
+        if (check) PV_TRY(prove_check_constraints(ctx, sh, pubchal, s2, &chal, comm));
         PV_TRY(dev.alloc(W2 * M, &ext2));
         PV_TRY(zp_lde(ctx, (const uint64_t *)s2, (uint64_t *)ext2, nullptr, logn, logb, (int32_t)W2, shift));   // replicated: W2 << W
         ZP_HIP(ctx, hipMemcpy2DAsync(ext + W * nloc, nloc * 8, ext2 + r0, M * 8, nloc * 8, W2, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1433,6 +1429,11 @@ int32_t zp_stark_set_air_kernel_rows(zp_ctx *ctx, const uint64_t *h_program, siz
 int32_t zp_stark_set_air_kernel_witness(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, void *witness_fn) {
     return set_air_kernel(ctx, "witness:", h_program, program_words, witness_fn);
 }
+// ... and its ROW-WINDOW form (`zpair_<air>_quotient_witness_rows`): what a rank of the sharded provers under "prove_check" and of
+// zp_stark_check_witness_sharded judges its rows with.  fn = NULL forgets it.
+int32_t zp_stark_set_air_kernel_witness_rows(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, void *witness_rows_fn) {
+    return set_air_kernel(ctx, "witness_rows:", h_program, program_words, witness_rows_fn);
+}
 
 // The verdict of the LAST proof zp_stark_prove / zp_stark_prove_bn128 checked on this ctx ("prove_check" = 1), accepted or refused: zp_stark_check_witness's
 // report layout, and the stage-2 challenge it was judged at (the transcript's; zeros without stage-2 arguments or when the trace was not canonical).
@@ -1515,7 +1516,9 @@ static int32_t prove_sharded_entry(zp_comm *comm, bool bn, const ProveArgs &a) {
     zp_ctx *ctx = zpi_comm_ctx(comm);
     if (a.out_json) *a.out_json = nullptr;
     if (a.out_len) *a.out_len = 0;
-    return zpi_comm_fail(comm, guarded(ctx, [&] { return prove_sharded_impl(comm, ctx, bn, a); }));
+    const int32_t rc = guarded(ctx, [&] { return prove_sharded_impl(comm, ctx, bn, a); });
+    // a refused witness ("prove_check") is a verdict every rank reached from gathered data, at the same point: the communicator lives on
+    return rc == ZP_ERR_WITNESS ? rc : zpi_comm_fail(comm, rc);
 }
 
 int32_t zp_stark_prove_sharded(zp_comm *comm, const char *air_name, const uint64_t *h_program, size_t program_words, const uint64_t *d_trace_local,

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "witness_merge.hpp"
 
 namespace {
 
@@ -67,16 +68,25 @@ struct WProgArgs {
     const u64 *fixedx, *fx_tab; // one period per sparse column; (offset, index mask) per column
     ull *counts, *first_row, *first_key;
     u64 N, wlast;
+    u64 stride, row0, nrows;    // the row-window form only: trace columns [W][stride], rows [row0, row0 + nrows) of the domain
     int W, lb, n_const, n_instr;
 };
 
+// WINDOW = false: the whole trace domain.  WINDOW = true: rows [row0, row0 + nrows) of it, what one rank of a sharded proof judges
+// (zpi_witness_sharded) -- a trace column is [stride] words, row r at r - row0, and unless nrows == N ONE halo row at index nrows holds row
+// (row0 + nrows) mod N, the next rank's first.  The stage-2 columns stay whole, [W2][N], read at the global row and the global next row; the
+// selectors, the sparse periods, x and every reported row are the GLOBAL row's.  A dead lane walks the window's first row.
+template <bool WINDOW>
 __global__ void __launch_bounds__(256) witness_program_kernel(WProgArgs a) {
     extern __shared__ __attribute__((aligned(16))) u64 slots[];   // [n_slots][256]
     const int tid = threadIdx.x;
-    const u64 r = (u64)blockIdx.x * 256 + tid;
-    const bool live = r < a.N;
-    const u64 rr = live ? r : 0;                                  // a dead lane (N < 256) walks row 0: in bounds, masked out of every ballot
+    const u64 wi = (u64)blockIdx.x * 256 + tid;                   // the row inside the window (the whole domain: the row)
+    const bool live = wi < (WINDOW ? a.nrows : a.N);
+    const u64 ii = live ? wi : 0;                                 // a dead lane walks the first row: in bounds, masked out of every ballot
+    const u64 r = WINDOW ? a.row0 + wi : wi, rr = WINDOW ? a.row0 + ii : ii;
     const u64 rn = (rr + 1) & (a.N - 1);
+    const u64 st = WINDOW ? a.stride : a.N;                       // a trace column's words, where its row and its next row sit
+    const u64 tc = WINDOW ? ii : rr, tn = WINDOW ? (a.nrows == a.N ? rn : ii + 1) : rn;
     const u64 x = gl_mul(a.xs_lo[rr & ((1ULL << a.lb) - 1)], a.xs_hi[rr >> a.lb]);
     const u64 xml = gl_sub(x, a.wlast);
     const u64 *consts = a.prog + ZPH_WORDS, *ins = consts + a.n_const;
@@ -91,8 +101,8 @@ __global__ void __launch_bounds__(256) witness_program_kernel(WProgArgs a) {
             u64 val;
             switch (kind) {
                 case ZPK_SLOT: val = slots[idx * 256 + tid]; break;
-                case ZPK_COL: val = idx < a.W ? a.trace[(u64)idx * a.N + rr] : a.s2[(u64)(idx - a.W) * a.N + rr]; break;
-                case ZPK_NEXT: val = idx < a.W ? a.trace[(u64)idx * a.N + rn] : a.s2[(u64)(idx - a.W) * a.N + rn]; break;
+                case ZPK_COL: val = idx < a.W ? a.trace[(u64)idx * st + tc] : a.s2[(u64)(idx - a.W) * a.N + rr]; break;
+                case ZPK_NEXT: val = idx < a.W ? a.trace[(u64)idx * st + tn] : a.s2[(u64)(idx - a.W) * a.N + rn]; break;
                 case ZPK_FIXED:
                     if (idx == 0) val = rr == 0;
                     else if (idx == 1) val = rr == a.N - 1;
@@ -154,76 +164,83 @@ void zpi_witness_noncanonical_report(size_t K, size_t N, u64 bad_n, u64 bad_at, 
 // (3) the constraints over (trace, GIVEN stage-2 columns on the trace domain, publics then the challenge): one period of every sparse fixed column,
 // then either the generated kernel of this program (AIR plug-in ABI: `<symbol>_witness`, registered under the digest dg32 by
 // zp_stark_set_air_kernel_witness; knob "witness_kernel" = 1; stage "witness_program_gen") with [publics | challenge | 0] as its only upload, or
-// the interpreter over the uploaded program (stage "witness_program").  One result buffer [first key][first_row: K][counts: K], one download.
-// Both callers -- zp_stark_check_witness on a ctx and the one-call provers under "prove_check" -- come through here.  pubchal: publics, then the
-// challenge when the program has stage-2 arguments (a trailing pad word is ignored); dg32 = NULL: no kernel is looked up.
-int32_t zpi_witness_constraints(zp_ctx *ctx, const ZpProgram &pg, const uint8_t *dg32, const std::vector<u64> &pubchal, const u64 *d_trace, const u64 *d_s2,
-                                int logn, uint64_t *h_report, uint64_t *h_counts, uint64_t *h_first_row) {
+// the interpreter over the uploaded program (stage "witness_program").  One result buffer [first key][first_row: K][counts: K].
+// win = NULL: the whole domain, d_trace u64[W][N].  Else rows [win->row0, win->row0 + win->nrows) of it, d_trace u64[W][win->stride] with the halo
+// row (witness_program_kernel<true>); the kernel is `<symbol>_witness_rows` (zp_stark_set_air_kernel_witness_rows), the stages
+// "witness_program_rows_gen" / "witness_program_rows".  d_s2 is whole either way.  pubchal: publics, then the challenge when the program has
+// stage-2 arguments (a trailing pad word is ignored); dg32 = NULL: no kernel is looked up.  The result stays on the device: d_res, 1 + 2 K words.
+int32_t zpi_witness_launch(zp_ctx *ctx, const ZpProgram &pg, const uint8_t *dg32, const std::vector<u64> &pubchal, const u64 *d_trace, const u64 *d_s2,
+                           int logn, const ZpWitnessWindow *win, u64 *d_res) {
     ZP_BIND(ctx);
     ZP_ARG(ctx, logn >= 1 && logn <= 30, "logn out of range");
     for (const ZpFixedCol &fc : pg.fxc) ZP_ARG(ctx, fc.lp <= logn, "fixed column longer than the trace");
     const size_t N = (size_t)1 << logn, K = pg.K, n_pc = pg.n_pub + pg.n_chal;
     ZP_ARG(ctx, pubchal.size() >= n_pc, "publics and challenge shorter than the program's");
+    if (win)      // every index the window form computes stays inside [W][stride]: rows, and the halo unless the window is the domain
+        ZP_ARG(ctx, win->nrows >= 1 && win->row0 + win->nrows <= N && win->stride >= win->nrows + (win->nrows == N ? 0 : 1), "row window outside the trace domain");
     NttPlan *pl;
     ZP_TRY(zpi_get_plan(ctx, logn, false, &pl));
     void *plug = nullptr;
     if (dg32 && ctx->tune_witness_kernel) {
-        auto it = ctx->air_kernels.find(zpi_air_kernel_key("witness:", dg32));
+        auto it = ctx->air_kernels.find(zpi_air_kernel_key(win ? "witness_rows:" : "witness:", dg32));
         if (it != ctx->air_kernels.end()) plug = it->second;
     }
-    const size_t res_words = 1 + 2 * K;
+    ull *res = (ull *)d_res;
+    ZpStage stage_(ctx, win ? (plug ? "witness_program_rows_gen" : "witness_program_rows") : (plug ? "witness_program_gen" : "witness_program"));
+    ZP_HIP(ctx, hipMemsetAsync(res, 0xFF, (1 + K) * 8, ctx->stream));
+    ZP_HIP(ctx, hipMemsetAsync(res + 1 + K, 0, K * 8, ctx->stream));
+    u64 *d_periods = nullptr;
+    size_t period_words = 0;
+    ZP_TRY(zpi_fixed_periods_build(ctx, pg.words, pg.fxc, (const uint64_t *)pubchal.data(), 0, false, &d_periods, &period_words));
+    const u64 wlast = gl_inv(gl_root(ctx->root32, logn));
+    const size_t rows = win ? win->nrows : N;
+    if (plug) {
+        std::vector<u64> ops(pubchal.begin(), pubchal.begin() + n_pc);
+        ops.push_back(0);                         // never empty
+        u64 *d_ops;
+        ZP_TRY(zpi_scratch(ctx, 3, ops.size(), &d_ops));
+        ZP_TRY(zpi_h2d(ctx, d_ops, ops.data(), ops.size() * 8));
+        const uint64_t *s2 = (const uint64_t *)(d_s2 ? d_s2 : d_trace), *periods = (const uint64_t *)(d_periods ? d_periods : d_ops);
+        const int hrc = win ? ((zp_air_witness_rows_fn)plug)((void *)ctx->stream, (const uint64_t *)d_trace, (uint64_t)win->stride, s2, periods, (const uint64_t *)d_ops,
+                                                            (const uint64_t *)pl->d_twl, (const uint64_t *)pl->d_twh, pl->lb, (uint64_t)N, (uint64_t)win->row0,
+                                                            (uint64_t)win->nrows, wlast, (uint64_t *)res)
+                            : ((zp_air_witness_fn)plug)((void *)ctx->stream, (const uint64_t *)d_trace, s2, periods, (const uint64_t *)d_ops, (const uint64_t *)pl->d_twl,
+                                                       (const uint64_t *)pl->d_twh, pl->lb, (uint64_t)N, wlast, (uint64_t *)res);
+        if (hrc != 0) {
+            ctx->err = "generated witness kernel: launch failed (hip error " + std::to_string(hrc) + ")";
+            return ZP_ERR_HIP;
+        }
+    } else {
+        // the upload comes after whatever made the stage-2 columns: those primitives use the same scratch slot
+        ZpProgramDev dv;
+        ZP_TRY(zpi_program_upload(ctx, pg, ZpSpan{pubchal.data(), n_pc}, {}, 0, &dv));
+        WProgArgs a;
+        a.prog = dv.consts - ZPH_WORDS; a.trace = d_trace; a.s2 = d_s2 ? d_s2 : d_trace; a.pub = dv.pubchal; a.fx_tab = dv.fx_tab; a.fixedx = d_periods;
+        a.xs_lo = pl->d_twl; a.xs_hi = pl->d_twh; a.lb = pl->lb;
+        a.first_key = res; a.first_row = res + 1; a.counts = res + 1 + K;
+        a.N = N; a.wlast = wlast;
+        a.stride = win ? win->stride : N; a.row0 = win ? win->row0 : 0; a.nrows = rows;
+        a.W = (int)pg.W; a.n_const = (int)pg.n_const; a.n_instr = (int)pg.n_instr;
+        const dim3 grid((unsigned)((rows + 255) / 256));
+        if (win) hipLaunchKernelGGL(witness_program_kernel<true>, grid, dim3(256), pg.slot_file() * 256 * 8, ctx->stream, a);
+        else hipLaunchKernelGGL(witness_program_kernel<false>, grid, dim3(256), pg.slot_file() * 256 * 8, ctx->stream, a);
+        ZP_HIP(ctx, hipGetLastError());
+    }
+    return ZP_OK;
+}
+
+// ... over the whole domain, with the report.  Both single-GPU callers -- zp_stark_check_witness on a ctx and the one-call provers under
+// "prove_check" -- come through here.
+int32_t zpi_witness_constraints(zp_ctx *ctx, const ZpProgram &pg, const uint8_t *dg32, const std::vector<u64> &pubchal, const u64 *d_trace, const u64 *d_s2,
+                                int logn, uint64_t *h_report, uint64_t *h_counts, uint64_t *h_first_row) {
+    const size_t res_words = zpi_witness_result_words(pg.K);
     void *poolv = nullptr;
     ZP_TRY(zpi_pool_alloc(ctx, res_words * 8, &poolv));
     struct Release { zp_ctx *c; void *p; size_t b; ~Release() { zpi_pool_release(c, p, b); } } release_{ctx, poolv, res_words * 8};
-    ull *res = (ull *)poolv;
     std::vector<u64> out(res_words);
-    {
-        ZpStage stage_(ctx, plug ? "witness_program_gen" : "witness_program");
-        ZP_HIP(ctx, hipMemsetAsync(res, 0xFF, (1 + K) * 8, ctx->stream));
-        ZP_HIP(ctx, hipMemsetAsync(res + 1 + K, 0, K * 8, ctx->stream));
-        u64 *d_periods = nullptr;
-        size_t period_words = 0;
-        ZP_TRY(zpi_fixed_periods_build(ctx, pg.words, pg.fxc, (const uint64_t *)pubchal.data(), 0, false, &d_periods, &period_words));
-        const u64 wlast = gl_inv(gl_root(ctx->root32, logn));
-        if (plug) {
-            std::vector<u64> ops(pubchal.begin(), pubchal.begin() + n_pc);
-            ops.push_back(0);                         // never empty
-            u64 *d_ops;
-            ZP_TRY(zpi_scratch(ctx, 3, ops.size(), &d_ops));
-            ZP_TRY(zpi_h2d(ctx, d_ops, ops.data(), ops.size() * 8));
-            const int hrc = ((zp_air_witness_fn)plug)((void *)ctx->stream, (const uint64_t *)d_trace, (const uint64_t *)(d_s2 ? d_s2 : d_trace),
-                                                      (const uint64_t *)(d_periods ? d_periods : d_ops), (const uint64_t *)d_ops, (const uint64_t *)pl->d_twl,
-                                                      (const uint64_t *)pl->d_twh, pl->lb, (uint64_t)N, wlast, (uint64_t *)res);
-            if (hrc != 0) {
-                ctx->err = "generated witness kernel: launch failed (hip error " + std::to_string(hrc) + ")";
-                return ZP_ERR_HIP;
-            }
-        } else {
-            // the upload comes after whatever made the stage-2 columns: those primitives use the same scratch slot
-            ZpProgramDev dv;
-            ZP_TRY(zpi_program_upload(ctx, pg, ZpSpan{pubchal.data(), n_pc}, {}, 0, &dv));
-            WProgArgs a;
-            a.prog = dv.consts - ZPH_WORDS; a.trace = d_trace; a.s2 = d_s2 ? d_s2 : d_trace; a.pub = dv.pubchal; a.fx_tab = dv.fx_tab; a.fixedx = d_periods;
-            a.xs_lo = pl->d_twl; a.xs_hi = pl->d_twh; a.lb = pl->lb;
-            a.first_key = res; a.first_row = res + 1; a.counts = res + 1 + K;
-            a.N = N; a.wlast = wlast;
-            a.W = (int)pg.W; a.n_const = (int)pg.n_const; a.n_instr = (int)pg.n_instr;
-            hipLaunchKernelGGL(witness_program_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), pg.slot_file() * 256 * 8, ctx->stream, a);
-            ZP_HIP(ctx, hipGetLastError());
-        }
-        ZP_TRY(zpi_d2h(ctx, out.data(), res, res_words * 8));
-    }
-    u64 rep[8] = {ZP_WITNESS_SATISFIED, ~0ULL, ~0ULL, 0, 0, 0, ~0ULL, ~0ULL};
-    const u64 *first = out.data() + 1, *counts = first + K;
-    for (size_t k = 0; k < K; k++) { rep[3] += counts[k]; rep[4] += counts[k] != 0; }
-    if (rep[3]) {
-        rep[0] = ZP_WITNESS_VIOLATED;
-        rep[1] = out[0] >> 24;
-        rep[2] = out[0] & 0xFFFFFF;
-    }
-    memcpy(h_report, rep, sizeof rep);
-    if (h_counts) memcpy(h_counts, counts, K * 8);
-    if (h_first_row) memcpy(h_first_row, first, K * 8);
+    ZP_TRY(zpi_witness_launch(ctx, pg, dg32, pubchal, d_trace, d_s2, logn, nullptr, (u64 *)poolv));
+    ZP_TRY(zpi_d2h(ctx, out.data(), poolv, res_words * 8));
+    zpi_witness_report((const uint64_t *)out.data(), pg.K, h_report, h_counts, h_first_row);
     return ZP_OK;
 }
 

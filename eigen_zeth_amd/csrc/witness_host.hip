@@ -172,45 +172,59 @@ int32_t check_host(const ZpProgram &pg, const std::vector<u64> &pubchal, const u
 
 }  // namespace
 
+// What zp_stark_check_witness and zp_stark_check_witness_sharded (csrc/witness_sharded.hip) require of their arguments, and what they derive from
+// them: the parsed program and [publics | challenge (given, or derived from the program) | 0].  The trace behind `trace` holds the columns of `rank`
+// among `world` (zpi_shard_range; world = 1: all of them) and may be NULL when that is none.  Returns NULL, or why the call is refused.
+const char *zpi_witness_args(const uint64_t *h_program, size_t program_words, const uint64_t *trace, size_t trace_words, int world, int rank,
+                             const uint64_t *h_pubs, int32_t n_pubs, int32_t logn, const uint64_t *h_chal3, const uint64_t *h_report, const uint64_t *h_counts,
+                             const uint64_t *h_first_row, int32_t n_constraints, ZpProgram *pgp, std::vector<u64> *pubchal) {
+    const char *why = "";
+    ZpProgram &pg = *pgp;
+    if (!zpi_program_read(h_program, program_words, ZPG_WITNESS, &pg, &why)) return why;
+    size_t first, cols;
+    zpi_shard_range(pg.W, world, rank, &first, &cols);
+    if ((!trace && cols) || !h_report) return "null pointer";
+    if (logn < 1 || logn > 32) return "logn out of range";
+    if (trace_words != cols << logn) return world == 1 ? "trace_words must be W * 2^logn" : "trace_words must be (this rank's columns) * 2^logn";
+    if (n_pubs < 0 || (size_t)n_pubs != pg.n_pub || (n_pubs && !h_pubs)) return "number of public inputs does not match the program";
+    for (int i = 0; i < n_pubs; i++)
+        if (h_pubs[i] >= GL_P) return "public input not canonical";
+    for (const ZpFixedCol &fc : pg.fxc)
+        if (fc.lp > logn) return "fixed column longer than the trace";
+    if ((h_counts || h_first_row) && (n_constraints < 0 || (size_t)n_constraints != pg.K)) return "n_constraints is not the program's";
+    pubchal->assign(h_pubs, h_pubs + n_pubs);
+    if (pg.n_s2) {
+        u64 g[3];
+        if (h_chal3) {
+            for (int c = 0; c < 3; c++) {
+                if (h_chal3[c] >= GL_P) return "challenge not canonical";
+                g[c] = h_chal3[c];
+            }
+        } else {                      // derived from the statement: finds mistakes, binds nobody (the header says so)
+            uint8_t dg[32];
+            Sha256::digest((const uint8_t *)h_program, program_words * 8, dg);
+            for (int i = 0; i < 3; i++) { u64 x = 0; for (int b = 7; b >= 0; b--) x = (x << 8) | dg[8 * i + b]; g[i] = x % GL_P; }
+            if (g[1] == 0 && g[2] == 0) g[1] = 1;       // outside the base field: value + g is never 0
+        }
+        pubchal->insert(pubchal->end(), g, g + 3);
+    }
+    pubchal->push_back(0);            // never empty: both paths take its address
+    return nullptr;
+}
+
 extern "C" int32_t zp_stark_check_witness(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const uint64_t *trace, size_t trace_words,
                                           const uint64_t *h_pubs, int32_t n_pubs, int32_t logn, const uint64_t *h_chal3, uint64_t *h_report,
                                           uint64_t *h_counts, uint64_t *h_first_row, int32_t n_constraints, int32_t threads) {
-    const char *why = "";
-    auto refuse = [&](const char *msg) {
-        if (ctx) {
-            try { ctx->err = std::string("bad argument: ") + msg; } catch (...) {}
-        }
-        return (int32_t)ZP_ERR_ARG;
-    };
     try {
         ZpProgram pg;
-        if (!zpi_program_read(h_program, program_words, ZPG_WITNESS, &pg, &why)) return refuse(why);
-        if (!trace || !h_report) return refuse("null pointer");
-        if (logn < 1 || logn > 32) return refuse("logn out of range");
-        if (trace_words != pg.W << logn) return refuse("trace_words must be W * 2^logn");
-        if (n_pubs < 0 || (size_t)n_pubs != pg.n_pub || (n_pubs && !h_pubs)) return refuse("number of public inputs does not match the program");
-        for (int i = 0; i < n_pubs; i++)
-            if (h_pubs[i] >= GL_P) return refuse("public input not canonical");
-        for (const ZpFixedCol &fc : pg.fxc)
-            if (fc.lp > logn) return refuse("fixed column longer than the trace");
-        if ((h_counts || h_first_row) && (n_constraints < 0 || (size_t)n_constraints != pg.K)) return refuse("n_constraints is not the program's");
-        std::vector<u64> pubchal(h_pubs, h_pubs + n_pubs);
-        if (pg.n_s2) {
-            u64 g[3];
-            if (h_chal3) {
-                for (int c = 0; c < 3; c++) {
-                    if (h_chal3[c] >= GL_P) return refuse("challenge not canonical");
-                    g[c] = h_chal3[c];
-                }
-            } else {                      // derived from the statement: finds mistakes, binds nobody (the header says so)
-                uint8_t dg[32];
-                Sha256::digest((const uint8_t *)h_program, program_words * 8, dg);
-                for (int i = 0; i < 3; i++) { u64 x = 0; for (int b = 7; b >= 0; b--) x = (x << 8) | dg[8 * i + b]; g[i] = x % GL_P; }
-                if (g[1] == 0 && g[2] == 0) g[1] = 1;       // outside the base field: value + g is never 0
+        std::vector<u64> pubchal;
+        if (const char *why = zpi_witness_args(h_program, program_words, trace, trace_words, 1, 0, h_pubs, n_pubs, logn, h_chal3, h_report, h_counts, h_first_row,
+                                               n_constraints, &pg, &pubchal)) {
+            if (ctx) {
+                try { ctx->err = std::string("bad argument: ") + why; } catch (...) {}
             }
-            pubchal.insert(pubchal.end(), g, g + 3);
+            return ZP_ERR_ARG;
         }
-        pubchal.push_back(0);             // never empty: both paths take its address
         if (ctx) {
             if (!zpi_witness_check_device) { ctx->err = "this build has no device witness check"; return ZP_ERR_UNSUPPORTED; }
             return zpi_witness_check_device(ctx, pg, pubchal, (const u64 *)trace, logn, h_report, h_counts, h_first_row);

@@ -75,6 +75,7 @@ SIGNATURES = {
     "zp_stark_set_air_kernel": (C.c_int32, [C.c_void_p, _u64p, C.c_size_t, C.c_void_p]),
     "zp_stark_set_air_kernel_rows": (C.c_int32, [C.c_void_p, _u64p, C.c_size_t, C.c_void_p]),
     "zp_stark_set_air_kernel_witness": (C.c_int32, [C.c_void_p, _u64p, C.c_size_t, C.c_void_p]),
+    "zp_stark_set_air_kernel_witness_rows": (C.c_int32, [C.c_void_p, _u64p, C.c_size_t, C.c_void_p]),
     "zp_stark_prove_witness_report": (C.c_int32, [_vp, _u64p, _u64p, _u64p, _u64p, C.c_int32]),
     "zp_poseidon_sponge": (C.c_int32, [_vp, _u64p, _u64p, C.c_size_t, C.c_size_t, _u64p]),
     "zp_poseidon_sponge_caps": (C.c_int32, [_vp, _u64p, _u64p, C.c_size_t, C.c_size_t, _u64p, _u64p]),
@@ -198,6 +199,7 @@ SIGNATURES = {
     "zp_groth16_verify": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.POINTER(C.c_int32)]),
     "zp_groth16_verify_batch": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, C.c_int32, _vp]),
     "zp_stark_check_witness": (C.c_int32, [_vp, _u64p, C.c_size_t, _vp, C.c_size_t, _u64p, C.c_int32, C.c_int32, _u64p, _u64p, _u64p, _u64p, C.c_int32, C.c_int32]),
+    "zp_stark_check_witness_sharded": (C.c_int32, [_vp, _u64p, C.c_size_t, _vp, C.c_size_t, _u64p, C.c_int32, C.c_int32, _u64p, _u64p, _u64p, _u64p, C.c_int32]),
 }
 
 
@@ -376,7 +378,7 @@ def program_eval_ext(program, pubchal, logn, root32, zeta, ev_z, ev_zw, threads=
 
 
 WITNESS_SATISFIED, WITNESS_VIOLATED, WITNESS_NONCANONICAL = range(3)
-ZP_ERR_WITNESS = -7     # zp_stark_prove / zp_stark_prove_bn128 under set_tuning("prove_check", 1): a false witness, no proof (include/zeth_prover.h)
+ZP_ERR_WITNESS = -7     # zp_stark_prove / zp_stark_prove_bn128 / the sharded provers under set_tuning("prove_check", 1): a false witness, no proof (include/zeth_prover.h)
 _NONE64 = (1 << 64) - 1
 
 
@@ -414,7 +416,8 @@ class WitnessError(ValueError):
         self.report = report
 
 
-def _check_witness(ctx, program, trace_ptr, trace_words, pubs, logn, chal, threads):
+def _check_witness(ctx, program, trace_ptr, trace_words, pubs, logn, chal, threads, comm=None):
+    """comm: a zp_comm handle -- zp_stark_check_witness_sharded on it (trace_ptr = this rank's columns) instead of zp_stark_check_witness on ctx"""
     prog = np.ascontiguousarray(np.asarray(program, dtype=np.uint64))
     if prog.ndim != 1 or prog.size < 12:
         return -1, None
@@ -427,8 +430,8 @@ def _check_witness(ctx, program, trace_ptr, trace_words, pubs, logn, chal, threa
         return -1, None
     rep, counts, first = np.zeros(8, dtype=np.uint64), np.zeros(max(K, 1), dtype=np.uint64), np.zeros(max(K, 1), dtype=np.uint64)
     p = lambda a: a.ctypes.data_as(_u64p)
-    rc = load_library().zp_stark_check_witness(ctx, p(prog), prog.size, trace_ptr, trace_words, p(pb), len(pb) - 1, logn, None if ch is None else p(ch), p(rep),
-                                               p(counts), p(first), K, threads)
+    head = (p(prog), prog.size, trace_ptr, trace_words, p(pb), len(pb) - 1, logn, None if ch is None else p(ch), p(rep), p(counts), p(first), K)
+    rc = load_library().zp_stark_check_witness_sharded(comm, *head) if comm is not None else load_library().zp_stark_check_witness(ctx, *head, threads)
     return rc, (WitnessReport(rep, counts[:K], first[:K]) if rc == 0 else None)
 
 
@@ -889,13 +892,24 @@ class Comm:
                 fri_final_log, n_queries)
         if bn128:
             assert pow_bits == 0
-            self.prover._chk(self.prover.lib.zp_stark_prove_sharded_bn128(*head, C.byref(out), C.byref(n)))
+            self.prover._chk_proof(self.prover.lib.zp_stark_prove_sharded_bn128(*head, C.byref(out), C.byref(n)), prog)
         else:
-            self.prover._chk(self.prover.lib.zp_stark_prove_sharded(*head, pow_bits, C.byref(out), C.byref(n)))
+            self.prover._chk_proof(self.prover.lib.zp_stark_prove_sharded(*head, pow_bits, C.byref(out), C.byref(n)), prog)
         try:
             return C.string_at(out.value, n.value).decode()
         finally:
             self.prover.lib.zp_free_buffer(out)
+
+    def check_witness_sharded(self, program, d_trace_local, pubs, logn, chal=None):
+        """zp_stark_check_witness_sharded: this rank's columns of the trace (my_columns; None when it has none) against the program -> the
+        WitnessReport of the WHOLE trace, the same on every rank.  Collective: every rank calls it"""
+        prog = np.asarray(program, dtype=np.uint64)
+        if prog.ndim != 1 or prog.size < 12:
+            raise ZpError(-1, "zp_stark_check_witness_sharded: malformed program")
+        words = d_trace_local.n if isinstance(d_trace_local, DeviceBuffer) else self.my_columns(int(prog[1]))[1] << logn
+        rc, rep = _check_witness(None, prog, _ptr(d_trace_local), words, pubs, logn, chal, 0, comm=self.h)
+        self.prover._chk(rc)
+        return rep
 
     def close(self):
         if self.h:
@@ -1310,7 +1324,8 @@ class Prover:
             self.lib.zp_free_buffer(out)
 
     def _chk_proof(self, rc, prog):
-        """a one-call prover's return code: ZP_ERR_WITNESS ("prove_check") becomes WitnessError with the report attached"""
+        """a one-call prover's return code (sharded ones included: the report is on this rank's ctx): ZP_ERR_WITNESS ("prove_check") becomes WitnessError
+        with the report attached"""
         if rc == ZP_ERR_WITNESS:
             raise WitnessError(self.prove_witness_report(int(prog[8])))      # its line is zp_last_error's (compared in tests/test_gpu_witness_inproof.py)
         self._chk(rc)
@@ -1508,6 +1523,13 @@ class Prover:
         blob = np.ascontiguousarray(program, dtype=np.uint64)
         addr = C.cast(fn, C.c_void_p).value if fn is not None else None
         self._chk(self.lib.zp_stark_set_air_kernel_rows(self.ctx, blob.ctypes.data_as(_u64p), blob.size, addr))
+
+    def set_air_kernel_witness_rows(self, program, fn):
+        """zp_stark_set_air_kernel_witness_rows: the row-window witness form (`<symbol>_witness_rows`), for the sharded provers of this ctx under
+        set_tuning("prove_check", 1) and for Comm.check_witness_sharded; set_tuning("witness_kernel", 0) keeps the interpreter"""
+        blob = np.ascontiguousarray(np.asarray(program, dtype=np.uint64))
+        addr = C.cast(fn, C.c_void_p) if fn is not None else None
+        self._chk(self.lib.zp_stark_set_air_kernel_witness_rows(self.ctx, blob.ctypes.data_as(_u64p), blob.size, addr))
 
     def set_air_kernel_witness(self, program, fn):
         """zp_stark_set_air_kernel_witness: the witness form of the generated constraint kernel (`<symbol>_witness`), for check_witness on this ctx and

@@ -86,8 +86,9 @@ class EngineConfig:
         # well-formed text that no verifier accepts.  Off by default: no extra call, launch, byte or timing.  What it costs: DESIGN.md par.5.
         # check_witness="prove": the check runs INSIDE the one-call provers instead (zp_set_tuning "prove_check" on the backends' contexts: canonical
         # words, then the constraints at the proof's own stage-2 challenge, on the stage-2 columns the proof makes anyway); a refusal (ZP_ERR_WITNESS)
-        # is the same WitnessError.  A proof that does not go through a one-call prover of a single ctx (the Python orchestration, the sharded final
-        # STARK) is checked by the separate call as under True.
+        # is the same WitnessError.  The sharded final STARK (final_ranks > 1) checks itself the same way, over its ranks (one more exchange and one
+        # verdict: csrc/witness_sharded.hip).  A proof that does not go through a one-call prover (the Python orchestration) is checked by the
+        # separate call as under True.
         self.check_witness = check_witness
         # GenFinalProof: run the native Groth16 verifier (zp_groth16_verify) on the proof about to be returned and raise unless it is accepted
         # ("groth16/verify" in the stage clock).  Off by default: no response and no timing changes.
@@ -290,10 +291,12 @@ class Engine:
             raise WitnessError(report)
 
     def _check_in_proof(self, be, sharded=False):
-        """cfg.check_witness == "prove": True when the proof about to be made on `be` checks its own trace (the knob is set on its ctx)"""
-        if self.cfg.check_witness != "prove" or sharded or not (self.cfg.native_prover and hasattr(be, "prove_native") and hasattr(be, "p")):
+        """cfg.check_witness == "prove": True when the proof about to be made on `be` checks its own trace (the knob is set on its ctx; a sharded
+        proof's rank ctxs get it from prove_native_sharded(check=True))"""
+        if self.cfg.check_witness != "prove" or not (self.cfg.native_prover and hasattr(be, "prove_native") and hasattr(be, "p")):
             return False
-        be.p.set_tuning("prove_check", 1)
+        if not sharded:
+            be.p.set_tuning("prove_check", 1)
         return True
 
     @staticmethod
@@ -581,12 +584,13 @@ class Engine:
         self._last_verifier_pubs = pubs                 # the public inputs of the STARK made next (GenFinalProof's wrap needs the final STARK's)
         params = params_of(shape)
         sharded = self.cfg.native_prover and self.cfg.final_ranks > 1 and params.hash == "bn128" and hasattr(be, "prove_native_sharded")
-        if self.cfg.check_witness and not self._check_in_proof(be, sharded):
+        in_proof = bool(self.cfg.check_witness) and self._check_in_proof(be, sharded)
+        if self.cfg.check_witness and not in_proof:
             self._check_witness(be, vair, trace, pubs, timings)
         t0 = time.perf_counter()
         self._sharded_openings = None
         if sharded:
-            text, self._sharded_openings = be.prove_native_sharded(vair, trace, pubs, params, self.cfg.final_ranks, self.cfg.final_devices)
+            text, self._sharded_openings = be.prove_native_sharded(vair, trace, pubs, params, self.cfg.final_ranks, self.cfg.final_devices, check=in_proof)
         elif self.cfg.native_prover and hasattr(be, "prove_native"):
             text = be.prove_native(vair, trace, pubs, params)
         else:

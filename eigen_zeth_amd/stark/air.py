@@ -510,9 +510,11 @@ class _WitnessEmitter(_Emitter):
     """the same straight-line code on the TRACE domain: a column or a fixed column is loaded where it is first named (a constraint's operands
     are live from there on, not from the top of the kernel), a sparse fixed column from its one period"""
 
-    def __init__(self, air):
+    def __init__(self, air, stride="N", cur="rr", nxt="rn"):
         super().__init__(air.n_pub)
         self.width = air.width
+        # a TRACE column is read at [column * stride + cur / nxt]; a stage-2 column, the selectors and the periods always at the global row rr / rn
+        self.stride, self.cur, self.nxt = stride, cur, nxt
         self.periods, acc = {}, 0          # zpi_fixed_periods_build without selectors: one period behind the other
         for k, fc in enumerate(air.fixed_cols):
             self.periods[2 + k] = (acc, (1 << fc.lp) - 1)
@@ -521,14 +523,25 @@ class _WitnessEmitter(_Emitter):
     def emit(self, e):
         if isinstance(e, (Col, Fixed)) and e.key() not in self.memo:
             if isinstance(e, Col):
-                base, i = ("trace", e.i) if e.i < self.width else ("s2", e.i - self.width)
-                self.lines.append("    const u64 c%d%s = %s[(u64)%d * N + %s];" % (e.i, "n" if e.nxt else "", base, i, "rn" if e.nxt else "rr"))
+                base, i, st, at = ("trace", e.i, self.stride, (self.cur, self.nxt)) if e.i < self.width else ("s2", e.i - self.width, "N", ("rr", "rn"))
+                self.lines.append("    const u64 c%d%s = %s[(u64)%d * %s + %s];" % (e.i, "n" if e.nxt else "", base, i, st, at[1] if e.nxt else at[0]))
             elif isinstance(e, Fixed):
                 if e.i < 2:
                     self.lines.append("    const u64 f%d = rr == %s;" % (e.i, "0" if e.i == 0 else "N - 1"))
                 else:
                     self.lines.append("    const u64 f%d = fixedx[%dULL + (rr & %dULL)];" % ((e.i,) + self.periods[e.i]))
         return super().emit(e)
+
+
+# one lane per violated (wave, constraint) reports: shared by both witness forms (each is a translation unit of its own)
+_ZPW_REPORT = ("#ifndef ZPW_REPORT\n#define ZPW_REPORT\n"
+               "__device__ __forceinline__ void zpw_report(unsigned long long *res, int K, int k, u64 v, bool live, u64 r) {\n"
+               "    const unsigned long long m = __ballot(live && v != 0);      // wave-uniform\n"
+               "    if (m != 0 && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) {     // the lowest violating lane: its row is the wave's smallest\n"
+               "        atomicAdd(&res[1 + K + k], (unsigned long long)__popcll(m));\n"
+               "        atomicMin(&res[1 + k], (unsigned long long)r);\n"
+               "        atomicMin(&res[0], ((unsigned long long)r << 24) | (unsigned long long)k);\n"
+               "    }\n}\n#endif\n")
 
 
 def emit_witness_source(air):
@@ -551,14 +564,7 @@ def emit_witness_source(air):
     return ("// generated by eigen_zeth_amd/stark/air.py for AIR '%s' (digest %s) -- do not edit\n"
             "// row-parallel constraint CHECK on the trace domain: lane = trace row, %d constraints, result [first key][first_row: K][counts: K].\n"
             % (air.name, air.digest(), K)
-            + "#ifndef ZPW_REPORT\n#define ZPW_REPORT\n"
-            "__device__ __forceinline__ void zpw_report(unsigned long long *res, int K, int k, u64 v, bool live, u64 r) {\n"
-            "    const unsigned long long m = __ballot(live && v != 0);      // wave-uniform\n"
-            "    if (m != 0 && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) {     // the lowest violating lane: its row is the wave's smallest\n"
-            "        atomicAdd(&res[1 + K + k], (unsigned long long)__popcll(m));\n"
-            "        atomicMin(&res[1 + k], (unsigned long long)r);\n"
-            "        atomicMin(&res[0], ((unsigned long long)r << 24) | (unsigned long long)k);\n"
-            "    }\n}\n#endif\n"
+            + _ZPW_REPORT
             + "template <bool REPORT>\n__device__ __forceinline__ u64 %s_body(%s) {\n    u64 any = 0;\n%s\n    return any;\n}\n"
             % (sym, ops, "\n".join(em.lines))
             # the reporting instance stays OUT of line: inlined next to the plain one the compiler keeps every constraint value of the first walk
@@ -577,4 +583,47 @@ def emit_witness_source(air):
             + 'extern "C" int %s(void *stream, %s) {\n' % (sym, kargs.replace("__restrict__ ", ""))
             + "    hipLaunchKernelGGL(%s_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,\n" % sym
             + "                       trace, s2, fixedx, pub, xs_lo, xs_hi, lb, N, wlast, res);\n"
+            "    return (int)hipGetLastError();\n}\n")
+
+
+def emit_witness_rows_source(air):
+    """emit_witness_source's check for a ROW WINDOW of the trace domain, exported as air.symbol + "_witness_rows": a rank of a sharded proof judges
+    rows [row0, row0 + nrows) of the N-row domain.  Trace columns are [W][st]; local row i = r - row0; unless the window is the whole domain every
+    column carries ONE halo row at index nrows (row (row0 + nrows) mod N, the next rank's first).  The stage-2 columns are whole ([W2][N], replicated)
+    and read at the global row and the global next row; selectors, sparse periods, x = w_N^r and the reported row are the GLOBAL row's.  Same
+    two-instance template, same result buffer; a file of its own (generated/<air>_witness_rows.hip), compiled into the AIR's library."""
+    em = _WitnessEmitter(air, stride="st", cur="i", nxt="in")
+    K = len(air.constraints)
+    for k, c in enumerate(air.constraints):
+        o = em.emit(c)
+        em.lines.append("    if (REPORT) zpw_report(res, %d, %d, %s, live, r); else any |= %s;" % (K, k, o, o))
+    sym = air.symbol + "_witness_rows"
+    ops = ("const u64 *__restrict__ trace, u64 st, const u64 *__restrict__ s2, const u64 *__restrict__ fixedx, const u64 *__restrict__ pub, u64 N, "
+           "u64 r, u64 rr, u64 rn, u64 i, u64 in, u64 xml, bool live, unsigned long long *res")
+    call = "trace, st, s2, fixedx, pub, N, r, rr, rn, i, in, xml, live, res"
+    kargs = ("const u64 *__restrict__ trace, u64 st, const u64 *__restrict__ s2, const u64 *__restrict__ fixedx, const u64 *__restrict__ pub, "
+             "const u64 *__restrict__ xs_lo, const u64 *__restrict__ xs_hi, int lb, u64 N, u64 row0, u64 nrows, u64 wlast, unsigned long long *res")
+    return ("// generated by eigen_zeth_amd/stark/air.py for AIR '%s' (digest %s) -- do not edit\n"
+            "// row-parallel constraint CHECK on a row window of the trace domain: lane = window row, %d constraints, result [first key][first_row: K][counts: K].\n"
+            % (air.name, air.digest(), K)
+            + '#include <hip/hip_runtime.h>\n#include "gl.hpp"\n'
+            + _ZPW_REPORT
+            + "template <bool REPORT>\n__device__ __forceinline__ u64 %s_body(%s) {\n    u64 any = 0;\n%s\n    return any;\n}\n"
+            % (sym, ops, "\n".join(em.lines))
+            # out of line for the reason emit_witness_source gives
+            + "__device__ __noinline__ void %s_report(%s) {\n    (void)%s_body<true>(%s);\n}\n" % (sym, ops, sym, call)
+            + "__global__ void __launch_bounds__(256) %s_kernel(%s) {\n" % (sym, kargs)
+            + "    const u64 i0 = (u64)blockIdx.x * 256 + threadIdx.x;\n"
+            "    const bool live = i0 < nrows;\n"
+            "    const u64 i = live ? i0 : 0;          // a dead lane walks the window's first row: in bounds, masked out of every ballot\n"
+            "    const u64 r = row0 + i0, rr = row0 + i;          // GLOBAL rows: the reported one, the one every operand but a trace column is read at\n"
+            "    const u64 rn = (rr + 1) & (N - 1);\n"
+            "    const u64 in = nrows == N ? rn : i + 1;          // a window that is not the whole domain: the halo row sits at index nrows\n"
+            "    const u64 xml = gl_sub(gl_mul(xs_lo[rr & ((1ULL << lb) - 1)], xs_hi[rr >> lb]), wlast);\n"
+            + "    const u64 any = %s_body<false>(%s);\n" % (sym, call)
+            + "    if (__ballot(live && any != 0) == 0) return;          // whole waves: an honest window ends here, no atomic issued\n"
+            + "    %s_report(%s);\n}\n" % (sym, call)
+            + 'extern "C" int %s(void *stream, %s) {\n' % (sym, kargs.replace("__restrict__ ", ""))
+            + "    hipLaunchKernelGGL(%s_kernel, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, (hipStream_t)stream,\n" % sym
+            + "                       trace, st, s2, fixedx, pub, xs_lo, xs_hi, lb, N, row0, nrows, wlast, res);\n"
             "    return (int)hipGetLastError();\n}\n")

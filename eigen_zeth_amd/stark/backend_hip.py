@@ -231,14 +231,16 @@ class HipBackend:
             if d_tr is not trace:
                 d_tr.free()
 
-    def prove_native_sharded(self, air, trace, pubs, params, ranks, devices=None):
+    def prove_native_sharded(self, air, trace, pubs, params, ranks, devices=None, check=False):
         """ONE proof over `ranks` thread-ranks of this process (zp_stark_prove_sharded / zp_stark_prove_sharded_bn128 on an in-process
         communicator, csrc/comm.hip: zp_comm_create_local): rank r drives devices[r] with a ctx of its own (default: every rank on this
         backend's GPU -- the ranks then share its CUs, which is a rehearsal, not a speed-up).  Rank r takes ITS columns of the trace
         (ceil(W / ranks) per rank, the tail ranks fewer: 47 columns of a verifier AIR over 8 ranks = 6 x 7 + 5).  Returns (proof text --
         byte-identical to prove_native's --, rank 0's binary openings record in BN128 mode, else None).  Round 6: every rank evaluates its row
         window of the quotient through the AIR's GENERATED kernel (`<symbol>_rows`, zp_stark_set_air_kernel_rows) when this backend runs in
-        kernel mode and the AIR's library exists; the interpreter serves otherwise -- same proof bytes."""
+        kernel mode and the AIR's library exists; the interpreter serves otherwise -- same proof bytes.
+        check: the proof checks its own trace over the ranks ("prove_check" on every rank's ctx, the generated `<symbol>_witness_rows` where there
+        is one); a false witness raises native.WitnessError with rank 0's report (every rank's is the same) and no proof is made."""
         assert self.hash_mode == params.hash and ranks >= 1 and (ranks & (ranks - 1)) == 0
         bn = params.hash == "bn128"
         devs = list(devices) if devices else [self.p_device] * ranks
@@ -252,14 +254,16 @@ class HipBackend:
         group = native.CommGroup(ranks)
         texts, errs, rec = [None] * ranks, [None] * ranks, [None]
         prog, pl = air.program(), [int(v) for v in pubs]
-        rows_fn = None
+        rows_fn = wrows_fn = None
         if self.quotient_mode == "kernel" and (not air.fixed_cols or os.path.exists(build_airs.lib_path(air))):
             try:
-                rows_fn = self._airlib_rows(air)
+                rows_fn, wrows_fn = self._airlib_rows(air), self._airlib_witness_rows(air)
             except (OSError, RuntimeError, AttributeError, subprocess.CalledProcessError):
-                rows_fn = None
+                rows_fn = wrows_fn = None
         for _, q in provers:
             q.set_air_kernel_rows(prog, rows_fn)
+            q.set_air_kernel_witness_rows(prog, wrows_fn)
+            q.set_tuning("prove_check", 1 if check else 0)      # the rank ctxs outlive the call: set both ways, alike on every rank
 
         def body(r):
             q = provers[r][1]
@@ -279,7 +283,7 @@ class HipBackend:
                     rec[0] = q.stark_openings()
             except BaseException as e:                      # noqa: every rank's error is looked at below
                 errs[r] = e
-                if c is not None:
+                if c is not None and not isinstance(e, native.WitnessError):      # a refused witness is every rank's verdict: nobody waits
                     try:
                         c.abort()                           # the peers are inside the same collective call: free them
                     except Exception:
@@ -462,7 +466,8 @@ class HipBackend:
 
     def _airlib_form(self, air, form):
         """another entry point of the AIR's generated library: "rows" = the quotient's row window, "witness" = the constraint check on the trace
-        domain (one library, three symbols: stark/air.py emit_quotient_source + emit_witness_source)"""
+        domain, "witness_rows" = that check on a row window (one library, four symbols: stark/air.py emit_quotient_source + emit_witness_source,
+        emit_witness_rows_source)"""
         k = (air.name, air.digest(), form)
         if k not in self._airlibs:
             lib = C.CDLL(build_airs.build_air(air))
@@ -476,6 +481,9 @@ class HipBackend:
 
     def _airlib_witness(self, air):
         return self._airlib_form(air, "witness")
+
+    def _airlib_witness_rows(self, air):
+        return self._airlib_form(air, "witness_rows")
 
     def compile_air_kernel(self, air):
         """generate, compile (hipcc: seconds to a minute for a verifier AIR) and load the constraint kernel of `air` and hand it to the one-call

@@ -1,5 +1,5 @@
 """Generates and compiles the constraint kernels of the built-in AIRs for gfx950:
-generated/<air>.hip -> generated/libzpair_<air>.so (AIR plug-in ABI, include/zeth_prover.h)."""
+generated/<air>.hip + generated/<air>_witness_rows.hip -> generated/libzpair_<air>.so (AIR plug-in ABI, include/zeth_prover.h)."""
 import os
 import subprocess
 import sys
@@ -18,18 +18,23 @@ def lib_path(air):
     return os.path.join(GEN, "libzpair_%s.so" % _stem(air))
 
 
-def build_air(air, force=False):
-    from .air import emit_quotient_source, emit_witness_source
-    os.makedirs(GEN, exist_ok=True)
-    src = os.path.join(GEN, _stem(air) + ".hip")
-    code = emit_quotient_source(air, "hip") + emit_witness_source(air)      # one library, three symbols: <symbol>, <symbol>_rows, <symbol>_witness
-    if force or not os.path.exists(src) or open(src).read() != code:
-        with open(src, "w") as f:
+def _write(path, code, force):
+    if force or not os.path.exists(path) or open(path).read() != code:
+        with open(path, "w") as f:
             f.write(code)
+    return path
+
+
+def build_air(air, force=False):
+    from .air import emit_quotient_source, emit_witness_source, emit_witness_rows_source
+    os.makedirs(GEN, exist_ok=True)
+    # one library, four symbols: <symbol>, <symbol>_rows, <symbol>_witness from <stem>.hip; <symbol>_witness_rows from a file of its own
+    srcs = [_write(os.path.join(GEN, _stem(air) + ".hip"), emit_quotient_source(air, "hip") + emit_witness_source(air), force),
+            _write(os.path.join(GEN, _stem(air) + "_witness_rows.hip"), emit_witness_rows_source(air), force)]
     out = lib_path(air)
-    if force or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(os.path.join(CSRC, "gl.hpp"))):
+    if force or not os.path.exists(out) or os.path.getmtime(out) < max([os.path.getmtime(s) for s in srcs] + [os.path.getmtime(os.path.join(CSRC, "gl.hpp"))]):
         subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950",
-                               "-I", CSRC, "-o", out, src])
+                               "-I", CSRC, "-o", out] + srcs)
     return out
 
 

@@ -8,13 +8,13 @@
 //   with rank / world / id-file: ONE proof over `world` GPUs, one process per GPU (zp_stark_prove_sharded on an RCCL communicator; rank 0
 //   publishes the 128-byte RCCL id in <id-file>, the others wait for the record that carries this run's nonce: host/rendezvous.hpp).  Rank r reads only ITS columns of trace.bin (ceil(W / world) per rank, the tail ranks fewer) and drives GPU r;
 //   every rank obtains the same proof text (rank 0 writes <out.json>), byte for byte the single-GPU text.
-//   --check (anywhere on the line): before proving, zp_stark_check_witness judges the trace against the program -- on the GPU, in HBM, for one
-//   process; on the host for a sharded run, where no rank holds all columns -- and prints the report as ONE JSON line
+//   --check (anywhere on the line): before proving, zp_stark_check_witness judges the trace against the program on the GPU, in HBM -- in a sharded
+//   run zp_stark_check_witness_sharded, every rank on ITS columns, all with the same report -- and prints the report (rank 0) as ONE JSON line
 //   {"witness_check":{"verdict":..,"first_row":..,"first_constraint":..,"violations":..,"violated_constraints":..,"noncanonical":..,
 //   "first_noncanonical":[column,row]}} (null where the report says none); a trace that is not satisfied ends the run with exit status 3, unproven.
-//   --check-prove (one process only): the check runs INSIDE the proof instead (zp_set_tuning "prove_check": canonical words, then the constraints at
-//   the proof's own stage-2 challenge); the same JSON line (zp_stark_prove_witness_report) in front of the result, and a refusal (ZP_ERR_WITNESS)
-//   ends the run with exit status 3, unproven.
+//   --check-prove: the check runs INSIDE the proof instead (zp_set_tuning "prove_check": canonical words, then the constraints at the proof's own
+//   stage-2 challenge; a sharded run checks over its ranks); the same JSON line (zp_stark_prove_witness_report; rank 0 prints it) in front of the
+//   result, and a refusal (ZP_ERR_WITNESS, on every rank) ends the run with exit status 3, unproven.
 //   program.bin : the constraint program blob (u64 words, layout in the header)
 //   trace.bin   : u64[W][2^logn] column-major, canonical values
 //   publics.bin : u64[n_pub]
@@ -92,14 +92,8 @@ int main(int argc, char **argv) {
     for (uint64_t v : trace)
         if (!check && !check_prove && v >= 0xFFFFFFFF00000001ULL) { fprintf(stderr, "%s: non-canonical trace value (precondition of zp_stark_prove)\n", argv[2]); return 2; }
     if (world < 1 || rank < 0 || rank >= world) { fprintf(stderr, "bad rank / world\n"); return 2; }
-    if (check_prove && sharded) { fprintf(stderr, "--check-prove: the sharded provers do not check their trace; use --check\n"); return 2; }
     zp_ctx *ctx = nullptr;
     uint64_t report[8];
-    if (check && sharded) {                            // every rank reads the whole file: each judges it on the host and they agree
-        CHECK(zp_stark_check_witness(nullptr, program.data(), program.size(), trace.data(), trace.size(), pubs.data(), (int32_t)pubs.size(), logn, nullptr, report,
-                                     nullptr, nullptr, 0, 0));
-        if (rank == 0 ? !print_report(report) : report[0] != ZP_WITNESS_SATISFIED) return 3;
-    }
     CHECK(zp_create(&ctx, rank));                      // one process per GPU: rank r drives device r
     // rank r owns columns [r wl, min((r + 1) wl, W)), wl = ceil(W / world): the tail ranks hold fewer columns, or none (include/zeth_prover.h)
     const size_t Wc = (size_t)prog_w, wl = (Wc + (size_t)world - 1) / (size_t)world, c0 = (size_t)rank * wl < Wc ? (size_t)rank * wl : Wc,
@@ -120,6 +114,12 @@ int main(int argc, char **argv) {
     char *json = nullptr;
     size_t len = 0;
     zp_comm *comm = nullptr;
+    auto give_up = [&](int status) {                   // a run that ends without a proof
+        if (comm) zp_comm_destroy(comm);
+        zp_dev_free(ctx, d_trace);
+        zp_destroy(ctx);
+        return status;
+    };
     if (sharded) {
         uint8_t id[128];
         const uint64_t nonce = argc > 15 ? strtoull(argv[15], nullptr, 0) : 0;
@@ -132,22 +132,24 @@ int main(int argc, char **argv) {
         }
         CHECK(zp_comm_create(ctx, rank, world, id, &comm));
         if (rank == 0) zp_rendezvous::retire(argv[14]);
-        CHECK(zp_stark_prove_sharded(comm, air_name, program.data(), program.size(), (const uint64_t *)d_trace, words, pubs.data(), (int32_t)pubs.size(), logn,
-                                     logb, fri_logf, fri_final_log, n_queries, pow_bits, &json, &len));
-    } else if (check_prove) {
-        CHECK(zp_set_tuning(ctx, "prove_check", 1));
-        const int32_t rc = zp_stark_prove(ctx, air_name, program.data(), program.size(), (const uint64_t *)d_trace, trace.size(), pubs.data(), (int32_t)pubs.size(),
-                                          logn, logb, fri_logf, fri_final_log, n_queries, pow_bits, &json, &len);
-        if (rc != 0 && rc != ZP_ERR_WITNESS) { fprintf(stderr, "zp_stark_prove -> %d: %s\n", rc, zp_last_error(ctx)); return 1; }
-        CHECK(zp_stark_prove_witness_report(ctx, report, nullptr, nullptr, nullptr, (int32_t)program[8]));
-        if (!print_report(report) || rc != 0) {
-            zp_dev_free(ctx, d_trace);
-            zp_destroy(ctx);
-            return 3;
+        if (check) {                                   // every rank hands in its own columns and receives the report of the whole trace
+            CHECK(zp_stark_check_witness_sharded(comm, program.data(), program.size(), words ? (const uint64_t *)d_trace : nullptr, words, pubs.data(),
+                                                 (int32_t)pubs.size(), logn, nullptr, report, nullptr, nullptr, 0));
+            if (rank == 0 ? !print_report(report) : report[0] != ZP_WITNESS_SATISFIED) return give_up(3);
         }
-    } else {
-        CHECK(zp_stark_prove(ctx, air_name, program.data(), program.size(), (const uint64_t *)d_trace, trace.size(), pubs.data(), (int32_t)pubs.size(), logn, logb,
-                             fri_logf, fri_final_log, n_queries, pow_bits, &json, &len));
+    }
+    if (check_prove) CHECK(zp_set_tuning(ctx, "prove_check", 1));
+    const int32_t rc = sharded ? zp_stark_prove_sharded(comm, air_name, program.data(), program.size(), (const uint64_t *)d_trace, words, pubs.data(),
+                                                        (int32_t)pubs.size(), logn, logb, fri_logf, fri_final_log, n_queries, pow_bits, &json, &len)
+                               : zp_stark_prove(ctx, air_name, program.data(), program.size(), (const uint64_t *)d_trace, trace.size(), pubs.data(),
+                                                (int32_t)pubs.size(), logn, logb, fri_logf, fri_final_log, n_queries, pow_bits, &json, &len);
+    if (rc != 0 && !(check_prove && rc == ZP_ERR_WITNESS)) {
+        fprintf(stderr, "%s -> %d: %s\n", sharded ? "zp_stark_prove_sharded" : "zp_stark_prove", rc, zp_last_error(ctx));
+        return 1;
+    }
+    if (check_prove) {                                 // the proof's own verdict, the same on every rank: rank 0 prints it
+        CHECK(zp_stark_prove_witness_report(ctx, report, nullptr, nullptr, nullptr, (int32_t)program[8]));
+        if ((rank == 0 ? !print_report(report) : report[0] != ZP_WITNESS_SATISFIED) || rc != 0) return give_up(3);
     }
     if (rank == 0) {
         FILE *o = fopen(argv[10], "wb");

@@ -43,7 +43,7 @@ enum {
     ZP_ERR_UNSUPPORTED = -4,
     ZP_ERR_INTERNAL = -5, /* an internal failure that is not the caller's (never an exception: nothing unwinds across this ABI) */
     ZP_ERR_COMM = -6,     /* the communicator is dead: a peer rank failed, aborted or did not reach a collective within the timeout */
-    ZP_ERR_WITNESS = -7   /* zp_stark_prove / zp_stark_prove_bn128 under "prove_check": the trace violates its program or holds a word >= p; no proof was made */
+    ZP_ERR_WITNESS = -7   /* the provers (one GPU or sharded) under "prove_check": the trace violates its program or holds a word >= p; no proof was made */
 };
 
 /* kinds for zp_set_constants */
@@ -198,8 +198,8 @@ int32_t zp_qap_quotient_bn254(zp_ctx *ctx, uint64_t *d_a, uint64_t *d_b, uint64_
  * "prove_check" = 0.  A violated or non-canonical one ends the call with ZP_ERR_WITNESS: no text, nothing launched after the point of
  * refusal, zp_last_error names the first constraint and row (or the first non-canonical column and row), the ctx stays usable and
  * zp_stark_prove_witness_report hands out the whole report.  The program must then also meet the interpreter's limits (at most 32
- * slots, canonical constants: ZP_ERR_ARG otherwise).  The sharded provers do NOT read the knob: their trace is column-sharded and a row
- * check would need one more exchange.
+ * slots, canonical constants: ZP_ERR_ARG otherwise).  The sharded provers read the knob too (of the communicator's ctx, set alike on every rank): one
+ * more exchange brings every rank a row window of the raw trace, and all ranks reach ONE verdict -- see zp_stark_prove_sharded below.
  * On any error *out_json = NULL, *out_len = 0; no C++ exception leaves the call (ZP_ERR_NOMEM / ZP_ERR_INTERNAL).          */
 int32_t zp_stark_prove(zp_ctx *ctx, const char *air_name, const uint64_t *h_program, size_t program_words, const uint64_t *d_trace,
                        size_t trace_words, const uint64_t *h_pubs, int32_t n_pubs, int32_t logn, int32_t logb, int32_t fri_logf,
@@ -223,7 +223,11 @@ int32_t zp_stark_set_air_kernel_rows(zp_ctx *ctx, const uint64_t *h_program, siz
  * `zpair_<air>_quotient_witness` of the same library (zp_air_witness_fn below) runs instead of the interpreter while "witness_kernel" is 1 (zp_set_tuning;
  * 0: always the interpreter).  Reports are the same word for word; the stage clock names the two forms "witness_program_gen" / "witness_program". */
 int32_t zp_stark_set_air_kernel_witness(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, void *witness_fn);
-/* The report of the LAST proof zp_stark_prove / zp_stark_prove_bn128 checked on this ctx ("prove_check" = 1), accepted or refused, in
+/* ... and for the check of a ROW WINDOW of the trace domain, what a rank of the sharded provers under "prove_check" and of zp_stark_check_witness_sharded
+ * judges: `zpair_<air>_quotient_witness_rows` of the same library (zp_air_witness_rows_fn below), under the same knob "witness_kernel".  Stage names
+ * "witness_program_rows_gen" / "witness_program_rows". */
+int32_t zp_stark_set_air_kernel_witness_rows(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, void *witness_rows_fn);
+/* The report of the LAST proof zp_stark_prove / zp_stark_prove_bn128 (or a sharded prover, on its rank's ctx: the same on every rank) checked on this ctx ("prove_check" = 1), accepted or refused, in
  * zp_stark_check_witness's layout: h_report[8], h_counts[K] / h_first_row[K] (or NULL); h_chal3 (or NULL) = the stage-2 challenge it was judged at --
  * the proof's own Fiat-Shamir challenge; zeros for a program without stage-2 arguments or a non-canonical trace.  ZP_ERR_ARG when no checked proof has
  * run on the ctx or n_constraints != K. */
@@ -360,9 +364,17 @@ int32_t zp_merkle_open_batch(zp_ctx *ctx, const uint64_t *d_tree, size_t M, cons
  *   lane = row r < N; d_trace [W][N], d_stage2 [W2][N] (columns >= W), d_fixed_periods = one period of every sparse fixed column, one behind the
  *   other; d_pub = publics then the challenge; w_N^r = lo[r & mask] * hi[r >> lb]; d_res [1 + 2K] = [first (row << 24 | k)][first_row: K][counts: K],
  *   pre-set by the caller to ~0 / ~0 / 0 and written only for violated constraints.
+ *   and the same check for a ROW WINDOW of the trace domain (a rank of a sharded proof): int zpair_<air>_quotient_witness_rows(void *hip_stream,
+ *        const u64 *d_trace, u64 stride_trace, const u64 *d_stage2, const u64 *d_fixed_periods, const u64 *d_pub, const u64 *d_xs_lo, const u64 *d_xs_hi,
+ *        int lb, u64 N, u64 row0, u64 nrows, u64 w_last, u64 *d_res);
+ *   lane = row r in [row0, row0 + nrows); d_trace [W][stride_trace] with row r at r - row0 and, unless nrows == N, ONE halo row at index nrows (row
+ *   (row0 + nrows) mod N); d_stage2 [W2][N] WHOLE, read at the global row and next row; selectors, periods, x and the reported rows are global.
  * zp_domain_tables hands such kernels the ctx-owned two-level table of w_M^e (x = shift*lo[e&mask]*hi[e>>lb]). */
 typedef int (*zp_air_witness_fn)(void *hip_stream, const uint64_t *d_trace, const uint64_t *d_stage2, const uint64_t *d_fixed_periods, const uint64_t *d_pub,
                                  const uint64_t *d_xs_lo, const uint64_t *d_xs_hi, int lb, uint64_t N, uint64_t w_last, uint64_t *d_res);
+typedef int (*zp_air_witness_rows_fn)(void *hip_stream, const uint64_t *d_trace, uint64_t stride_trace, const uint64_t *d_stage2, const uint64_t *d_fixed_periods,
+                                      const uint64_t *d_pub, const uint64_t *d_xs_lo, const uint64_t *d_xs_hi, int lb, uint64_t N, uint64_t row0, uint64_t nrows,
+                                      uint64_t w_last, uint64_t *d_res);
 int32_t zp_domain_tables(zp_ctx *ctx, int32_t logm, const uint64_t **d_lo, const uint64_t **d_hi, int32_t *lb);
 /* ---- N4 as data: the constraint program ----------------------------------------------------------------
  * An AIR handed over as a u64 blob instead of a generated kernel (a host without hipcc at run time can still
@@ -563,6 +575,14 @@ int32_t zp_sha256(const uint8_t *data, size_t len, uint8_t *out32);
  *                                 trace on one GPU.  Column-sharded: LDE, out-of-domain evaluations; row-sharded: the three
  *                                 commitments, the constraint quotient (with a blow-up halo), the DEEP quotient; replicated: the
  *                                 stage-2 columns, FRI.  Goldilocks-hash mode.  Collective: every rank must call it.
+ *                                 "prove_check" = 1 (on every rank's ctx alike; a mismatch is the caller's error): zp_stark_prove's check over
+ *                                 the ranks.  Every rank passes ITS words against p and the (count, first word) pairs are all-gathered; then
+ *                                 ONE more exchange (stage "witness_exchange") turns the raw columns into row windows of 2^logn / world rows
+ *                                 with one halo row, each rank judges its window (stage-2 columns: the replicated ones the proof made at the
+ *                                 transcript's challenge) and the per-rank results are all-gathered and merged.  Every stop is decided from
+ *                                 gathered data: EVERY rank returns ZP_ERR_WITNESS with zp_stark_prove's error line and report
+ *                                 (zp_stark_prove_witness_report on its ctx), no text, and the communicator stays usable.  A satisfied
+ *                                 trace gives the bytes of "prove_check" = 0.  Needs 2^logn / world >= 2 (ZP_ERR_ARG on every rank otherwise).
  *   zp_stark_prove_sharded_bn128: the same in BN128-hash mode (the last STARK before the Groth16 wrap, src/prover/provider.rs:431-
  *                                 451): zp_stark_prove_bn128's text, byte for byte, on every rank, and its openings record
  *                                 (zp_stark_openings) on every rank's ctx.  The 16-ary trace tree is sharded by rows (local
@@ -621,6 +641,14 @@ int32_t zp_stark_prove_sharded_bn128(zp_comm *comm, const char *air_name, const 
                                      const uint64_t *d_trace_local, size_t trace_words, const uint64_t *h_pubs, int32_t n_pubs, int32_t logn,
                                      int32_t logb, int32_t fri_logf, int32_t fri_final_log, int32_t n_queries, char **out_json, size_t *out_len);
 int32_t zp_exchange_columns_to_rows(zp_comm *comm, const uint64_t *d_cols, size_t Wl, size_t M, uint64_t *d_pack, uint64_t *d_rows);
+/* zp_stark_check_witness over the ranks of a communicator: the check BEFORE a sharded proof.  Every rank passes ITS columns of the trace (the rule of
+ * zp_stark_prove_sharded; trace_words = columns << logn; a rank without columns may pass NULL) and receives the SAME report, word for word what
+ * zp_stark_check_witness writes for the whole trace: semantics, report layout, derived challenge (h_chal3 = NULL) and argument refusals are that
+ * call's.  The stage-2 columns are made as the sharded prover makes them (a broadcast of the columns an argument reads, then zp_grand_product /
+ * zp_logup_columns on every rank); the first non-canonical word is reported with its GLOBAL column.  Needs 2^logn / world >= 2.  Collective. */
+int32_t zp_stark_check_witness_sharded(zp_comm *comm, const uint64_t *h_program, size_t program_words, const uint64_t *d_trace_local, size_t trace_words,
+                                       const uint64_t *h_pubs, int32_t n_pubs, int32_t logn, const uint64_t *h_chal3, uint64_t *h_report /* [8] */,
+                                       uint64_t *h_counts /* [K] or NULL */, uint64_t *h_first_row /* [K] or NULL */, int32_t n_constraints);
 /* four-step NTT of ONE column of 2^logn elements split over the ranks (BASELINE.json configs[3]: "RCCL all-to-all over xGMI for the
  * four-step NTT transpose"; replaces the torch.distributed orchestration eigen_zeth_amd/multigpu.py:four_step_ntt): d_data = this
  * rank's contiguous block of 2^logn / G elements, transformed in place (natural_output != 0: this rank's contiguous block of the

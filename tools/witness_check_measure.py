@@ -11,7 +11,12 @@ is a child process of its own with its own time limit (a step that fails or runs
 (b) zp_stark_prove with "prove_check" 0 and 1, for each kernel form, wall clock, and under 1 the stage clock's canonical pass and program kernel;
 (c) "prove_check" 0 of this library against ANOTHER build of the library (--parent-lib: the parent commit's), as child processes of the two libraries
     alternating, --rounds each; per library the median of its processes' medians and their spread (max - min).  The new library sits inside the parent's
-    own run-to-run spread, or the refactoring has cost something."""
+    own run-to-run spread, or the refactoring has cost something.
+
+--sharded (profiles/witness_check_sharded.json): what "prove_check" adds to zp_stark_prove_sharded, chunk64 at --logn (default 20): a world of one on
+RCCL and four thread-ranks on the one GPU (an in-process communicator: the ranks share the GPU's CUs -- a REHEARSAL of the multi-rank path, not a
+multi-GPU number).  One child process per shape; in it knob 0 and knob 1 ALTERNATE, --reps proofs each after a warm-up of both; wall clock of the slowest
+rank per proof, and under knob 1 rank 0's stage clock: canonical pass, exchange, row-window program kernel, each separately."""
 import argparse
 import json
 import os
@@ -26,7 +31,8 @@ from eigen_zeth_amd.stark import air as AIR
 
 PARAMS = dict(logb=1, fri_logf=3, fri_final_log=5, n_queries=80, pow_bits=20)
 STAGES = {"witness_canonical": "canonical_pass_ms", "witness_stage2": "stage2_columns_ms", "witness_program": "program_kernel_ms",
-          "witness_program_gen": "program_kernel_ms"}
+          "witness_program_gen": "program_kernel_ms", "witness_exchange": "exchange_ms", "witness_program_rows": "program_kernel_ms",
+          "witness_program_rows_gen": "program_kernel_ms"}
 
 
 def median(v):
@@ -89,6 +95,101 @@ def child(a):
     p.close()
 
 
+def sharded_child(a):
+    """one shape in this process: --ranks 1 = a world of one on RCCL, else thread-ranks on GPU 0.  Prints ONE JSON line"""
+    import threading
+    logn, G = int(a.logn), a.ranks
+    air = AIR.get_air("chunk64")
+    prog = np.ascontiguousarray(air.program(), dtype=np.uint64)
+    tr, pub = native.synth_trace(air.trace_kind, logn, air.width, 5)
+    pubs = [int(v) for v in pub]
+    from eigen_zeth_amd.stark.backend_hip import HipBackend
+    group = native.CommGroup(G) if G > 1 else None
+    uid = native.comm_unique_id() if G == 1 else None
+    gate = threading.Barrier(G)
+    wall = {0: [[] for _ in range(G)], 1: [[] for _ in range(G)]}
+    split, errs, texts = {}, [], set()
+
+    def rank(r):
+        try:
+            p = native.Prover(0)
+            be = HipBackend(prover=p)
+            c = native.Comm(p, r, G, unique_id=uid, group=group)
+            p.set_air_kernel_rows(prog, be._airlib_rows(air))
+            p.set_air_kernel_witness_rows(prog, be._airlib_witness_rows(air))
+            p.set_tuning("witness_kernel", a.witness_kernel)
+            first, count = c.my_columns(air.width)
+            d = p.upload(np.ascontiguousarray(tr[first:first + count]))
+
+            def prove(knob, timed):
+                p.set_tuning("prove_check", knob)
+                p.set_profiling(timed and r == 0)
+                p.stage_timings()
+                p.sync()
+                gate.wait()
+                t0 = time.perf_counter()
+                texts.add(c.stark_prove_sharded(air.name, prog, d, pubs, logn, PARAMS["logb"], PARAMS["fri_logf"], PARAMS["fri_final_log"], PARAMS["n_queries"],
+                                                PARAMS["pow_bits"]))
+                if timed:
+                    wall[knob][r].append((time.perf_counter() - t0) * 1e3)
+                    if r == 0 and knob:
+                        for ev in p.stage_timings():
+                            if ev["stage"] in STAGES:
+                                split.setdefault(STAGES[ev["stage"]], []).append(ev["ms"])
+                                split.setdefault("stages_seen", set()).add(ev["stage"])
+                p.set_profiling(False)
+            for knob in (0, 1):
+                prove(knob, False)
+            for _ in range(a.reps):
+                for knob in (0, 1):                         # alternating: both see the same neighbours on the machine
+                    prove(knob, True)
+            d.free()
+            c.close()
+            p.close()
+        except BaseException as e:      # noqa: the other ranks must not wait for this one
+            errs.append(e)
+            gate.abort()
+    ts = [threading.Thread(target=rank, args=(r,)) for r in range(G)]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join()
+    if errs:
+        raise errs[0]
+    assert len(texts) == 1, "knob 0 and knob 1 must give the same bytes on every rank"
+    seen = sorted(split.pop("stages_seen", []))
+    row = {"logn": logn, "ranks": G, "transport": "rccl" if G == 1 else "threads on one GPU (rehearsal)", "witness_kernel": a.witness_kernel, "reps": a.reps}
+    for knob in (0, 1):
+        per_proof = [max(wall[knob][r][i] for r in range(G)) for i in range(a.reps)]          # a proof is done when its slowest rank is
+        row["prove_check_%d" % knob] = {"ms": median(per_proof), "ms_min": round(min(per_proof), 4), "ms_max": round(max(per_proof), 4)}
+    row["check_over_proof"] = round(row["prove_check_1"]["ms"] / row["prove_check_0"]["ms"] - 1, 4)
+    row["stages"] = seen
+    row.update({k: median(v) for k, v in split.items()})
+    print(json.dumps(row), flush=True)
+
+
+def sharded(a):
+    import subprocess
+    here = os.path.abspath(__file__)
+    air = AIR.get_air("chunk64")
+    res = {"air": "chunk64", "width": air.width, "constraints": len(air.constraints), "params": PARAMS,
+           "note": "thread-ranks share one GPU: a rehearsal of the multi-rank path, not a multi-GPU number", "shapes": []}
+    for logn in [int(v) for v in a.logn.split(",")]:
+        for G in (1, 4):
+            cmd = [sys.executable, here, "--sharded-child", "--logn", str(logn), "--ranks", str(G), "--reps", str(a.reps), "--witness-kernel", str(a.witness_kernel)]
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)          # a time limit per GPU step; TimeoutExpired ends the run
+            if r.returncode != 0:
+                sys.stderr.write(r.stdout + r.stderr)
+                raise SystemExit("step %s failed with status %d: nothing more is started" % (cmd[2:], r.returncode))
+            row = json.loads(r.stdout.strip().splitlines()[-1])
+            print(json.dumps(row), flush=True)
+            res["shapes"].append(row)
+    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
 def inproof(a):
     import subprocess
     here = os.path.abspath(__file__)
@@ -146,9 +247,19 @@ def main():
     ap.add_argument("--witness-kernel", type=int, default=1)
     ap.add_argument("--prove-check", type=int, default=0)
     ap.add_argument("--no-new-calls", action="store_true")
+    ap.add_argument("--sharded", action="store_true")
+    ap.add_argument("--sharded-child", action="store_true")
+    ap.add_argument("--ranks", type=int, default=1)
     a = ap.parse_args()
     if a.child:
         return child(a)
+    if a.sharded_child:
+        return sharded_child(a)
+    if a.sharded:
+        a.out = a.out or os.path.join("profiles", "witness_check_sharded.json")
+        if a.logn == "20,22":
+            a.logn = "20"
+        return sharded(a)
     if a.inproof:
         a.out = a.out or os.path.join("profiles", "witness_check_inproof.json")
         return inproof(a)
