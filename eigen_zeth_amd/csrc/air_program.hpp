@@ -33,6 +33,12 @@ GL_HD int zpi_kind(u64 w, int o) { return (int)((w >> (24 + 20 * o)) & 0xF); }  
 GL_HD int zpi_idx(u64 w, int o) { return (int)((w >> (28 + 20 * o)) & 0xFFFF); }
 GL_HD ZpInstr zpi_decode(u64 w) { return ZpInstr{zpi_op(w), zpi_dst(w), {zpi_kind(w, 0), zpi_kind(w, 1)}, {zpi_idx(w, 0), zpi_idx(w, 1)}}; }
 
+// ---- stage-2 table: (kind, three trace columns) per argument.  A grand product reads two of them (a, b) and makes 3 planes (Z in F_{p^3}); LogUp
+// reads three (a, t, m) and makes 9 (h1, h2, S).  The kind test of every reader (W2 below, the columns themselves in csrc/stage2.hip)
+enum : u64 { ZPS2_PRODUCT = 1, ZPS2_LOGUP = 2 };
+GL_HD size_t zpi_stage2_inputs(u64 kind) { return kind == ZPS2_PRODUCT ? 2 : 3; }
+GL_HD size_t zpi_stage2_planes(u64 kind) { return kind == ZPS2_PRODUCT ? 3 : 9; }
+
 // ---- the sparse periodic fixed columns (2 .. n_fixed - 1): the table behind the stage-2 table
 struct ZpFixedCol { int lp; size_t first_entry_word, n_entries; bool has_pub; };
 struct ZpFixedEntry { u64 pos; bool is_pub; u64 value; };       // value: the constant, or (is_pub) the index of the public input that stands there
@@ -151,10 +157,10 @@ inline bool zpi_program_check(const ZpProgram *pg, unsigned mask, const char **w
         for (size_t k = 0; k < pg->n_s2; k++) {
             const u64 *st = pg->stage2 + 4 * k;
             w = "unknown stage-2 argument";
-            if (st[0] != 1 && st[0] != 2) return false;
+            if (st[0] != ZPS2_PRODUCT && st[0] != ZPS2_LOGUP) return false;
             w = "stage-2 column out of range";
             if (st[1] >= pg->W || st[2] >= pg->W || st[3] >= pg->W) return false;
-            w2sum += st[0] == 1 ? 3 : 9;
+            w2sum += zpi_stage2_planes(st[0]);
         }
         w = "stage-2 width does not match its table";
         if (w2sum != pg->W2) return false;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <initializer_list>
 #include <map>
 #include <string>
@@ -212,6 +213,9 @@ int32_t zpi_d2h(zp_ctx *ctx, void *h_dst, const void *d_src, size_t bytes);
 int32_t zpi_h2d(zp_ctx *ctx, void *d_dst, const void *h_src, size_t bytes);
 int32_t zpi_upload(zp_ctx *ctx, const std::vector<u64> &h, u64 **d);   // a new device buffer holding h (synchronous)
 #define ZP_SMALL_COPY (4u << 20)
+// csrc/stark.hip: nq query indices up, the gather kernel that launch(d_idx, d_out) enqueues, `total` words down to h_out; staging: a small round trip
+// may go through the page-locked staging buffer, which the kernel then reads and writes directly
+int32_t zpi_query_round_trip(zp_ctx *ctx, const u64 *h_idx, int nq, u64 total, u64 *h_out, bool staging, const std::function<void(const u64 *, u64 *)> &launch);
 int32_t zpi_get_plan(zp_ctx *ctx, int logn, bool inverse, NttPlan **out);
 int32_t zpi_get_plan_role(zp_ctx *ctx, int logn, bool inverse, int role, NttPlan **out);   // role 1 / 2: ends / starts with a radix-256 pass (csrc/ntt.hip)
 // The shape of one pass of radix 2^L: register rounds of radix 2^A1, 2^A2, 2^A3 on tiles of 2^logT columns.  Decided by the knobs ntt_logt / ntt_logt9 / ntt_logt12, by whether the transform has more than
@@ -310,6 +314,11 @@ int32_t zpi_comm_fail(zp_comm *comm, int32_t rc);   // rc != ZP_OK: kill the com
 int32_t zpi_witness_sharded_canonical(zp_comm *comm, size_t W, int logn, const u64 *d_trace_local, u64 *bad_n, u64 *bad_at);
 int32_t zpi_witness_sharded_constraints(zp_comm *comm, const ZpProgram &pg, const uint8_t *dg32, const std::vector<u64> &pubchal, const u64 *d_trace_local,
                                         const u64 *d_s2, int logn, uint64_t *h_report, uint64_t *h_counts, uint64_t *h_first_row);
+// csrc/stage2.hip: the k-th stage-2 argument of pg (st = pg.stage2 + 4 k) from three whole columns on this device (c unused by a grand product); writes its
+// planes at d_s2 + *at * N, advances *at
+int32_t zpi_stage2_argument(zp_ctx *ctx, const u64 *st, const u64 *a, const u64 *b, const u64 *c, size_t N, const u64 g[3], u64 *d_s2, size_t *at);
+// all of them, columns taken from a whole trace u64[W][N] on this device
+int32_t zpi_stage2_columns(zp_ctx *ctx, const ZpProgram &pg, const u64 *d_trace, int logn, const u64 g[3], u64 *d_s2);
 int32_t zpi_stage2_columns_sharded(zp_comm *comm, const ZpProgram &pg, const u64 *d_trace_local, int logn, const u64 g[3], u64 *d_colb, u64 *d_s2);
 // csrc/witness_host.hip: the argument checks of zp_stark_check_witness and its sharded twin, the parsed program and [publics | challenge | 0]; NULL or the refusal
 const char *zpi_witness_args(const uint64_t *h_program, size_t program_words, const uint64_t *trace, size_t trace_words, int world, int rank,

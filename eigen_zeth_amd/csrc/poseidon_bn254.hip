@@ -1104,16 +1104,11 @@ int32_t zp_merkle16_open_batch_bn254(zp_ctx *ctx, const uint64_t *d_tree, size_t
     ZP_ARG(ctx, d_tree && h_idx && h_paths, "null pointer");
     for (int i = 0; i < nq; i++) ZP_ARG(ctx, h_idx[i] < M, "leaf index out of range");
     const u64 total = (u64)nq * levels * 64;
-    u64 *d = nullptr;
-    ZP_TRY(zpi_scratch(ctx, 3, (size_t)nq + total, &d));
-    ZP_TRY(zpi_h2d_small(ctx, d, h_idx, (size_t)nq * 8));
-    hipLaunchKernelGGL(merkle16_paths_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, (const u64 *)d_tree, (u64)M, levels, d,
-                       (int)nq, d + nq);
-    ZP_HIP(ctx, hipGetLastError());
-    if (total * 8 <= ZP_SMALL_COPY) return zpi_d2h_small(ctx, h_paths, d + nq, total * 8);
-    ZP_HIP(ctx, hipMemcpyAsync(h_paths, d + nq, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return ZP_OK;
+    // staging "no": this entry point has never taken the staging route; whether it should is a question for a measured change
+    return zpi_query_round_trip(ctx, (const u64 *)h_idx, nq, total, (u64 *)h_paths, false, [&](const u64 *d_idx, u64 *d_paths) {
+        hipLaunchKernelGGL(merkle16_paths_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, (const u64 *)d_tree, (u64)M, levels, d_idx,
+                           (int)nq, d_paths);
+    });
 }
 
 // the device primitive of the BN128-mode verifier on its own: n openings into ONE 16-ary tree of M leaves (zp_merkle16_commit_bn254's)

@@ -845,17 +845,7 @@ int32_t prove_impl(zp_ctx *ctx, bool bn, const ProveArgs &a) {
         PV_TRY(tr.rc);
         u64 *s2;
         PV_TRY(dev.alloc(W2 * N, &s2));
-        size_t at = 0;
-        for (size_t k = 0; k < n_s2; k++) {
-            const u64 *st = sh.pg.stage2 + 4 * k;
-            if (st[0] == 1) {
-                PV_TRY(zp_grand_product(ctx, d_trace + st[1] * N, d_trace + st[2] * N, N, (const uint64_t *)chal.c, (uint64_t *)(s2 + at * N)));
-                at += 3;
-            } else {
-                PV_TRY(zp_logup_columns(ctx, d_trace + st[1] * N, d_trace + st[2] * N, d_trace + st[3] * N, N, (const uint64_t *)chal.c, (uint64_t *)(s2 + at * N)));
-                at += 9;
-            }
-        }
+        PV_TRY(zpi_stage2_columns(ctx, sh.pg, (const u64 *)d_trace, logn, chal.c, s2));
         // the stage-2 columns exist on the trace domain, made with the challenge that binds; nothing has been extended from them yet
         if (check) PV_TRY(prove_check_constraints(ctx, sh, pubchal, s2, &chal));
         PV_TRY(zp_lde(ctx, (const uint64_t *)s2, (uint64_t *)(ext + W * M), nullptr, logn, logb, (int32_t)W2, shift));

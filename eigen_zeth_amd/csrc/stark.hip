@@ -1,5 +1,6 @@
 // STARK stages around the committed columns (SURVEY.md 8a N4/N5 support): out-of-domain
-// evaluation, DEEP quotient, row gathers and batched Merkle openings.  No reference counterpart in
+// evaluation, DEEP quotient, row gathers and batched Merkle openings (with the query round trip every batched opening goes through), the
+// constraint-program interpreter on the LDE domain and the fixed columns.  The stage-2 columns are csrc/stage2.hip's.  No reference counterpart in
 // /root/reference (the prover behind src/prover/provider.rs:358-377 is external); definitions follow
 // the public DEEP-FRI construction, checked against oracle/ and an independent verifier in tests/.
 #include <hip/hip_runtime.h>
@@ -510,32 +511,11 @@ int32_t zp_gather_rows(zp_ctx *ctx, const uint64_t *d_cols, size_t M, int32_t W,
     if (nq == 0) return ZP_OK;
     ZP_ARG(ctx, d_cols && h_idx && h_out, "null pointer");
     for (int i = 0; i < nq; i++) ZP_ARG(ctx, h_idx[i] < M, "row index out of range");
-    u64 *d = nullptr;
     const u64 total = (u64)nq * W;
-    if ((total + (u64)nq) * 8 <= ZP_SMALL_COPY) {
-        // query openings are a few hundred kilobytes: indices in and rows out through the page-locked, device-visible staging buffer -- the
-        // kernel reads and writes it directly: one launch, two synchronisations (round 5; before: copy kernels in and out, four synchronisations)
-        void *stv = nullptr;
-        ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        ZP_TRY(zpi_pinned(ctx, (size_t)(total + (u64)nq) * 8, &stv));
-        u64 *st = (u64 *)stv;
-        memcpy(st, h_idx, (size_t)nq * 8);
-        hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const u64 *)d_cols, (u64)M, (int)W, (const u64 *)st, (int)nq, st + nq);
-        ZP_HIP(ctx, hipGetLastError());
-        ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        memcpy(h_out, st + nq, (size_t)total * 8);
-        return ZP_OK;
-    }
-    ZP_TRY(zpi_scratch(ctx, 3, (size_t)nq * (W + 1), &d));
-    ZP_TRY(zpi_h2d_small(ctx, d, h_idx, (size_t)nq * 8));
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const u64 *)d_cols, (u64)M, (int)W, d, (int)nq, d + nq);
-    ZP_HIP(ctx, hipGetLastError());
-    if (total * 8 <= ZP_SMALL_COPY) return zpi_d2h_small(ctx, h_out, d + nq, total * 8);
-    ZP_HIP(ctx, hipMemcpyAsync(h_out, d + nq, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return ZP_OK;
+    return zpi_query_round_trip(ctx, (const u64 *)h_idx, nq, total, (u64 *)h_out, true, [&](const u64 *d_idx, u64 *d_rows) {
+        hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, (const u64 *)d_cols, (u64)M, (int)W, d_idx,
+                           (int)nq, d_rows);
+    });
 }
 
 int32_t zp_merkle_open_batch(zp_ctx *ctx, const uint64_t *d_tree, size_t M, const uint64_t *h_idx, int32_t nq,
@@ -549,260 +529,37 @@ int32_t zp_merkle_open_batch(zp_ctx *ctx, const uint64_t *d_tree, size_t M, cons
     if (nq == 0 || depth == 0) return ZP_OK;
     ZP_ARG(ctx, d_tree && h_idx && h_paths, "null pointer");
     for (int i = 0; i < nq; i++) ZP_ARG(ctx, h_idx[i] < M, "leaf index out of range");
-    u64 *d = nullptr;
     const u64 total = (u64)nq * depth * 4;
-    if ((total + (u64)nq) * 8 <= ZP_SMALL_COPY) {      // as zp_gather_rows: through the staging buffer, one launch
+    return zpi_query_round_trip(ctx, (const u64 *)h_idx, nq, total, (u64 *)h_paths, true, [&](const u64 *d_idx, u64 *d_paths) {
+        hipLaunchKernelGGL(merkle_paths_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, (const u64 *)d_tree, (u64)M, depth, d_idx,
+                           (int)nq, d_paths);
+    });
+}
+
+}  // extern "C"
+
+// A query round trip: nq indices up, one gather kernel (launch(d_idx, d_out) puts it on the ctx stream), `total` words down.  Query openings are a
+// few hundred kilobytes: where `staging` allows it and they fit, indices in and words out go through the page-locked, device-visible staging
+// buffer -- the kernel reads and writes it directly: one launch, two synchronisations.  Otherwise scratch 3, a small copy up and a copy down.
+int32_t zpi_query_round_trip(zp_ctx *ctx, const u64 *h_idx, int nq, u64 total, u64 *h_out, bool staging, const std::function<void(const u64 *, u64 *)> &launch) {
+    if (staging && (total + (u64)nq) * 8 <= ZP_SMALL_COPY) {
         void *stv = nullptr;
         ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
         ZP_TRY(zpi_pinned(ctx, (size_t)(total + (u64)nq) * 8, &stv));
         u64 *st = (u64 *)stv;
         memcpy(st, h_idx, (size_t)nq * 8);
-        hipLaunchKernelGGL(merkle_paths_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const u64 *)d_tree, (u64)M, depth, (const u64 *)st, (int)nq, st + nq);
+        launch(st, st + nq);
         ZP_HIP(ctx, hipGetLastError());
         ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        memcpy(h_paths, st + nq, (size_t)total * 8);
+        memcpy(h_out, st + nq, (size_t)total * 8);
         return ZP_OK;
     }
+    u64 *d = nullptr;
     ZP_TRY(zpi_scratch(ctx, 3, (size_t)nq + total, &d));
     ZP_TRY(zpi_h2d_small(ctx, d, h_idx, (size_t)nq * 8));
-    hipLaunchKernelGGL(merkle_paths_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const u64 *)d_tree, (u64)M, depth, d, (int)nq, d + nq);
+    launch(d, d + nq);
     ZP_HIP(ctx, hipGetLastError());
-    if (total * 8 <= ZP_SMALL_COPY) return zpi_d2h_small(ctx, h_paths, d + nq, total * 8);
-    ZP_HIP(ctx, hipMemcpyAsync(h_paths, d + nq, total * 8, hipMemcpyDeviceToHost, ctx->stream));
-    ZP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return ZP_OK;
-}
-
-}  // extern "C"
-
-// ---- grand product (stage-2 witness of a permutation argument) ---------------------------------------
-// Z[0] = 1,  Z[i+1] = Z[i] * (a[i] + g) / (b[i] + g)   in F_{p^3};  out planes u64[3][N].
-// Three launches: (1) per-lane ratios r_i and the exclusive product of each lane's 16 ratios, block scan
-// in LDS, one total per block;  (2) exclusive scan of the block totals (one workgroup);  (3) offsets.
-namespace {
-
-struct GpArgs {
-    const u64 *a, *b;
-    u64 *out;       // [3][N]
-    e3 *totals;     // [nblocks]
-    u64 g[3];
-    u64 n;
-};
-#define GP_PER 16
-#define GP_BLK 256
-
-__device__ __forceinline__ e3 gp_ratio(const GpArgs &A, u64 i) {
-    const e3 num = e3_make(gl_add(A.a[i], A.g[0]), A.g[1], A.g[2]);
-    const e3 den = e3_make(gl_add(A.b[i], A.g[0]), A.g[1], A.g[2]);
-    return e3_mul(num, e3_inv(den));
-}
-
-__global__ void __launch_bounds__(GP_BLK) gp_local_kernel(GpArgs A) {
-    __shared__ e3 sh[GP_BLK];
-    const int t = threadIdx.x;
-    const u64 base = ((u64)blockIdx.x * GP_BLK + t) * GP_PER;
-    e3 acc = e3_make(1, 0, 0);
-    // exclusive products inside the lane's run, stored unscaled; scaled by the lane/block prefix later
-    for (int k = 0; k < GP_PER; k++) {
-        const u64 i = base + k;
-        if (i < A.n) {
-#pragma unroll
-            for (int c = 0; c < 3; c++) A.out[(u64)c * A.n + i] = acc.c[c];
-            acc = e3_mul(acc, gp_ratio(A, i));
-        }
-    }
-    sh[t] = acc;
-    __syncthreads();
-    // inclusive Hillis-Steele scan of the lane totals
-    for (int d = 1; d < GP_BLK; d <<= 1) {
-        e3 v = sh[t];
-        if (t >= d) v = e3_mul(sh[t - d], v);
-        __syncthreads();
-        sh[t] = v;
-        __syncthreads();
-    }
-    const e3 lane_prefix = t ? sh[t - 1] : e3_make(1, 0, 0);
-    if (t == GP_BLK - 1) A.totals[blockIdx.x] = sh[t];
-    for (int k = 0; k < GP_PER; k++) {
-        const u64 i = base + k;
-        if (i < A.n) {
-            e3 v = e3_mul(lane_prefix, e3_make(A.out[i], A.out[A.n + i], A.out[2 * A.n + i]));
-#pragma unroll
-            for (int c = 0; c < 3; c++) A.out[(u64)c * A.n + i] = v.c[c];
-        }
-    }
-}
-
-// exclusive scan of the block totals, in place, one workgroup (sequential over chunks of GP_BLK)
-__global__ void __launch_bounds__(GP_BLK) gp_scan_totals_kernel(e3 *totals, u64 nblocks) {
-    __shared__ e3 sh[GP_BLK];
-    __shared__ e3 carry;
-    const int t = threadIdx.x;
-    if (t == 0) carry = e3_make(1, 0, 0);
-    __syncthreads();
-    for (u64 base = 0; base < nblocks; base += GP_BLK) {
-        const u64 i = base + t;
-        sh[t] = i < nblocks ? totals[i] : e3_make(1, 0, 0);
-        __syncthreads();
-        for (int d = 1; d < GP_BLK; d <<= 1) {
-            e3 v = sh[t];
-            if (t >= d) v = e3_mul(sh[t - d], v);
-            __syncthreads();
-            sh[t] = v;
-            __syncthreads();
-        }
-        const e3 excl = e3_mul(carry, t ? sh[t - 1] : e3_make(1, 0, 0));
-        const e3 last = e3_mul(carry, sh[GP_BLK - 1]);
-        __syncthreads();
-        if (i < nblocks) totals[i] = excl;
-        if (t == 0) carry = last;
-        __syncthreads();
-    }
-}
-
-__global__ void __launch_bounds__(GP_BLK) gp_apply_kernel(GpArgs A) {
-    const e3 off = A.totals[blockIdx.x];
-    const u64 base = ((u64)blockIdx.x * GP_BLK + threadIdx.x) * GP_PER;
-    for (int k = 0; k < GP_PER; k++) {
-        const u64 i = base + k;
-        if (i < A.n) {
-            e3 v = e3_mul(off, e3_make(A.out[i], A.out[A.n + i], A.out[2 * A.n + i]));
-#pragma unroll
-            for (int c = 0; c < 3; c++) A.out[(u64)c * A.n + i] = v.c[c];
-        }
-    }
-}
-
-// ---- LogUp lookup columns (stage-2 witness of a range-check / lookup argument)
-// h1 = 1/(a+g), h2 = m/(t+g), S[0] = 0, S[i+1] = S[i] + h1[i] - h2[i]   (all in F_{p^3}; planes h1 0..2, h2 3..5, S 6..8)
-struct LuArgs {
-    const u64 *a, *t, *m;
-    u64 *out;
-    e3 *totals;
-    u64 n;
-    u64 g[3];
-};
-
-__global__ void __launch_bounds__(GP_BLK) lu_local_kernel(LuArgs A) {
-    __shared__ e3 sh[GP_BLK];
-    const int t = threadIdx.x;
-    const u64 base = ((u64)blockIdx.x * GP_BLK + t) * GP_PER;
-    e3 acc = e3_make(0, 0, 0);
-    for (int k = 0; k < GP_PER; k++) {
-        const u64 i = base + k;
-        if (i < A.n) {
-            const e3 h1 = e3_inv(e3_make(gl_add(A.a[i], A.g[0]), A.g[1], A.g[2]));
-            const e3 h2 = e3_scale(e3_inv(e3_make(gl_add(A.t[i], A.g[0]), A.g[1], A.g[2])), A.m[i]);
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                A.out[(u64)c * A.n + i] = h1.c[c];
-                A.out[(u64)(3 + c) * A.n + i] = h2.c[c];
-                A.out[(u64)(6 + c) * A.n + i] = acc.c[c];
-            }
-            acc = e3_add(acc, e3_sub(h1, h2));
-        }
-    }
-    sh[t] = acc;
-    __syncthreads();
-    for (int d = 1; d < GP_BLK; d <<= 1) {
-        e3 v = sh[t];
-        if (t >= d) v = e3_add(sh[t - d], v);
-        __syncthreads();
-        sh[t] = v;
-        __syncthreads();
-    }
-    const e3 lane_prefix = t ? sh[t - 1] : e3_make(0, 0, 0);
-    if (t == GP_BLK - 1) A.totals[blockIdx.x] = sh[t];
-    for (int k = 0; k < GP_PER; k++) {
-        const u64 i = base + k;
-        if (i < A.n) {
-#pragma unroll
-            for (int c = 0; c < 3; c++) A.out[(u64)(6 + c) * A.n + i] = gl_add(A.out[(u64)(6 + c) * A.n + i], lane_prefix.c[c]);
-        }
-    }
-}
-
-__global__ void __launch_bounds__(GP_BLK) lu_scan_totals_kernel(e3 *totals, u64 nblocks) {
-    __shared__ e3 sh[GP_BLK];
-    __shared__ e3 carry;
-    const int t = threadIdx.x;
-    if (t == 0) carry = e3_make(0, 0, 0);
-    __syncthreads();
-    for (u64 base = 0; base < nblocks; base += GP_BLK) {
-        const u64 i = base + t;
-        sh[t] = i < nblocks ? totals[i] : e3_make(0, 0, 0);
-        __syncthreads();
-        for (int d = 1; d < GP_BLK; d <<= 1) {
-            e3 v = sh[t];
-            if (t >= d) v = e3_add(sh[t - d], v);
-            __syncthreads();
-            sh[t] = v;
-            __syncthreads();
-        }
-        const e3 excl = e3_add(carry, t ? sh[t - 1] : e3_make(0, 0, 0));
-        const e3 last = e3_add(carry, sh[GP_BLK - 1]);
-        __syncthreads();
-        if (i < nblocks) totals[i] = excl;
-        if (t == 0) carry = last;
-        __syncthreads();
-    }
-}
-
-__global__ void __launch_bounds__(GP_BLK) lu_apply_kernel(LuArgs A) {
-    const e3 off = A.totals[blockIdx.x];
-    const u64 base = ((u64)blockIdx.x * GP_BLK + threadIdx.x) * GP_PER;
-    for (int k = 0; k < GP_PER; k++) {
-        const u64 i = base + k;
-        if (i < A.n) {
-#pragma unroll
-            for (int c = 0; c < 3; c++) A.out[(u64)(6 + c) * A.n + i] = gl_add(A.out[(u64)(6 + c) * A.n + i], off.c[c]);
-        }
-    }
-}
-
-}  // namespace
-
-extern "C" int32_t zp_logup_columns(zp_ctx *ctx, const uint64_t *d_a, const uint64_t *d_t, const uint64_t *d_m, size_t n,
-                                    const uint64_t gamma[3], uint64_t *d_out) {
-    if (!ctx) return ZP_ERR_ARG;
-    ZpStage stage_(ctx, "logup_columns");
-    ZP_ARG(ctx, n >= 1, "n must be >= 1");
-    ZP_ARG(ctx, d_a && d_t && d_m && gamma && d_out, "null pointer");
-    ZP_ARG(ctx, gamma[0] < GL_P && gamma[1] < GL_P && gamma[2] < GL_P, "challenge not canonical");
-    const u64 nblocks = (n + (u64)GP_BLK * GP_PER - 1) / ((u64)GP_BLK * GP_PER);
-    u64 *scr = nullptr;
-    ZP_TRY(zpi_scratch(ctx, 3, nblocks * 3 + 8, &scr));
-    LuArgs A;
-    A.a = (const u64 *)d_a; A.t = (const u64 *)d_t; A.m = (const u64 *)d_m; A.out = (u64 *)d_out; A.totals = (e3 *)scr; A.n = n;
-    for (int i = 0; i < 3; i++) A.g[i] = gamma[i];
-    hipLaunchKernelGGL(lu_local_kernel, dim3((unsigned)nblocks), dim3(GP_BLK), 0, ctx->stream, A);
-    hipLaunchKernelGGL(lu_scan_totals_kernel, dim3(1), dim3(GP_BLK), 0, ctx->stream, (e3 *)scr, nblocks);
-    hipLaunchKernelGGL(lu_apply_kernel, dim3((unsigned)nblocks), dim3(GP_BLK), 0, ctx->stream, A);
-    ZP_HIP(ctx, hipGetLastError());
-    return ZP_OK;
-}
-
-
-extern "C" int32_t zp_grand_product(zp_ctx *ctx, const uint64_t *d_a, const uint64_t *d_b, size_t n, const uint64_t gamma[3],
-                                    uint64_t *d_out) {
-    if (!ctx) return ZP_ERR_ARG;
-    ZpStage stage_(ctx, "grand_product");
-    ZP_ARG(ctx, n >= 1, "n must be >= 1");
-    ZP_ARG(ctx, d_a && d_b && gamma && d_out, "null pointer");
-    ZP_ARG(ctx, gamma[0] < GL_P && gamma[1] < GL_P && gamma[2] < GL_P, "challenge not canonical");
-    const u64 nblocks = (n + (u64)GP_BLK * GP_PER - 1) / ((u64)GP_BLK * GP_PER);
-    u64 *scr = nullptr;
-    ZP_TRY(zpi_scratch(ctx, 3, nblocks * 3 + 8, &scr));
-    GpArgs A;
-    A.a = (const u64 *)d_a; A.b = (const u64 *)d_b; A.out = (u64 *)d_out; A.totals = (e3 *)scr; A.n = n;
-    for (int i = 0; i < 3; i++) A.g[i] = gamma[i];
-    hipLaunchKernelGGL(gp_local_kernel, dim3((unsigned)nblocks), dim3(GP_BLK), 0, ctx->stream, A);
-    hipLaunchKernelGGL(gp_scan_totals_kernel, dim3(1), dim3(GP_BLK), 0, ctx->stream, (e3 *)scr, nblocks);
-    hipLaunchKernelGGL(gp_apply_kernel, dim3((unsigned)nblocks), dim3(GP_BLK), 0, ctx->stream, A);
-    ZP_HIP(ctx, hipGetLastError());
-    return ZP_OK;
+    return zpi_d2h(ctx, h_out, d + nq, total * 8);
 }
 
 // ---- N4 through the C-ABI: interpreter of a constraint program (include/zeth_prover.h "constraint program") ----------

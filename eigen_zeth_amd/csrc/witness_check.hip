@@ -263,19 +263,7 @@ int32_t zpi_witness_check_device(zp_ctx *ctx, const ZpProgram &pg, const std::ve
     u64 *s2 = (u64 *)s2v;
     {
         ZpStage stage_(ctx, "witness_stage2");
-        const uint64_t *g = (const uint64_t *)pubchal.data() + pg.n_pub;
-        size_t at = 0;
-        for (size_t k = 0; k < pg.n_s2; k++) {
-            const u64 *st = pg.stage2 + 4 * k;
-            const uint64_t *tr = (const uint64_t *)d_trace;
-            if (st[0] == 1) {
-                ZP_TRY(zp_grand_product(ctx, tr + st[1] * N, tr + st[2] * N, N, g, (uint64_t *)(s2 + at * N)));
-                at += 3;
-            } else {
-                ZP_TRY(zp_logup_columns(ctx, tr + st[1] * N, tr + st[2] * N, tr + st[3] * N, N, g, (uint64_t *)(s2 + at * N)));
-                at += 9;
-            }
-        }
+        ZP_TRY(zpi_stage2_columns(ctx, pg, d_trace, logn, pubchal.data() + pg.n_pub, s2));
     }
     // the digest names the kernel: one SHA-256 of the blob per call (a program of >= 2^14 words: one memcmp against the ctx's digest cache) -- paid only
     // by a ctx that has a generated kernel registered and the knob on; the provers pass the digest their transcript needs anyway

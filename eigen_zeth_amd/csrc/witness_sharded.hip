@@ -121,17 +121,8 @@ int32_t zpi_stage2_columns_sharded(zp_comm *comm, const ZpProgram &pg, const u64
     size_t at = 0;
     for (size_t k = 0; k < pg.n_s2; k++) {
         const u64 *st = pg.stage2 + 4 * k;
-        ZP_TRY(column(st[1], d_colb));
-        ZP_TRY(column(st[2], d_colb + N));
-        if (st[0] == 1) {
-            ZP_TRY(zp_grand_product(ctx, (const uint64_t *)d_colb, (const uint64_t *)(d_colb + N), N, (const uint64_t *)g, (uint64_t *)(d_s2 + at * N)));
-            at += 3;
-        } else {
-            ZP_TRY(column(st[3], d_colb + 2 * N));
-            ZP_TRY(zp_logup_columns(ctx, (const uint64_t *)d_colb, (const uint64_t *)(d_colb + N), (const uint64_t *)(d_colb + 2 * N), N, (const uint64_t *)g,
-                                    (uint64_t *)(d_s2 + at * N)));
-            at += 9;
-        }
+        for (size_t j = 0; j < zpi_stage2_inputs(st[0]); j++) ZP_TRY(column(st[1 + j], d_colb + j * N));
+        ZP_TRY(zpi_stage2_argument(ctx, st, d_colb, d_colb + N, d_colb + 2 * N, N, g, d_s2, &at));
     }
     return ZP_OK;
 }

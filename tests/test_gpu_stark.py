@@ -2,10 +2,14 @@
 the MI355X proof must (a) be bit-identical to the proof the CPU restatement produces from the same
 witness and (b) pass the independent verifier (oracle/stark_verify.py)."""
 import copy
+import os
+import re
 
 import numpy as np
 import pytest
 
+import witness_cases as WC
+from test_witness_check_host import host_check, raw_check
 from eigen_zeth_amd import native
 from eigen_zeth_amd.stark import air as AIR
 from eigen_zeth_amd.stark import prover as PR
@@ -169,6 +173,100 @@ def test_gather_and_batch_open(prover, tables):
         assert (paths[i] == O.merkle_path(tree, j)).all()
     with pytest.raises(native.ZpError):
         prover.gather_rows(d, M, W, [M])
+
+
+def _small_copy_words():
+    """ZP_SMALL_COPY of csrc/ctx.hpp, in words: a query round trip of more (indices + outputs) leaves the staging route"""
+    text = open(os.path.join(os.path.dirname(native.__file__), "csrc", "ctx.hpp")).read()
+    a, b = re.search(r"#define ZP_SMALL_COPY \((\d+)u << (\d+)\)", text).groups()
+    return (int(a) << int(b)) // 8
+
+
+@pytest.fixture(scope="module")
+def opened(prover, tables):
+    """one set of columns at M = 2^10 with its binary tree (and the checker's) and a 16-ary BN254 tree, shared by the round-trip cases"""
+    M, W = 1 << 10, 127
+    cols = O.random_field((W, M), 61)
+    d = prover.upload(cols)
+    d_tree = prover.alloc((2 * M - 1) * 4)
+    prover.merkle_commit(d, M, W, d_tree)
+    prover.install_poseidon_bn254(17)
+    d_tree16 = prover.alloc(prover.merkle16_nodes(M) * 4)
+    prover.merkle16_commit_bn254(d, M, 3, d_tree16)
+    return M, W, cols, d, d_tree, O.merkle_commit(cols, *tables), d_tree16
+
+
+def test_query_round_trips_with_no_query_leave_the_outputs_alone(prover, opened):
+    M, W, _, d, d_tree, _, d_tree16 = opened
+    idx, out = np.zeros(1, dtype=np.uint64), np.full(64, 0xA5A5A5A5, dtype=np.uint64)
+    lib, p = prover.lib, lambda a: a.ctypes.data_as(native._u64p)
+    assert lib.zp_gather_rows(prover.ctx, d.ptr, M, W, p(idx), 0, p(out)) == 0
+    assert lib.zp_merkle_open_batch(prover.ctx, d_tree.ptr, M, p(idx), 0, p(out)) == 0
+    assert lib.zp_merkle16_open_batch_bn254(prover.ctx, d_tree16.ptr, M, idx.ctypes.data, 0, out.ctypes.data) == 0
+    assert (out == 0xA5A5A5A5).all()
+
+
+def test_query_round_trips_just_above_the_staging_threshold(prover, opened):
+    """the smallest query counts whose indices and outputs together exceed ZP_SMALL_COPY: the Goldilocks pair leaves the staging buffer for
+    scratch 3 there (the BN128 form always goes that way); every entry point against the same reference as below the threshold"""
+    M, W, cols, d, d_tree, tree, d_tree16 = opened
+    limit = _small_copy_words()
+    rng = np.random.default_rng(62)
+    draw = lambda per_query: rng.integers(0, M, size=limit // (per_query + 1) + 1, dtype=np.uint64)
+    idx = draw(W)
+    assert (len(idx) - 1) * (W + 1) <= limit < len(idx) * (W + 1)
+    assert (prover.gather_rows(d, M, W, idx) == cols[:, idx.astype(np.int64)].T).all()
+    idx = draw(10 * 4)
+    assert (len(idx) - 1) * 41 <= limit < len(idx) * 41
+    want = np.array([O.merkle_path(tree, j) for j in range(M)], dtype=np.uint64)
+    assert (prover.merkle_open_batch(d_tree, M, idx) == want[idx.astype(np.int64)]).all()
+    idx = draw(3 * 64)
+    assert (len(idx) - 1) * 193 <= limit < len(idx) * 193
+    paths = np.zeros((len(idx), 3, 16, 4), dtype=np.uint64)
+    prover._chk(prover.lib.zp_merkle16_open_batch_bn254(prover.ctx, d_tree16.ptr, M, idx.ctypes.data, len(idx), paths.ctypes.data))
+    single = np.zeros((M, 3, 16, 4), dtype=np.uint64)
+    for j in sorted(set(idx.tolist())):
+        prover._chk(prover.lib.zp_merkle16_open_bn254(prover.ctx, d_tree16.ptr, M, j, single[j].ctypes.data))
+    assert (paths == single[idx.astype(np.int64)]).all()
+
+
+def lookup_then_perm_air():
+    """the range check and the permutation of the chunk AIR on its own trace (16 columns), the stage-2 table in the order LogUp, grand product:
+    Z lives behind the nine LogUp planes, so a reader that advances by the wrong width after the first argument breaks every Z constraint"""
+    width, Ww = 16, 8
+    r, q, t, m = [AIR.Col(Ww + i) for i in (2, 3, 4, 5)]
+    g = [AIR.Chal(i) for i in range(3)]
+    s2 = lambda j, nxt=False: [AIR.Col(width + 3 * j + i, nxt) for i in range(3)]
+    H1, H2, S, Sn, Z, Zn = s2(0), s2(1), s2(2), s2(2, True), s2(3), s2(3, True)
+    ext = lambda v: [v + g[0], g[1], g[2]]
+    p1, p2 = AIR.e3x_mul(H1, ext(r)), AIR.e3x_mul(H2, ext(t))
+    lhs, rhs = AIR.e3x_mul(Zn, ext(q)), AIR.e3x_mul(Z, ext(r))
+    cs = [p1[0] - 1, p1[1], p1[2], p2[0] - m, p2[1], p2[2]]
+    cs += [Sn[i] - S[i] - H1[i] + H2[i] for i in range(3)] + [AIR.L_FIRST * S[i] for i in range(3)]
+    cs += [lhs[i] - rhs[i] for i in range(3)] + [AIR.L_FIRST * (Z[0] - 1), AIR.L_FIRST * Z[1], AIR.L_FIRST * Z[2]]
+    return AIR.Air("lookup_perm", width, 8, cs, trace_kind=3,
+                   stage2=[{"kind": "lookup", "a": Ww + 2, "t": Ww + 4, "m": Ww + 5}, {"kind": "perm", "a": Ww + 2, "b": Ww + 3}])
+
+
+def test_witness_check_of_a_logup_argument_followed_by_a_grand_product(prover):
+    """both argument kinds in one stage-2 table, the nine-plane one first, at logn = 5: the verdict, the counts and the first rows of
+    zp_stark_check_witness on the device equal the host checker's and the oracle's, on the satisfied trace and with the permutation broken"""
+    logn = 5
+    air = lookup_then_perm_air()
+    blob = np.ascontiguousarray(air.program(), dtype=np.uint64)
+    assert [int(blob[12 + int(blob[6]) + int(blob[7]) + 4 * k]) for k in range(2)] == [2, 1]      # the table's kinds: LogUp, grand product
+    tr, pub = native.synth_trace(air.trace_kind, logn, air.width, 11)
+    pubs = [int(v) for v in pub]
+    broken = WC.flipped(tr, 8 + 3, 7)            # q is no permutation of r any more: the grand product does not close
+    for trace, verdict in ((tr, WC.SATISFIED), (broken, WC.VIOLATED)):
+        for chal in (None, WC.EXPLICIT_CHALLENGE):
+            want = WC.oracle_report(blob, trace, pubs, logn, chal)
+            assert want[0][0] == verdict
+            assert host_check(blob, trace, pubs, logn, chal) == want
+            d = prover.upload(np.ascontiguousarray(trace, dtype=np.uint64))
+            rc, rep, counts, first = raw_check(prover.ctx, blob, d.ptr, trace.size, pubs, logn, chal)
+            d.free()
+            assert rc == 0 and (rep, counts, first) == want
 
 
 # rows the large stage-2 cases sample: the first blocks, the middle, the end, and both sides of block 256 -- where the scan of the block
