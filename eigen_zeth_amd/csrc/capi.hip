@@ -485,6 +485,7 @@ int32_t zp_set_tuning(zp_ctx *ctx, const char *key, int32_t value) {
     else if (!strcmp(key, "fixed_eval_dev_min")) ctx->tune_fixed_eval_dev_min = value < 0 ? 1 << 15 : value;
     else if (!strcmp(key, "witness_kernel")) { ZP_ARG(ctx, value == 0 || value == 1, "witness_kernel is 0 (interpreter) or 1 (a registered generated kernel)"); ctx->tune_witness_kernel = value; }
     else if (!strcmp(key, "prove_check")) { ZP_ARG(ctx, value == 0 || value == 1, "prove_check is 0 or 1"); ctx->tune_prove_check = value; }
+    else if (!strcmp(key, "s2_diag_merge")) { ZP_ARG(ctx, value == 0 || value == 1, "s2_diag_merge is 0 or 1"); ctx->tune_s2_diag_merge = value; }
     else { ctx->err = "unknown tuning key"; return ZP_ERR_ARG; }
     return ZP_OK;
 }

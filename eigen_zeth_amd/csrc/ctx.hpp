@@ -111,6 +111,7 @@ struct zp_ctx {
     int tune_fixed_eval_dev_min = 1 << 15;   // zp_program_fixed_eval_ext_batch with a ctx: calls of fewer (points x sparse entries) run on the host (0: always the device; < 0 restores this default).  2^15: from ~12.5 ns per entry on 16 host threads against ~0.5 ms per device call (profiles/r12_fixed_eval_batch.json: every size measured there is above it and the device wins, 10x at one point of 4.4 x 10^5 entries); not measured AT the crossover
     int tune_witness_kernel = 1;  // the constraint check (zp_stark_check_witness on a ctx, the provers under "prove_check") runs the program's GENERATED witness kernel when one is registered (zp_stark_set_air_kernel_witness); 0: always the interpreter.  Same reports either way (figures: profiles/witness_check_inproof.json)
     int tune_prove_check = 0;     // 1: zp_stark_prove / zp_stark_prove_bn128 check the trace inside the proof (canonical words first, the constraints at the transcript's own stage-2 challenge) and refuse a false witness with ZP_ERR_WITNESS; 0: they prove whatever they are handed
+    int tune_s2_diag_merge = 1;   // zp_stark_diagnose_stage2 on a ctx: a wave whose live lanes all carry ONE key issues its table atomics from one lane (the wave_count idea of csrc/msm.hip); 0: every lane its own.  Same records either way (A/B: tools/stage2_diag_measure.py)
     // zp_stark_prove: device buffers kept between proofs (chunk after chunk has the same shapes; hipMalloc / hipFree of ~20 buffers
     // cost milliseconds per proof) and the LDE of the two boundary selectors per (logn, logb, shift, root)
     std::multimap<size_t, void *> prove_pool;
@@ -289,6 +290,10 @@ int32_t zpi_witness_constraints(zp_ctx *ctx, const ZpProgram &pg, const uint8_t 
 struct ZpWitnessWindow { size_t stride, row0, nrows; };
 int32_t zpi_witness_launch(zp_ctx *ctx, const ZpProgram &pg, const uint8_t *dg32, const std::vector<u64> &pubchal, const u64 *d_trace, const u64 *d_s2, int logn,
                            const ZpWitnessWindow *win, u64 *d_res);
+// zp_stark_diagnose_stage2 on a ctx (csrc/stage2_diag.hip): arguments validated by the caller (csrc/stage2_diag_host.hip), which also owns the records of
+// a trace with words >= p; h_diag u64[n_s2][ZP_S2_WORDS] is written only when ZP_OK is returned
+int32_t zpi_stage2_diag_device(zp_ctx *ctx, const ZpProgram &pg, const u64 *d_trace, int logn, uint64_t *h_diag);
+void zpi_stage2_diag_noncanonical(const ZpProgram &pg, uint64_t *h_diag);
 // csrc/prove.hip: the SHA-256 of a program through the ctx's cache of large blobs; the key a generated kernel of that digest is kept under
 void zpi_program_digest_cached(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, uint8_t dg[32]);
 std::string zpi_air_kernel_key(const char *form, const uint8_t dg[32]);

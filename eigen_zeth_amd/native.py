@@ -199,6 +199,7 @@ SIGNATURES = {
     "zp_groth16_verify": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.POINTER(C.c_int32)]),
     "zp_groth16_verify_batch": (C.c_int32, [_vp, _vp, C.c_int32, _vp, _vp, C.c_size_t, C.c_int32, _vp]),
     "zp_stark_check_witness": (C.c_int32, [_vp, _u64p, C.c_size_t, _vp, C.c_size_t, _u64p, C.c_int32, C.c_int32, _u64p, _u64p, _u64p, _u64p, C.c_int32, C.c_int32]),
+    "zp_stark_diagnose_stage2": (C.c_int32, [_vp, _u64p, C.c_size_t, _vp, C.c_size_t, C.c_int32, _u64p, C.c_int32, C.c_int32]),
     "zp_stark_check_witness_sharded": (C.c_int32, [_vp, _u64p, C.c_size_t, _vp, C.c_size_t, _u64p, C.c_int32, C.c_int32, _u64p, _u64p, _u64p, _u64p, C.c_int32]),
 }
 
@@ -414,6 +415,57 @@ class WitnessError(ValueError):
     def __init__(self, report):
         super().__init__(str(report))
         self.report = report
+        self.stage2 = None      # [Stage2Diagnosis] per stage-2 argument, where whoever raised it was asked to diagnose (EngineConfig(diagnose_stage2=True))
+
+
+S2_HOLDS, S2_FAILS, S2_NONCANONICAL = range(3)
+S2_WORDS = 12
+
+
+class Stage2Diagnosis:
+    """one record of zp_stark_diagnose_stage2 (include/zeth_prover.h): verdict (S2_*) / ok; kind (1 permutation, 2 lookup); unbalanced (distinct
+    values v with lhs(v) != rhs(v)); row_a, value_a, lhs_a, rhs_a: the smallest row of column a holding an unbalanced value, that value, its
+    occurrences in a and its count on the other side (occurrences in b; the sum of m over the rows with t = v, mod p) -- None when there is no such
+    row; row_b, value_b, lhs_b, rhs_b: the same for the smallest row of b (t); rows_a: rows of a holding an unbalanced value; words: the record"""
+
+    def __init__(self, words):
+        w = self.words = [int(v) for v in words]
+        self.verdict, self.kind, self.unbalanced, self.rows_a = w[0], w[1], w[2], w[11]
+        self.ok = self.verdict == S2_HOLDS
+        self.row_a, self.value_a, self.lhs_a, self.rhs_a = w[3:7] if w[3] != _NONE64 else (None,) * 4
+        self.row_b, self.value_b, self.lhs_b, self.rhs_b = w[7:11] if w[7] != _NONE64 else (None,) * 4
+
+    def __str__(self):
+        what = {1: "permutation", 2: "lookup"}.get(self.kind, "argument")
+        if self.verdict == S2_NONCANONICAL:
+            return "%s not compared: the trace holds words >= p" % what
+        if self.ok:
+            return "%s holds" % what
+        side = lambda name, r, v, l, h: "" if r is None else "; %s row %d holds %d (%d in a, %d on the other side)" % (name, r, v, l, h)
+        return "%s fails: %d unbalanced value(s) on %d row(s) of a%s%s" % (
+            what, self.unbalanced, self.rows_a, side("a", self.row_a, self.value_a, self.lhs_a, self.rhs_a),
+            side("b" if self.kind == 1 else "t", self.row_b, self.value_b, self.lhs_b, self.rhs_b))
+
+
+def _diagnose_stage2(ctx, program, trace_ptr, trace_words, logn, threads):
+    prog = np.ascontiguousarray(np.asarray(program, dtype=np.uint64))
+    if prog.ndim != 1 or prog.size < 12 or int(prog[10]) > (1 << 16):
+        return -1, None
+    n = int(prog[10])
+    diag = np.zeros(max(n, 1) * S2_WORDS, dtype=np.uint64)
+    rc = load_library().zp_stark_diagnose_stage2(ctx, prog.ctypes.data_as(_u64p), prog.size, trace_ptr, trace_words, logn, diag.ctypes.data_as(_u64p), n, threads)
+    return rc, ([Stage2Diagnosis(diag[S2_WORDS * j:S2_WORDS * (j + 1)]) for j in range(n)] if rc == 0 else None)
+
+
+def diagnose_stage2_host(program, trace, logn, threads=0):
+    """zp_stark_diagnose_stage2 without a ctx: host trace uint64 [W][2^logn] (or flat) -> [Stage2Diagnosis], one per stage-2 argument of the program in
+    its table's order (none: []).  Names the rows and values that break a permutation or a lookup, which zp_stark_check_witness reports at row N - 1.
+    ZpError: a malformed blob or argument"""
+    tr = np.ascontiguousarray(np.asarray(trace, dtype=np.uint64))
+    rc, out = _diagnose_stage2(None, program, tr.ctypes.data, tr.size, logn, threads)
+    if rc != 0:
+        raise ZpError(rc, "zp_stark_diagnose_stage2: malformed program, or a trace that is not the program's")
+    return out
 
 
 def _check_witness(ctx, program, trace_ptr, trace_words, pubs, logn, chal, threads, comm=None):
@@ -1350,6 +1402,15 @@ class Prover:
             raise ZpError(rc, "zp_stark_check_witness: malformed program")
         self._chk(rc)
         return rep
+
+    def diagnose_stage2(self, program, d_trace, logn):
+        """zp_stark_diagnose_stage2 on this ctx: the device trace u64[W][2^logn] (only read) -> [Stage2Diagnosis] per stage-2 argument of the program"""
+        prog = np.asarray(program, dtype=np.uint64)
+        rc, out = _diagnose_stage2(self.ctx, prog, _ptr(d_trace), self._words(d_trace, prog, logn), logn, 0)
+        if rc != 0 and prog.size < 12:
+            raise ZpError(rc, "zp_stark_diagnose_stage2: malformed program")
+        self._chk(rc)
+        return out
 
     def stark_prove_bn128(self, air_name, program, d_trace, pubs, logn, logb, fri_logf, fri_final_log, n_queries):
         """zp_stark_prove_bn128: the one-call prover in BN128-hash mode (install_poseidon_bn254(17) first)"""

@@ -78,7 +78,7 @@ class EngineConfig:
                  final_air="chunk16", final_logn=10, final_logb=2, final_queries=50, native_prover=True,
                  agg_queries=50, agg_pow_bits=0, aggregate_all_chunks=False, groth16_seed=None, witness="device",
                  speculate_recursion=False, verify_before_wrap=True, final_ranks=1, final_devices=None, wrap_ranks=1, wrap_devices=None,
-                 verify_final=False, check_witness=False):
+                 verify_final=False, check_witness=False, diagnose_stage2=False):
         self.air, self.logn, self.logb = air, logn, logb
         # Every STARK this engine proves (chunk proofs, the aggregation STARK, the final STARK) first has its trace checked against its constraint
         # program (zp_stark_check_witness: on the proving backend's GPU where it can, on the host otherwise; "witness_check" in the stage timings).
@@ -90,6 +90,12 @@ class EngineConfig:
         # verdict: csrc/witness_sharded.hip).  A proof that does not go through a one-call prover (the Python orchestration) is checked by the
         # separate call as under True.
         self.check_witness = check_witness
+        # A WitnessError for an AIR with stage-2 arguments (a permutation, a lookup) says "row N - 1": where the running product or sum fails to
+        # close.  True: while the refused trace is still held, zp_stark_diagnose_stage2 compares the arguments' columns as multisets (on the backend's
+        # GPU where it can, on the host otherwise; "stage2_diagnose" in the stage timings) and the error carries the records as .stage2
+        # ([native.Stage2Diagnosis]: the row and the value that break each argument).  Under both forms of check_witness.  Off by default: .stage2 is
+        # None and nothing else changes; on, only a refusal costs anything.
+        self.diagnose_stage2 = diagnose_stage2
         # GenFinalProof: run the native Groth16 verifier (zp_groth16_verify) on the proof about to be returned and raise unless it is accepted
         # ("groth16/verify" in the stage clock).  Off by default: no response and no timing changes.
         self.verify_final = verify_final
@@ -286,9 +292,19 @@ class Engine:
             report = native.check_witness_host(air.program(), trace, [int(v) for v in pubs], int(trace.shape[-1]).bit_length() - 1)
         timings["witness_check"] = time.perf_counter() - t0
         if not report.ok:
-            if isinstance(trace, native.DeviceBuffer):
-                trace.free()
-            raise WitnessError(report)
+            err = WitnessError(report)
+            try:
+                if self.cfg.diagnose_stage2 and air.stage2:
+                    t0 = time.perf_counter()
+                    if hasattr(be, "diagnose_stage2"):
+                        err.stage2 = be.diagnose_stage2(air, trace)
+                    else:
+                        err.stage2 = native.diagnose_stage2_host(air.program(), trace, int(trace.shape[-1]).bit_length() - 1)
+                    timings["stage2_diagnose"] = time.perf_counter() - t0
+            finally:
+                if isinstance(trace, native.DeviceBuffer):
+                    trace.free()
+            raise err
 
     def _check_in_proof(self, be, sharded=False):
         """cfg.check_witness == "prove": True when the proof about to be made on `be` checks its own trace (the knob is set on its ctx; a sharded
@@ -298,6 +314,10 @@ class Engine:
         if not sharded:
             be.p.set_tuning("prove_check", 1)
         return True
+
+    def _diagnose_in_proof(self, be):
+        """cfg.diagnose_stage2 for a proof that checks itself: the backend diagnoses a refused trace before it frees it (prove_native(diagnose=True))"""
+        return {"diagnose": True} if self.cfg.diagnose_stage2 and self.cfg.check_witness == "prove" and hasattr(be, "diagnose_stage2") else {}
 
     @staticmethod
     def _chunk_witness(air, ch, out=None):
@@ -429,7 +449,7 @@ class Engine:
                 if self.cfg.native_prover and hasattr(be, "prove_native"):
                     # one C-ABI call per chunk (zp_stark_prove): the orchestration runs in the library, Python only frames the result
                     t0 = time.perf_counter()
-                    text = be.prove_native(air, trace, pubs, params)
+                    text = be.prove_native(air, trace, pubs, params, **self._diagnose_in_proof(be))
                     tm["total"] = time.perf_counter() - t0
                     text = text[:-1] + ',"chunk":%s}' % json.dumps(self._chunk_label(ch), separators=(",", ":"))
                 else:
@@ -592,7 +612,7 @@ class Engine:
         if sharded:
             text, self._sharded_openings = be.prove_native_sharded(vair, trace, pubs, params, self.cfg.final_ranks, self.cfg.final_devices, check=in_proof)
         elif self.cfg.native_prover and hasattr(be, "prove_native"):
-            text = be.prove_native(vair, trace, pubs, params)
+            text = be.prove_native(vair, trace, pubs, params, **self._diagnose_in_proof(be))
         else:
             text = PR.proof_to_json(PR.prove(vair, trace, pubs, params, be))
         timings["verifier-stark"] = time.perf_counter() - t0

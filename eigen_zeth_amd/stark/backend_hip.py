@@ -202,9 +202,11 @@ class HipBackend:
                 pass
             self._native_kernels.add(kkey)
 
-    def prove_native(self, air, trace, pubs, params):
+    def prove_native(self, air, trace, pubs, params, diagnose=False):
         """the whole chunk STARK through zp_stark_prove (one C-ABI call, orchestration in the library's host C++): proof TEXT,
-        byte-identical to proof_to_json(prove(...)) over this backend.  trace: host array or a device buffer from prefetch_trace."""
+        byte-identical to proof_to_json(prove(...)) over this backend.  trace: host array or a device buffer from prefetch_trace.
+        diagnose: a refusal under set_tuning("prove_check", 1) (native.WitnessError) of an AIR with stage-2 arguments gets .stage2 from
+        diagnose_stage2 on the device trace, which the prover only read, before it is freed"""
         assert self.hash_mode == params.hash
         self._register_kernels(air)
         d_tr = trace if isinstance(trace, native.DeviceBuffer) else self.p.upload(trace)
@@ -214,8 +216,23 @@ class HipBackend:
                                                 params.fri_final_log, params.n_queries)
             return self.p.stark_prove(air.name, air.program(), d_tr, [int(v) for v in pubs], params.logn, params.logb, params.fri_logf,
                                       params.fri_final_log, params.n_queries, params.pow_bits)
+        except native.WitnessError as err:
+            if diagnose and air.stage2:
+                err.stage2 = self.p.diagnose_stage2(air.program(), d_tr, params.logn)
+            raise
         finally:
             d_tr.free()
+
+    def diagnose_stage2(self, air, trace):
+        """zp_stark_diagnose_stage2 on this backend's GPU: which rows and values break the AIR's permutations and lookups (trace: host array, uploaded
+        for the call, or a device buffer, only read) -> [native.Stage2Diagnosis] per stage-2 argument"""
+        logn = int(trace.shape[-1]).bit_length() - 1
+        d_tr = trace if isinstance(trace, native.DeviceBuffer) else self.p.upload(trace)
+        try:
+            return self.p.diagnose_stage2(air.program(), d_tr, logn)
+        finally:
+            if d_tr is not trace:
+                d_tr.free()
 
     def check_witness(self, air, trace, pubs):
         """zp_stark_check_witness on this backend's GPU: does the trace (host array, uploaded for the check, or a device buffer from prefetch_trace,

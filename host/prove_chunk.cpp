@@ -15,6 +15,11 @@
 //   --check-prove: the check runs INSIDE the proof instead (zp_set_tuning "prove_check": canonical words, then the constraints at the proof's own
 //   stage-2 challenge; a sharded run checks over its ranks); the same JSON line (zp_stark_prove_witness_report; rank 0 prints it) in front of the
 //   result, and a refusal (ZP_ERR_WITNESS, on every rank) ends the run with exit status 3, unproven.
+//   --diagnose (one GPU; with --check or --check-prove): after a refusal, zp_stark_diagnose_stage2 compares the columns of the program's permutations
+//   and lookups as multisets, in HBM, and one line per argument that fails says which cell is wrong -- the report above names only row N - 1, where
+//   the running product or sum fails to close:  {"stage2":{"argument":j,"kind":"lookup","column":"a","row":..,"value":..,"lhs":..,"rhs":..}}
+//   (the smallest row of column a holding an unbalanced value, lhs = its occurrences in a, rhs = its count on the other side; when only the other
+//   column holds one, that column -- "b" or "t" -- and its smallest such row).
 //   program.bin : the constraint program blob (u64 words, layout in the header)
 //   trace.bin   : u64[W][2^logn] column-major, canonical values
 //   publics.bin : u64[n_pub]
@@ -61,13 +66,33 @@ static bool print_report(const uint64_t *r) {
     return r[0] == ZP_WITNESS_SATISFIED;
 }
 
+// zp_stark_diagnose_stage2 on the refused trace: one JSON line per argument that fails
+static int32_t print_diagnosis(zp_ctx *ctx, const std::vector<uint64_t> &program, const void *d_trace, size_t trace_words, int logn) {
+    const size_t n = (size_t)program[10];              // n_stage2 of the header; the library checks it against the blob
+    if (n == 0 || n > 65536) return 0;
+    std::vector<uint64_t> diag(n * ZP_S2_WORDS);
+    const int32_t rc = zp_stark_diagnose_stage2(ctx, program.data(), program.size(), (const uint64_t *)d_trace, trace_words, logn, diag.data(), (int32_t)n, 0);
+    if (rc != 0) return rc;
+    for (size_t j = 0; j < n; j++) {
+        const uint64_t *r = diag.data() + j * ZP_S2_WORDS;
+        if (r[0] != ZP_S2_FAILS) continue;
+        const uint64_t *s = r[3] != ~0ULL ? r + 3 : r + 7;         // (row, value, lhs, rhs) of column a, else of the other column
+        printf("{\"stage2\":{\"argument\":%zu,\"kind\":\"%s\",\"column\":\"%s\",\"row\":%llu,\"value\":%llu,\"lhs\":%llu,\"rhs\":%llu}}\n", j,
+               r[1] == 1 ? "permutation" : "lookup", s == r + 3 ? "a" : r[1] == 1 ? "b" : "t", (unsigned long long)s[0], (unsigned long long)s[1],
+               (unsigned long long)s[2], (unsigned long long)s[3]);
+    }
+    fflush(stdout);
+    return 0;
+}
+
 int main(int argc, char **argv) {
-    bool check = false, check_prove = false;
+    bool check = false, check_prove = false, diagnose = false;
     {
         int n = 1;
         for (int i = 1; i < argc; i++) {
             if (strcmp(argv[i], "--check") == 0) check = true;
             else if (strcmp(argv[i], "--check-prove") == 0) check_prove = true;
+            else if (strcmp(argv[i], "--diagnose") == 0) diagnose = true;
             else argv[n++] = argv[i];
         }
         argc = n;
@@ -106,6 +131,7 @@ int main(int argc, char **argv) {
         CHECK(zp_stark_check_witness(ctx, program.data(), program.size(), (const uint64_t *)d_trace, trace.size(), pubs.data(), (int32_t)pubs.size(), logn, nullptr,
                                      report, nullptr, nullptr, 0, 0));
         if (!print_report(report)) {
+            if (diagnose && report[0] == ZP_WITNESS_VIOLATED) CHECK(print_diagnosis(ctx, program, d_trace, trace.size(), logn));
             zp_dev_free(ctx, d_trace);
             zp_destroy(ctx);
             return 3;
@@ -149,7 +175,9 @@ int main(int argc, char **argv) {
     }
     if (check_prove) {                                 // the proof's own verdict, the same on every rank: rank 0 prints it
         CHECK(zp_stark_prove_witness_report(ctx, report, nullptr, nullptr, nullptr, (int32_t)program[8]));
-        if ((rank == 0 ? !print_report(report) : report[0] != ZP_WITNESS_SATISFIED) || rc != 0) return give_up(3);
+        const bool refused = (rank == 0 ? !print_report(report) : report[0] != ZP_WITNESS_SATISFIED) || rc != 0;
+        if (refused && diagnose && !sharded && report[0] == ZP_WITNESS_VIOLATED) CHECK(print_diagnosis(ctx, program, d_trace, trace.size(), logn));   // the prover only read the trace
+        if (refused) return give_up(3);
     }
     if (rank == 0) {
         FILE *o = fopen(argv[10], "wb");

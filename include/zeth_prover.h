@@ -252,7 +252,8 @@ int32_t zp_program_digest(const uint64_t *h_program, size_t program_words, uint8
  * >= W reading those columns.  h_chal3 = the challenge (canonical); NULL derives one from the program: words 0..2 of zp_program_digest's out_words4,
  * word 1 set to 1 if words 1 and 2 are both 0 (outside the base field, so a base-field value plus it is never zero).  A derived challenge finds
  * MISTAKES, not adversaries: whoever knows it can build a wrong permutation or lookup that passes; only the prover's Fiat-Shamir challenge binds.
- * A broken permutation or lookup shows at the cyclic row N - 1 of the wrap-around constraints.
+ * A broken permutation or lookup shows at the cyclic row N - 1 of the wrap-around constraints: that is where a running product or sum fails to
+ * close, not where the trace is wrong -- zp_stark_diagnose_stage2 below names the row and the value.
  * Returns ZP_OK whenever a verdict was reached (a violated witness is a verdict, not an error); ZP_ERR_ARG for the caller's mistakes -- a malformed
  * blob (everything zp_eval_quotient_rows and zp_stark_prove refuse: more than 32 slots included), trace_words != W * 2^logn, n_pubs not the program's,
  * a public input or challenge word >= p, logn < 1, a sparse column with lp > logn, h_counts or h_first_row given with n_constraints != K.  On an
@@ -265,6 +266,29 @@ enum { ZP_WITNESS_SATISFIED = 0, ZP_WITNESS_VIOLATED = 1, ZP_WITNESS_NONCANONICA
 int32_t zp_stark_check_witness(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const uint64_t *trace, size_t trace_words,
                                const uint64_t *h_pubs, int32_t n_pubs, int32_t logn, const uint64_t *h_chal3, uint64_t *h_report /* [8] */,
                                uint64_t *h_counts /* [K] or NULL */, uint64_t *h_first_row /* [K] or NULL */, int32_t n_constraints, int32_t threads);
+
+/* ---- which cell breaks a permutation or a lookup ------------------------------------------------------------------------------------------
+ * The check above reports a broken stage-2 argument at row N - 1, where its running product or sum fails to close; which trace cell is wrong is
+ * another computation: a comparison of multisets.  A permutation argument {a, b} holds iff the columns a and b are equal as multisets; a lookup
+ * {a, t, m} holds iff for every value v  #{r : a[r] = v} = sum of m[i] over the rows i with t[i] = v  (mod p) -- the LogUp identity as rational
+ * functions (N < p: the left side never wraps).  This call compares them: no public input, no challenge, no constraint is evaluated.
+ * Per argument j of the program's stage-2 table, in its order: lhs(v) = occurrences of v in column a; rhs(v) = occurrences in b (permutation) or
+ * the sum of m[i] over the rows with t[i] = v reduced mod p (lookup); v is UNBALANCED when lhs(v) != rhs(v) (a table row with m = 0 that nothing
+ * hits is balanced).  h_diag[j][ZP_S2_WORDS]:
+ *   [0] verdict (ZP_S2_*)   [1] kind from the table (1 permutation, 2 lookup)   [2] distinct unbalanced values
+ *   [3] r_a = the smallest row r with a[r] unbalanced, or ~0   [4] a[r_a]  [5] its lhs  [6] its rhs   (~0, 0, 0 when r_a = ~0)
+ *   [7] r_b = the smallest row i with b[i] (t[i]) unbalanced, or ~0   [8] that value  [9] its lhs  [10] its rhs   (~0, 0, 0 when r_b = ~0)
+ *   [11] rows of a that hold an unbalanced value (the sum of lhs over the unbalanced values)
+ * Every word is a function of the trace alone.  Any trace word >= p (in any column, as in the check above): every record is
+ * [NONCANONICAL, kind, 0, ~0, ~0, 0, 0, ~0, ~0, 0, 0, 0] and nothing else runs.
+ * Pointers and threads as for zp_stark_check_witness: with a ctx, trace is a DEVICE pointer u64[W][2^logn], only read (csrc/stage2_diag.hip: a hash
+ * join in HBM, 192 bytes of pool memory per row), and the call returns synchronised; ctx = NULL: a HOST pointer, `threads` host threads.
+ * ZP_ERR_ARG: a blob zp_stark_check_witness refuses, trace_words != W * 2^logn, logn < 1, n_stage2 not the program's.  n_stage2 == 0 (of a program
+ * without arguments): ZP_OK, nothing written.  On an error h_diag is left as it was; no exception crosses the ABI.                                */
+enum { ZP_S2_HOLDS = 0, ZP_S2_FAILS = 1, ZP_S2_NONCANONICAL = 2 };
+#define ZP_S2_WORDS 12
+int32_t zp_stark_diagnose_stage2(zp_ctx *ctx, const uint64_t *h_program, size_t program_words, const uint64_t *trace, size_t trace_words, int32_t logn,
+                                 uint64_t *h_diag /* [n_stage2][ZP_S2_WORDS] */, int32_t n_stage2, int32_t threads);
 
 /* ---- N5: FRI fold ------------------------------------------------------------------------------
  * d_in u64[3][2^logn] = f on shift*<w_n> (natural order);  d_out u64[3][2^(logn-logf)] =
@@ -798,6 +822,8 @@ int32_t zp_hbm_copy_probe(zp_ctx *ctx, const void *d_src, void *d_dst, size_t by
  * device, < 0 restores the default 2^15 (derived from profiles/r12_fixed_eval_batch.json, not measured at that size));
  * "witness_kernel" 1 (default): the constraint check runs a registered generated witness kernel, 0: always the interpreter; "prove_check" 1: the one-call
  * provers check their trace inside the proof and refuse a false witness with ZP_ERR_WITNESS (0, the default: they prove whatever they are handed);
+ * "s2_diag_merge" 1 (default): in zp_stark_diagnose_stage2 a wave whose lanes all carry one value issues its table atomics from one lane, 0: every lane
+ * its own (the same records);
  * not for production hosts */
 int32_t zp_set_tuning(zp_ctx *ctx, const char *key, int32_t value);
 
